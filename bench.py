@@ -36,6 +36,12 @@ batches of G consecutive steps go through ONE library call side by side; every s
 exchanged on their own, in step order (`config.steps_per_call`, `config.calls_in_flight_per_gpu`).  `--inflight`
 then counts calls.
 
+`--dump-outputs DIR`: after the timed steps, what the LAST timed step computed (rank 0's view) goes to DIR as .npy
+files, float32 / float64: `onsets` [n, 3] (clip, channel, sample: the records of the exchange, every rank's), `counts`
+(onsets per clip of this rank) and, from the step's own clips, `rel`, `power`, `mel`, `logits` -- whole when they
+have at most DUMP_SAMPLE elements, else DUMP_SAMPLE elements at fixed seeded positions (the same for the same shape).
+The inputs depend on the arguments only, so two builds run with the same arguments can be compared file by file.
+
 `--rehearsal` (no GPU needed): the launcher, rendezvous, sharding, exchange, max-over-ranks timing and
 JSON line with fabricated onset records instead of GPU work -- the control flow of the N > 1 path for
 CPU tests (gloo).  Its `value` is not a measurement and says so.
@@ -48,10 +54,6 @@ import subprocess
 import sys
 import time
 from pathlib import Path
-
-# Steps in flight live on separate HIP streams; by default the runtime multiplexes all streams of a
-# process onto 4 hardware queues.  Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 REPO = Path(__file__).resolve().parent
 sys.path.insert(0, str(REPO))
@@ -71,6 +73,7 @@ BYTES_E2E = BYTES_DETECT + BYTES_SPECTRUM + BYTES_FINGERPRINT  # 4 100 + 192
 TRAFFIC_FILE = REPO / "profiles" / "r03" / "pmc_traffic_per_kernel.json"
 SQ_FILE = REPO / "profiles" / "r03" / "pmc_sq_per_kernel.json"   # instruction-level counters per kernel (tools/profile_r3.sh)
 MFMA_F32_PEAK_TFLOPS = 157.3   # v_mfma_f32_16x16x4_f32 / 32x32x2: the FP32 matrix peak of the guide
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: elements kept of a dense output (4 x 8 MB at most, plus the onsets)
 
 
 def free_port():
@@ -294,6 +297,31 @@ def cpu_fanout(kind, seconds, sd):
                        "slowest (process start-up and clip synthesis excluded)")
 
 
+def dump_outputs(dirname, recs, counts=None, dense=None):
+    """--dump-outputs: recs = the exchanged onset records (structured clip / channel / sample), counts = onsets per
+    clip, dense = {name: device tensor}.  A dense output larger than DUMP_SAMPLE elements is sampled at positions drawn
+    from a generator seeded with its name and shape, so the same shape gives the same positions in every run."""
+    import zlib
+
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    on = np.stack([recs["clip"], recs["channel"], recs["sample"]], axis=1).astype(np.float64).reshape(-1, 3)
+    np.save(d / "onsets.npy", on)
+    if counts is not None:
+        np.save(d / "counts.npy", counts.cpu().numpy().astype(np.float64))
+    for name, t in (dense or {}).items():
+        if t is None:
+            continue
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            seed = zlib.crc32(f"{name}{tuple(t.shape)}".encode())
+            idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(d / f"{name}.npy", flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -311,6 +339,8 @@ def main():
     ap.add_argument("--tuning", type=str, default="", help="JSON dict of ofp_detect_tuning fields (experiments)")
     ap.add_argument("--exp", type=str, default="", help="EXPERIMENTS (the line says so in config.experiment and is not the "
                     "metric): JSON dict with detector kwargs (hipass_freq, on_threshold, ...) and/or \"no_stft\": true")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="write what the last timed step computed "
+                    "to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--rehearsal", action="store_true", help="control flow only, no GPU work (CPU tests)")
     ap.add_argument("--shard-of", type=int, default=0, help="c4 on ONE GPU: process only rank 0's shard of a world of this "
                     "size (what one rank of an N-GPU run does per step, without the exchange partners); the line is "
@@ -468,6 +498,7 @@ def main():
                 pp.detector.set_tuning(**tuning)
         streams = [torch.cuda.Stream(dev) for _ in range(D)]
         stage_acc, lat_acc, gather_acc = {}, [], []
+        last_gathered = [None]   # the exchange of the last step finished (G > 1: the call's last step)
 
         def run_step(w, timed):
             torch.cuda.set_device(local)
@@ -494,6 +525,9 @@ def main():
                     g_i = all_gather_blocks(b_i)
                     if gathered is None:           # (the checks below read the call's FIRST step: its clip 0 is out[...][0])
                         gathered = g_i
+                last_gathered[0] = g_i
+            if G == 1:
+                last_gathered[0] = gathered
             if timed:
                 gather_acc.append((time.perf_counter() - t_g) / G)
                 st = dict(out["info"]["stage_ms"])
@@ -535,6 +569,16 @@ def main():
     dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = frames_total / (ms_per_step / 1e3)
+
+    if args.dump_outputs:  # before anything else reuses the pipelines' output buffers
+        if rehearsal:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, records_to_numpy(unpack_gathered(res)))
+        elif rank == 0:
+            o_l = res[0]
+            s_l = slice((G - 1) * n_local, G * n_local)   # the last step's clips in its call
+            dump_outputs(args.dump_outputs, records_to_numpy(unpack_gathered(last_gathered[0])), o_l["counts"][s_l],
+                         {k: (o_l[k][s_l] if o_l[k] is not None else None) for k in ("rel", "power", "mel", "logits")})
 
     if rehearsal:
         gathered = unpack_gathered(res)

@@ -66,3 +66,17 @@ def test_a_failed_rank_fails_the_launcher():
     r = _run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--rehearsal"],
              env={"OFP_BENCH_TEST_FAIL_RANK": "1"})
     assert r.returncode != 0 and r.stdout.strip() == "" and "ranks failed" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_steps_exchanged_records(tmp_path):
+    """--dump-outputs in a rehearsal: rank 0 writes the records the last step's exchange delivered (every rank's)."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = _run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--rehearsal", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["steps"] == 2
+    assert sorted(p.name for p in d.iterdir()) == ["onsets.npy"]
+    on = np.load(d / "onsets.npy")
+    assert on.dtype == np.float64 and on.shape == (3 * 512, 3)
+    assert np.array_equal(np.unique(on[:, 0]), np.arange(512))   # (clip, channel, sample) of both shards
+    assert np.array_equal(on[:, 2], 1000 * on[:, 0] + np.tile(np.arange(3), 512))

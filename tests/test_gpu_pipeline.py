@@ -365,6 +365,45 @@ def test_bench_two_ranks_with_several_steps_per_call(tmp_path):
     assert c["onsets_gathered"] > 512 * 50  # (a C4 clip has ~140 onsets: both ranks' records arrived)
 
 
+def test_bench_dump_outputs_is_what_the_last_timed_step_computed(mods, tmp_path):
+    """`bench.py --dump-outputs DIR` (two C2 clips per step, two steps in flight, three timed steps): the files hold
+    what the pipeline computes on the clips of the last timed step (slot 2 % 2 = 0), sampled at the same positions;
+    the onsets and `rel` bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import bench
+    from onset_fingerprinting_amd.distributed import pack_clips, records_to_numpy, unpack_gathered
+    _, pipeline = mods
+    d = tmp_path / "bench"
+    r = subprocess.run([sys.executable, str(Path(bench.__file__).resolve()), "--clips", "2", "--inflight", "2", "--steps", "3",
+                        "--warmup", "1", "--no-cpu", "--no-extras", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["steps"] == 3
+    names = sorted(p.name for p in d.iterdir())
+    assert names == ["counts.npy", "logits.npy", "mel.npy", "onsets.npy", "power.npy", "rel.npy"]
+    assert sum((d / n).stat().st_size for n in names) <= 64 << 20
+
+    xs = bench.synth_batch("c2", [1, 1 + 7919], bench.C2["seconds"], bench.C2["C"], 2)
+    x = torch.from_numpy(np.stack(xs)).cuda().contiguous()
+    pipe = pipeline.FingerprintPipeline(bench.C2["C"], bench.NFFT, bench.HOP, SR, bench.NMELS, device=0, cap_per_clip=4096)
+    out = pipe.run(x)
+    torch.cuda.synchronize()
+    recs = records_to_numpy(unpack_gathered(pack_clips(out["records"], out["counts"], 2 * 1024)[None]))
+    e = tmp_path / "direct"
+    bench.dump_outputs(e, recs, out["counts"], {k: out[k] for k in ("rel", "power", "mel", "logits")})
+    for n in names:
+        a, b = np.load(d / n), np.load(e / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        if n in ("onsets.npy", "counts.npy", "rel.npy"):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), n
+        else:
+            assert np.allclose(a, b, rtol=1e-5, atol=1e-6 * np.abs(b).max()), n
+
+
 @pytest.mark.slow
 def test_c4_at_its_stated_size_512_clips_on_one_gpu(mods):
     """BASELINE configs[3] at full size on one GPU: 512 clips x 4 ch x 10 s in ONE call (2 048 chains) in the bench's

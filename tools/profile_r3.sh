@@ -7,7 +7,7 @@ TAG=${1:-r03}; QUICK=$2
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $O
-export OFP_SYNTH_CACHE=/tmp/ofp_clip_cache GPU_MAX_HW_QUEUES=16
+export OFP_SYNTH_CACHE=/tmp/ofp_clip_cache
 cd /tmp && export TMPDIR=/tmp
 B="python3 $ROOT/bench.py"
 echo "== bench (default command; fills the clip cache)"; date
