@@ -23,6 +23,7 @@
  *   data.py:657-680                 cspec_to_mfcc (mel + dB + DCT)
  *   calibration.py:463-560          FCNN forward
  *   model.py:52-120                 CNN forward
+ *   model.py:168-440                RNN / CNNRNN forward
  */
 #ifndef ONSETFP_H
 #define ONSETFP_H
@@ -399,6 +400,47 @@ int ofp_groupnorm1(const float* d_x, int64_t n, int32_t K, int32_t V, const floa
 /* CCCNN correlation head (model.py:524-534): d_x [n][K][V] feature maps -> d_out [n][2V-1]:
  * full auto-correlation of every map, summed over the K maps, soft-maxed over the lags. */
 int ofp_autocorr_softmax(const float* d_x, int64_t n, int32_t K, int32_t V, float* d_out, void* stream);
+
+/* ---- recurrent classifiers: model.RNN / model.CNNRNN (model.py:168-440), eval mode ----------------
+ * Cell codes of ofp_rnn_layer: torch's gate order and equations, zero initial state.
+ *   RNN:  h' = act(W_ih x + b_ih + W_hh h + b_hh)                        (nn.RNN, tanh or relu)
+ *   GRU:  r, z, n;  n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),  h' = (1 - z) n + z h   (nn.GRU)
+ *   LSTM: i, f, g, o;  c' = f c + i g,  h' = o tanh(c')                   (nn.LSTM, no projection) */
+#define OFP_CELL_RNN_TANH 0
+#define OFP_CELL_RNN_RELU 1
+#define OFP_CELL_GRU 2
+#define OFP_CELL_LSTM 3
+/* One layer and direction of an nn.RNN / nn.GRU / nn.LSTM over n_seq sequences of T steps, one launch.
+ * With G gates per cell (1, 3, 4) and H <= 256 hidden units:
+ *   input, one of:
+ *     d_gx != NULL: the input projection x W_ihᵀ + b_ih, already computed (e.g. by ofp_dense), element
+ *       (s, t, g*H + j) at d_gx[s*gx_seq + t*gx_t + g*H + j]; d_x, d_w_ih, d_b_ih are then ignored;
+ *     d_gx == NULL: element (s, t, f) of the input at d_x[s*x_seq + t*x_t + f*x_f] (any strides, so a
+ *       channel slice or a permuted view is read in place), in <= 8 features, d_w_ih [G*H][in],
+ *       d_b_ih [G*H] or NULL;
+ *   d_w_hh [G*H][H], d_b_hh [G*H] or NULL (torch's weight_hh_l{k}, bias_hh_l{k});
+ *   reverse != 0: the backward direction (t = T-1 .. 0);
+ *   output: h_t of sequence s, unit j at d_y[s*y_seq + t*y_t + y_off + j] (so the two directions, or
+ *     several runs, fill their slots of one [.., T, F] tensor without a copy).
+ * Every output element depends only on its own sequence.  W_hh is kept in LDS when
+ * ofp_rnn_lds_bytes(cell, H) <= 160 KiB and streamed from L2 otherwise.  OFP_ERR_INVALID: unknown cell,
+ * T < 1, H outside 1..256, in > 8 without d_gx, NULL d_w_hh / d_y. */
+int ofp_rnn_layer(int32_t cell, int64_t n_seq, int32_t T, int32_t in, int32_t H, int32_t reverse, const float* d_x,
+                  int64_t x_seq, int64_t x_t, int64_t x_f, const float* d_gx, int64_t gx_seq, int64_t gx_t,
+                  const float* d_w_ih, const float* d_b_ih, const float* d_w_hh, const float* d_b_hh, float* d_y,
+                  int64_t y_seq, int64_t y_t, int32_t y_off, void* stream);
+/* LDS a workgroup of ofp_rnn_layer needs to keep W_hh resident; -1 for an invalid cell or H */
+int64_t ofp_rnn_lds_bytes(int32_t cell, int32_t H);
+/* nn.LayerNorm(E) over rows: d_x [n][E] -> d_y [n][E] (may alias d_x); d_gamma / d_beta [E] or NULL. */
+int ofp_layernorm(const float* d_x, int64_t n, int32_t E, const float* d_gamma, const float* d_beta, float eps,
+                  float* d_y, void* stream);
+/* nn.MultiheadAttention self-attention (eval, need_weights=False) before out_proj, averaged over time:
+ * d_qkv [n_seq][T][3E] is the in-projection (q | k | v column blocks, head h in columns h*d .. h*d+d-1 of
+ * each, d = E / n_heads); d_out [n_seq][E] = mean_t of softmax(Q Kᵀ / sqrt(d)) V per head.  out_proj and
+ * a following Linear commute with the mean and are applied to d_out (ofp_dense).  Keys are streamed with
+ * an online softmax, so T is unbounded.  OFP_ERR_INVALID: T < 1, E not divisible by n_heads, d > 128. */
+int ofp_attention_mean(const float* d_qkv, int64_t n_seq, int32_t T, int32_t E, int32_t n_heads, float* d_out,
+                       void* stream);
 
 /* ---- per-hop streaming session (BASELINE config 5) -------------------------------------------
  * The reference's realtime pattern -- PortAudio callback: ring-buffer write (realtime/audio.py:97),

@@ -163,6 +163,11 @@ SIGNATURES = {
     "ofp_conv1d": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                   _i32, _vp, _vp]),
     "ofp_groupnorm1": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp]),
+    "ofp_rnn_layer": (ctypes.c_int, [_i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
+                                     _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "ofp_rnn_lds_bytes": (_i64, [_i32, _i32]),
+    "ofp_layernorm": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp]),
+    "ofp_attention_mean": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "ofp_group_workspace_bytes": (_i64, [_i64, _i64]),
     "ofp_group_onsets": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64,
                                         _vp]),
