@@ -603,6 +603,53 @@ int ofp_peak_pick(const float* d_x, int64_t n, int32_t pre_max, int32_t post_max
                   float delta, int64_t wait, int64_t* d_peaks, int64_t cap, int64_t* d_count, uint8_t* d_flags,
                   void* stream);
 
+/* ---- hit location: lag maps, legality search, TDoA trilateration (multilateration.py) ------------
+ * All geometry is fp64 (numpy's float64), positions in cm.  Grid of a lag map: side = 2r+1 cells, cell
+ * (row, col) is the point (col - r, row - r, 0) (np.meshgrid puts i on columns, j on rows).
+ * ofp_lag_maps: d_sensors [S][3] -> d_maps [S][S][side][side] float32 with map (i, j) =
+ *   rint((|p - s_j| / c - |p - s_i| / c) * sr), i.e. lag_map_3d(s_j, s_i) (multilateration.py:945-1001; 2-D
+ *   sensors have z = 0, lag_map_2d :902-942); NaN where col'^2 + row'^2 > mask_r2 (the caller's
+ *   (r + tol*scale)^2) and where the value is below floor_v (-INFINITY for none; Multilaterate3D uses
+ *   -samples_per_cm, :372); maps (i, i) are all NaN.  d_min / d_max [S][S] (both or neither): nanmin /
+ *   nanmax of each map, NaN for an all-NaN map.  S in 2..64, r <= 4096.
+ * ofp_locate_legal: is_legal_3d (:413-426) for G groups: d_sensors [G][3] int32 (origin, a, b), d_onsets
+ *   [G][3] -> d_idx [G][2] = np.unravel_index(np.argmax(legal), shape, "F") of the mask
+ *   |map(o,a) - lag_a| < tolerance and |map(o,b) - lag_b| < tolerance (strict, NaN illegal): the first
+ *   legal cell in row-major order as (col, row); (0, 0) if none; (-1, -1) for a sensor index outside 0..S-1.
+ * ofp_trilaterate: solve_trilateration_3d (:230-316) for G groups: scipy.optimize.fsolve(xtol, maxfev,
+ *   fprime) = MINPACK hybrj, mode 1, factor 100 (csrc/ofp_hybrj.h).  d_geom [G][9] = origin, a, b (x, y, z);
+ *   d_delta [G][2] = delta_d_a, delta_d_b; d_guess [G][2] -> d_root [G][2] (the last iterate), d_ier [G]
+ *   (fsolve's ier; the reference accepts only 1) and d_nfev [G] (MINPACK's count; fsolve's info["nfev"]
+ *   also counts two calls of its own and is 2 higher), both may be NULL.
+ * ofp_locate_groups: per row of ofp_group_onsets' output (d_groups [n_clips][cap_groups][n_channels], rows
+ *   beyond d_n_groups[clip] unused, d_n_groups may be NULL; channel k is sensor k, n_channels <= S): the three
+ *   earliest channels present, ordered by onset (ties by channel), are origin, a, b; is_legal on (origin, a)
+ *   and (origin, b) against d_min / d_max, the legality search with `tolerance` (samples), the guess
+ *   (col, row) - radius, trilaterate's reordering when a's slot holds sensor 1 (:542-544), then hybrj with
+ *   delta = lag / sr * c -- or, with mlp != NULL, the network on the float32 lags, times 100 (:554-557).
+ *   d_xy [rows][2] (NaN unless a solve ran), d_status [rows]: the ier (1 = located) or an OFP_LOCATE_* code,
+ *   d_guess [rows][2] or NULL; d_ws: ofp_locate_workspace_bytes(n_clips * cap_groups) bytes.
+ * ofp_locate_section: Multilaterate3D.locate's cross-correlation input (:466-476) from d_x [n][ld] (a ring
+ *   section): for columns c0, c1, median filter of size 5 along time (scipy.ndimage 'reflect'), first
+ *   difference, values >= 0 set to 0, absolute value -> d_out [2][n-1].  n >= 3. */
+#define OFP_LOCATE_UNUSED (-1)        /* row beyond the clip's group count */
+#define OFP_LOCATE_FEW_CHANNELS (-2)  /* fewer than three channels in the row */
+#define OFP_LOCATE_ILLEGAL_LAG (-3)   /* is_legal failed for (origin, a) or (origin, b) */
+#define OFP_LOCATE_NO_CELL (-4)       /* is_legal_3d returned (0, 0) */
+int ofp_lag_maps(const double* d_sensors, int32_t S, int32_t r, double c, double sr, double mask_r2, double floor_v,
+                 float* d_maps, float* d_min, float* d_max, void* stream);
+int ofp_locate_legal(const float* d_maps, int32_t S, int32_t r, const int32_t* d_sensors, const int64_t* d_onsets,
+                     int64_t G, double tolerance, int32_t* d_idx, void* stream);
+int ofp_trilaterate(const double* d_geom, const double* d_delta, const double* d_guess, int64_t G, double xtol,
+                    int32_t maxfev, double* d_root, int32_t* d_ier, int32_t* d_nfev, void* stream);
+int64_t ofp_locate_workspace_bytes(int64_t n_rows);
+int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_groups, int32_t n_channels,
+                      const int64_t* d_n_groups, const double* d_sensors, int32_t S, const float* d_maps,
+                      const float* d_min, const float* d_max, int32_t r, double tolerance, double sr, double c,
+                      double radius, double xtol, int32_t maxfev, const ofp_mlp* mlp, double* d_xy,
+                      int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int32_t c1, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,7 +94,7 @@ class HopConfig(ctypes.Structure):
     ]
 
 
-_vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+_vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _f32p_h = ctypes.POINTER(ctypes.c_float)
 _long_p = ctypes.POINTER(ctypes.c_long)
 
@@ -186,6 +186,13 @@ SIGNATURES = {
     "ofp_fix_onsets_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "ofp_fix_onsets": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                       _i32, _i32, _vp, _vp, _i64, _vp]),
+    "ofp_lag_maps": (ctypes.c_int, [_vp, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "ofp_locate_legal": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, _f64, _vp, _vp]),
+    "ofp_trilaterate": (ctypes.c_int, [_vp, _vp, _vp, _i64, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "ofp_locate_workspace_bytes": (_i64, [_i64]),
+    "ofp_locate_groups": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
+                                         _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_locate_section": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None
