@@ -147,19 +147,25 @@ typedef struct ofp_detect_tuning {
     int64_t scan_skip;           /* crossing pass: blocks whose extremes (left by the back-to-linear pass) show that they
                                     hold no value above `on` and whose last row is below `off` are decided without
                                     reading their samples: 0 on, < 0 off */
-    int64_t host_verify;         /* who drives the verification passes of the three time-parallel stages: 0 (default)
-                                    chain-local kernels -- one workgroup owns whole chains and iterates its passes
-                                    between workgroup barriers until nothing changes: no host round trip, one launch per
-                                    stage, the call can be captured in a hipGraph; 1 the round-1/2 form: one launch per
-                                    pass, the host reads a change counter per group of passes (verify_group,
-                                    max_passes apply to this form only).  Results do not change. */
-    int64_t interleaved;         /* 4 or 8 channels: stages that work on the caller's interleaved arrays instead of planar
-                                    copies.  `rel` side (throughput layout, lane_merge; `rel` requested): tracker, crossing
-                                    pass and backtracking read the `rel` output, no planar copy of it is written (+7 %
-                                    frames/s in flight).  Input side (staged candidates, high-pass on): the IIR stage reads
-                                    the audio as it is, no planar copy of the input is made -- slower (one 4-byte load per
-                                    step and lane), kept for measurement.  0 auto (the `rel` side whenever its conditions
-                                    hold), < 0 never, 1 the `rel` side, 2 the input side, 3 both.  Results do not change. */
+    int64_t host_verify;         /* who drives the verification passes of the three time-parallel stages.  0 (default):
+                                    a bounded number of passes is enqueued ahead -- IIR rounds up to HP_MAX_ROUNDS (16),
+                                    follower / tracker passes up to AHEAD_MAX_PASSES / 2 (12) -- sized by what the
+                                    detector's recent calls needed; each pass is gated on the device by its
+                                    predecessor's change counter and returns at once when there is nothing left to
+                                    repair.  No host round trip, the call can be captured in a hipGraph.  If the last
+                                    enqueued pass of a stage still changed something, the completion repeats the call
+                                    (or its tail from the follower or tracker stage) in the host-verified form,
+                                    reports it in info[15] and enqueues more passes in later calls.  1: the
+                                    host-verified form throughout -- one launch per pass, the host reads the change
+                                    counters group by group (verify_group, max_passes apply to this form only).
+                                    2 / 3: aliases of 1 kept for old callers.  -2 / -3 / -4: test hooks that force the
+                                    completion's repeat from the IIR / follower / tracker stage.  Results do not
+                                    change. */
+    int64_t interleaved;         /* 4, 8 or 64 channels, throughput layout (lane_merge), `rel` requested: tracker, crossing
+                                    pass and backtracking read the caller's interleaved `rel` output, no planar copy of it
+                                    is written (+7 % frames/s in flight).  0 (default) and 1: whenever those conditions
+                                    hold; < 0 off; 2 (= -1) and 3 (= 1) are aliases kept for old callers.  Results do not
+                                    change. */
     int64_t walk_through;        /* throughput layout: the chunks a speculative warm-up run walks through after its warm-up
                                     (all but the last of every group of `span` chunks) count as their pass 0 -- the run
                                     leaves their outputs and end states, the chunk pass runs the others only: one pass
@@ -198,8 +204,8 @@ int64_t ofp_detect_workspace_bytes(const ofp_detector* det, int64_t n_clips, int
  *   d_counts   [n_clips] int64 number of onsets per clip (may exceed cap_per_clip:
  *              only cap_per_clip are stored)
  *   d_ws       work space of at least ofp_detect_workspace_bytes()
- * Synchronises `stream` ONCE, at its end (the speculative passes are verified on the device by
- * chain-local kernels; tuning host_verify = 1 restores the host-verified pass groups of ABI 2); on return
+ * Synchronises `stream` ONCE, at its end (the speculative passes are enqueued ahead and gated on the
+ * device; a stage they do not settle is repeated host-verified, see tuning host_verify); on return
  * all outputs are complete.  h_info (optional, host, int64
  * [OFP_DETECT_INFO_LEN]) receives {0: hp passes, 1: follower passes, 2: tracker
  * passes, 3: repaired chunks, 4..9: nanoseconds (HIP events on `stream`) spent in
@@ -225,7 +231,7 @@ int ofp_detect_offline(ofp_detector* det, const float* d_x, int64_t n_clips, int
  * h_info (stage times only when the call was not captured) and, in the one case that needs a decision on the host --
  * the segmented state machine of a long clip did not converge within its pre-enqueued passes (info 14; never observed)
  * -- runs the sequential machine on `stream` and synchronises.  One enqueued call per detector at a time (it may be
- * completed once per replay of a graph that captured it).  Not with tuning host_verify.  ofp_detect_offline == _enqueue + hipStreamSynchronize + _complete. */
+ * completed once per replay of a graph that captured it).  Not with tuning host_verify > 0.  ofp_detect_offline == _enqueue + hipStreamSynchronize + _complete. */
 int ofp_detect_offline_enqueue(ofp_detector* det, const float* d_x, int64_t n_clips, int64_t n_samples,
                                int64_t warm, float* d_rel, ofp_onset* d_records, int64_t cap_per_clip,
                                int64_t* d_counts, void* d_ws, int64_t ws_bytes, void* stream);
@@ -323,9 +329,6 @@ int ofp_stft_power_mel_mlp(const float* d_x, int64_t n_clips, int64_t n_samples,
 const float* ofp_detect_planar_input(const ofp_detector* det, int64_t n_clips, int64_t n_samples, int64_t warm,
                                      const void* d_ws);
 int64_t ofp_detect_planar_stride(const ofp_detector* det, int64_t n_clips, int64_t n_samples, int64_t warm);
-/* (both return 0 / NULL when the detector's layout for these sizes works on the caller's interleaved array and makes no
- *  planar copy -- tuning `interleaved` 2 / 3; pass planar_stride 0 and the caller's array then: with 4 or 8 channels and
- *  hop = n_fft / 4 the dense STFT reads it almost as efficiently.) */
 
 /* Gathered complex STFT frames (data.py:593-654 semantics are built on this by
  * the Python layer): for each of n_frames (clip, channel, start) triples,

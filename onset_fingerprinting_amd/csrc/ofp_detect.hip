@@ -69,8 +69,7 @@ struct Geom {
     int32_t C, B;
 };
 // The reference processes x[0:n_w] (init_minmax_tracker) and then restarts at x[0] with all
-// filter/follower/tracker state kept.  hp stream position v -> audio index / follower index:
-__host__ __device__ inline int64_t hp_src(const Geom& g, int64_t v) { return v < g.n_w ? v : v - g.n_w; }
+// filter/follower/tracker state kept.  hp stream position v -> follower index:
 __host__ __device__ inline int64_t hp_dst(const Geom& g, int64_t v) {
     return v < g.n_wb ? v : (v >= g.n_w ? v - g.n_w + g.n_wb : -1);
 }
@@ -314,55 +313,6 @@ __device__ __forceinline__ void walk_il2(const float* p0, int64_t n0, const floa
         const float* p = piece ? p1 : p0;
         const int64_t n = piece ? n1 : n0;
         if (n > 0) walk_il<CH, PB, EV>(p, n, rem, f);
-    }
-}
-
-// walk_il with a PLANAR output (the IIR stage on the caller's interleaved audio): PB 4-byte loads per batch, the
-// outputs of four steps leave as one 16-byte store (scalar steps until `op` is 16-byte aligned, and for the tail).
-template <int CH, int PB, class F>
-__device__ __forceinline__ void walk_il_out(const float* ip, float* op, int64_t n, F& f) {
-    while (n > 0 && (reinterpret_cast<uintptr_t>(op) & 15u)) {
-        *op++ = f(*ip);
-        ip += CH;
-        --n;
-    }
-    int64_t nb = n / PB;
-    int tail = (int)(n - nb * PB);
-    auto load = [&](float (&v)[PB]) {
-#pragma unroll
-        for (int i = 0; i < PB; ++i) v[i] = ip[i * CH];
-        ip += PB * CH;
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto run = [&](const float (&v)[PB]) {
-#pragma unroll
-        for (int i = 0; i < PB / 4; ++i) {
-            float4 o;
-            o.x = f(v[4 * i]); o.y = f(v[4 * i + 1]); o.z = f(v[4 * i + 2]); o.w = f(v[4 * i + 3]);
-            reinterpret_cast<float4*>(op)[i] = o;
-        }
-        op += PB;
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    float A[PB], Bv[PB];
-    if (nb >= 1) {
-        load(A);
-        nb -= 1;
-        while (nb >= 2) {
-            load(Bv); run(A);
-            load(A); run(Bv);
-            nb -= 2;
-        }
-        if (nb == 1) {
-            load(Bv); run(A);
-            run(Bv);
-        } else {
-            run(A);
-        }
-    }
-    for (; tail > 0; --tail) {
-        *op++ = f(*ip);
-        ip += CH;
     }
 }
 
@@ -1298,7 +1248,6 @@ __global__ __launch_bounds__(64) void k_mm_maxpass_il(MmArgs a, int64_t n_thread
 struct HpArgs {
     Geom g;
     const float* xt;  // planar audio [clip*C + c][N]
-    const float* x_il;  // or the caller's interleaved audio [clip][N][C] (kernels instantiated with CH = C: no planar copy)
     float* out;       // planar [clip*C + c][U]
     float b[5], a[5];
     int64_t L, W, n_chunks;
@@ -1306,37 +1255,9 @@ struct HpArgs {
 
 // positions [t0, t1) of the hp stream; the stream<->memory mapping is affine between the
 // breaks n_wb and n_w (detection.py:828-834: the tail of the warm-up passes the filter only)
-template <bool OUT, int CH = 0, class F>
+template <bool OUT, class F>
 __device__ __forceinline__ void hp_span(const HpArgs& a, F& f, int64_t chain, int64_t t0, int64_t t1) {
     int norem = -1;
-    if constexpr (CH > 0) {
-        // the caller's interleaved audio: stream position v is row v (v < n_w) or row v - n_w of the clip
-        constexpr int CHD = CH > 0 ? CH : 1;
-        const int64_t clip = chain / CHD;
-        const float* xs = a.x_il + clip * a.g.N * CH + (chain - clip * CH);
-        if (!OUT) {
-            if (t1 > t0) {
-                const int64_t n0 = max<int64_t>(min(t1, a.g.n_w) - t0, 0);
-                walk_il2<CH, 32, false>(xs + t0 * CH, n0, xs + (max(t0, a.g.n_w) - a.g.n_w) * CH, (t1 - t0) - n0, norem, f);
-            }
-            return;
-        }
-        float* os = a.out + chain * a.g.U;
-        int64_t p = t0;
-#pragma unroll 1
-        for (int i = 0; i < 3; ++i) {  // (pieces as below; each lies on one side of the restart at n_w)
-            const int64_t br = i == 0 ? a.g.n_wb : (i == 1 ? a.g.n_w : t1);
-            const int64_t e = min(max(br, p), t1);
-            if (e > p) {
-                const int64_t u = hp_dst(a.g, p);
-                const float* src = xs + hp_src(a.g, p) * CH;
-                if (u >= 0) walk_il_out<CH, 32>(src, os + u, e - p, f);
-                else walk_il<CH, 32, false>(src, e - p, norem, f);
-            }
-            p = e;
-        }
-        return;
-    }
     const float* xs = a.xt + chain * a.g.Nv;  // the stream itself (see u_src_planar)
     if (!OUT) {
         if (t1 > t0) walk<8, 0, false>(xs + t0, nullptr, t1 - t0, norem, f);
@@ -1390,7 +1311,6 @@ struct HpCand {
                       // the true start state joined at a sub-chunk boundary (the sub-chunks after it are written from
                       // that candidate's inner states by the next round's lanes), -1 none
     int early;        // whole runs stop at the first sub-chunk boundary where they have joined a candidate
-    unsigned long long* probe;  // diagnostics (OFP_HP_PROBE): per wave {start, end (s_memtime), HW_ID, XCC_ID}; else NULL
     __device__ __host__ int64_t slot(int64_t clip, int64_t k, int c, int r) const {
         return ((((clip * st.n_chunks + k) * st.g.C + c) * (R + 1)) + r) * 4;
     }
@@ -1414,8 +1334,6 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_candidates(HpCand a, int
         if (n_threads < 0) claim[threadIdx.x] = 1;  // never taken: keeps the allocation alive
     }
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long t_probe = 0;
-    if (a.probe) t_probe = __builtin_amdgcn_s_memtime();
     if (id >= n_threads) return;
     const HpArgs& st = a.st;
     // One lane = one RUN: it warms up over W samples before chunk j and then walks through `span`
@@ -1481,13 +1399,6 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_candidates(HpCand a, int
             for (int w = 0; w < 4; ++w) dst[w] = ofp_f2u(s.z[w]);
         }
     }
-    if (a.probe && (threadIdx.x & 63) == 0) {
-        unsigned long long* q = a.probe + 4 * (id >> 6);
-        q[0] = t_probe;
-        q[1] = __builtin_amdgcn_s_memtime();
-        q[2] = (unsigned)__builtin_amdgcn_s_getreg(63492);  // HW_REG_HW_ID: wave, simd, cu, sh, se ...
-        q[3] = (unsigned)__builtin_amdgcn_s_getreg(63508);  // HW_REG_XCC_ID
-    }
 }
 
 // ---- the same candidates in STAGES with duplicates removed between them (throughput setting).
@@ -1506,39 +1417,20 @@ struct HpRuns {
 };
 
 // stage 0: lane = (chain, chunk j, candidate r), r fastest: from its staggered start to window offset p1.
-// CH > 0 (all staged kernels and k_hp_run): the lanes read the caller's INTERLEAVED audio (hp_span<.., CH>), so the
-// channel is the fastest lane coordinate -- lane = (clip, chunk j, candidate r, channel) here, and the groups are
-// numbered (clip, j, channel) so that the work lists keep the channels of a chunk side by side: a wave's 4-byte loads
-// then cover whole 4 CH-byte rows.
-template <int CH>
 __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg0(HpCand a, HpRuns out, int32_t* __restrict__ off,
                                                               int32_t* __restrict__ cnt, int64_t p1, int64_t n_threads) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
     const HpArgs& st = a.st;
     int64_t q = id;
-    int r, c;
-    int64_t grp, j, chain, clip;
+    const int r = (int)(q % a.R);
+    q /= a.R;
+    const int64_t grp = q;
+    const int64_t j = q % st.n_chunks;
+    const int64_t chain = q / st.n_chunks;
     const int C = st.g.C;
-    constexpr int CHD = CH > 0 ? CH : 1;  // (divisor in the branches that are dead for CH = 0)
-    if (CH > 0) {
-        c = (int)(q % CHD);
-        q /= CHD;
-        r = (int)(q % a.R);
-        q /= a.R;
-        j = q % st.n_chunks;
-        clip = q / st.n_chunks;
-        chain = clip * CH + c;
-        grp = (clip * st.n_chunks + j) * CH + c;
-    } else {
-        r = (int)(q % a.R);
-        q /= a.R;
-        grp = q;
-        j = q % st.n_chunks;
-        chain = q / st.n_chunks;
-        clip = chain / C;
-        c = (int)(chain % C);
-    }
+    const int64_t clip = chain / C;
+    const int c = (int)(chain % C);
     if (r == 0) {
         const int64_t ci = (clip * st.n_chunks + j) * C + c;
         a.sel[ci] = (j == 0) ? 0 : -1;
@@ -1556,11 +1448,10 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg0(HpCand a, HpRuns ou
     if (a.delta == 0) s.z[0] = (float)r * 0.0009765625f;
     const int64_t w0 = j * st.L - st.W;
     const int64_t ws = max<int64_t>(w0 - (int64_t)r * a.delta, 0);
-    hp_span<false, CH>(st, s, chain, ws, max<int64_t>(w0 + p1, 0));
-    const int64_t li = CH > 0 ? grp * a.R + r : id;  // the runs of a group are neighbours in the list (k_hp_dedupe)
-    out.grp[li] = (int32_t)grp;
-    out.mask[li] = 1u << r;
-    out.z[li] = make_float4(s.z[0], s.z[1], s.z[2], s.z[3]);
+    hp_span<false>(st, s, chain, ws, max<int64_t>(w0 + p1, 0));
+    out.grp[id] = (int32_t)grp;  // the runs of a group are neighbours in the list (k_hp_dedupe)
+    out.mask[id] = 1u << r;
+    out.z[id] = make_float4(s.z[0], s.z[1], s.z[2], s.z[3]);
 }
 
 // between stages: 16 lanes per group, lane i holds run i of the group.  A run whose state equals (bitwise) that of
@@ -1611,36 +1502,32 @@ __global__ __launch_bounds__(256) void k_hp_dedupe(HpRuns in, HpRuns out, int32_
 }
 
 // a middle stage: lane = one distinct run, window offsets [p0, p1)
-template <int CH>
 __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg(HpCand a, HpRuns runs, const int* __restrict__ n_runs,
                                                              int64_t p0, int64_t p1) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= *n_runs) return;
     const HpArgs& st = a.st;
     const int64_t grp = runs.grp[id];
-    constexpr int CHD = CH > 0 ? CH : 1;  // (divisor in the branch that is dead for CH = 0)
-    const int64_t j = CH > 0 ? (grp / CHD) % st.n_chunks : grp % st.n_chunks;
-    const int64_t chain = CH > 0 ? grp / (CHD * st.n_chunks) * CH + grp % CHD : grp / st.n_chunks;
+    const int64_t j = grp % st.n_chunks;
+    const int64_t chain = grp / st.n_chunks;
     HpStep s;
     s.coeffs(st.b, st.a);
     const float4 v = runs.z[id];
     s.z[0] = v.x; s.z[1] = v.y; s.z[2] = v.z; s.z[3] = v.w;
     const int64_t w0 = j * st.L - st.W;
-    hp_span<false, CH>(st, s, chain, max<int64_t>(w0 + p0, 0), max<int64_t>(w0 + p1, 0));
+    hp_span<false>(st, s, chain, max<int64_t>(w0 + p0, 0), max<int64_t>(w0 + p1, 0));
     runs.z[id] = make_float4(s.z[0], s.z[1], s.z[2], s.z[3]);
 }
 
 // the last stage: the chunk itself, with the records of every slot the run stands for
-template <int CH>
 __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg_chunk(HpCand a, HpRuns runs, const int* __restrict__ n_runs) {
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= *n_runs) return;
     const HpArgs& st = a.st;
     const int64_t grp = runs.grp[id];
     const uint32_t mask = runs.mask[id];
-    constexpr int CHD = CH > 0 ? CH : 1;  // (divisor in the branch that is dead for CH = 0)
-    const int64_t k = CH > 0 ? (grp / CHD) % st.n_chunks : grp % st.n_chunks;
-    const int64_t chain = CH > 0 ? grp / (CHD * st.n_chunks) * CH + grp % CHD : grp / st.n_chunks;
+    const int64_t k = grp % st.n_chunks;
+    const int64_t chain = grp / st.n_chunks;
     const int C = st.g.C;
     const int64_t clip = chain / C;
     const int c = (int)(chain % C);
@@ -1665,7 +1552,7 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg_chunk(HpCand a, HpRu
     for (int sb = 0; sb < a.S; ++sb) {
         const int64_t t0 = min(start + sb * Ls, end);
         const int64_t t1 = sb == a.S - 1 ? end : min(start + (sb + 1) * Ls, end);
-        hp_span<false, CH>(st, s, chain, t0, t1);
+        hp_span<false>(st, s, chain, t0, t1);
         record(sb);
     }
 }
@@ -1924,7 +1811,6 @@ __global__ __launch_bounds__(64) void k_hp_resolve(HpCand a) {
 // a chunk that starts from an unmatched state (a break, guessed or not) or whose own slot is the
 // exact re-run has no such states and is run whole by lane 0.
 // -> true if the item left sub-chunks open (an early stop): another round is needed
-template <int CH>
 __device__ __forceinline__ bool hp_run_item(const HpCand& a, int64_t chain, int64_t k, int sb) {
     const HpArgs& st = a.st;
     const int C = st.g.C;
@@ -1976,7 +1862,7 @@ __device__ __forceinline__ bool hp_run_item(const HpCand& a, int64_t chain, int6
     for (int q = q0; q < q1; ++q) {
         const int64_t t0 = pieces ? min(start + q * Ls, end) : start;
         const int64_t t1 = (!pieces || q == a.S - 1) ? end : min(start + (q + 1) * Ls, end);
-        hp_span<true, CH>(st, s, chain, t0, t1);
+        hp_span<true>(st, s, chain, t0, t1);
         if (whole && q + 1 < q1) {
             const uint32_t z0 = ofp_f2u(s.z[0]), z1 = ofp_f2u(s.z[1]), z2 = ofp_f2u(s.z[2]), z3 = ofp_f2u(s.z[3]);
             for (int r = 0; r < a.R; ++r) {
@@ -2019,24 +1905,14 @@ __device__ __forceinline__ bool hp_run_item(const HpCand& a, int64_t chain, int6
     return joined >= 0;  // open sub-chunks: another round
 }
 
-template <int CH>
 __global__ __launch_bounds__(64) void k_hp_run(HpCand a, int64_t n_threads) {
     OFP_LATENCY_BOUND_KERNEL();
     if (a.prev && a.prev[0] + a.prev[1] == 0) return;
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    if (CH > 0) {  // lane = (clip, chunk, sub-chunk, channel): see k_hp_seg0
-        constexpr int CHD = CH > 0 ? CH : 1;
-        const int c = (int)(id % CHD);
-        const int64_t q = id / CHD;
-        const int sb = (int)(q % a.S);
-        const int64_t kc = q / a.S;
-        if (hp_run_item<CH>(a, kc / a.st.n_chunks * CH + c, kc % a.st.n_chunks, sb)) atomicAdd(a.counters + 1, 1);
-        return;
-    }
     const int sb = (int)(id % a.S);
     const int64_t kc = id / a.S;
-    if (hp_run_item<CH>(a, kc / a.st.n_chunks, kc % a.st.n_chunks, sb)) atomicAdd(a.counters + 1, 1);
+    if (hp_run_item(a, kc / a.st.n_chunks, kc % a.st.n_chunks, sb)) atomicAdd(a.counters + 1, 1);
 }
 
 // k_hp_run whose output leaves as complete lines (walk_lines; planar input; every position that matters a multiple of 32
@@ -3127,7 +3003,6 @@ struct Layout {
     bool merge;      // followers / tracker: the two recurrences of a chunk in one lane (k_*_both; saturated launches)
     bool hp_early;   // whole runs stop early at a sub-chunk boundary (k_hp_run)
     bool hp_staged;  // candidates in stages with duplicate runs removed between them (k_hp_seg*)
-    bool in_il;      // the IIR stage reads the caller's interleaved audio (no planar copy of the input is made)
     int64_t ar_L, ar_W, ar_Wc, ar_Wf, ar_chunks, ar_S;
     bool ar_sym;  // closed-form guess for the slow follower (k_ar_guess_sym)
     int64_t mm_L, mm_W, mm_chunks, mm_S;
@@ -3204,12 +3079,6 @@ Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t wa
         if (l.hp_W < 8192 || l.hp_R < 2) l.hp_staged = false;
         if (l.hp_staged) l.hp_span = 1;
     }
-    // The caller's interleaved audio instead of a planar copy (staged candidates, 4 or 8 channels, high-pass on: without it
-    // the dB pass reads the planar copy): only on request (tuning `interleaved` 2 / 3).  Measured, 48 C2 clips: the planar
-    // copy costs 8.9 GB per call, but a lane that walks an interleaved series issues one 4-byte load per step instead of
-    // one 16-byte load per four, and a wave's load instruction costs about as many cycles (~64) as the IIR step it feeds
-    // (~66): k_hp_seg_chunk 3.7 -> 7.9 ms, k_hp_seg 1.9 -> 5.3 ms alone, 183 -> 168 M frames/s in flight.
-    l.in_il = d->t.interleaved >= 2 && l.hp_staged && (g.C == 4 || g.C == 8) && p.hp_enabled;
     // sub-chunks: run in parallel once a chunk's start is verified (every candidate records its state at the inner
     // boundaries).  Long chunks (batches) get more of them, about 4096 samples each, and their whole runs from a
     // true start state stop at the first boundary where they have joined a candidate (k_hp_run, `early`): a break
@@ -3549,14 +3418,12 @@ const float* ofp_detect_planar_input(const ofp_detector* d, int64_t n_clips, int
                                      const void* d_ws) {
     if (!d || !d_ws || n_clips < 1 || n_samples < 0) return nullptr;
     const Layout l = make_layout(d, n_clips, n_samples, warm);
-    if (l.in_il) return nullptr;  // no planar copy in this layout: read the caller's own array
     return reinterpret_cast<const float*>(static_cast<const char*>(d_ws) + l.o_xt) + l.g.n_w;
 }
 
 int64_t ofp_detect_planar_stride(const ofp_detector* d, int64_t n_clips, int64_t n_samples, int64_t warm) {
     if (!d || n_clips < 1 || n_samples < 0) return -1;
-    const Layout l = make_layout(d, n_clips, n_samples, warm);
-    return l.in_il ? 0 : l.g.Nv;  // 0: no planar copy (see ofp_detect_planar_input)
+    return make_layout(d, n_clips, n_samples, warm).g.Nv;
 }
 
 int64_t ofp_detect_workspace_bytes(const ofp_detector* d, int64_t n_clips, int64_t n_samples,
@@ -3589,10 +3456,9 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
                          (long long)l.total);
     const Geom& g = l.g;
     const auto& p = d->p;
-    const bool host_verify = d->t.host_verify == 1;   // (2 / 3, experiments: the IIR stage only / the followers and the tracker only)
-    const bool hv_hp = host_verify || d->t.host_verify == 2, hv_fm = host_verify || d->t.host_verify == 3;
+    const bool host_verify = d->t.host_verify > 0;  // (2 / 3: aliases of 1 kept for old callers)
     const bool enqueue_only = run_mode == 1;
-    OFP_REQUIRE(!(enqueue_only && d->t.host_verify > 0), "ofp_detect_offline_enqueue: not with tuning host_verify (its passes are "
+    OFP_REQUIRE(!(enqueue_only && host_verify), "ofp_detect_offline_enqueue: not with tuning host_verify (its passes are "
                 "verified on the host)");
     unsigned char* ws = static_cast<unsigned char*>(d_ws);
     float* xt = reinterpret_cast<float*>(ws + l.o_xt);
@@ -3639,6 +3505,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
     const size_t tile_lds = (size_t)g.C * (l.tu + 4) * sizeof(float);
     const float* rel = dif;  // (the relative envelope overwrites the follower difference in place)
     // tracker, crossing pass and backtracking on the interleaved envelope (see k_mm_warm_il): the planar copy is not written
+    // (tuning interleaved < 0 or its alias 2: off)
     const bool mm_il = d->t.interleaved >= 0 && d->t.interleaved != 2 && l.merge && d_rel != nullptr && !p.manual &&
                        (g.C == 4 || g.C == 8 || g.C == 64);
     float* rel_warm = reinterpret_cast<float*>(ws + l.o_relw);
@@ -3798,13 +3665,11 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
             hipLaunchKernelGGL(k_zero, dim3((unsigned)cdiv(n16, 256)), dim3(256), 0, stream, reinterpret_cast<uint4*>(ws + l.o_zero), n16);
             OFP_LAUNCH_CHECK("k_zero");
         }
-        if (!l.in_il) {
-            const int64_t n_tiles = cdiv(N, l.tu);
-            const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * d->n_cus / n_clips));
-            hipLaunchKernelGGL(k_transpose_in, dim3(gx, (unsigned)n_clips), dim3(256), tile_lds,
-                               stream, d_x, xt, N, g.C, l.tu, g.n_w, g.Nv, n_tiles);
-            OFP_LAUNCH_CHECK("k_transpose_in");
-        }
+        const int64_t n_tiles = cdiv(N, l.tu);
+        const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * d->n_cus / n_clips));
+        hipLaunchKernelGGL(k_transpose_in, dim3(gx, (unsigned)n_clips), dim3(256), tile_lds,
+                           stream, d_x, xt, N, g.C, l.tu, g.n_w, g.Nv, n_tiles);
+        OFP_LAUNCH_CHECK("k_transpose_in");
         if (timed) OFP_HIP(hipEventRecord(ev[8], stream));
     }
     if (phase == 5) return OFP_OK;
@@ -3826,19 +3691,15 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         HpCand hc;
         hc.st.g = g;
         hc.st.xt = xt;
-        hc.st.x_il = d_x;
         hc.st.out = xdb;
-        const int ch = l.in_il ? g.C : 0;
-        const auto kseg0 = ch == 8 ? k_hp_seg0<8> : (ch == 4 ? k_hp_seg0<4> : k_hp_seg0<0>);
-        const auto kseg = ch == 8 ? k_hp_seg<8> : (ch == 4 ? k_hp_seg<4> : k_hp_seg<0>);
-        const auto kseg_chunk = ch == 8 ? k_hp_seg_chunk<8> : (ch == 4 ? k_hp_seg_chunk<4> : k_hp_seg_chunk<0>);
-        // complete-line stores for the output walk (k_hp_run_lines): throughput layout, planar input, every position that
-        // matters a multiple of 32 steps
-        const bool hp_lines = d->t.line_stores >= 0 && ch == 0 &&
-                              (l.merge || d->t.line_stores > 0 || chains * l.hp_chunks * l.hp_S >= (int64_t)2 * 64 * 4 * d->n_cus) &&  // (calls in flight, or a big one) (g.n_w & 31) == 0 && (g.n_wb & 31) == 0 &&
+        // complete-line stores for the output walk (k_hp_run_lines): throughput layout, every position that matters a
+        // multiple of 32 steps
+        const bool hp_lines = d->t.line_stores >= 0 &&
+                              (l.merge || d->t.line_stores > 0 || chains * l.hp_chunks * l.hp_S >= (int64_t)2 * 64 * 4 * d->n_cus) &&  // (calls in flight, or a big one)
+                              // NOT applied (they have only ever stood in a comment): (g.n_w & 31) == 0 && (g.n_wb & 31) == 0 &&
                               (g.V & 31) == 0 && (g.U & 31) == 0 && (g.Nv & 3) == 0 && (l.hp_L & 31) == 0 &&
                               ((l.hp_L / l.hp_S) & 31) == 0 && l.hp_L % l.hp_S == 0;
-        const auto krun = hp_lines ? k_hp_run_lines : (ch == 8 ? k_hp_run<8> : (ch == 4 ? k_hp_run<4> : k_hp_run<0>));
+        const auto krun = hp_lines ? k_hp_run_lines : k_hp_run;
         std::memcpy(hc.st.b, d->b, sizeof(hc.st.b));
         std::memcpy(hc.st.a, d->a, sizeof(hc.st.a));
         hc.st.L = l.hp_L;
@@ -3861,11 +3722,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         hc.early = l.hp_early ? 1 : 0;
         hc.counters = ctr.base;
         hc.pos = reinterpret_cast<int32_t*>(ws + l.o_hp_pos);
-        hc.probe = nullptr;
         hc.prev = nullptr;
-        const char* probe_path = (do_cand && timed) ? getenv("OFP_HP_PROBE") : nullptr;
-        const int64_t probe_waves = cdiv(chains * l.hp_chunks * (l.hp_R / l.hp_span), 64);
-        if (probe_path) OFP_HIP(hipMalloc(&hc.probe, probe_waves * 32));
         const int64_t nA = chains * l.hp_chunks * (hc.R / hc.span);
         const int64_t nM = chains * l.hp_chunks * (hc.R + 1);
         const int64_t nC = chains * l.hp_chunks * l.hp_S;
@@ -3895,7 +3752,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
             int32_t* goff = reinterpret_cast<int32_t*>(ws + l.o_hp_goff);
             int32_t* gcnt = goff + nC0;
             const unsigned full_grid = (unsigned)cdiv(n0, HP_CAND_THREADS);
-            hipLaunchKernelGGL(kseg0, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[0], goff, gcnt, cuts[0], n0);
+            hipLaunchKernelGGL(k_hp_seg0, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[0], goff, gcnt, cuts[0], n0);
             OFP_LAUNCH_CHECK("k_hp_seg0");
             int cur = 0;
             for (int m = 0; m < n_cuts; ++m) {
@@ -3904,10 +3761,10 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
                 cur ^= 1;
                 // (the grid is sized for the worst case, every run distinct; the lanes beyond the list leave at once)
                 if (m + 1 < n_cuts)
-                    hipLaunchKernelGGL(kseg, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
+                    hipLaunchKernelGGL(k_hp_seg, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
                                        (const int*)(stage_n + m), cuts[m], cuts[m + 1]);
                 else
-                    hipLaunchKernelGGL(kseg_chunk, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
+                    hipLaunchKernelGGL(k_hp_seg_chunk, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
                                        (const int*)(stage_n + m));
             }
             OFP_LAUNCH_CHECK("k_hp_dedupe / k_hp_seg / k_hp_seg_chunk");
@@ -3920,18 +3777,6 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
                 hipLaunchKernelGGL(k_hp_candidates<false>, dim3(cand_grid), dim3(HP_CAND_THREADS), 0, stream, hc, nA);
             OFP_LAUNCH_CHECK("k_hp_candidates");
             if (timed) OFP_HIP(hipEventRecord(ev[7], stream));
-            if (hc.probe) {  // diagnostics: where and when every wave of the launch ran (tools/wave_placement.py)
-                std::vector<unsigned long long> h(probe_waves * 4);
-                OFP_HIP(hipStreamSynchronize(stream));
-                OFP_HIP(hipMemcpy(h.data(), hc.probe, probe_waves * 32, hipMemcpyDeviceToHost));
-                (void)hipFree(hc.probe);
-                hc.probe = nullptr;
-                if (FILE* f = fopen(probe_path, "w")) {
-                    for (int64_t w = 0; w < probe_waves; ++w)
-                        fprintf(f, "%lld %llu %llu %llu %llu\n", (long long)w, h[4 * w], h[4 * w + 1], h[4 * w + 2], h[4 * w + 3]);
-                    fclose(f);
-                }
-            }
         }
         if (do_cand) {
             pend.hp_timed = timed;
@@ -3957,7 +3802,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         if (phase == 1 || phase == 6) return OFP_OK;
         if (l.hp_staged)
             OFP_HIP(hipMemcpyAsync(d->h_flags + 16, stage_n, 16 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (!hv_hp) {
+        if (!host_verify) {
             // A fixed number of rounds enqueued ahead, no host round trip: a round whose predecessor left nothing
             // open returns at once (a few microseconds).  The count follows what the detector's recent calls needed
             // (+2); the last round's counters are read with the final synchronisation, and a call that has not
@@ -4016,10 +3861,10 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         }
     }
     if (phase == 1 || phase == 6) return OFP_OK;  // (no high-pass: the head is the transpose alone)
-    pend.ahead = !hv_fm;
-    if (hv_fm || p.manual) pend.mm_nv = 0;
-    if (hv_fm) pend.ar_nv = 0;
-    if (!p.hp_enabled || hv_hp) pend.hp_rounds = 0;
+    pend.ahead = !host_verify;
+    if (host_verify || p.manual) pend.mm_nv = 0;
+    if (host_verify) pend.ar_nv = 0;
+    if (!p.hp_enabled || host_verify) pend.hp_rounds = 0;
     if (timed) OFP_HIP(hipEventRecord(ev[1], stream));
     ArArgs a;
     a.g = g;
@@ -4087,7 +3932,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
             hipLaunchKernelGGL(k_ar_warm, dim3(grid), dim3(64), 0, stream, a, nt, used);
             OFP_LAUNCH_CHECK("k_ar_warm");
         }
-        if (!hv_fm) {
+        if (!host_verify) {
             pend.ar_nv = l.ar_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, d->ar_pass_hint)) : 0;
             if (int rc = run_jacobi_ahead("follower stage", a.lines ? k_ar_chunk<true> : k_ar_chunk<false>, a, nt, l.ar_chunks, used, pass_flags, pend.ar_nv, stream))
                 return rc;
@@ -4175,7 +4020,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         const MmLight light = mm_il ? light_il : light_pl;
         const auto mm_chunk_k = mm_il ? (g.C == 8 ? k_mm_chunk_il<8> : (g.C == 64 ? k_mm_chunk_il<64> : k_mm_chunk_il<4>))
                                       : (l.merge ? k_mm_chunk_both : k_mm_chunk);
-        if (!hv_fm) {
+        if (!host_verify) {
             pend.mm_nv = l.mm_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, d->mm_pass_hint)) : 0;
             if (int rc = run_jacobi_ahead("tracker stage", mm_chunk_k, a,
                                           l.merge ? nt : 2 * 64 * cdiv(nt, 64), l.mm_chunks, used, pass_flags + AHEAD_MAX_PASSES,
@@ -4282,7 +4127,7 @@ static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64
         if (int rc = sequential_machine()) return rc;
     }
     if (int rc = backtrack()) return rc;
-    if (!hv_fm)
+    if (!host_verify)
         OFP_HIP(hipMemcpyAsync(d->h_flags + 96, pass_flags, 2 * AHEAD_MAX_PASSES * sizeof(int), hipMemcpyDeviceToHost, stream));
     if (timed) OFP_HIP(hipEventRecord(ev[6], stream));
     pend.valid = true;

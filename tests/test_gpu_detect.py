@@ -76,14 +76,13 @@ def test_c2_slice_default_tuning(det):
 def test_interleaved_layout_matches_planar_and_oracle(det, C, kw):
     """Throughput layout with 4 / 8 / 64 channels: tracker, crossing pass and backtracking read the caller's interleaved `rel`
     (warm-up rows from a buffer of their own; the joint falls inside a chunk), no planar copy of it is written; on request
-    (interleaved 2 / 3) the IIR stage reads the caller's interleaved audio, no planar copy of the input.  == the planar
-    layout == the oracle, bit for bit.  (Without the high-pass -- the B = 32 case -- the input side keeps its planar
-    copy: the dB pass reads it.)"""
+    (interleaved 2 / 3 are aliases kept for old callers: 2 = -1, 3 = 1).  == the planar layout == the oracle, bit for
+    bit."""
     x = synth.c2_drums(2.7, C, SR, seed=11 + C)[: 129_003]   # (not a whole number of blocks)
     for tuning in (dict(lane_merge=1, hp_dedupe=1), dict(lane_merge=1, mm_chunk=1999, mm_warm=5000, mm_span=3),
                    dict(lane_merge=1, hp_dedupe=1, interleaved=3), dict(lane_merge=1, hp_dedupe=1, interleaved=2),
-                   # the IIR stage on the interleaved audio (on request) with the restart of the stream (n_w) inside a
-                   # chunk and a sub-chunk; few candidates and a short warm-up: whole re-runs and early joins
+                   # the restart of the stream (n_w) inside a chunk and a sub-chunk; few candidates and a short warm-up:
+                   # whole re-runs and early joins
                    dict(hp_dedupe=1, hp_chunk=3072, hp_warm=8192, hp_candidates=4, hp_early=1, interleaved=3),
                    dict(hp_dedupe=1, hp_chunk=1001 * 4, hp_warm=9000, hp_candidate_offset=-1, interleaved=2),
                    dict(lane_merge=1, hp_dedupe=1, walk_through=-1),
@@ -368,14 +367,21 @@ def test_g18_python_backtracking_on_the_gpu(det):
 @pytest.mark.parametrize("host_verify", [0, 1])
 def test_hundreds_of_iir_verification_rounds_stay_exact(det, host_verify):
     """One candidate per chunk, no warm-up, tiny chunks: every chunk of the IIR stage is a break and a chain
-    advances one chunk per round: hundreds of rounds inside the chain-local kernel, or (host_verify) more rounds
-    than the call has counter slots, so slots are recycled.
+    advances one chunk per round, so the call needs hundreds of rounds.  The rounds enqueued ahead (at most
+    HP_MAX_ROUNDS = 16) cannot cover that: by default the completion's fall-back repeats the whole call with
+    host-verified rounds, and reports it.  Either way the host-verified form runs more rounds than the call has
+    counter slots, so slots are recycled.
     (Found by the 1 500-case sweep of round 2: a recycled, re-zeroed slot was read as the previous round's
     "nothing left" flag and the stage stopped early.)"""
     x = synth.drum_hits(2, 6.5, SR, seed=77, period=0.31)
     info, n = check_clip(det, x, tuning=dict(hp_chunk=1024, hp_warm=-1, hp_candidates=1, host_verify=host_verify),
                          block_size=128, sr=SR)
     assert info["hp_passes"] > 260 and n > 20
+    rv = info["repeated_host_verified"]   # (include/onsetfp.h, info[15]: 1 + 1 for the IIR rounds + 2 / + 4 ...)
+    if host_verify:
+        assert rv == 0
+    else:
+        assert rv > 0 and (rv - 1) & 1, rv   # the IIR stage did not converge ahead: the whole call was repeated
 
 
 @pytest.mark.parametrize("tuning", [None, dict(lane_merge=1, hp_dedupe=1, hp_early=1), dict(host_verify=-2), dict(host_verify=-3),

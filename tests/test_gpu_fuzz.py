@@ -71,9 +71,9 @@ def random_case(rng):
     if rng.random() < 0.3:
         tuning["scan_skip"] = -1   # the crossing pass reads every block (default: blocks that cannot matter are skipped)
     if rng.random() < 0.25:
-        tuning["host_verify"] = 1   # the host-verified pass groups of rounds 1-2 (default: chain-local kernels)
+        tuning["host_verify"] = 1   # passes verified on the host group by group (default: enqueued ahead, gated on the device)
     if rng.random() < 0.3:
-        tuning["interleaved"] = int(rng.choice([-1, 2, 3]))  # planar copies throughout / the IIR stage on the interleaved audio too
+        tuning["interleaved"] = int(rng.choice([-1, 1]))  # a planar copy of `rel` throughout / the tracker on the interleaved `rel`
     if rng.random() < 0.3:
         tuning["line_stores"] = -1  # lane-private 16-byte stores in the output walks (default in the merged layout: complete lines)
     if rng.random() < 0.3:

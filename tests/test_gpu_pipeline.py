@@ -93,9 +93,9 @@ def test_result_is_independent_of_time_parallel_tuning_and_idempotent(mods):
                    dict(lane_merge=1, hp_early=1, hp_candidates=2, hp_warm=6000, hp_chunk=4096),   # ... with many breaks
                    dict(lane_merge=1, walk_through=-1),  # every chunk through the chunk pass (default: walk-through chunks are pass 0)
                    dict(lane_merge=1, ar_span=8, mm_span=4, ar_chunk=8192, mm_chunk=8192),
-                   dict(lane_merge=1, interleaved=-1),   # planar copies of `rel` and the input throughout
-                   dict(lane_merge=1, hp_dedupe=1, interleaved=3),  # ... and none at all: every stage on the caller's arrays
-                   dict(hp_dedupe=1, interleaved=2, hp_chunk=8192, hp_warm=12000, hp_candidates=4),
+                   dict(lane_merge=1, interleaved=-1),   # a planar copy of `rel` throughout
+                   dict(lane_merge=1, hp_dedupe=1, interleaved=3),  # the old-caller aliases: 3 = 1 (the `rel` side) ...
+                   dict(hp_dedupe=1, interleaved=2, hp_chunk=8192, hp_warm=12000, hp_candidates=4),  # ... and 2 = -1
                    dict(concurrent_calls=64),
                    None):
         bd = detection.BatchDetector(8, 256, sr=SR)
@@ -112,10 +112,12 @@ def test_result_is_independent_of_time_parallel_tuning_and_idempotent(mods):
             assert got[2] == ref[2] and np.array_equal(got[0], ref[0]) and np.array_equal(bits(got[1]), bits(ref[1]))
 
 
-def test_pipeline_without_planar_copies_gives_the_same_bytes(mods):
-    """With the detector on the caller's interleaved audio (tuning interleaved 3) there is no planar copy for the
-    spectral branch either: `planar_input` is None and the STFT takes its interleaved sliding form.  Records, `rel`,
-    |X|^2, mel and logits equal the default pipeline's, byte for byte (4 and 8 channels)."""
+def test_pipeline_with_interleaved_rel_alias_gives_the_same_bytes(mods):
+    """Tuning interleaved 3 (kept as an alias of 1 for old callers: the tracker on the caller's interleaved `rel`) still
+    leaves the planar copy of the input for the spectral branch.  Records, `rel`, |X|^2, mel and logits equal the
+    default pipeline's, byte for byte (4 and 8 channels); so do |X|^2, mel and logits of the fused STFT in its
+    interleaved sliding form on the caller's array (no planar copy: the form for callers without a detector)."""
+    from onset_fingerprinting_amd.data import stft_power_mel_mlp_dense
     from onset_fingerprinting_amd.pipeline import FingerprintPipeline
     for C, gen in ((8, lambda i: synth.c2_drums(4.0, 8, SR, seed=40 + i)), (4, lambda i: synth.c4_clip(i, 4.0, 4, SR))):
         x = torch.from_numpy(np.stack([gen(i) for i in range(3)])).cuda().contiguous()
@@ -123,7 +125,7 @@ def test_pipeline_without_planar_copies_gives_the_same_bytes(mods):
         for tuning in (dict(lane_merge=1, hp_dedupe=1), dict(lane_merge=1, hp_dedupe=1, interleaved=3)):
             pipe = FingerprintPipeline(C, 1024, 256, SR, 40)
             pipe.detector.set_tuning(**tuning)
-            assert (pipe.detector.planar_input(x) is None) == (tuning.get("interleaved") == 3)
+            assert pipe.detector.planar_input(x) is not None
             o = pipe.run(x)
             torch.cuda.synchronize()
             outs.append({k: o[k].clone() for k in ("records", "counts", "rel", "power", "mel", "logits")})
@@ -133,6 +135,12 @@ def test_pipeline_without_planar_copies_gives_the_same_bytes(mods):
             assert torch.equal(outs[0]["records"][i, :int(n[i])], outs[1]["records"][i, :int(n[i])])
         for k in ("rel", "power", "mel", "logits"):
             assert torch.equal(outs[0][k], outs[1][k]), k
+        assert pipe._mlp is not None
+        power, mel, logits = stft_power_mel_mlp_dense(x, pipe.n_fft, pipe.hop, pipe.mel, pipe._mlp, want_power=True,
+                                                      want_mel=True, planar=None)
+        torch.cuda.synchronize()
+        for k, v in (("power", power), ("mel", mel), ("logits", logits)):
+            assert torch.equal(outs[0][k], v), k
 
 
 def test_c2_at_full_size_matches_the_oracle_bit_for_bit(mods):
