@@ -2994,6 +2994,12 @@ constexpr int HP_MAX_ROUNDS = 16;     // IIR verification rounds enqueued ahead,
 constexpr int AHEAD_MAX_PASSES = 24;  // follower / tracker: verifying passes enqueued ahead, at most (light groups count as one)
 constexpr int OFP_N_COUNTERS = 512;  // int slots at the head of the zeroed region
 
+// The stages of one call, in the order they are enqueued (see run)
+enum Stage { HEAD, CANDIDATES, ROUNDS, FOLLOWERS, TRACKER, END };
+
+// The plan of one call: the work-space layout and every kernel-variant decision, made here from the detector's
+// parameters, its tuning and the call's sizes.  The byte offsets do not depend on `rel` (ofp_detect_workspace_bytes and
+// the planar-input queries do not know it).
 struct Layout {
     Geom g;
     int64_t nb;
@@ -3007,6 +3013,25 @@ struct Layout {
     bool ar_sym;  // closed-form guess for the slow follower (k_ar_guess_sym)
     int64_t mm_L, mm_W, mm_chunks, mm_S;
     int tu;  // time steps per transpose tile
+    // kernel variants
+    bool hp_lines;      // IIR output walk with complete-line stores (k_hp_run_lines instead of k_hp_run)
+    bool hp_spread;     // k_hp_candidates<true>: the launch has no more workgroups than the chip has CUs
+    int n_cuts = 0;     // staged candidates: window offsets at which duplicates are removed (the last one is the chunk start)
+    int64_t cuts[16] = {};
+    bool ar_through;    // followers: walk-through chunks as their own pass 0 (k_ar_warm_both)
+    bool ar_lines;      // followers: complete-line stores (k_ar_warm_both<true>, k_ar_chunk<true>)
+    bool db_sym;        // the dB pass also forms the per-chunk sums of the closed-form guess (k_rect_db_sym)
+    bool mm_il;         // tracker, crossing pass and backtracking on the caller's interleaved `rel` (k_*_il)
+    bool mm_through;    // tracker: walk-through chunks as their own pass 0 (k_mm_warm_il)
+    bool use_sum;       // block extremes for the crossing pass (k_rel_out -> k_block_scan)
+    // verification
+    bool host_verify;   // passes verified on the host (run_jacobi, one synchronisation per group), not enqueued ahead
+    int hp_group;       // host-verified IIR rounds per synchronisation (0: three, then two)
+    int verify_group;   // host-verified follower / tracker passes per synchronisation
+    int max_passes;     // host-verified passes / rounds before giving up (0: no limit)
+    Stage forced_from;  // test hooks host_verify -2 / -3 / -4: the completion repeats the call from HEAD / FOLLOWERS /
+                        // TRACKER on (END: no hook)
+    bool sm_force_sequential;  // test hook sm_segments 2: the sequential machine decides after the segmented one
     // byte offsets
     int64_t o_xt, o_xdb, o_dif, o_relw, o_hp_U, o_hp_E, o_hp_sel, o_hp_done, o_hp_M, o_hp_nxt, o_hp_guess, o_hp_ran, o_hp_gs, o_hp_pos, o_hp_mrg, o_hp_runs, o_hp_goff, o_hp_stage_n, o_ar_state, o_ar_P, o_mm_state, o_mm_dirty, o_hp_rounds, o_pass_flags, o_sum,
         o_thr_mn, o_thr_mx, o_first, o_last, o_vflag, o_pc, o_visj, o_vrec, o_nv, o_vtile, o_ltile, o_smseg, o_flags, o_zero, zero_bytes, total;
@@ -3015,7 +3040,8 @@ struct Layout {
 int64_t pick(int64_t user, int64_t dflt) { return user > 0 ? user : dflt; }
 int64_t pick_warm(int64_t user, int64_t dflt) { return user > 0 ? user : (user < 0 ? 0 : dflt); }
 
-Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t warm) {
+// rel: the call writes the relative envelope (d_rel != NULL)
+Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t warm, bool rel = false) {
     Layout l;
     const auto& p = d->p;
     Geom& g = l.g;
@@ -3144,6 +3170,77 @@ Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t wa
     l.ar_S = l.ar_sym ? pick_span(d->t.ar_span, l.ar_W, l.ar_L, l.ar_chunks, 16.0) : 1;
     l.mm_S = pick_span(d->t.mm_span, l.mm_W, l.mm_L, l.mm_chunks, 11.0);
     l.tu = (int)std::max<int64_t>(1, std::min<int64_t>(256, 8192 / g.C));
+
+    // IIR output walk with complete-line stores (k_hp_run_lines): the throughput layout (calls in flight, or a big
+    // call), and every position that matters a multiple of 32 steps -- a batch of 32 outputs lies inside one of the
+    // three regions of the stream (hp_dst: warm-up rows, the dropped gap up to n_w, the rest) and starts in one chunk
+    // and sub-chunk
+    l.hp_lines = d->t.line_stores >= 0 &&
+                 (l.merge || d->t.line_stores > 0 || chains * l.hp_chunks * l.hp_S >= (int64_t)2 * 64 * 4 * d->n_cus) &&
+                 (g.n_w & 31) == 0 &&
+                 (g.n_wb & 31) == 0 &&
+                 (g.V & 31) == 0 &&
+                 (g.U & 31) == 0 &&
+                 (g.Nv & 3) == 0 &&
+                 (l.hp_L & 31) == 0 &&
+                 ((l.hp_L / l.hp_S) & 31) == 0 &&
+                 l.hp_L % l.hp_S == 0;
+    // k_hp_candidates<SPREAD>: a lone call whose candidates launch fits one workgroup per CU
+    l.hp_spread = (int64_t)(unsigned)cdiv(chains * l.hp_chunks * (l.hp_R / l.hp_span), HP_CAND_THREADS) <= d->n_cus &&
+                  d->t.concurrent_calls <= 1;
+    if (l.hp_staged) {
+        // (the runs of a group merge fastest early on: 8 -> 4.8 distinct within 8 192 steps, -> 2.2 by 24 576)
+        for (int64_t c = 4096; c < l.hp_W && l.n_cuts < 15; c += (c < 8192 ? 4096 : (c < 40960 ? 8192 : 16384)))
+            l.cuts[l.n_cuts++] = c;
+        l.cuts[l.n_cuts++] = l.hp_W;
+    }
+    // walk-through chunks as the followers' pass 0 (k_ar_warm_both): the merged layout with the closed-form guess and
+    // 16-byte-congruent buffers
+    l.ar_through = d->t.walk_through >= 0 &&
+                   l.merge &&
+                   l.ar_sym &&
+                   (g.U & 3) == 0 &&
+                   (l.ar_L & 3) == 0;
+    // complete-line stores for the followers' output walks (walk_lines): the throughput layout, everything a multiple of
+    // 32 steps
+    l.ar_lines = d->t.line_stores >= 0 &&
+                 (l.ar_through || d->t.line_stores > 0 || chains * l.ar_chunks >= (int64_t)32 * 4 * d->n_cus) &&
+                 (g.U & 31) == 0 &&
+                 (l.ar_L & 31) == 0;
+    // dB and the per-chunk sums of the closed-form guess in one pass (k_rect_db_sym) whenever both are wanted and the
+    // geometry allows 16-byte groups (otherwise k_rect_db, then k_ar_sym_local reading the dB stream once more)
+    l.db_sym = d->t.fuse_db_sums >= 0 &&
+               l.ar_sym &&
+               p.hp_enabled &&
+               (g.U & 3) == 0 &&
+               (l.ar_L & 3) == 0;
+    // tracker, crossing pass and backtracking on the caller's interleaved envelope (see k_mm_warm_il; the planar copy is
+    // not written): the throughput layout with `rel` requested, relative thresholds, the instantiated channel counts
+    // (tuning interleaved < 0 or its alias 2: off)
+    l.mm_il = d->t.interleaved >= 0 &&
+              d->t.interleaved != 2 &&
+              l.merge &&
+              rel &&
+              !p.manual &&
+              (g.C == 4 || g.C == 8 || g.C == 64);
+    l.mm_through = l.mm_il && d->t.walk_through >= 0;
+    // block extremes for the crossing pass: whenever the 16-byte path of k_rel_out is taken for every tile (the same
+    // conditions as in the kernel) and a group of four never straddles two blocks
+    l.use_sum = d->t.scan_skip >= 0 &&
+                (g.U & 3) == 0 &&
+                (l.tu & 3) == 0 &&
+                ((g.n_wb * g.C) & 3) == 0 &&
+                (((int64_t)l.tu * g.C) & 3) == 0 &&
+                ((g.Nm * g.C) & 3) == 0 &&
+                (g.B & 3) == 0 &&
+                g.B >= 32;
+    l.host_verify = d->t.host_verify > 0;  // (2 / 3: aliases of 1 kept for old callers)
+    l.hp_group = d->t.verify_group > 0 ? (int)std::min<int64_t>(d->t.verify_group, 8) : 0;
+    l.verify_group = d->t.verify_group > 0 ? (int)d->t.verify_group : 2;
+    l.max_passes = d->t.max_passes;
+    l.forced_from = d->t.host_verify == -2 ? HEAD : (d->t.host_verify == -3 ? FOLLOWERS : (d->t.host_verify <= -4 ? TRACKER : END));
+    l.sm_force_sequential = d->t.sm_segments == 2;
+
     int64_t o = 0;
     auto take = [&](int64_t bytes) {
         int64_t r = o;
@@ -3324,6 +3421,689 @@ int run_jacobi_ahead(const char* name, K chunk, const A& args, int64_t n_threads
     return OFP_OK;
 }
 
+
+// One call of the offline detector: its arguments, plan, work-space arrays and stream.  `rec` is what its stages leave
+// for the completion: the detector's pending record, or the completion's own copy when it repeats a part of the call.
+struct Call {
+    ofp_detector* d;
+    Layout l;
+    const float* x;
+    ofp_detect_args a;
+    unsigned char* ws;
+    hipStream_t stream;
+    bool timed;  // stage times by HIP events (not while the stream is capturing: an event recorded into a graph has no time)
+    ofp_detect_pending* rec;
+    Counters ctr;
+    float *xt, *xdb, *dif, *rel_warm;  // (the relative envelope overwrites the follower difference `dif` in place)
+    uint32_t *sum_max, *sum_minv;      // block extremes for the crossing pass, or NULL (Layout::use_sum)
+    template <class T>
+    T* at(int64_t off) const { return reinterpret_cast<T*>(ws + off); }
+    int64_t chains() const { return a.n_clips * l.g.C; }
+    size_t tile_lds() const { return (size_t)l.g.C * (l.tu + 4) * sizeof(float); }
+};
+
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// The checks every entry point makes, the plan and the work-space arrays.  may_capture: the entry point only enqueues
+// (the stream may be capturing a hipGraph).
+int open_call(Call& c, ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm, float* d_rel,
+              ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws, int64_t ws_bytes, void* stream,
+              bool may_capture) {
+    OFP_REQUIRE(d && d_counts && d_ws, "ofp_detect_offline: NULL argument");
+    OFP_REQUIRE(n_clips >= 1 && N >= 0 && cap >= 0, "ofp_detect_offline: bad sizes");
+    OFP_REQUIRE(d_x || N == 0, "ofp_detect_offline: d_x is NULL");
+    OFP_REQUIRE(d_records || cap == 0, "ofp_detect_offline: d_records is NULL");
+    OFP_REQUIRE(n_clips <= 65535, "ofp_detect_offline: at most 65535 clips per call");
+    c.l = make_layout(d, n_clips, N, warm, d_rel != nullptr);
+    const Layout& l = c.l;
+    if (ws_bytes < l.total)
+        return ofp::fail(OFP_ERR_WORKSPACE, "work space %lld < required %lld bytes", (long long)ws_bytes, (long long)l.total);
+    c.d = d; c.x = d_x; c.rec = &d->pend;
+    c.a = ofp_detect_args{n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes};
+    c.ws = static_cast<unsigned char*>(d_ws);
+    c.stream = (hipStream_t)stream;
+    c.timed = !capturing(c.stream);
+    OFP_REQUIRE(c.timed || may_capture, "ofp_detect_offline: the stream is capturing; use ofp_detect_offline_enqueue");
+    c.ctr = Counters{c.at<int>(l.o_flags), 0, c.stream};
+    c.xt = c.at<float>(l.o_xt); c.xdb = c.at<float>(l.o_xdb); c.dif = c.at<float>(l.o_dif); c.rel_warm = c.at<float>(l.o_relw);
+    c.sum_max = l.use_sum ? c.at<uint32_t>(l.o_sum) : nullptr;
+    c.sum_minv = l.use_sum ? c.sum_max + n_clips * l.nb * l.g.C : nullptr;
+    return OFP_OK;
+}
+
+// The interleaved kernels are instantiated for 4, 8 and 64 channels (Layout::mm_il): f(std::integral_constant<int, C>)
+template <class F>
+auto with_il_channels(int C, F f) {
+    if (C == 8) return f(std::integral_constant<int, 8>());
+    if (C == 64) return f(std::integral_constant<int, 64>());
+    return f(std::integral_constant<int, 4>());
+}
+
+// --- head: the counters region zeroed (see make_layout; regions are 256-byte multiples), the planar copy of the input
+int head(Call& c) {
+    const Layout& l = c.l;
+    const Geom& g = l.g;
+    if (c.timed) OFP_HIP(hipEventRecord(c.d->ev[0], c.stream));
+    const int64_t n16 = l.zero_bytes / 16;
+    hipLaunchKernelGGL(k_zero, dim3((unsigned)cdiv(n16, 256)), dim3(256), 0, c.stream, c.at<uint4>(l.o_zero), n16);
+    OFP_LAUNCH_CHECK("k_zero");
+    const int64_t n_tiles = cdiv(g.N, l.tu);
+    const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * c.d->n_cus / c.a.n_clips));
+    hipLaunchKernelGGL(k_transpose_in, dim3(gx, (unsigned)c.a.n_clips), dim3(256), c.tile_lds(), c.stream, c.x, c.xt, g.N,
+                       g.C, l.tu, g.n_w, g.Nv, n_tiles);
+    OFP_LAUNCH_CHECK("k_transpose_in");
+    if (c.timed) OFP_HIP(hipEventRecord(c.d->ev[8], c.stream));
+    return OFP_OK;
+}
+
+HpCand hp_cand(const Call& c) {
+    const Layout& l = c.l;
+    HpCand hc;
+    hc.st.g = l.g;
+    hc.st.xt = c.xt; hc.st.out = c.xdb;
+    std::memcpy(hc.st.b, c.d->b, sizeof(hc.st.b));
+    std::memcpy(hc.st.a, c.d->a, sizeof(hc.st.a));
+    hc.st.L = l.hp_L; hc.st.W = l.hp_W; hc.st.n_chunks = l.hp_chunks;
+    hc.R = l.hp_R; hc.delta = l.hp_delta; hc.span = l.hp_span; hc.S = l.hp_S; hc.early = l.hp_early ? 1 : 0;
+    hc.U = c.at<uint32_t>(l.o_hp_U); hc.E = c.at<uint32_t>(l.o_hp_E); hc.M = c.at<uint32_t>(l.o_hp_M);
+    hc.sel = c.at<int8_t>(l.o_hp_sel); hc.ran = c.at<int8_t>(l.o_hp_ran); hc.gs = c.at<int8_t>(l.o_hp_gs);
+    hc.mrg = c.at<int8_t>(l.o_hp_mrg);
+    hc.done = c.at<uint8_t>(l.o_hp_done); hc.nxt = c.at<uint8_t>(l.o_hp_nxt); hc.guessed = c.at<uint8_t>(l.o_hp_guess);
+    hc.pos = c.at<int32_t>(l.o_hp_pos);
+    hc.counters = c.ctr.base; hc.prev = nullptr;
+    return hc;
+}
+
+// --- IIR candidates: one speculative launch, or the staged launches with duplicate runs removed between them
+int iir_candidates(Call& c) {
+    const Layout& l = c.l;
+    if (!c.d->p.hp_enabled) return OFP_OK;
+    const HpCand hc = hp_cand(c);
+    const int64_t chains = c.chains();
+    const int64_t nC0 = chains * l.hp_chunks;
+    ofp_detect_pending& rec = *c.rec;
+    int64_t steps = 0;
+    if (l.hp_staged) {
+        const int64_t n0 = nC0 * hc.R;
+        OFP_REQUIRE(n0 < (1ll << 31), "ofp_detect_offline: %lld speculative runs in one call", (long long)n0);
+        HpRuns rl[2];
+        // layout of the two lists: z (16 B) of both first, then grp, then mask
+        unsigned char* rb = c.ws + l.o_hp_runs;
+        rl[0].z = reinterpret_cast<float4*>(rb);
+        rl[1].z = reinterpret_cast<float4*>(rb + n0 * 16);
+        rl[0].grp = reinterpret_cast<int32_t*>(rb + n0 * 32);
+        rl[1].grp = reinterpret_cast<int32_t*>(rb + n0 * 36);
+        rl[0].mask = reinterpret_cast<uint32_t*>(rb + n0 * 40);
+        rl[1].mask = reinterpret_cast<uint32_t*>(rb + n0 * 44);
+        int32_t* goff = c.at<int32_t>(l.o_hp_goff);
+        int32_t* gcnt = goff + nC0;
+        int* stage_n = c.at<int>(l.o_hp_stage_n);
+        const unsigned full_grid = (unsigned)cdiv(n0, HP_CAND_THREADS);
+        hipLaunchKernelGGL(k_hp_seg0, dim3(full_grid), dim3(HP_CAND_THREADS), 0, c.stream, hc, rl[0], goff, gcnt, l.cuts[0], n0);
+        OFP_LAUNCH_CHECK("k_hp_seg0");
+        int cur = 0;
+        for (int m = 0; m < l.n_cuts; ++m) {
+            hipLaunchKernelGGL(k_hp_dedupe, dim3((unsigned)cdiv(nC0 * 16, 256)), dim3(256), 0, c.stream, rl[cur], rl[cur ^ 1],
+                               goff, gcnt, nC0, stage_n + m);
+            cur ^= 1;
+            // (the grid is sized for the worst case, every run distinct; the lanes beyond the list leave at once)
+            if (m + 1 < l.n_cuts)
+                hipLaunchKernelGGL(k_hp_seg, dim3(full_grid), dim3(HP_CAND_THREADS), 0, c.stream, hc, rl[cur],
+                                   (const int*)(stage_n + m), l.cuts[m], l.cuts[m + 1]);
+            else
+                hipLaunchKernelGGL(k_hp_seg_chunk, dim3(full_grid), dim3(HP_CAND_THREADS), 0, c.stream, hc, rl[cur],
+                                   (const int*)(stage_n + m));
+        }
+        OFP_LAUNCH_CHECK("k_hp_dedupe / k_hp_seg / k_hp_seg_chunk");
+        // IIR steps of stage 0 here; the later stages once their run counts are on the host (completion)
+        for (int64_t j = 0; j < l.hp_chunks; ++j)
+            for (int r = 0; r < hc.R; ++r)
+                steps += std::max<int64_t>(j * l.hp_L - l.hp_W + l.cuts[0], 0) -
+                         std::max<int64_t>(j * l.hp_L - l.hp_W - r * hc.delta, 0);
+    } else {
+        const int64_t nA = chains * l.hp_chunks * (hc.R / hc.span);
+        hipLaunchKernelGGL(l.hp_spread ? k_hp_candidates<true> : k_hp_candidates<false>,
+                           dim3((unsigned)cdiv(nA, HP_CAND_THREADS)), dim3(HP_CAND_THREADS), 0, c.stream, hc, nA);
+        OFP_LAUNCH_CHECK("k_hp_candidates");
+        // IIR steps this launch executes over all its lanes (the speculation's redundant work)
+        for (int64_t j = 0; j < l.hp_chunks; ++j) {
+            const int64_t run_end = std::min<int64_t>((j + hc.span) * l.hp_L, l.g.V);
+            for (int r = 0; r < hc.R / hc.span; ++r)
+                steps += run_end - std::max<int64_t>(j * l.hp_L - l.hp_W - r * hc.delta, 0);
+        }
+    }
+    if (c.timed) OFP_HIP(hipEventRecord(c.d->ev[7], c.stream));
+    rec.hp_timed = c.timed;
+    rec.staged = l.hp_staged;
+    rec.n_cuts = l.n_cuts;
+    std::memcpy(rec.cuts, l.cuts, sizeof(rec.cuts));
+    rec.info[12] = steps * chains;
+    return OFP_OK;
+}
+
+// one IIR verification round: the candidates matched against the chunk ends, the chains resolved, the chunks whose
+// start is now known walked again; `prev`: the preceding round's counters (both zero: this round returns at once)
+void iir_round(const Call& c, HpCand& hc, int* counters, const int* prev) {
+    const int64_t nM = c.chains() * c.l.hp_chunks * (hc.R + 1);
+    const int64_t nC = c.chains() * c.l.hp_chunks * c.l.hp_S;
+    hc.counters = counters;
+    hc.prev = prev;
+    hipLaunchKernelGGL(k_hp_match, dim3((unsigned)cdiv(nM, 256)), dim3(256), 0, c.stream, hc, nM);
+    hipLaunchKernelGGL(k_hp_resolve, dim3((unsigned)c.chains()), dim3(64), 0, c.stream, hc);
+    hipLaunchKernelGGL(c.l.hp_lines ? k_hp_run_lines : k_hp_run, dim3((unsigned)cdiv(nC, 64)), dim3(64), 0, c.stream, hc, nC);
+}
+
+// --- IIR verification rounds
+int iir_rounds(Call& c, bool host_verified) {
+    const Layout& l = c.l;
+    if (!c.d->p.hp_enabled) return OFP_OK;
+    HpCand hc = hp_cand(c);
+    ofp_detect_pending& rec = *c.rec;
+    int* h_flags = c.d->h_flags;
+    const int64_t nC0 = c.chains() * l.hp_chunks;
+    if (l.hp_staged)
+        OFP_HIP(hipMemcpyAsync(h_flags + 16, c.at<int>(l.o_hp_stage_n), 16 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    hipLaunchKernelGGL(k_hp_plurality, dim3((unsigned)cdiv(nC0 * 16, 256)), dim3(256), 0, c.stream, hc, nC0);
+    OFP_LAUNCH_CHECK("k_hp_plurality");
+    if (!host_verified) {
+        // A fixed number of rounds enqueued ahead, no host round trip: a round whose predecessor left nothing
+        // open returns at once (a few microseconds).  The count follows what the detector's recent calls needed
+        // (+2); the last round's counters are read with the final synchronisation, and a call that has not
+        // converged by then (never seen with the margin) is repeated in the host-verified form.
+        const int NR = std::max(3, std::min(HP_MAX_ROUNDS, c.d->hp_rounds_hint));
+        int* cnt = c.at<int>(l.o_hp_rounds);
+        for (int q = 0; q < NR; ++q) iir_round(c, hc, cnt + 2 * q, q > 0 ? cnt + 2 * (q - 1) : nullptr);
+        OFP_LAUNCH_CHECK("k_hp_match / k_hp_resolve / k_hp_run");
+        rec.hp_rounds = NR;
+        OFP_HIP(hipMemcpyAsync(h_flags + 64, cnt, 2 * NR * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+        return OFP_OK;
+    }
+    // Verification rounds are enqueued a group at a time (three, then two) with ONE host synchronisation
+    // per group; a round whose predecessor left nothing unresolved returns at once (HpCand::prev).
+    const int* last = nullptr;
+    for (int it = 0;;) {
+        const int G = l.hp_group > 0 ? l.hp_group : (it == 0 ? 3 : 2);
+        int* cnt = nullptr;
+        if (int rc = c.ctr.take(2 * G, &cnt)) return rc;
+        // (a call that needs hundreds of rounds recycles the last counter slots, which are zeroed again: the
+        //  previous round's counters may be among them and would then read "nothing left" -- no skip check then)
+        if (cnt == c.ctr.base + OFP_N_COUNTERS - 16) last = nullptr;
+        for (int q = 0; q < G; ++q) {
+            iir_round(c, hc, cnt + 2 * q, last);
+            last = cnt + 2 * q;
+        }
+        OFP_LAUNCH_CHECK("k_hp_match / k_hp_resolve / k_hp_run");
+        // per round: chains stuck at a break, chains with unverified guesses
+        OFP_HIP(hipMemcpyAsync(h_flags, cnt, 2 * G * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+        OFP_HIP(hipStreamSynchronize(c.stream));
+        int stuck = 0;
+        for (int q = 0; q < G; ++q) {
+            stuck = h_flags[2 * q] + h_flags[2 * q + 1];
+            rec.info[0] += 1;
+            rec.info[3] += stuck;
+            if (stuck == 0) break;
+        }
+        it += G;
+        if (stuck == 0) break;
+        if (l.max_passes > 0 && it > l.max_passes)
+            return ofp::fail(OFP_ERR_NOCONVERGE, "hp stage: %d chains still unresolved after %d rounds", stuck, it);
+    }
+    return OFP_OK;
+}
+
+ArArgs ar_args(const Call& c) {
+    const Layout& l = c.l;
+    const auto& p = c.d->p;
+    ArArgs a;
+    a.g = l.g;
+    a.xdb = c.xdb; a.dif = c.dif;
+    a.fa = p.fast_attack; a.fr = p.fast_release; a.sa = p.slow_attack; a.sr = p.slow_release; a.floor_db = p.floor_db;
+    a.L = l.ar_L; a.W = l.ar_W; a.Wc = l.ar_Wc; a.Wf = l.ar_Wf; a.n_chunks = l.ar_chunks; a.S = l.ar_S;
+    a.through = l.ar_through ? 1 : 0; a.lines = l.ar_lines ? 1 : 0;
+    return a;
+}
+
+// --- dB of the filtered (or the raw) stream
+int decibels(Call& c) {
+    const Layout& l = c.l;
+    const auto& p = c.d->p;
+    const int64_t chains = c.chains();
+    if (l.db_sym) {
+        hipLaunchKernelGGL(k_rect_db_sym, dim3((unsigned)(chains * l.ar_chunks)), dim3(64), 0, c.stream, ar_args(c), c.xdb,
+                           chains * l.ar_chunks, c.at<double>(l.o_ar_P));
+        OFP_LAUNCH_CHECK("k_rect_db_sym");
+    } else {
+        const unsigned ew_grid = (unsigned)std::min<int64_t>(cdiv(chains * l.g.U, 256), 256 * 16);
+        hipLaunchKernelGGL(k_rect_db, dim3(ew_grid), dim3(256), 0, c.stream, l.g, c.xt, c.xdb, chains, p.hp_enabled ? 0 : 1,
+                           p.floor_db);
+        OFP_LAUNCH_CHECK("k_rect_db");
+    }
+    return OFP_OK;
+}
+
+// --- followers: the starting guesses, the speculative warm-ups, then the chunk passes (enqueued ahead or host-verified)
+int followers(Call& c, bool host_verified) {
+    const Layout& l = c.l;
+    const ArArgs a = ar_args(c);
+    const int64_t chains = c.chains();
+    const int64_t nt = chains * l.ar_chunks;
+    uint32_t* used = c.at<uint32_t>(l.o_ar_state);
+    if (l.ar_sym) {
+        double* P = c.at<double>(l.o_ar_P);
+        if (!l.db_sym) {
+            hipLaunchKernelGGL(k_ar_sym_local, dim3((unsigned)nt), dim3(64), 0, c.stream, a, nt, P);
+            OFP_LAUNCH_CHECK("k_ar_sym_local");
+        }
+        hipLaunchKernelGGL(k_ar_sym_combine, dim3((unsigned)chains), dim3(64), 0, c.stream, a, (const double*)P, used);
+        OFP_LAUNCH_CHECK("k_ar_sym_combine");
+        const int64_t ntg = chains * cdiv(l.ar_chunks, l.ar_S);  // one run per group of S chunks
+        if (l.merge)
+            hipLaunchKernelGGL(l.ar_lines ? k_ar_warm_both<true> : k_ar_warm_both<false>, dim3((unsigned)cdiv(ntg, 64)), dim3(64),
+                               0, c.stream, a, ntg, used, used + 2 * nt);
+        else
+            hipLaunchKernelGGL(k_ar_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
+        OFP_LAUNCH_CHECK("k_ar_warm2");
+    } else {
+        const unsigned grid = (unsigned)cdiv(nt, 64);
+        hipLaunchKernelGGL(k_ar_coarse, dim3(grid), dim3(64), 0, c.stream, a, nt, used);
+        OFP_LAUNCH_CHECK("k_ar_coarse");
+        hipLaunchKernelGGL(k_ar_warm, dim3(grid), dim3(64), 0, c.stream, a, nt, used);
+        OFP_LAUNCH_CHECK("k_ar_warm");
+    }
+    const auto chunk = l.ar_lines ? k_ar_chunk<true> : k_ar_chunk<false>;
+    ofp_detect_pending& rec = *c.rec;
+    if (!host_verified) {
+        rec.ar_nv = l.ar_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, c.d->ar_pass_hint)) : 0;
+        return run_jacobi_ahead("follower stage", chunk, a, nt, l.ar_chunks, used, c.at<int>(l.o_pass_flags), rec.ar_nv,
+                                c.stream);
+    }
+    return run_jacobi("follower stage", chunk, a, nt, l.ar_chunks, used, c.ctr, c.d->h_flags, l.max_passes, l.verify_group,
+                      c.stream, &rec.info[1], &rec.info[3]);
+}
+
+// --- back to linear: the relative envelope (k_rel_out), the block extremes for the crossing pass
+int rel_out(Call& c) {
+    const Layout& l = c.l;
+    const Geom& g = l.g;
+    const int64_t n_clips = c.a.n_clips;
+    const size_t lds = c.tile_lds() + (l.use_sum ? (size_t)2 * g.C * (l.tu / g.B + 2) * 4 : 0);
+    const int64_t n_tiles = cdiv(g.U, l.tu);
+    const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * c.d->n_cus / n_clips));
+    hipLaunchKernelGGL(k_rel_out, dim3(gx, (unsigned)n_clips), dim3(256), lds, c.stream, g, c.dif, c.a.rel, c.d->p.floor_db,
+                       l.tu, c.sum_max, c.sum_minv, l.nb, l.mm_il ? c.rel_warm : nullptr, l.mm_il ? 0 : 1, n_tiles);
+    OFP_LAUNCH_CHECK("k_rel_out");
+    return OFP_OK;
+}
+
+// --- min / max tracker (relative thresholds only; in manual mode its state is never read)
+int tracker(Call& c, bool host_verified) {
+    const Layout& l = c.l;
+    const auto& p = c.d->p;
+    ofp_detect_pending& rec = *c.rec;
+    if (p.manual) return OFP_OK;
+    const int64_t chains = c.chains();
+    MmArgs a;
+    a.g = l.g;
+    a.rel = c.dif; a.rel_il = c.a.rel; a.rel_warm = c.rel_warm;
+    a.thr_mn = c.at<float>(l.o_thr_mn); a.thr_mx = c.at<float>(l.o_thr_mx);
+    a.alpha_min = p.alpha_min; a.alpha_max = p.alpha_max;
+    a.ialpha_min = c.d->ialpha_min; a.ialpha_max = c.d->ialpha_max;
+    a.minmin = p.minmin; a.min0 = p.min0; a.max0 = p.max0;
+    a.nb = l.nb; a.L = l.mm_L; a.W = l.mm_W; a.n_chunks = l.mm_chunks; a.n_chains = chains; a.S = l.mm_S;
+    a.through = l.mm_through ? 1 : 0;
+    a.dirty = c.at<uint8_t>(l.o_mm_dirty);
+    const int64_t nt = chains * l.mm_chunks;
+    uint32_t* used = c.at<uint32_t>(l.o_mm_state);
+    const int64_t ntg = chains * cdiv(l.mm_chunks, l.mm_S);  // one run per group of S chunks
+    if (l.mm_il)
+        with_il_channels(l.g.C, [&](auto ch) {
+            hipLaunchKernelGGL(k_mm_warm_il<decltype(ch)::value>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg,
+                               used, used + 2 * nt);
+        });
+    else if (l.merge)
+        hipLaunchKernelGGL(k_mm_warm_both, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
+    else
+        hipLaunchKernelGGL(k_mm_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
+    OFP_LAUNCH_CHECK("k_mm_warm2");
+    using MmLight = void (*)(const MmArgs&, int64_t, const uint32_t*, uint32_t*, uint32_t*, int*, const int*, hipStream_t);
+    const MmLight light_pl = +[](const MmArgs& m, int64_t, const uint32_t* ep, uint32_t* en, uint32_t* u, int* ch, const int* gate,
+                                 hipStream_t st) {
+        const int64_t n = m.n_chains * m.n_chunks;
+        hipLaunchKernelGGL(k_mm_maxpass, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u, ch, gate);
+    };
+    const MmLight light_il = +[](const MmArgs& m, int64_t, const uint32_t* ep, uint32_t* en, uint32_t* u, int* ch, const int* gate,
+                                 hipStream_t st) {
+        const int64_t n = m.n_chains * m.n_chunks;
+        with_il_channels(m.g.C, [&](auto cc) {
+            hipLaunchKernelGGL(k_mm_maxpass_il<decltype(cc)::value>, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u,
+                               ch, gate);
+        });
+    };
+    const MmLight light = l.mm_il ? light_il : light_pl;
+    const auto chunk = l.mm_il ? with_il_channels(l.g.C, [](auto ch) { return k_mm_chunk_il<decltype(ch)::value>; })
+                               : (l.merge ? k_mm_chunk_both : k_mm_chunk);
+    const int64_t n_threads = l.merge ? nt : 2 * 64 * cdiv(nt, 64);
+    if (!host_verified) {
+        rec.mm_nv = l.mm_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, c.d->mm_pass_hint)) : 0;
+        return run_jacobi_ahead("tracker stage", chunk, a, n_threads, l.mm_chunks, used,
+                                c.at<int>(l.o_pass_flags) + AHEAD_MAX_PASSES, rec.mm_nv, c.stream, light, 2 * nt);
+    }
+    return run_jacobi("tracker stage", chunk, a, n_threads, l.mm_chunks, used, c.ctr, c.d->h_flags, l.max_passes,
+                      l.verify_group, c.stream, &rec.info[2], &rec.info[3], light, 2 * nt);
+}
+
+SmArgs sm_args(const Call& c) {
+    const Layout& l = c.l;
+    SmArgs sm;
+    sm.g = l.g;
+    sm.nb = l.nb; sm.n_clips = c.a.n_clips; sm.cap = c.a.cap; sm.cooldown = c.d->p.cooldown;
+    sm.vis_j = c.at<int32_t>(l.o_visj);
+    sm.vfc = c.at<int32_t>(l.o_vrec);
+    sm.vlb = sm.vfc + c.a.n_clips * l.nb * l.g.C;
+    sm.vpc = sm.vlb + c.a.n_clips * l.nb * l.g.C;
+    sm.nv = c.at<int32_t>(l.o_nv);
+    sm.records = c.a.records; sm.counts = c.a.counts; sm.clip_base = 0;
+    return sm;
+}
+
+// --- crossings per block, then the list of the blocks the state machine visits
+int crossings(Call& c) {
+    const Layout& l = c.l;
+    const Geom& g = l.g;
+    const int64_t n_clips = c.a.n_clips;
+    const int64_t chains = c.chains();
+    ScanArgs sa;
+    sa.g = g;
+    sa.rel = c.dif; sa.thr_mn = c.at<float>(l.o_thr_mn); sa.thr_mx = c.at<float>(l.o_thr_mx);
+    sa.on_f = c.d->d_on_f; sa.off_f = c.d->d_off_f; sa.on_d = c.d->d_on_d; sa.manual = c.d->p.manual;
+    sa.nb = l.nb; sa.n_clips = n_clips;
+    sa.first_cross = c.at<int32_t>(l.o_first); sa.last_below = c.at<int32_t>(l.o_last); sa.vflag = c.at<uint32_t>(l.o_vflag);
+    sa.sum_max = c.sum_max; sa.sum_minv = c.sum_minv;
+    if (l.mm_il) {
+        const unsigned il_grid = (unsigned)std::min<int64_t>(cdiv(n_clips * l.nb, 4), 256 * 32);
+        with_il_channels(g.C, [&](auto ch) {
+            hipLaunchKernelGGL(k_block_scan_il<decltype(ch)::value>, dim3(il_grid), dim3(256), 0, c.stream, sa, c.a.rel);
+        });
+    } else {
+        const unsigned bs_grid = (unsigned)std::min<int64_t>(cdiv(n_clips * l.nb * g.C, 4), 256 * 32);  // 4 waves per workgroup
+        hipLaunchKernelGGL(k_block_scan, dim3(bs_grid), dim3(256), 0, c.stream, sa);
+    }
+    OFP_LAUNCH_CHECK("k_block_scan");
+    const SmArgs sm = sm_args(c);
+    VisArgs va;
+    va.vflag = sa.vflag; va.fc = sa.first_cross; va.lb = sa.last_below;
+    int32_t* pc = c.at<int32_t>(l.o_pc);
+    va.pc = pc; va.nb = l.nb; va.C = g.C;
+    va.vis_j = const_cast<int32_t*>(sm.vis_j); va.nv = const_cast<int32_t*>(sm.nv);
+    va.vfc = const_cast<int32_t*>(sm.vfc); va.vlb = const_cast<int32_t*>(sm.vlb); va.vpc = const_cast<int32_t*>(sm.vpc);
+    {
+        const int64_t n_lt = cdiv(l.nb, 256);
+        int32_t* lt = c.at<int32_t>(l.o_ltile);
+        OFP_REQUIRE(n_lt * chains < (1ll << 31), "ofp_detect_offline: %lld block tiles in one call", (long long)(n_lt * chains));
+        const dim3 lgrid((unsigned)(n_lt * chains));
+        hipLaunchKernelGGL(k_last_clear<false>, lgrid, dim3(64), 0, c.stream, (const int32_t*)sa.last_below, pc, lt, l.nb, g.C, n_lt);
+        hipLaunchKernelGGL(k_last_clear_scan, dim3((unsigned)chains), dim3(64), 0, c.stream, lt, n_lt);
+        hipLaunchKernelGGL(k_last_clear<true>, lgrid, dim3(64), 0, c.stream, (const int32_t*)sa.last_below, pc, lt, l.nb, g.C, n_lt);
+        OFP_LAUNCH_CHECK("k_last_clear");
+    }
+    const int64_t n_tiles = cdiv(l.nb, 256);
+    int32_t* vtile = c.at<int32_t>(l.o_vtile);
+    hipLaunchKernelGGL(k_visit_count, dim3((unsigned)n_tiles, (unsigned)n_clips), dim3(256), 0, c.stream, va, vtile, n_tiles);
+    hipLaunchKernelGGL(k_visit_scan, dim3((unsigned)n_clips), dim3(64), 0, c.stream, vtile, n_tiles, va.nv);
+    hipLaunchKernelGGL(k_visit_scatter, dim3((unsigned)n_tiles, (unsigned)n_clips), dim3(256), 0, c.stream, va,
+                       (const int32_t*)vtile, n_tiles);
+    OFP_LAUNCH_CHECK("k_visit_count / k_visit_scan / k_visit_scatter");
+    return OFP_OK;
+}
+
+int sequential_machine(const Call& c) {
+    const int C = c.l.g.C;
+    const int tb = std::max(1, std::min(64, (64 * SM_NPL) / C));
+    const size_t lds = (size_t)C * (8 + 4 + 1 + 1) + (size_t)3 * tb * C * 4 + 64 * 4 + 16;
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_state_machine), lds, attr)) return rc;
+    hipLaunchKernelGGL(k_state_machine, dim3((unsigned)c.a.n_clips), dim3(64), lds, c.stream, sm_args(c));
+    OFP_LAUNCH_CHECK("k_state_machine");
+    return OFP_OK;
+}
+
+// --- hysteresis / cooldown state machine: time-parallel over the visit list (its last verification pass's change
+// counter is read by the completion: a segment start still changing means the sequential machine decides) or sequential
+int state_machine(Call& c) {
+    const Layout& l = c.l;
+    c.rec->sm_flag = false;
+    if (!l.sm_seg) return sequential_machine(c);
+    const int64_t n_clips = c.a.n_clips;
+    const SmArgs sm = sm_args(c);
+    SmSegArgs ss;
+    ss.n_seg = cdiv(l.nb, SM_SEG);
+    const int64_t words = n_clips * ss.n_seg * 64 * 2;
+    ss.used = c.at<int32_t>(l.o_smseg);
+    ss.endA = ss.used + words;
+    ss.endB = ss.endA + words;
+    ss.cnt = ss.endB + words;
+    const int tb = std::max(1, std::min(64, 1024 / l.g.C));
+    const size_t lds = (size_t)3 * tb * l.g.C * 4 + 64 * 4;
+    const dim3 grid((unsigned)ss.n_seg, (unsigned)n_clips);
+    constexpr int V = 4;  // verification passes enqueued ahead (a pass that finds nothing costs microseconds)
+    int* cnt = nullptr;
+    if (int rc = c.ctr.take(V, &cnt)) return rc;
+    hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, c.stream, sm, ss, 0, cnt);
+    for (int q = 1; q <= V; ++q) hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, c.stream, sm, ss, q, cnt + q - 1);
+    hipLaunchKernelGGL(k_sm_offsets, dim3((unsigned)n_clips), dim3(64), 0, c.stream, sm, ss);
+    hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, c.stream, sm, ss, -1, cnt);
+    OFP_LAUNCH_CHECK("k_sm_seg / k_sm_offsets");
+    c.rec->sm_flag = true;
+    OFP_HIP(hipMemcpyAsync(c.d->h_flags + 40, cnt + V - 1, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    return OFP_OK;
+}
+
+// --- backtracking of the onsets' sample positions
+int backtrack(const Call& c) {
+    const auto& p = c.d->p;
+    if (!(p.backtrack && c.a.cap > 0)) return OFP_OK;
+    BtArgs bt;
+    bt.g = c.l.g;
+    bt.rel = c.dif; bt.rel_il = c.l.mm_il ? c.a.rel : nullptr;
+    bt.records = c.a.records; bt.counts = c.a.counts; bt.cap = c.a.cap; bt.n_clips = c.a.n_clips;
+    bt.N = p.backtrack_buffer_size; bt.alpha = p.backtrack_alpha; bt.tol = p.backtrack_tol;
+    hipLaunchKernelGGL(k_backtrack, dim3((unsigned)cdiv(c.a.n_clips * c.a.cap, 64)), dim3(64), 0, c.stream, bt);
+    OFP_LAUNCH_CHECK("k_backtrack");
+    return OFP_OK;
+}
+
+// The stages of a call from `first` through `last` (HEAD, CANDIDATES: the head that _begin enqueues; END: everything
+// up to the completion), enqueued on the call's stream.  host_verified: the verification passes are driven from the
+// host, one synchronisation per group, instead of being enqueued ahead.  A run from FOLLOWERS / TRACKER on (the
+// completion's repeat) finds the dB stream / the relative envelope in the work space.
+int run(Call& c, Stage first, Stage last, bool host_verified) {
+    ofp_detect_pending& rec = *c.rec;
+    rec.valid = false;
+    if (first == HEAD) rec.timed = c.timed;
+    else c.timed = c.timed && rec.timed;  // (a call in parts is timed when its head was)
+    rec.empty = c.l.nb == 0;
+    if (rec.empty) {  // fewer samples than one block: nothing is processed (detection.py:74-75)
+        if (last == END) {
+            hipLaunchKernelGGL(k_zero_i64, dim3((unsigned)cdiv(c.a.n_clips, 256)), dim3(256), 0, c.stream, c.a.counts, c.a.n_clips);
+            OFP_LAUNCH_CHECK("k_zero_i64");
+        }
+        return OFP_OK;
+    }
+    if (first == HEAD) {
+        rec.hp_timed = rec.staged = false;
+        std::memset(rec.info, 0, sizeof(rec.info));
+        if (int rc = head(c)) return rc;
+    }
+    if (first <= CANDIDATES && last >= CANDIDATES)
+        if (int rc = iir_candidates(c)) return rc;
+    if (last != END) return OFP_OK;
+    rec.ahead = !host_verified;
+    rec.hp_rounds = rec.ar_nv = rec.mm_nv = 0;  // (passes enqueued ahead: set by their stages)
+    hipEvent_t* ev = c.d->ev;
+    if (first <= ROUNDS)
+        if (int rc = iir_rounds(c, host_verified)) return rc;
+    if (c.timed) OFP_HIP(hipEventRecord(ev[1], c.stream));
+    if (first <= ROUNDS)
+        if (int rc = decibels(c)) return rc;
+    if (c.timed) OFP_HIP(hipEventRecord(ev[2], c.stream));
+    if (first <= FOLLOWERS)
+        if (int rc = followers(c, host_verified)) return rc;
+    if (c.timed) OFP_HIP(hipEventRecord(ev[3], c.stream));
+    if (first <= FOLLOWERS)
+        if (int rc = rel_out(c)) return rc;
+    if (c.timed) OFP_HIP(hipEventRecord(ev[4], c.stream));
+    if (int rc = tracker(c, host_verified)) return rc;
+    if (c.timed) OFP_HIP(hipEventRecord(ev[5], c.stream));
+    if (int rc = crossings(c)) return rc;
+    if (int rc = state_machine(c)) return rc;
+    if (int rc = backtrack(c)) return rc;
+    if (!host_verified)
+        OFP_HIP(hipMemcpyAsync(c.d->h_flags + 96, c.at<int>(c.l.o_pass_flags), 2 * AHEAD_MAX_PASSES * sizeof(int),
+                               hipMemcpyDeviceToHost, c.stream));
+    if (c.timed) OFP_HIP(hipEventRecord(ev[6], c.stream));
+    return OFP_OK;
+}
+
+int complete(const Call& c, int64_t* h_info);
+
+// What was enqueued ahead did not suffice: the call again from the first stage that has not converged, its passes
+// verified on the host -- everything (the IIR rounds), from the follower stage on (the dB stream is final) or from the
+// tracker stage on (the relative envelope is final).  The repeat records into a copy of the pending record, so d->pend
+// stays as the enqueued call left it (a graph that captured the call may be replayed and completed again).
+// open: 1 the IIR rounds, + 2 the follower passes, + 4 the tracker passes had not converged; info: the call's figures.
+int repeat(const Call& c, Stage from, int open, const int64_t* info, int64_t* h_info) {
+    ofp_detect_pending rec = *c.rec;
+    Call r = c;
+    r.rec = &rec;
+    r.ctr.next = 0;
+    if (from == HEAD) {
+        r.timed = !capturing(r.stream);
+    } else {
+        r.timed = rec.timed = false;
+        // the words the repeated stages count in / flag must start as zero again
+        const Layout& l = c.l;
+        auto zero = [&](int64_t off, int64_t bytes) {
+            const int64_t n16 = align_up(bytes, 256) / 16;
+            hipLaunchKernelGGL(k_zero, dim3((unsigned)cdiv(n16, 256)), dim3(256), 0, r.stream, r.at<uint4>(off), n16);
+        };
+        zero(l.o_flags, OFP_N_COUNTERS * 4);
+        zero(l.o_mm_dirty, c.chains() * l.mm_chunks);
+        zero(l.o_vflag, c.a.n_clips * l.nb * 4);
+        if (from == FOLLOWERS) zero(l.o_sum, 2 * c.chains() * l.nb * 4);
+        OFP_LAUNCH_CHECK("k_zero");
+    }
+    if (int rc = run(r, from, END, true)) return rc;
+    OFP_HIP(hipStreamSynchronize(r.stream));
+    if (int rc = complete(r, h_info)) return rc;  // (host-verified: nothing to repeat)
+    if (h_info) {
+        if (from > HEAD) h_info[0] = info[0];  // (the stages that were not repeated keep their figures)
+        if (from > FOLLOWERS) h_info[1] = info[1];
+        h_info[15] = 1 + open;  // (see include/onsetfp.h)
+    }
+    return OFP_OK;
+}
+
+// After the final synchronisation: the segmented machine's verdict, the pass statistics, the stage times -- or the repeat
+// of the call's unsettled part
+int complete(const Call& c, int64_t* h_info) {
+    const ofp_detect_pending& pend = *c.rec;
+    ofp_detector* d = c.d;
+    int64_t info[OFP_DETECT_INFO_LEN] = {0};
+    if (pend.empty) {
+        if (h_info) std::memcpy(h_info, info, sizeof(info));
+        return OFP_OK;
+    }
+    std::memcpy(info, pend.info, sizeof(info));
+    hipEvent_t* ev = d->ev;
+    if (pend.sm_flag && (d->h_flags[40] != 0 || c.l.sm_force_sequential)) {
+        // the last verification pass still changed a segment's start state (a machine that does not forget within
+        // four segments): the sequential machine decides
+        if (int rc = sequential_machine(c)) return rc;
+        if (int rc = backtrack(c)) return rc;
+        if (pend.timed) OFP_HIP(hipEventRecord(ev[6], c.stream));
+        OFP_HIP(hipStreamSynchronize(c.stream));
+        info[14] = 1;
+    }
+    if (pend.ahead) {
+        const int* pf = d->h_flags + 96;  // change counters of the follower (0..) / tracker (AHEAD_MAX_PASSES..) passes
+        const int* hr = d->h_flags + 64;  // {stuck, pending} per enqueued IIR round
+        bool hp_open = false;
+        if (pend.hp_rounds > 0) {  // (0: no high-pass)
+            int used_rounds = 1;
+            while (used_rounds < pend.hp_rounds && hr[2 * (used_rounds - 1)] + hr[2 * (used_rounds - 1) + 1] != 0) ++used_rounds;
+            for (int q = 0; q < used_rounds; ++q) info[3] += hr[2 * q] + hr[2 * q + 1];
+            hp_open = hr[2 * (pend.hp_rounds - 1)] + hr[2 * (pend.hp_rounds - 1) + 1] != 0;
+            // the next call enqueues what this one needed plus a margin (decaying slowly)
+            d->hp_rounds_hint = std::max(used_rounds + 2, d->hp_rounds_hint - 1);
+            info[0] = used_rounds;
+        }
+        // passes that ran: pass 0, the first verifying one, and every further one whose predecessor repaired
+        auto ran = [&](const int* f, int nv, int* hint, int64_t* passes) -> bool {
+            if (nv == 0) {
+                *passes = 1;
+                return false;
+            }
+            int used_v = 1;
+            while (used_v < nv && f[used_v - 1] != 0) ++used_v;
+            for (int j = 0; j < used_v; ++j) info[3] += f[j];
+            for (int j = nv; j < 2 * nv; ++j) info[3] += f[j];  // (the light groups)
+            *passes = 1 + used_v;
+            *hint = std::max(used_v + 1, *hint - 1);
+            return f[nv - 1] != 0;
+        };
+        const bool ar_open = ran(pf, pend.ar_nv, &d->ar_pass_hint, &info[1]);
+        const bool mm_open = ran(pf + AHEAD_MAX_PASSES, pend.mm_nv, &d->mm_pass_hint, &info[2]);
+        if (d->p.manual) info[2] = 0;
+        const Stage from = std::min({c.l.forced_from, hp_open ? HEAD : END, ar_open ? FOLLOWERS : END, mm_open ? TRACKER : END});
+        if (from != END) {
+            if (hp_open) d->hp_rounds_hint = std::min(HP_MAX_ROUNDS, 2 * pend.hp_rounds);
+            if (ar_open) d->ar_pass_hint = std::min(AHEAD_MAX_PASSES / 2, 2 * pend.ar_nv);
+            if (mm_open) d->mm_pass_hint = std::min(AHEAD_MAX_PASSES / 2, 2 * pend.mm_nv);
+            return repeat(c, from, (hp_open ? 1 : 0) + (ar_open ? 2 : 0) + (mm_open ? 4 : 0), info, h_info);
+        }
+    }
+    if (pend.staged) {  // distinct runs that walked each later segment / the chunk (slightly over: clamped windows)
+        const int* n = d->h_flags + 16;
+        for (int m = 0; m + 1 < pend.n_cuts; ++m) info[12] += (int64_t)n[m] * (pend.cuts[m + 1] - pend.cuts[m]);
+        info[12] += (int64_t)n[pend.n_cuts - 1] * c.l.hp_L;
+        info[13] = n[pend.n_cuts - 1];  // runs that walked a chunk (of chains * chunks * R candidates)
+    }
+    if (pend.timed) {  // stage durations in nanoseconds (HIP events on the launch stream)
+        float ms = 0.0f;
+        for (int k = 0; k < 6; ++k) {
+            OFP_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+            info[4 + k] = (int64_t)(ms * 1.0e6);
+        }
+        OFP_HIP(hipEventElapsedTime(&ms, ev[0], ev[6]));
+        info[10] = (int64_t)(ms * 1.0e6);
+        if (pend.hp_timed) {  // the IIR candidate launch(es)
+            OFP_HIP(hipEventElapsedTime(&ms, ev[8], ev[7]));
+            info[11] = (int64_t)(ms * 1.0e6);
+        }
+    }
+    if (h_info) std::memcpy(h_info, info, sizeof(info));
+    return OFP_OK;
+}
+
+// ofp_detect_offline / _finish: the call from `first` on, the synchronisation, the completion
+int run_sync(Call& c, Stage first, int64_t* h_info) {
+    if (int rc = run(c, first, END, c.l.host_verify)) return rc;
+    OFP_HIP(hipStreamSynchronize(c.stream));
+    return complete(c, h_info);
+}
+
+// ofp_detect_offline_enqueue / _finish_enqueue: the call from `first` on, left pending for ofp_detect_offline_complete
+int run_enqueued(Call& c, Stage first) {
+    OFP_REQUIRE(!c.l.host_verify, "ofp_detect_offline_enqueue: not with tuning host_verify (its passes are verified on the host)");
+    if (int rc = run(c, first, END, false)) return rc;
+    c.d->pend.args = c.a;
+    c.d->pend.valid = true;
+    return OFP_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -3432,756 +4212,70 @@ int64_t ofp_detect_workspace_bytes(const ofp_detector* d, int64_t n_clips, int64
     return make_layout(d, n_clips, n_samples, warm).total;
 }
 
-// phase 0: everything; phase 1: only the asynchronous head (transpose + candidates launch);
-// phase 2: everything after the head (the caller ran phase 1 with the same arguments);
-// phase 5 + phase 6: phase 1 in two calls, the planar input copy / the IIR candidate launch;
-// phase 7: completion of a call that was only enqueued (run_mode 1), after the caller has synchronised.
-// run_mode 0: enqueue, synchronise, complete; 1: enqueue only (phases 0 and 2; nothing in it blocks or reads
-// device results on the host, so the stream may be capturing a hipGraph).
-// from_stage (with phase 2, by the completion's fall-back only): 1 = repeat the call from the follower stage on, 2 = from
-// the tracker stage on -- everything before it (the filtered dB stream / the relative envelope) is in the work space.
-static int detect_impl(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
-                       float* d_rel, ofp_onset* d_records, int64_t cap, int64_t* d_counts,
-                       void* d_ws, int64_t ws_bytes, int64_t* h_info, void* stream_, int phase, int run_mode = 0,
-                       int from_stage = 0) {
-    OFP_REQUIRE(d && d_counts && d_ws, "ofp_detect_offline: NULL argument");
-    OFP_REQUIRE(n_clips >= 1 && N >= 0 && cap >= 0, "ofp_detect_offline: bad sizes");
-    OFP_REQUIRE(d_x || N == 0, "ofp_detect_offline: d_x is NULL");
-    OFP_REQUIRE(d_records || cap == 0, "ofp_detect_offline: d_records is NULL");
-    OFP_REQUIRE(n_clips <= 65535, "ofp_detect_offline: at most 65535 clips per call");
-    hipStream_t stream = (hipStream_t)stream_;
-    const Layout l = make_layout(d, n_clips, N, warm);
-    if (ws_bytes < l.total)
-        return ofp::fail(OFP_ERR_WORKSPACE, "work space %lld < required %lld bytes", (long long)ws_bytes,
-                         (long long)l.total);
-    const Geom& g = l.g;
-    const auto& p = d->p;
-    const bool host_verify = d->t.host_verify > 0;  // (2 / 3: aliases of 1 kept for old callers)
-    const bool enqueue_only = run_mode == 1;
-    OFP_REQUIRE(!(enqueue_only && host_verify), "ofp_detect_offline_enqueue: not with tuning host_verify (its passes are "
-                "verified on the host)");
-    unsigned char* ws = static_cast<unsigned char*>(d_ws);
-    float* xt = reinterpret_cast<float*>(ws + l.o_xt);
-    float* xdb = reinterpret_cast<float*>(ws + l.o_xdb);
-    float* dif = reinterpret_cast<float*>(ws + l.o_dif);
-    Counters ctr{reinterpret_cast<int*>(ws + l.o_flags), 0, stream};
-    int* pass_flags = reinterpret_cast<int*>(ws + l.o_pass_flags);  // follower passes at 0, tracker passes at AHEAD_MAX_PASSES
-    ofp_detect_pending& pend = d->pend;
-    int64_t info[OFP_DETECT_INFO_LEN] = {0};
-    hipEvent_t* ev = d->ev;
-    const bool do_head = phase == 0 || phase == 1 || phase == 5;   // zero fill + transpose
-    const bool do_cand = phase == 0 || phase == 1 || phase == 6;   // the IIR candidate launch
-    // stage timing by HIP events -- not while the stream is capturing (an event recorded into a graph has no time)
-    bool timed = true;
-    if (phase != 7) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) timed = false;
-        if (!timed) OFP_REQUIRE(enqueue_only || phase == 1 || phase == 5 || phase == 6,
-                                "ofp_detect_offline: the stream is capturing; use ofp_detect_offline_enqueue");
-        if (do_head) pend.timed = timed;
-        else timed = timed && pend.timed;
-    }
-    if (from_stage > 0) timed = pend.timed = false;
-    if (do_head && timed) OFP_HIP(hipEventRecord(ev[0], stream));
-    if (l.nb == 0) {  // fewer samples than one block: nothing is processed (detection.py:74-75)
-        if (phase == 1 || phase == 5 || phase == 6) return OFP_OK;
-        if (phase != 7) {
-            hipLaunchKernelGGL(k_zero_i64, dim3((unsigned)cdiv(n_clips, 256)), dim3(256), 0, stream, d_counts, n_clips);
-            OFP_LAUNCH_CHECK("k_zero_i64");
-        }
-        if (enqueue_only) {
-            pend.valid = true;
-            pend.empty = true;
-            return OFP_OK;
-        }
-        if (phase != 7) OFP_HIP(hipStreamSynchronize(stream));
-        pend.valid = false;
-        if (h_info) std::memcpy(h_info, info, sizeof(info));
-        return OFP_OK;
-    }
-    const int64_t chains = n_clips * g.C;
-    const int64_t n_elem = chains * g.U;
-    const unsigned ew_grid = (unsigned)std::min<int64_t>(cdiv(n_elem, 256), 256 * 16);
-    const size_t tile_lds = (size_t)g.C * (l.tu + 4) * sizeof(float);
-    const float* rel = dif;  // (the relative envelope overwrites the follower difference in place)
-    // tracker, crossing pass and backtracking on the interleaved envelope (see k_mm_warm_il): the planar copy is not written
-    // (tuning interleaved < 0 or its alias 2: off)
-    const bool mm_il = d->t.interleaved >= 0 && d->t.interleaved != 2 && l.merge && d_rel != nullptr && !p.manual &&
-                       (g.C == 4 || g.C == 8 || g.C == 64);
-    float* rel_warm = reinterpret_cast<float*>(ws + l.o_relw);
-
-    // --- the last stage's arguments, needed by the completion as well (sequential machine as the fall-back)
-    int32_t* va_nv = reinterpret_cast<int32_t*>(ws + l.o_nv);
-    SmArgs sm;
-    sm.g = g;
-    sm.nb = l.nb;
-    sm.n_clips = n_clips;
-    sm.cap = cap;
-    sm.cooldown = p.cooldown;
-    sm.vis_j = reinterpret_cast<int32_t*>(ws + l.o_visj);
-    sm.vfc = reinterpret_cast<int32_t*>(ws + l.o_vrec);
-    sm.vlb = sm.vfc + n_clips * l.nb * g.C;
-    sm.vpc = sm.vlb + n_clips * l.nb * g.C;
-    sm.nv = va_nv;
-    sm.records = d_records;
-    sm.counts = d_counts;
-    sm.clip_base = 0;
-    auto sequential_machine = [&]() -> int {
-        const int tb = std::max(1, std::min(64, (64 * SM_NPL) / g.C));
-        size_t lds = (size_t)g.C * (8 + 4 + 1 + 1) + (size_t)3 * tb * g.C * 4 + 64 * 4 + 16;
-        static ofp::LdsAttrCache attr;
-        if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_state_machine), lds, attr)) return rc;
-        hipLaunchKernelGGL(k_state_machine, dim3((unsigned)n_clips), dim3(64), lds, stream, sm);
-        OFP_LAUNCH_CHECK("k_state_machine");
-        return OFP_OK;
-    };
-    auto backtrack = [&]() -> int {
-        if (!(p.backtrack && cap > 0)) return OFP_OK;
-        BtArgs bt;
-        bt.g = g;
-        bt.rel = rel;
-        bt.rel_il = mm_il ? d_rel : nullptr;
-        bt.records = d_records;
-        bt.counts = d_counts;
-        bt.cap = cap;
-        bt.n_clips = n_clips;
-        bt.N = p.backtrack_buffer_size;
-        bt.alpha = p.backtrack_alpha;
-        bt.tol = p.backtrack_tol;
-        hipLaunchKernelGGL(k_backtrack, dim3((unsigned)cdiv(n_clips * cap, 64)), dim3(64), 0, stream, bt);
-        OFP_LAUNCH_CHECK("k_backtrack");
-        return OFP_OK;
-    };
-    // after the final synchronisation: the segmented machine's verdict, the pass statistics, the stage times
-    auto complete = [&]() -> int {
-        // (pend stays valid: a graph that captured the enqueued call may be replayed and completed any number of times)
-        std::memcpy(info, pend.info, sizeof(info));
-        if (pend.sm_flag && (d->h_flags[40] != 0 || d->t.sm_segments == 2)) {  // (2: tests exercise this path)
-            // the last verification pass still changed a segment's start state (a machine that does not forget within
-            // four segments): the sequential machine decides
-            if (int rc = sequential_machine()) return rc;
-            if (int rc = backtrack()) return rc;
-            if (pend.timed) OFP_HIP(hipEventRecord(ev[6], stream));
-            OFP_HIP(hipStreamSynchronize(stream));
-            info[14] = 1;
-        }
-        {
-            const int* pf = d->h_flags + 96;   // change counters of the follower (0..) / tracker (AHEAD_MAX_PASSES..) passes
-            const int* hr = d->h_flags + 64;   // {stuck, pending} per enqueued IIR round
-            bool hp_open = false, ar_err = false, mm_err = false;
-            if (pend.hp_rounds > 0) {  // (0: no high-pass, or its rounds were verified on the host)
-                int used_rounds = 1;
-                while (used_rounds < pend.hp_rounds && hr[2 * (used_rounds - 1)] + hr[2 * (used_rounds - 1) + 1] != 0) ++used_rounds;
-                for (int q = 0; q < used_rounds; ++q) info[3] += hr[2 * q] + hr[2 * q + 1];
-                hp_open = hr[2 * (pend.hp_rounds - 1)] + hr[2 * (pend.hp_rounds - 1) + 1] != 0;
-                // the next call enqueues what this one needed plus a margin (decaying slowly)
-                d->hp_rounds_hint = std::max(used_rounds + 2, d->hp_rounds_hint - 1);
-                info[0] = used_rounds;
-            }
-            if (pend.ahead) {
-                // passes that ran: pass 0, the first verifying one, and every further one whose predecessor repaired
-                auto ran = [&](const int* f, int nv, int* hint, int64_t* passes) -> bool {
-                    if (nv == 0) {
-                        *passes = 1;
-                        return false;
-                    }
-                    int used_v = 1;
-                    while (used_v < nv && f[used_v - 1] != 0) ++used_v;
-                    for (int j = 0; j < used_v; ++j) info[3] += f[j];
-                    for (int j = nv; j < 2 * nv; ++j) info[3] += f[j];  // (the light groups)
-                    *passes = 1 + used_v;
-                    *hint = std::max(used_v + 1, *hint - 1);
-                    return f[nv - 1] != 0;
-                };
-                ar_err = ran(pf, pend.ar_nv, &d->ar_pass_hint, &info[1]);
-                mm_err = ran(pf + AHEAD_MAX_PASSES, pend.mm_nv, &d->mm_pass_hint, &info[2]);
-                if (p.manual) info[2] = 0;
-            }
-            if (hp_open || ar_err || mm_err || d->t.host_verify <= -2) {  // (-2 / -3 / -4: tests exercise these paths)
-                // What was enqueued ahead did not suffice: the call again from the first stage that has not converged,
-                // its passes verified on the host -- everything (the IIR rounds), from the follower stage on (the dB
-                // stream is final) or from the tracker stage on (the relative envelope is final).
-                const int from = (hp_open || d->t.host_verify == -2) ? 0 : ((ar_err || d->t.host_verify == -3) ? 1 : 2);
-                const ofp_detect_tuning keep = d->t;
-                const ofp_detect_pending keep_pend = pend;  // (a graph that captured this call may be replayed again)
-                d->t.host_verify = 1;
-                if (hp_open) d->hp_rounds_hint = std::min(HP_MAX_ROUNDS, 2 * pend.hp_rounds);
-                if (ar_err) d->ar_pass_hint = std::min(AHEAD_MAX_PASSES / 2, 2 * pend.ar_nv);
-                if (mm_err) d->mm_pass_hint = std::min(AHEAD_MAX_PASSES / 2, 2 * pend.mm_nv);
-                const int rc = detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, h_info,
-                                           stream_, from == 0 ? 0 : 2, 0, from);
-                d->t = keep;
-                d->pend = keep_pend;
-                if (rc == OFP_OK && h_info) {
-                    if (from >= 1) h_info[0] = info[0];   // (the stages that were not repeated keep their figures)
-                    if (from >= 2) h_info[1] = info[1];
-                    h_info[15] = 1 + (hp_open ? 1 : 0) + (ar_err ? 2 : 0) + (mm_err ? 4 : 0);  // (see include/onsetfp.h)
-                }
-                return rc;
-            }
-        }
-        if (pend.staged) {  // distinct runs that walked each later segment / the chunk (slightly over: clamped windows)
-            const int* n = d->h_flags + 16;
-            for (int m = 0; m + 1 < pend.n_cuts; ++m) info[12] += (int64_t)n[m] * (pend.cuts[m + 1] - pend.cuts[m]);
-            info[12] += (int64_t)n[pend.n_cuts - 1] * l.hp_L;
-            info[13] = n[pend.n_cuts - 1];  // runs that walked a chunk (of chains * chunks * R candidates)
-        }
-        if (pend.timed) {  // stage durations in nanoseconds (HIP events on the launch stream)
-            for (int k = 0; k < 6; ++k) {
-                float ms = 0.0f;
-                OFP_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-                info[4 + k] = (int64_t)(ms * 1.0e6);
-            }
-            float ms = 0.0f;
-            OFP_HIP(hipEventElapsedTime(&ms, ev[0], ev[6]));
-            info[10] = (int64_t)(ms * 1.0e6);
-            if (pend.hp_timed) {  // the IIR candidate launch(es)
-                OFP_HIP(hipEventElapsedTime(&ms, ev[8], ev[7]));
-                info[11] = (int64_t)(ms * 1.0e6);
-            }
-        }
-        if (h_info) std::memcpy(h_info, info, sizeof(info));
-        return OFP_OK;
-    };
-    if (phase == 7) {
-        OFP_REQUIRE(pend.valid, "ofp_detect_offline_complete: no enqueued call is pending on this detector");
-        if (pend.empty) {
-            if (h_info) std::memcpy(h_info, info, sizeof(info));
-            return OFP_OK;
-        }
-        return complete();
-    }
-    if (do_head) {
-        pend.hp_timed = false;
-        pend.staged = false;
-        pend.empty = false;
-        std::memset(pend.info, 0, sizeof(pend.info));
-    }
-
-    // --- transpose in
-    if (do_head) {
-        {  // counters, flags: see make_layout (regions are 256-byte multiples)
-            const int64_t n16 = l.zero_bytes / 16;
-            hipLaunchKernelGGL(k_zero, dim3((unsigned)cdiv(n16, 256)), dim3(256), 0, stream, reinterpret_cast<uint4*>(ws + l.o_zero), n16);
-            OFP_LAUNCH_CHECK("k_zero");
-        }
-        const int64_t n_tiles = cdiv(N, l.tu);
-        const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * d->n_cus / n_clips));
-        hipLaunchKernelGGL(k_transpose_in, dim3(gx, (unsigned)n_clips), dim3(256), tile_lds,
-                           stream, d_x, xt, N, g.C, l.tu, g.n_w, g.Nv, n_tiles);
-        OFP_LAUNCH_CHECK("k_transpose_in");
-        if (timed) OFP_HIP(hipEventRecord(ev[8], stream));
-    }
-    if (phase == 5) return OFP_OK;
-
-    if (from_stage > 0) {  // the words the repeated stages count in / flag must start as zero again
-        auto zero = [&](int64_t off, int64_t bytes) {
-            const int64_t n16 = align_up(bytes, 256) / 16;
-            hipLaunchKernelGGL(k_zero, dim3((unsigned)cdiv(n16, 256)), dim3(256), 0, stream, reinterpret_cast<uint4*>(ws + off), n16);
-        };
-        zero(l.o_flags, OFP_N_COUNTERS * 4);
-        zero(l.o_mm_dirty, n_clips * l.mm_chunks * g.C);
-        zero(l.o_vflag, n_clips * l.nb * 4);
-        if (from_stage == 1) zero(l.o_sum, 2 * n_clips * l.nb * g.C * 4);
-        OFP_LAUNCH_CHECK("k_zero");
-    }
-
-    // --- hp + dB
-    if (p.hp_enabled && from_stage == 0) {
-        HpCand hc;
-        hc.st.g = g;
-        hc.st.xt = xt;
-        hc.st.out = xdb;
-        // complete-line stores for the output walk (k_hp_run_lines): throughput layout, every position that matters a
-        // multiple of 32 steps
-        const bool hp_lines = d->t.line_stores >= 0 &&
-                              (l.merge || d->t.line_stores > 0 || chains * l.hp_chunks * l.hp_S >= (int64_t)2 * 64 * 4 * d->n_cus) &&  // (calls in flight, or a big one)
-                              // NOT applied (they have only ever stood in a comment): (g.n_w & 31) == 0 && (g.n_wb & 31) == 0 &&
-                              (g.V & 31) == 0 && (g.U & 31) == 0 && (g.Nv & 3) == 0 && (l.hp_L & 31) == 0 &&
-                              ((l.hp_L / l.hp_S) & 31) == 0 && l.hp_L % l.hp_S == 0;
-        const auto krun = hp_lines ? k_hp_run_lines : k_hp_run;
-        std::memcpy(hc.st.b, d->b, sizeof(hc.st.b));
-        std::memcpy(hc.st.a, d->a, sizeof(hc.st.a));
-        hc.st.L = l.hp_L;
-        hc.st.W = l.hp_W;
-        hc.st.n_chunks = l.hp_chunks;
-        hc.R = l.hp_R;
-        hc.delta = l.hp_delta;
-        hc.span = l.hp_span;
-        hc.U = reinterpret_cast<uint32_t*>(ws + l.o_hp_U);
-        hc.E = reinterpret_cast<uint32_t*>(ws + l.o_hp_E);
-        hc.sel = reinterpret_cast<int8_t*>(ws + l.o_hp_sel);
-        hc.done = reinterpret_cast<uint8_t*>(ws + l.o_hp_done);
-        hc.S = l.hp_S;
-        hc.M = reinterpret_cast<uint32_t*>(ws + l.o_hp_M);
-        hc.nxt = reinterpret_cast<uint8_t*>(ws + l.o_hp_nxt);
-        hc.guessed = reinterpret_cast<uint8_t*>(ws + l.o_hp_guess);
-        hc.ran = reinterpret_cast<int8_t*>(ws + l.o_hp_ran);
-        hc.gs = reinterpret_cast<int8_t*>(ws + l.o_hp_gs);
-        hc.mrg = reinterpret_cast<int8_t*>(ws + l.o_hp_mrg);
-        hc.early = l.hp_early ? 1 : 0;
-        hc.counters = ctr.base;
-        hc.pos = reinterpret_cast<int32_t*>(ws + l.o_hp_pos);
-        hc.prev = nullptr;
-        const int64_t nA = chains * l.hp_chunks * (hc.R / hc.span);
-        const int64_t nM = chains * l.hp_chunks * (hc.R + 1);
-        const int64_t nC = chains * l.hp_chunks * l.hp_S;
-        const int64_t nC0 = chains * l.hp_chunks;
-        // staged candidates: window offsets at which duplicates are removed (the last one is the chunk start)
-        int64_t cuts[16];
-        int n_cuts = 0;
-        if (l.hp_staged) {
-            // (the runs of a group merge fastest early on: 8 -> 4.8 distinct within 8 192 steps, -> 2.2 by 24 576)
-            for (int64_t c = 4096; c < l.hp_W && n_cuts < 15; c += (c < 8192 ? 4096 : (c < 40960 ? 8192 : 16384)))
-                cuts[n_cuts++] = c;
-            cuts[n_cuts++] = l.hp_W;
-        }
-        int* stage_n = reinterpret_cast<int*>(ws + l.o_hp_stage_n);
-        if (do_cand && l.hp_staged) {
-            const int64_t n0 = nC0 * hc.R;
-            OFP_REQUIRE(n0 < (1ll << 31), "ofp_detect_offline: %lld speculative runs in one call", (long long)n0);
-            HpRuns rl[2];
-            // layout of the two lists: z (16 B) of both first, then grp, then mask
-            unsigned char* rb = ws + l.o_hp_runs;
-            rl[0].z = reinterpret_cast<float4*>(rb);
-            rl[1].z = reinterpret_cast<float4*>(rb + n0 * 16);
-            rl[0].grp = reinterpret_cast<int32_t*>(rb + n0 * 32);
-            rl[1].grp = reinterpret_cast<int32_t*>(rb + n0 * 36);
-            rl[0].mask = reinterpret_cast<uint32_t*>(rb + n0 * 40);
-            rl[1].mask = reinterpret_cast<uint32_t*>(rb + n0 * 44);
-            int32_t* goff = reinterpret_cast<int32_t*>(ws + l.o_hp_goff);
-            int32_t* gcnt = goff + nC0;
-            const unsigned full_grid = (unsigned)cdiv(n0, HP_CAND_THREADS);
-            hipLaunchKernelGGL(k_hp_seg0, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[0], goff, gcnt, cuts[0], n0);
-            OFP_LAUNCH_CHECK("k_hp_seg0");
-            int cur = 0;
-            for (int m = 0; m < n_cuts; ++m) {
-                hipLaunchKernelGGL(k_hp_dedupe, dim3((unsigned)cdiv(nC0 * 16, 256)), dim3(256), 0, stream, rl[cur], rl[cur ^ 1],
-                                   goff, gcnt, nC0, stage_n + m);
-                cur ^= 1;
-                // (the grid is sized for the worst case, every run distinct; the lanes beyond the list leave at once)
-                if (m + 1 < n_cuts)
-                    hipLaunchKernelGGL(k_hp_seg, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
-                                       (const int*)(stage_n + m), cuts[m], cuts[m + 1]);
-                else
-                    hipLaunchKernelGGL(k_hp_seg_chunk, dim3(full_grid), dim3(HP_CAND_THREADS), 0, stream, hc, rl[cur],
-                                       (const int*)(stage_n + m));
-            }
-            OFP_LAUNCH_CHECK("k_hp_dedupe / k_hp_seg / k_hp_seg_chunk");
-            if (timed) OFP_HIP(hipEventRecord(ev[7], stream));
-        } else if (do_cand) {
-            const unsigned cand_grid = (unsigned)cdiv(nA, HP_CAND_THREADS);
-            if ((int64_t)cand_grid <= d->n_cus && d->t.concurrent_calls <= 1)
-                hipLaunchKernelGGL(k_hp_candidates<true>, dim3(cand_grid), dim3(HP_CAND_THREADS), 0, stream, hc, nA);
-            else
-                hipLaunchKernelGGL(k_hp_candidates<false>, dim3(cand_grid), dim3(HP_CAND_THREADS), 0, stream, hc, nA);
-            OFP_LAUNCH_CHECK("k_hp_candidates");
-            if (timed) OFP_HIP(hipEventRecord(ev[7], stream));
-        }
-        if (do_cand) {
-            pend.hp_timed = timed;
-            pend.staged = l.hp_staged;
-            pend.n_cuts = n_cuts;
-            std::memcpy(pend.cuts, cuts, sizeof(cuts));
-            int64_t steps = 0;
-            if (l.hp_staged) {  // stage 0 here; the later stages once their run counts are on the host (completion)
-                for (int64_t j = 0; j < l.hp_chunks; ++j)
-                    for (int r = 0; r < hc.R; ++r)
-                        steps += std::max<int64_t>(j * l.hp_L - l.hp_W + cuts[0], 0) -
-                                 std::max<int64_t>(j * l.hp_L - l.hp_W - r * hc.delta, 0);
-            } else {  // IIR steps this launch executes over all its lanes (the speculation's redundant work)
-                const int Rm = hc.R / hc.span;
-                for (int64_t j = 0; j < l.hp_chunks; ++j) {
-                    const int64_t run_end = std::min<int64_t>((j + hc.span) * l.hp_L, g.V);
-                    for (int r = 0; r < Rm; ++r)
-                        steps += run_end - std::max<int64_t>(j * l.hp_L - l.hp_W - r * hc.delta, 0);
-                }
-            }
-            pend.info[12] = steps * chains;
-        }
-        if (phase == 1 || phase == 6) return OFP_OK;
-        if (l.hp_staged)
-            OFP_HIP(hipMemcpyAsync(d->h_flags + 16, stage_n, 16 * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (!host_verify) {
-            // A fixed number of rounds enqueued ahead, no host round trip: a round whose predecessor left nothing
-            // open returns at once (a few microseconds).  The count follows what the detector's recent calls needed
-            // (+2); the last round's counters are read with the final synchronisation, and a call that has not
-            // converged by then (never seen with the margin) is repeated in the host-verified form.
-            hipLaunchKernelGGL(k_hp_plurality, dim3((unsigned)cdiv(nC0 * 16, 256)), dim3(256), 0, stream, hc, nC0);
-            OFP_LAUNCH_CHECK("k_hp_plurality");
-            const int NR = std::max(3, std::min(HP_MAX_ROUNDS, d->hp_rounds_hint));
-            int* c = reinterpret_cast<int*>(ws + l.o_hp_rounds);
-            for (int q = 0; q < NR; ++q) {
-                hc.counters = c + 2 * q;
-                hc.prev = q > 0 ? c + 2 * (q - 1) : nullptr;
-                hipLaunchKernelGGL(k_hp_match, dim3((unsigned)cdiv(nM, 256)), dim3(256), 0, stream, hc, nM);
-                hipLaunchKernelGGL(k_hp_resolve, dim3((unsigned)chains), dim3(64), 0, stream, hc);
-                hipLaunchKernelGGL(krun, dim3((unsigned)cdiv(nC, 64)), dim3(64), 0, stream, hc, nC);
-            }
-            OFP_LAUNCH_CHECK("k_hp_match / k_hp_resolve / k_hp_run");
-            pend.hp_rounds = NR;
-            OFP_HIP(hipMemcpyAsync(d->h_flags + 64, c, 2 * NR * sizeof(int), hipMemcpyDeviceToHost, stream));
-        } else {
-            hipLaunchKernelGGL(k_hp_plurality, dim3((unsigned)cdiv(nC0 * 16, 256)), dim3(256), 0, stream, hc, nC0);
-            OFP_LAUNCH_CHECK("k_hp_plurality");
-            // Verification rounds are enqueued a group at a time (three, then two) with ONE host synchronisation
-            // per group; a round whose predecessor left nothing unresolved returns at once (HpCand::prev).
-            const int* last = nullptr;
-            for (int it = 0;;) {
-                const int G = d->t.verify_group > 0 ? (int)std::min<int64_t>(d->t.verify_group, 8) : (it == 0 ? 3 : 2);
-                int* c = nullptr;
-                if (int rc = ctr.take(2 * G, &c)) return rc;
-                // (a call that needs hundreds of rounds recycles the last counter slots, which are zeroed again: the
-                //  previous round's counters may be among them and would then read "nothing left" -- no skip check then)
-                if (c == ctr.base + OFP_N_COUNTERS - 16) last = nullptr;
-                for (int q = 0; q < G; ++q) {
-                    hc.counters = c + 2 * q;
-                    hc.prev = last;
-                    hipLaunchKernelGGL(k_hp_match, dim3((unsigned)cdiv(nM, 256)), dim3(256), 0, stream, hc, nM);
-                    hipLaunchKernelGGL(k_hp_resolve, dim3((unsigned)chains), dim3(64), 0, stream, hc);
-                    hipLaunchKernelGGL(krun, dim3((unsigned)cdiv(nC, 64)), dim3(64), 0, stream, hc, nC);
-                    last = hc.counters;
-                }
-                OFP_LAUNCH_CHECK("k_hp_match / k_hp_resolve / k_hp_run");
-                int* flags = d->h_flags;  // per round: chains stuck at a break, chains with unverified guesses
-                OFP_HIP(hipMemcpyAsync(flags, c, 2 * G * sizeof(int), hipMemcpyDeviceToHost, stream));
-                OFP_HIP(hipStreamSynchronize(stream));
-                int stuck = 0;
-                for (int q = 0; q < G; ++q) {
-                    stuck = flags[2 * q] + flags[2 * q + 1];
-                    pend.info[0] += 1;
-                    pend.info[3] += stuck;
-                    if (stuck == 0) break;
-                }
-                it += G;
-                if (stuck == 0) break;
-                if (d->t.max_passes > 0 && it > d->t.max_passes)
-                    return ofp::fail(OFP_ERR_NOCONVERGE, "hp stage: %d chains still unresolved after %d rounds", stuck, it);
-            }
-        }
-    }
-    if (phase == 1 || phase == 6) return OFP_OK;  // (no high-pass: the head is the transpose alone)
-    pend.ahead = !host_verify;
-    if (host_verify || p.manual) pend.mm_nv = 0;
-    if (host_verify) pend.ar_nv = 0;
-    if (!p.hp_enabled || host_verify) pend.hp_rounds = 0;
-    if (timed) OFP_HIP(hipEventRecord(ev[1], stream));
-    ArArgs a;
-    a.g = g;
-    a.xdb = xdb;
-    a.dif = dif;
-    a.fa = p.fast_attack;
-    a.fr = p.fast_release;
-    a.sa = p.slow_attack;
-    a.sr = p.slow_release;
-    a.floor_db = p.floor_db;
-    a.L = l.ar_L;
-    a.W = l.ar_W;
-    a.Wc = l.ar_Wc;
-    a.Wf = l.ar_Wf;
-    a.n_chunks = l.ar_chunks;
-    a.S = l.ar_S;
-    {   // walk-through chunks as their own pass 0 (k_ar_warm_both): the merged layout with 16-byte-congruent buffers
-        a.through = (d->t.walk_through >= 0 && l.merge && l.ar_sym && (g.U & 3) == 0 && (l.ar_L & 3) == 0) ? 1 : 0;
-        // complete-line stores for the output walks (walk_lines): the throughput layout, everything a multiple of 32 steps
-        a.lines = (d->t.line_stores >= 0 && (a.through || d->t.line_stores > 0 || chains * l.ar_chunks >= (int64_t)32 * 4 * d->n_cus) && (g.U & 31) == 0 && (l.ar_L & 31) == 0) ? 1 : 0;
-    }
-    // dB and the per-chunk sums of the closed-form guess in one pass whenever both are wanted and the geometry
-    // allows 16-byte groups (otherwise k_rect_db, then k_ar_sym_local reading the dB stream once more)
-    const bool db_sym = l.ar_sym && p.hp_enabled && (g.U & 3) == 0 && (l.ar_L & 3) == 0 && d->t.fuse_db_sums >= 0;
-    if (from_stage > 0) {
-        // (the dB stream and the sums of the follower guess are in place)
-    } else if (db_sym) {
-        hipLaunchKernelGGL(k_rect_db_sym, dim3((unsigned)(chains * l.ar_chunks)), dim3(64), 0, stream, a, xdb,
-                           chains * l.ar_chunks, reinterpret_cast<double*>(ws + l.o_ar_P));
-        OFP_LAUNCH_CHECK("k_rect_db_sym");
-    } else {
-        hipLaunchKernelGGL(k_rect_db, dim3(ew_grid), dim3(256), 0, stream, g, xt, xdb, chains, p.hp_enabled ? 0 : 1,
-                           p.floor_db);
-        OFP_LAUNCH_CHECK("k_rect_db");
-    }
-    if (timed) OFP_HIP(hipEventRecord(ev[2], stream));
-
-    // --- followers
-    if (from_stage <= 1) {
-        const int64_t nt = chains * l.ar_chunks;
-        uint32_t* used = reinterpret_cast<uint32_t*>(ws + l.o_ar_state);
-        const unsigned grid = (unsigned)cdiv(nt, 64);
-        if (l.ar_sym) {
-            double* P = reinterpret_cast<double*>(ws + l.o_ar_P);
-            if (!db_sym) {
-                hipLaunchKernelGGL(k_ar_sym_local, dim3((unsigned)nt), dim3(64), 0, stream, a, nt, P);
-                OFP_LAUNCH_CHECK("k_ar_sym_local");
-            }
-            hipLaunchKernelGGL(k_ar_sym_combine, dim3((unsigned)chains), dim3(64), 0, stream, a, (const double*)P,
-                               used);
-            OFP_LAUNCH_CHECK("k_ar_sym_combine");
-        } else {
-            hipLaunchKernelGGL(k_ar_coarse, dim3(grid), dim3(64), 0, stream, a, nt, used);
-            OFP_LAUNCH_CHECK("k_ar_coarse");
-        }
-        if (l.ar_sym) {
-            const int64_t ntg = chains * cdiv(l.ar_chunks, l.ar_S);  // one run per group of S chunks
-            if (l.merge)
-                hipLaunchKernelGGL(a.lines ? k_ar_warm_both<true> : k_ar_warm_both<false>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0,
-                                   stream, a, ntg, used, used + 2 * nt);
-            else
-                hipLaunchKernelGGL(k_ar_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used);
-            OFP_LAUNCH_CHECK("k_ar_warm2");
-        } else {
-            hipLaunchKernelGGL(k_ar_warm, dim3(grid), dim3(64), 0, stream, a, nt, used);
-            OFP_LAUNCH_CHECK("k_ar_warm");
-        }
-        if (!host_verify) {
-            pend.ar_nv = l.ar_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, d->ar_pass_hint)) : 0;
-            if (int rc = run_jacobi_ahead("follower stage", a.lines ? k_ar_chunk<true> : k_ar_chunk<false>, a, nt, l.ar_chunks, used, pass_flags, pend.ar_nv, stream))
-                return rc;
-        } else {
-            int rc = run_jacobi("follower stage", a.lines ? k_ar_chunk<true> : k_ar_chunk<false>, a, nt, l.ar_chunks, used, ctr, d->h_flags, d->t.max_passes,
-                                d->t.verify_group > 0 ? (int)d->t.verify_group : 2, stream, &pend.info[1], &pend.info[3]);
-            if (rc != OFP_OK) return rc;
-        }
-    }
-    if (timed) OFP_HIP(hipEventRecord(ev[3], stream));
-    // block extremes for the crossing pass: whenever the 16-byte path of k_rel_out is taken for every tile (the same
-    // conditions as in the kernel) and a group of four never straddles two blocks
-    const bool use_sum = d->t.scan_skip >= 0 && (g.U & 3) == 0 && (l.tu & 3) == 0 && ((g.n_wb * g.C) & 3) == 0 &&
-                         (((int64_t)l.tu * g.C) & 3) == 0 && ((g.Nm * g.C) & 3) == 0 && (g.B & 3) == 0 && g.B >= 32;
-    uint32_t* sum_max = use_sum ? reinterpret_cast<uint32_t*>(ws + l.o_sum) : nullptr;
-    uint32_t* sum_minv = use_sum ? sum_max + n_clips * l.nb * g.C : nullptr;
-    if (from_stage <= 1) {
-        const size_t lds = tile_lds + (use_sum ? (size_t)2 * g.C * (l.tu / g.B + 2) * 4 : 0);
-        const int64_t n_tiles = cdiv(g.U, l.tu);
-        const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * d->n_cus / n_clips));
-        hipLaunchKernelGGL(k_rel_out, dim3(gx, (unsigned)n_clips), dim3(256), lds, stream, g, dif, d_rel,
-                           p.floor_db, l.tu, sum_max, sum_minv, l.nb, mm_il ? rel_warm : nullptr, mm_il ? 0 : 1, n_tiles);
-        OFP_LAUNCH_CHECK("k_rel_out");
-    }
-    if (timed) OFP_HIP(hipEventRecord(ev[4], stream));
-
-    // --- tracker (relative thresholds only; in manual mode its state is never read)
-    float* thr_mn = reinterpret_cast<float*>(ws + l.o_thr_mn);
-    float* thr_mx = reinterpret_cast<float*>(ws + l.o_thr_mx);
-    if (!p.manual) {
-        MmArgs a;
-        a.g = g;
-        a.rel = rel;
-        a.rel_il = d_rel;
-        a.rel_warm = rel_warm;
-        a.thr_mn = thr_mn;
-        a.thr_mx = thr_mx;
-        a.alpha_min = p.alpha_min;
-        a.alpha_max = p.alpha_max;
-        a.ialpha_min = d->ialpha_min;
-        a.ialpha_max = d->ialpha_max;
-        a.minmin = p.minmin;
-        a.min0 = p.min0;
-        a.max0 = p.max0;
-        a.nb = l.nb;
-        a.L = l.mm_L;
-        a.W = l.mm_W;
-        a.n_chunks = l.mm_chunks;
-        a.n_chains = chains;
-        a.S = l.mm_S;
-        a.through = (mm_il && d->t.walk_through >= 0) ? 1 : 0;
-        a.dirty = reinterpret_cast<uint8_t*>(ws + l.o_mm_dirty);
-        const int64_t nt = chains * l.mm_chunks;
-        uint32_t* used = reinterpret_cast<uint32_t*>(ws + l.o_mm_state);
-        {
-            const int64_t ntg = chains * cdiv(l.mm_chunks, l.mm_S);  // one run per group of S chunks
-            if (mm_il && g.C == 8)
-                hipLaunchKernelGGL(k_mm_warm_il<8>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used, used + 2 * nt);
-            else if (mm_il && g.C == 64)
-                hipLaunchKernelGGL(k_mm_warm_il<64>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used, used + 2 * nt);
-            else if (mm_il)
-                hipLaunchKernelGGL(k_mm_warm_il<4>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used, used + 2 * nt);
-            else if (l.merge)
-                hipLaunchKernelGGL(k_mm_warm_both, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used);
-            else
-                hipLaunchKernelGGL(k_mm_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, stream, a, ntg, used);
-            OFP_LAUNCH_CHECK("k_mm_warm2");
-        }
-        using MmLight = void (*)(const MmArgs&, int64_t, const uint32_t*, uint32_t*, uint32_t*, int*, const int*, hipStream_t);
-        const MmLight light_pl = +[](const MmArgs& m, int64_t, const uint32_t* ep, uint32_t* en, uint32_t* u, int* ch, const int* gate,
-                                     hipStream_t st) {
-            const int64_t n = m.n_chains * m.n_chunks;
-            hipLaunchKernelGGL(k_mm_maxpass, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u, ch, gate);
-        };
-        const MmLight light_il = +[](const MmArgs& m, int64_t, const uint32_t* ep, uint32_t* en, uint32_t* u, int* ch, const int* gate,
-                                     hipStream_t st) {
-            const int64_t n = m.n_chains * m.n_chunks;
-            if (m.g.C == 8)
-                hipLaunchKernelGGL(k_mm_maxpass_il<8>, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u, ch, gate);
-            else if (m.g.C == 64)
-                hipLaunchKernelGGL(k_mm_maxpass_il<64>, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u, ch, gate);
-            else
-                hipLaunchKernelGGL(k_mm_maxpass_il<4>, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, st, m, n, ep, en, u, ch, gate);
-        };
-        const MmLight light = mm_il ? light_il : light_pl;
-        const auto mm_chunk_k = mm_il ? (g.C == 8 ? k_mm_chunk_il<8> : (g.C == 64 ? k_mm_chunk_il<64> : k_mm_chunk_il<4>))
-                                      : (l.merge ? k_mm_chunk_both : k_mm_chunk);
-        if (!host_verify) {
-            pend.mm_nv = l.mm_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, d->mm_pass_hint)) : 0;
-            if (int rc = run_jacobi_ahead("tracker stage", mm_chunk_k, a,
-                                          l.merge ? nt : 2 * 64 * cdiv(nt, 64), l.mm_chunks, used, pass_flags + AHEAD_MAX_PASSES,
-                                          pend.mm_nv, stream, light, 2 * nt))
-                return rc;
-        } else {
-            int rc = run_jacobi("tracker stage", mm_chunk_k, a, l.merge ? nt : 2 * 64 * cdiv(nt, 64),
-                                l.mm_chunks, used, ctr, d->h_flags,
-                                d->t.max_passes, d->t.verify_group > 0 ? (int)d->t.verify_group : 2, stream, &pend.info[2], &pend.info[3],
-                                light, 2 * nt);
-            if (rc != OFP_OK) return rc;
-        }
-    }
-    if (timed) OFP_HIP(hipEventRecord(ev[5], stream));
-
-    // --- crossings per block, then the hysteresis state machine
-    ScanArgs sa;
-    sa.g = g;
-    sa.rel = rel;
-    sa.thr_mn = thr_mn;
-    sa.thr_mx = thr_mx;
-    sa.on_f = d->d_on_f;
-    sa.off_f = d->d_off_f;
-    sa.on_d = d->d_on_d;
-    sa.manual = p.manual;
-    sa.nb = l.nb;
-    sa.n_clips = n_clips;
-    sa.first_cross = reinterpret_cast<int32_t*>(ws + l.o_first);
-    sa.last_below = reinterpret_cast<int32_t*>(ws + l.o_last);
-    sa.vflag = reinterpret_cast<uint32_t*>(ws + l.o_vflag);
-    sa.sum_max = sum_max;
-    sa.sum_minv = sum_minv;
-    {
-        const int64_t total = n_clips * l.nb * g.C;
-        const unsigned bs_grid = (unsigned)std::min<int64_t>(cdiv(total, 4), 256 * 32);  // 4 waves per workgroup
-        if (mm_il) {
-            const unsigned il_grid = (unsigned)std::min<int64_t>(cdiv(n_clips * l.nb, 4), 256 * 32);
-            if (g.C == 8)
-                hipLaunchKernelGGL(k_block_scan_il<8>, dim3(il_grid), dim3(256), 0, stream, sa, d_rel);
-            else if (g.C == 64)
-                hipLaunchKernelGGL(k_block_scan_il<64>, dim3(il_grid), dim3(256), 0, stream, sa, d_rel);
-            else
-                hipLaunchKernelGGL(k_block_scan_il<4>, dim3(il_grid), dim3(256), 0, stream, sa, d_rel);
-        } else {
-            hipLaunchKernelGGL(k_block_scan, dim3(bs_grid), dim3(256), 0, stream, sa);
-        }
-        OFP_LAUNCH_CHECK("k_block_scan");
-    }
-    VisArgs va;
-    va.vflag = sa.vflag;
-    va.fc = sa.first_cross;
-    va.lb = sa.last_below;
-    int32_t* pc = reinterpret_cast<int32_t*>(ws + l.o_pc);
-    va.pc = pc;
-    va.nb = l.nb;
-    va.C = g.C;
-    va.vis_j = const_cast<int32_t*>(sm.vis_j);
-    va.vfc = const_cast<int32_t*>(sm.vfc);
-    va.vlb = const_cast<int32_t*>(sm.vlb);
-    va.vpc = const_cast<int32_t*>(sm.vpc);
-    va.nv = va_nv;
-    {
-        const int64_t n_lt = cdiv(l.nb, 256);
-        int32_t* lt = reinterpret_cast<int32_t*>(ws + l.o_ltile);
-        OFP_REQUIRE(n_lt * chains < (1ll << 31), "ofp_detect_offline: %lld block tiles in one call", (long long)(n_lt * chains));
-        const dim3 lgrid((unsigned)(n_lt * chains));
-        hipLaunchKernelGGL(k_last_clear<false>, lgrid, dim3(64), 0, stream, (const int32_t*)sa.last_below, pc, lt, l.nb, g.C, n_lt);
-        hipLaunchKernelGGL(k_last_clear_scan, dim3((unsigned)chains), dim3(64), 0, stream, lt, n_lt);
-        hipLaunchKernelGGL(k_last_clear<true>, lgrid, dim3(64), 0, stream, (const int32_t*)sa.last_below, pc, lt, l.nb, g.C, n_lt);
-        OFP_LAUNCH_CHECK("k_last_clear");
-    }
-    {
-        const int64_t n_tiles = cdiv(l.nb, 256);
-        int32_t* vtile = reinterpret_cast<int32_t*>(ws + l.o_vtile);
-        hipLaunchKernelGGL(k_visit_count, dim3((unsigned)n_tiles, (unsigned)n_clips), dim3(256), 0, stream, va, vtile, n_tiles);
-        hipLaunchKernelGGL(k_visit_scan, dim3((unsigned)n_clips), dim3(64), 0, stream, vtile, n_tiles, va.nv);
-        hipLaunchKernelGGL(k_visit_scatter, dim3((unsigned)n_tiles, (unsigned)n_clips), dim3(256), 0, stream, va,
-                           (const int32_t*)vtile, n_tiles);
-        OFP_LAUNCH_CHECK("k_visit_count / k_visit_scan / k_visit_scatter");
-    }
-    pend.sm_flag = false;
-    if (l.sm_seg && l.nb > 0) {
-        SmSegArgs ss;
-        ss.n_seg = cdiv(l.nb, SM_SEG);
-        const int64_t words = n_clips * ss.n_seg * 64 * 2;
-        ss.used = reinterpret_cast<int32_t*>(ws + l.o_smseg);
-        ss.endA = ss.used + words;
-        ss.endB = ss.endA + words;
-        ss.cnt = ss.endB + words;
-        const int tb = std::max(1, std::min(64, 1024 / g.C));
-        const size_t lds = (size_t)3 * tb * g.C * 4 + 64 * 4;
-        const dim3 grid((unsigned)ss.n_seg, (unsigned)n_clips);
-        constexpr int V = 4;  // verification passes enqueued ahead (a pass that finds nothing costs microseconds)
-        int* c = nullptr;
-        if (int rc = ctr.take(V, &c)) return rc;
-        hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, stream, sm, ss, 0, c);
-        for (int q = 1; q <= V; ++q) hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, stream, sm, ss, q, c + q - 1);
-        hipLaunchKernelGGL(k_sm_offsets, dim3((unsigned)n_clips), dim3(64), 0, stream, sm, ss);
-        hipLaunchKernelGGL(k_sm_seg, grid, dim3(64), lds, stream, sm, ss, -1, c);
-        OFP_LAUNCH_CHECK("k_sm_seg / k_sm_offsets");
-        pend.sm_flag = true;
-        OFP_HIP(hipMemcpyAsync(d->h_flags + 40, c + V - 1, sizeof(int), hipMemcpyDeviceToHost, stream));
-    } else {
-        if (int rc = sequential_machine()) return rc;
-    }
-    if (int rc = backtrack()) return rc;
-    if (!host_verify)
-        OFP_HIP(hipMemcpyAsync(d->h_flags + 96, pass_flags, 2 * AHEAD_MAX_PASSES * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (timed) OFP_HIP(hipEventRecord(ev[6], stream));
-    pend.valid = true;
-    if (enqueue_only) return OFP_OK;
-    OFP_HIP(hipStreamSynchronize(stream));
-    return complete();
-}
-
 int ofp_detect_offline(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm, float* d_rel,
                        ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws, int64_t ws_bytes,
                        int64_t* h_info, void* stream) {
-    return detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, h_info, stream, 0);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, stream, false)) return rc;
+    return run_sync(c, HEAD, h_info);
 }
 
 int ofp_detect_offline_enqueue(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm, float* d_rel,
                                ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws, int64_t ws_bytes,
                                void* stream) {
-    return detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, nullptr, stream, 0, 1);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, stream, true)) return rc;
+    return run_enqueued(c, HEAD);
 }
 
 int ofp_detect_offline_complete(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm, float* d_rel,
                                 ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws, int64_t ws_bytes,
                                 int64_t* h_info, void* stream) {
-    return detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, h_info, stream, 7);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, stream, true)) return rc;
+    OFP_REQUIRE(d->pend.valid, "ofp_detect_offline_complete: no enqueued call is pending on this detector");
+    OFP_REQUIRE(d->pend.args == c.a, "ofp_detect_offline_complete: the arguments differ from those of the enqueued call");
+    return complete(c, h_info);
 }
 
 int ofp_detect_offline_begin(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
                              void* d_ws, int64_t ws_bytes, void* stream) {
     int64_t dummy = 0;  // d_counts is not touched by the head; a non-NULL value passes the argument check
-    return detect_impl(d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, nullptr, stream, 1);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, stream, true)) return rc;
+    return run(c, HEAD, CANDIDATES, false);
 }
 
 int ofp_detect_offline_finish(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
                               float* d_rel, ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws,
                               int64_t ws_bytes, int64_t* h_info, void* stream) {
-    return detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, h_info, stream, 2);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, stream, false)) return rc;
+    return run_sync(c, ROUNDS, h_info);
 }
 
 int ofp_detect_offline_finish_enqueue(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
                                       float* d_rel, ofp_onset* d_records, int64_t cap, int64_t* d_counts, void* d_ws,
                                       int64_t ws_bytes, void* stream) {
-    return detect_impl(d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, nullptr, stream, 2, 1);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, d_rel, d_records, cap, d_counts, d_ws, ws_bytes, stream, true)) return rc;
+    return run_enqueued(c, ROUNDS);
 }
 
 int ofp_detect_offline_begin_input(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
                                    void* d_ws, int64_t ws_bytes, void* stream) {
     int64_t dummy = 0;
-    return detect_impl(d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, nullptr, stream, 5);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, stream, true)) return rc;
+    return run(c, HEAD, HEAD, false);
 }
 
 int ofp_detect_offline_begin_iir(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm,
                                  void* d_ws, int64_t ws_bytes, void* stream) {
     int64_t dummy = 0;
-    return detect_impl(d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, nullptr, stream, 6);
+    Call c;
+    if (int rc = open_call(c, d, d_x, n_clips, N, warm, nullptr, nullptr, 0, &dummy, d_ws, ws_bytes, stream, true)) return rc;
+    return run(c, CANDIDATES, CANDIDATES, false);
 }
 
 }  // extern "C"

@@ -4,9 +4,25 @@
 
 #include "ofp_common.h"
 
-// what a call that was only enqueued (ofp_detect_offline_enqueue) leaves for its completion
+// the arguments of an enqueued call, which ofp_detect_offline_complete must be given again
+struct ofp_detect_args {
+    int64_t n_clips = 0, N = 0, warm = 0;
+    float* rel = nullptr;
+    ofp_onset* records = nullptr;
+    int64_t cap = 0;
+    int64_t* counts = nullptr;
+    void* ws = nullptr;
+    int64_t ws_bytes = 0;
+    bool operator==(const ofp_detect_args& o) const {
+        return n_clips == o.n_clips && N == o.N && warm == o.warm && rel == o.rel && records == o.records && cap == o.cap &&
+               counts == o.counts && ws == o.ws && ws_bytes == o.ws_bytes;
+    }
+};
+
+// what the stages of a call leave for its completion (ofp_detect_offline_complete, or the synchronous call's own)
 struct ofp_detect_pending {
-    bool valid = false;        // an enqueued call awaits ofp_detect_offline_complete
+    bool valid = false;        // an enqueued call awaits ofp_detect_offline_complete (false after a synchronous call)
+    ofp_detect_args args;      // its arguments
     bool empty = false;        // fewer samples than one block: nothing ran
     bool timed = false;        // the stage events were recorded (not while capturing a graph)
     bool hp_timed = false;

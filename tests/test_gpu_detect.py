@@ -421,11 +421,41 @@ def test_the_whole_call_is_one_hipgraph_and_replays_on_other_clips(det, tuning):
         assert len(c) > 50
 
 
+def test_complete_without_the_enqueued_call_is_refused(det):
+    """ofp_detect_offline_complete refuses on the host, before any launch, when no enqueued call is pending (a plain
+    detect leaves none) or when its arguments are not those of the enqueued call; the pending call stays completable."""
+    import torch
+    from onset_fingerprinting_amd._lib import OnsetFPError
+    src = synth.c2_drums(3.0, 8, SR, seed=3)
+    bd = det.BatchDetector(8, 256, sr=SR)
+    x = torch.from_numpy(src[None]).cuda().contiguous()
+    out = bd.detect(x, cap_per_clip=2048)
+    torch.cuda.synchronize()
+    before = {k: out[k].clone() for k in ("records", "counts", "rel")}
+    with pytest.raises(OnsetFPError, match="no enqueued call"):
+        bd.complete(x, out)
+    bd.enqueue(x, out=out, cap_per_clip=2048)
+    torch.cuda.synchronize()
+    shorter = x[:, : x.shape[1] // 2].contiguous()
+    with pytest.raises(OnsetFPError, match="arguments differ"):
+        bd.complete(shorter, out)
+    torch.cuda.synchronize()
+    for k, v in before.items():   # (the enqueued call wrote the same outputs again; nothing else ran)
+        assert torch.equal(out[k], v), k
+    bd.complete(x, out)
+    recs = det.BatchDetector.records_to_numpy(out)[0]
+    c, o, _ = oracle_records(src, block_size=256, sr=SR)
+    assert np.array_equal(recs["channel"], c) and np.array_equal(recs["sample"], o)
+
+
 THROUGHPUT = dict(lane_merge=1, hp_dedupe=1, hp_early=1, sm_segments=1)
 
 
 @pytest.mark.parametrize("B,sr,C,N", [(100, 44100, 3, 133333), (250, 48000, 2, 100001), (441, 44100, 5, 88200),
-                                      (30, 22050, 1, 50003), (512, 96000, 7, 200000)])
+                                      (30, 22050, 1, 50003), (512, 96000, 7, 200000),
+                                      # warm-up 24132 (its gap to the block-aligned 24100 not a multiple of 32) while the
+                                      # stream's ends U, V are: the complete-line IIR walk must not be taken
+                                      (100, 48264, 4, 128700)])
 @pytest.mark.parametrize("tuning", [None, THROUGHPUT])
 def test_sizes_that_are_multiples_of_nothing(det, B, sr, C, N, tuning):
     """Block sizes, rates and lengths that break every alignment the fast paths rely on (16-byte groups, block-aligned
