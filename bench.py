@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the onset-fingerprinting hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c4] [--clips n] [--inflight D]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c4] [--clips n] [--inflight D] [--full]
 
 One step = one pass of detect -> rFFT |X|^2 -> 40-mel -> FCNN (the last three in ONE kernel) over one
 batch of synthetic clips already resident in HBM, followed by the exchange that collates the onset
 records (an RCCL all-gather when N > 1).  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's `value` needs: it synthesises the clips, warms up, times the K steps, writes
+`--dump-outputs` if asked and prints the line (with the figures that come from the timed steps themselves: `stage_ms`,
+`roofline`, `roofline_e2e`, ...).  `--full` adds everything that takes runs of its own, after the timed region: the
+device-copy rate (`roofline.peak_measured`), the same step with nothing else on the GPU (`roofline.alone`,
+`stage_ms_alone`), the extra configurations under `config` (below; `--no-extras` drops them), the CPU baseline and
+the parity check of the timed result against the oracle (`cpu_baseline`, `parity`; `--no-cpu` drops them).
 
 Launch.  `--gpus N` with N > 1 and no RANK in the environment makes THIS process a launcher: before
 anything touches a GPU it starts N ranks of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one
@@ -19,10 +26,10 @@ Workloads (BASELINE.json configs):
       the clips side by side -- 384 chains, 4.4 GB of audio; rounds 1-2 used 16: the larger batch lets the
       detector's speculative passes use longer chunks, 145 -> 173 M frames/s with the same command; 212 M on the last build of round 3).
       Every rank owns its own clips: scaling "weak".
-      `config.one_clip_per_step` is the same path on ONE clip per step (8 chains, latency-bound).
+      `config.one_clip_per_step` (--full) is the same path on ONE clip per step (8 chains, latency-bound).
   c4  (default at N > 1)  512 clips x 4 ch x 10 s in total, sharded contiguously over the ranks
-      (configs[3]): total work fixed, scaling "strong".  `config.whole_batch_on_one_gpu` (rank 0, after
-      the timed region, four steps in flight) is the same 512 clips on one GPU -- the base the strong-scaling
+      (configs[3]): total work fixed, scaling "strong".  `config.whole_batch_on_one_gpu` (--full; rank 0,
+      after the timed region, four steps in flight) is the same 512 clips on one GPU -- the base the strong-scaling
       ratio refers to.
 `--inflight D` keeps D steps in flight per GPU (default 6 for c2; 6 / 12 for C4 shards of > 128 / <= 128 clips), each on its own pipeline instance with its own DISTINCT clips, streams and host thread: while one
 batch sits in the latency-bound verification rounds of its detector the others keep the chip busy.  With steps
@@ -185,53 +192,32 @@ def _fanout_worker(job):
     return r["frames"], r["seconds"]
 
 
-def _synth_worker(job):
-    kind, ident, seconds, C = job
-    from onset_fingerprinting_amd import synth
-    return synth.c2_drums(seconds, C, SR, seed=ident) if kind == "c2" else synth.c4_clip(ident, seconds, C, SR)
-
-
-def under_profiler():
-    """rocprofv3 preloads its tool library into this process AND into every child; with --pmc that library has
-    initialised the GPU before main() runs, and a process that has done so must not start (exec) others on this pool.
-    Round 2's first counter pass of tools/pmc_detect.sh sat in exactly that: eight spawned synthesis workers, each
-    with the counter service attached, were SIGTERMed by Pool.__exit__ while the tool was finalising in them, and the
-    parent then never came out of its own counter-service initialisation (no "HSA version ... initialized" line in
-    gpurun_out/pmc_detect/SQ_INSTS_VALU...log before the 200 s limit).  Under a profiler nothing is spawned."""
-    e = os.environ
-    return any("rocprof" in e.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB")) or \
-        any(k.startswith("ROCPROF") for k in e)
-
-
-def synth_batch(kind, idents, seconds, C, workers):
-    """The clips of one batch (host synthesis, several processes: a C2 clip takes seconds of numpy).  OFP_SYNTH_CACHE
-    names a directory of per-clip .npy files (filled on first use): a profiled run loads its clips from there instead
-    of synthesising them in child processes (see under_profiler)."""
+def synth_batch(kind, idents, seconds, C, workers, out=None):
+    """The clips of one batch, synthesised on the host by `workers` threads: a C2 clip takes half a second of numpy,
+    nearly all of it in the generator and the array arithmetic, which release the GIL, and threads hand their 92 MB
+    clips over without copying them between processes.  -> [len(idents), N, C] float32; with `out` (a tensor of that
+    shape, on the GPU for the bench) every clip goes into its row as soon as it is made, and `out` is returned."""
     import numpy as np
-    jobs = [(kind, int(i), seconds, C) for i in idents]
-    cache = os.environ.get("OFP_SYNTH_CACHE")
-    if cache:
-        os.makedirs(cache, exist_ok=True)
-        paths = [Path(cache) / f"{k}_{i}_{s:g}_{c}.npy" for k, i, s, c in jobs]
-        missing = [j for j, p in zip(jobs, paths) if not p.exists()]
-        if missing:
-            made = synth_batch_uncached(missing, 1 if under_profiler() else workers)
-            for j, x in zip(missing, made):
-                np.save(Path(cache) / f"{j[0]}_{j[1]}_{j[2]:g}_{j[3]}.npy", x)
-        return [np.load(p) for p in paths]
-    return synth_batch_uncached(jobs, 1 if under_profiler() else workers)
+    from concurrent.futures import ThreadPoolExecutor
 
+    from onset_fingerprinting_amd import synth
+    idents = [int(i) for i in idents]
+    if out is None:
+        out = np.empty((len(idents), int(seconds * SR), C), dtype=np.float32)
+    if isinstance(out, np.ndarray):
+        put = out.__setitem__
+    else:
+        import torch
 
-def synth_batch_uncached(jobs, workers):
-    if workers <= 1 or len(jobs) == 1:
-        return [_synth_worker(j) for j in jobs]
-    import multiprocessing as mp
-    pool = mp.get_context("spawn").Pool(min(workers, len(jobs)))
-    try:
-        return pool.map(_synth_worker, jobs, chunksize=max(1, len(jobs) // (4 * workers)))
-    finally:  # close + join: the workers leave by themselves (terminate() signals them while a profiler's preloaded
-        pool.close()  # library is finalising in them, which fills its log with "Aborted")
-        pool.join()
+        def put(i, x):
+            out[i].copy_(torch.from_numpy(x))
+
+    def one(i):
+        put(i, synth.c2_drums(seconds, C, SR, seed=idents[i]) if kind == "c2" else synth.c4_clip(idents[i], seconds, C, SR))
+
+    with ThreadPoolExecutor(max(1, min(workers, len(idents)))) as ex:
+        list(ex.map(one, range(len(idents))))
+    return out
 
 
 _CAL = {}
@@ -334,8 +320,11 @@ def main():
                     "processes side by side; every step keeps its own exchange (0: small shards are grouped up to ~384 clips per "
                     "call, by a divisor of --steps; 1: never)")
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="audio seconds of one clip given to the CPU baseline")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra figures (one clip per step, whole batch)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what takes runs of its own: "
+                    "device-copy rate, the step alone, the extra configurations, CPU baseline and parity (see the module docstring)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the untimed extra configurations (one clip per "
+                    "step, whole batch)")
     ap.add_argument("--tuning", type=str, default="", help="JSON dict of ofp_detect_tuning fields (experiments)")
     ap.add_argument("--exp", type=str, default="", help="EXPERIMENTS (the line says so in config.experiment and is not the "
                     "metric): JSON dict with detector kwargs (hipass_freq, on_threshold, ...) and/or \"no_stft\": true")
@@ -442,17 +431,17 @@ def main():
             dist.barrier()
 
     def make_clips(slot):
-        """[n_local, N, C] on the device.  c2: one DISTINCT clip per (rank, slot, clip): seed 1 + rank + 97*slot
-        + 7919*clip.  c4: clip ids clip_lo.. from the recipe for slot 0; further slots (steps in flight) are
-        distinct derived batches (channels rotated, gain changed) -- the host-side synthesis of another 512
-        clips would take longer than the whole bench."""
+        """[n_local, N, C] on the device, and (--full: the parity check reads it) a host copy of its clip 0.  c2: one
+        DISTINCT clip per (rank, slot, clip): seed 1 + rank + 97*slot + 7919*clip.  c4: clip ids clip_lo.. from the
+        recipe for slot 0; further slots (steps in flight) are distinct derived batches (channels rotated, gain
+        changed) -- the host-side synthesis of another 512 clips would take longer than the whole bench."""
         workers = max(1, usable_cpus() // (world if world <= 2 else 1))
+        x = torch.empty((n_local, N, C), dtype=torch.float32, device=dev)
         if workload == "c2":
-            xs = synth_batch("c2", [1 + rank + 97 * slot + 7919 * i for i in range(n_local)], seconds, C, workers)
+            synth_batch("c2", [1 + rank + 97 * slot + 7919 * i for i in range(n_local)], seconds, C, workers, out=x)
         else:
-            xs = synth_batch("c4", [clip_lo + i for i in range(n_local)], seconds, C, workers)
-        x = torch.from_numpy(np.stack(xs)).to(dev)
-        return x.contiguous(), xs[0]
+            synth_batch("c4", [clip_lo + i for i in range(n_local)], seconds, C, workers, out=x)
+        return x, (x[0].cpu().numpy() if args.full else None)
 
     def derive(slot0, slot):
         """c4, steps in flight: a distinct batch per slot derived on the device (channels rotated, gain changed)."""
@@ -596,13 +585,14 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- untimed extras on the same process: what one clip per step costs (c2) / the whole batch on one GPU (c4)
+    # ---- --full: untimed figures that take runs of their own, on the same process (the device-copy rate, the step alone,
+    # what one clip per step costs (c2) / the whole batch on one GPU (c4), the CPU baseline and the parity check)
     extras = {}
     alone_ms = {}
     copy_gbs = None
     host_clip0 = None
     parity_out = None
-    if not rehearsal:
+    if args.full:
         host_clip0 = slots[(args.steps // G - 1) % D][1]  # host copy of clip 0 of the batch the last timed step ran on (c4: slot 0 only)
         if rank == 0 and world == 1 and not args.no_cpu and res is not None:
             # clip 0 of the last TIMED step, taken to the host before anything else reuses the pipelines' output buffers
@@ -626,7 +616,7 @@ def main():
                 del ca, cb
             except Exception:
                 copy_gbs = None
-    if D > 1 and not rehearsal:
+    if args.full and D > 1:
         # the SAME batch step with nothing else on the GPU (two repetitions after the timed region): what each launch
         # takes when it does not share the chip with the other steps in flight -- next to the in-flight durations
         barrier()
@@ -637,7 +627,7 @@ def main():
             st.update(o_a["spectral_ms"])
             alone_ms = {k: float(v) for k, v in st.items()}
         barrier()
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if workload == "c2" and (n_local > 1 or D > 1):
             p1 = FingerprintPipeline(C, NFFT, HOP, SR, NMELS, device=local, cap_per_clip=cap_clip)
             x1 = slots[0][0][:1].contiguous()
@@ -700,9 +690,8 @@ def main():
                 slots.clear()
                 torch.cuda.empty_cache()
                 Dc, Cc, Nc = 6, C4["C"], int(C4["seconds"] * SR)
-                xs4 = synth_batch("c4", list(range(C4["clips"])), C4["seconds"], Cc, max(1, usable_cpus()))
-                x4 = torch.from_numpy(np.stack(xs4)).to(dev).contiguous()
-                del xs4
+                x4 = torch.empty((C4["clips"], Nc, Cc), dtype=torch.float32, device=dev)
+                synth_batch("c4", range(C4["clips"]), C4["seconds"], Cc, usable_cpus(), out=x4)
                 xs_slots = [x4] + [(torch.roll(x4, s, dims=2) * (1.0 - 0.07 * s)).contiguous() for s in range(1, Dc)]
                 p4 = [FingerprintPipeline(Cc, NFFT, HOP, SR, NMELS, device=local, cap_per_clip=1024) for _ in range(Dc)]
                 for pp in p4:
@@ -891,7 +880,7 @@ def main():
                     "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
                     "ms": cand_ms, "algorithmic_bytes_per_frame": 4 * HOP,
                     "runs_that_walk_a_chunk": passes.get("hp_chunk_runs"), "issue": issue}]
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             secs = min(args.cpu_seconds, seconds)
             n = int(secs * SR)
             sd = fcnn_state()

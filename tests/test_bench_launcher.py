@@ -80,3 +80,22 @@ def test_dump_outputs_writes_the_last_steps_exchanged_records(tmp_path):
     assert on.dtype == np.float64 and on.shape == (3 * 512, 3)
     assert np.array_equal(np.unique(on[:, 0]), np.arange(512))   # (clip, channel, sample) of both shards
     assert np.array_equal(on[:, 2], 1000 * on[:, 0] + np.tile(np.arange(3), 512))
+
+
+def test_synth_batch_gives_the_recipes_clips_bit_for_bit():
+    """The bench's clips come from threads that write into one batch, or into a given tensor row by row (the GPU
+    batch in a real run): every row is the synth recipe's clip, bit for bit, in the order of the seeds."""
+    import numpy as np
+    import torch
+
+    import bench
+    from onset_fingerprinting_amd import synth
+    seeds = [1, 1 + 7919, 2 + 97]
+    x = bench.synth_batch("c2", seeds, 2.0, 8, 2)
+    assert x.shape == (3, 96000, 8) and x.dtype == np.float32
+    for row, s in zip(x, seeds):
+        assert np.array_equal(row.view(np.uint32), synth.c2_drums(2.0, 8, 48000, seed=s).view(np.uint32))
+    t = torch.empty((5, 480000, 4))
+    assert bench.synth_batch("c4", range(3, 8), 10.0, 4, 3, out=t) is t
+    for i in range(5):
+        assert np.array_equal(t[i].numpy().view(np.uint32), synth.c4_clip(3 + i, 10.0, 4, 48000).view(np.uint32))

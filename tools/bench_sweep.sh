@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r02_bench_sweep; mkdir -p $O
 for cfg in "8 1" "1 1" "4 1" "16 1" "8 2" "1 8"; do
   set -- $cfg
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --clips $1 --inflight $2 --no-cpu > $O/c2_clips$1_if$2.json 2> $O/c2_clips$1_if$2.err || echo "FAILED $cfg"
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --clips $1 --inflight $2 --full --no-cpu > $O/c2_clips$1_if$2.json 2> $O/c2_clips$1_if$2.err || echo "FAILED $cfg"
   python -c "
 import json,sys
 j=json.load(open('$O/c2_clips$1_if$2.json'))

@@ -1,17 +1,16 @@
 #!/bin/bash
 # Round 3: the whole measurement set behind the bench line, on the GPU box through gpurun -> gpurun_out/prof_<tag>/
-# (copy what is to be judged into profiles/r03/).  Nothing here spawns processes under the profiler: the clips of
-# the profiled runs come from the cache the un-profiled bench run fills (bench.py: under_profiler / OFP_SYNTH_CACHE).
+# (copy what is to be judged into profiles/r03/).  Nothing here spawns processes under the profiler: bench.py
+# synthesises its clips in threads.
 #   tools/profile_r3.sh <tag> [quick]
 TAG=${1:-r03}; QUICK=$2
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $O
-export OFP_SYNTH_CACHE=/tmp/ofp_clip_cache
 cd /tmp && export TMPDIR=/tmp
 B="python3 $ROOT/bench.py"
-echo "== bench (default command; fills the clip cache)"; date
-timeout -k 10 900 $B > $O/bench.json 2> $O/bench.err || { echo "bench FAILED"; tail -5 $O/bench.err; }
+echo "== bench (default command, --full)"; date
+timeout -k 10 900 $B --full > $O/bench.json 2> $O/bench.err || { echo "bench FAILED"; tail -5 $O/bench.err; }
 timeout -k 10 300 $B --clips 1 --inflight 1 --no-cpu --no-extras > $O/bench_one_clip_per_step.json 2>> $O/bench.err
 echo "== kernel statistics of the in-flight regime (40 timed steps, 6 in flight)"; date
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --no-cpu --no-extras --steps 40 --warmup 6 > $O/bench_under_rocprof.json 2> $O/stats.err

@@ -8,7 +8,7 @@ O=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python3 $ROOT/bench.py"
-timeout -k 10 400 $B > $O/bench.json 2> $O/bench.err || echo "bench FAILED"
+timeout -k 10 400 $B --full > $O/bench.json 2> $O/bench.err || echo "bench FAILED"
 timeout -k 10 300 $B --clips 1 --inflight 1 --no-cpu --no-extras > $O/bench_one_clip_per_step.json 2>> $O/bench.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --no-cpu --no-extras > $O/bench_under_rocprof.json 2> $O/stats.err
 cp $(ls $O/stats/*/*kernel_stats.csv | tail -1) $O/kernel_stats.csv
