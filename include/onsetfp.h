@@ -653,6 +653,70 @@ int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_grou
                       int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream);
 int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int32_t c1, float* d_out, void* stream);
 
+/* ---- 2-D hit location: find_lag, MultilateratePaired, lag_intensity_map (multilateration.py) -------------------
+ * ofp_find_lags: find_lag / find_lag_multi (:878-899) for n_rows row pairs.  Row r of a starts at
+ *   d_a + (d_a_off ? d_a_off[r] : r * a_stride) and steps elem_stride floats (b likewise, same element stride), so
+ *   the rows can be columns of an [N][C] clip; lengths d_len_a[r] / d_len_b[r] (or len_a / len_b for every row,
+ *   which are also the upper bounds of the per-row lengths), 1..4096.  The correlation is np.correlate(a, b,
+ *   "full") by the canon of ofp_xcorr_lag (fp64 over ascending index, rounded once to fp32).
+ *   d_lag [n_rows]: np.argmax (first maximum, a NaN wins) - (len_a - 1); INT32_MIN for a row of length 0.
+ *   top_n in 0..16; with top_n > 0: d_peak_lag / d_peak_val [n_rows][top_n] the peaks of
+ *   scipy.signal.find_peaks(cc) (strict local maxima, a plateau at its middle (left + right) // 2, never an end
+ *   point) by descending value, exact ties by ascending index (numpy's argsort leaves their order undefined), as
+ *   lags and cc ** 2 in fp32; unused slots (0, NaN).  d_n_peaks [n_rows] (may be NULL when top_n == 0): the slots
+ *   used (<= top_n; 0 when top_n == 0), -1 when the correlation holds a non-finite value (no peaks reported), -2
+ *   for a row of length 0.
+ * ofp_vote_index: a bucket index of n_maps lag maps (map k is d_maps + d_map_ids[k] * cells), built once: every
+ *   value must be NaN or an integer in [d_vmin[k], d_vmin[k] + n_buckets).  d_starts [n_maps][n_buckets + 1]: the
+ *   first slot of each value; d_sorted [n_maps][cells]: the non-NaN cells ordered by value, ascending cell index
+ *   within a value (a stable counting sort).  d_bad [n_maps]: 1 where a value broke the rule (the index is then
+ *   incomplete).  cells <= 2^20, n_buckets <= 32768, n_maps <= 128.
+ * ofp_paired_windows: MultilateratePaired.locate_cc's windows x[onset - left : onset + right] (clipped at the
+ *   clip's end) of B hits in clips [n_clips][n_samples][n_channels] (channel k is sensor k, n_channels >= S), for
+ *   the first channel i and its neighbours (i - 1) % S, (i + 1) % S: rows 2h, 2h + 1 of d_a_off / d_b_off / d_len
+ *   [2B], ready for ofp_find_lags (elem_stride n_channels).  Hits are d_onset / d_first / d_clip [B] (d_clip may
+ *   be NULL: clip 0), or, with d_groups, the rows of ofp_group_onsets (B = n_clips * cap_groups): the earliest
+ *   channel present, ties by channel.  d_first_out, d_status [B]: OFP_PAIRED_OK or an OFP_PAIRED_* code (length 0
+ *   rows then).  left >= 0, right >= 1, left + right <= 4096.
+ * ofp_paired_vote: the vote of locate_cc (:839-875) for B hits, from the index (map 2i + k of the index is
+ *   sensor i's neighbour k, as above) and d_lags [B][2] (from ofp_find_lags): the cells with
+ *   lag - tol < map < lag + tol are counted over the neighbour maps (one map when S == 2) and the smallest flat
+ *   index among the cells with the highest count is returned (np.argmax; cell 0 when no cell counts).  Hits whose
+ *   d_status_in is not OFP_PAIRED_OK keep it and get cell -1, NaN coordinates.  d_cell [B], d_xy [B][2] = (col -
+ *   (side-1)/2, (side-1)/2 - row), d_rphi [B][2] = cartesian_to_polar(x, y, radius), d_status [B].  d_res (NULL, or
+ *   with d_maps and d_map_ids): the full vote grids [B][side][side] float32 (the reference's self.res), B <= 65535.
+ * ofp_paired_solve: MultilateratePaired.locate (:798-834) for B rows: d_sensors [S][3] (z = 0), d_lags [B][2],
+ *   d_first [B] -> the weighted initial guess, hybrj as ofp_trilaterate (origin i, a = (i-1) % S, b = (i+1) % S,
+ *   delta = lag * c / sr), d_root [B][2], d_rphi [B][2] = cartesian_to_polar(root, radius), d_ier [B] (fsolve's
+ *   ier; the reference raises unless 1; OFP_PAIRED_BAD_HIT for a first sensor outside 0..S-1).
+ * ofp_intensity_maps: lag_intensity_map's signal strengths (:1065-1101): d_mics [2][3] -> d_out [2][side][side],
+ *   10 log10 of attenuate_intensity (source intensity 1) at p = (col - r, row - r, 0), fp64 rounded to float32. */
+#define OFP_PAIRED_OK 0
+#define OFP_PAIRED_UNUSED (-1)        /* group row beyond the clip's group count */
+#define OFP_PAIRED_NO_CHANNEL (-2)    /* group row without a channel */
+#define OFP_PAIRED_NEG_WINDOW (-5)    /* onset - left < 0 (refused; the reference's slice would wrap) */
+#define OFP_PAIRED_EMPTY_WINDOW (-6)  /* the window is empty (onset beyond the clip) */
+#define OFP_PAIRED_BAD_HIT (-7)       /* first sensor or clip index out of range */
+int ofp_find_lags(const float* d_a, const float* d_b, int64_t n_rows, int64_t a_stride, int64_t b_stride,
+                  int32_t elem_stride, const int64_t* d_a_off, const int64_t* d_b_off, int32_t len_a, int32_t len_b,
+                  const int32_t* d_len_a, const int32_t* d_len_b, int32_t top_n, int32_t* d_lag, int32_t* d_peak_lag,
+                  float* d_peak_val, int32_t* d_n_peaks, void* stream);
+int ofp_vote_index(const float* d_maps, int64_t cells, const int32_t* d_map_ids, int32_t n_maps,
+                   const int32_t* d_vmin, int32_t n_buckets, int32_t* d_starts, int32_t* d_sorted, int32_t* d_bad,
+                   void* stream);
+int ofp_paired_windows(int64_t n_clips, int64_t n_samples, int32_t n_channels, int32_t S, const int64_t* d_onset,
+                       const int32_t* d_first, const int32_t* d_clip, const int64_t* d_groups, int64_t cap_groups,
+                       const int64_t* d_n_groups, int64_t B, int32_t left, int32_t right, int64_t* d_a_off,
+                       int64_t* d_b_off, int32_t* d_len, int32_t* d_first_out, int32_t* d_status, void* stream);
+int ofp_paired_vote(const float* d_maps, const int32_t* d_map_ids, const int32_t* d_starts, const int32_t* d_sorted,
+                    const int32_t* d_vmin, int32_t n_buckets, int32_t S, int32_t side, const int32_t* d_first,
+                    const int32_t* d_lags, const int32_t* d_status_in, int64_t B, double tol, double radius,
+                    int32_t* d_cell, double* d_xy, double* d_rphi, int32_t* d_status, float* d_res, void* stream);
+int ofp_paired_solve(const double* d_sensors, int32_t S, const int32_t* d_lags, const int32_t* d_first, int64_t B,
+                     double c, double sr, double radius, double xtol, int32_t maxfev, double* d_root, double* d_rphi,
+                     int32_t* d_ier, void* stream);
+int ofp_intensity_maps(const double* d_mics, int32_t r, double reflectivity, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

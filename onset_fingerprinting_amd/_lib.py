@@ -193,6 +193,16 @@ SIGNATURES = {
     "ofp_locate_groups": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
                                          _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_locate_section": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ofp_find_lags": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp,
+                                     _vp, _vp, _vp, _vp]),
+    "ofp_vote_index": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ofp_paired_windows": (ctypes.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofp_paired_vote": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _f64, _f64,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofp_paired_solve": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp,
+                                        _vp]),
+    "ofp_intensity_maps": (ctypes.c_int, [_vp, _i32, _f64, _vp, _vp]),
 }
 
 _lib = None

@@ -5,10 +5,12 @@
 // Canon for the correlation values (the tests' CPU checker accumulates the same way): every
 // lag's dot product is accumulated in fp64 over ascending i by ONE thread (fp32 x fp32 products
 // are exact in fp64), rounded once to fp32 and divided by its contribution count in fp32.  Only
-// the lags inside the searched window are computed, never the full 2n-1.
+// the lags inside the searched window are computed, never the full 2n-1.  The accumulation itself is
+// ofp::cc_dot (ofp_xcorr_canon.h), shared with ofp_locate2d.hip.
 #include <algorithm>
 
 #include "ofp_common.h"
+#include "ofp_xcorr_canon.h"
 
 namespace {
 
@@ -31,10 +33,7 @@ __device__ __forceinline__ void py_slice(int start, int stop, int len, int* lo, 
 
 // Entry j of the normalised full correlation of xs, ys (length n), detection.py:244-250.
 __device__ __forceinline__ float cc_entry(const float* xs, const float* ys, int n, int cutoff, int j) {
-    const int k = j - (n - 1);
-    const int i0 = k < 0 ? -k : 0, i1 = k > 0 ? n - k : n;
-    double acc = 0.0;
-    for (int i = i0; i < i1; ++i) acc += (double)xs[i + k] * (double)ys[i];
+    const double acc = ofp::cc_dot(xs, n, ys, n, j - (n - 1));
     const int m = j < n ? j : 2 * n - 2 - j;
     const int cnt = m < cutoff ? cutoff : m + 1;
     return __fdiv_rn((float)acc, (float)cnt);

@@ -10,12 +10,24 @@ Same names, arguments and returns as the reference for:
     ``locate`` -- the reference's host state machine, whose cross-correlation step runs on the device
     (``ofp_locate_section`` -> ``ofp_xcorr_lag`` -> ``ofp_adjust_onset``).
 
-Batched, device-resident addition: ``locate_groups_device`` locates every onset group ``group_onsets_device``
-found, in one pass without host synchronisation.
+  * ``find_lag`` / ``find_lag_multi`` (GPU, ``ofp_find_lags``: np.correlate by the fp64 canon of ofp_xcorr_lag,
+    np.argmax, scipy.signal.find_peaks and the top-n order; ties in that order by ascending lag, and a correlation
+    with a non-finite value raises ValueError in ``find_lag_multi``),
+  * ``Multilaterate``: the 2-D locator, its maps by ``ofp_lag_maps``, ``is_legal_3d`` by ``ofp_locate_legal``,
+    ``trilaterate`` by ``ofp_trilaterate`` and ``locate`` the reference's host state machine,
+  * ``MultilateratePaired``: the grid-voting locator.  Its neighbour maps are indexed once by lag value
+    (``ofp_vote_index``); ``locate_cc`` correlates the windows (``ofp_find_lags``) and votes (``ofp_paired_vote``)
+    by reading only the cells whose lag matches, and ``locate`` solves with ``ofp_trilaterate``.  2 <= S <= 16;
+    ``locate_cc`` refuses onset_idx - left < 0 (the reference's slice would wrap),
+  * ``lag_intensity_map`` (GPU: ``ofp_lag_maps`` and ``ofp_intensity_maps``) and its host helpers ``vec_sub``,
+    ``attenuate_intensity``, ``sound_intensity_at_source``.
 
-Out of scope: the 2-D ``Multilaterate`` and ``MultilateratePaired`` classes, ``lag_intensity_map``,
-``find_lag_multi`` and the other helpers of the reference file.  There is no CPU path: every GPU function raises
-without the library or a gfx950 GPU.
+Batched, device-resident additions: ``locate_groups_device`` locates every onset group ``group_onsets_device``
+found, in one pass without host synchronisation; ``find_lags_device``, ``MultilateratePaired.locate_cc_device`` /
+``locate_device`` and ``locate_cc_groups_device`` do the same for the 2-D functions.
+
+There is no CPU path: every GPU function raises without the library or a gfx950 GPU.  Inputs to the correlations
+are taken as float32.
 """
 import ctypes
 from typing import Optional
@@ -423,3 +435,437 @@ def locate_groups_device(groups, n_groups, m: Multilaterate3D, xtol=XTOL, maxfev
                               status.data_ptr(), _ptr(guess), ws.data_ptr(), ws.numel(), _stream(dev)),
           "ofp_locate_groups")
     return (xy, status, guess) if return_guess else (xy, status)
+
+
+# ---- find_lag / find_lag_multi ------------------------------------------------------------------------------
+
+FIND_LAG_MAX_LEN = 4096  # longest row ofp_find_lags correlates
+FIND_LAG_MAX_TOP = 16    # most peaks it reports
+
+
+def find_lags_device(a, b, top_n: int = 0, len_a=None, len_b=None):
+    """find_lag / find_lag_multi for every row pair of float32 CUDA tensors a [n, La], b [n, Lb] (ofp_find_lags).
+
+    len_a / len_b: optional int32 CUDA [n] row lengths (1..La / 1..Lb), the full rows otherwise.  Returns CUDA
+    tensors lag int32 [n] (np.argmax of np.correlate(a, b, "full") - (len_a - 1)), peak_lag int32 [n, top_n],
+    peak_val float32 [n, top_n] (cc ** 2; NaN in unused slots) and n_peaks int32 [n]: the slots used (0 when
+    top_n == 0), -1 for a row
+    whose correlation holds a non-finite value (no peaks reported), -2 for a row of length 0."""
+    for name, t in (("a", a), ("b", b)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+            raise ValueError(f"find_lags_device: {name} must be a float32 CUDA tensor [n, L]")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"find_lags_device: {a.shape[0]} rows of a but {b.shape[0]} of b")
+    n, La = a.shape
+    Lb = b.shape[1]
+    if not (1 <= La <= FIND_LAG_MAX_LEN and 1 <= Lb <= FIND_LAG_MAX_LEN):
+        raise ValueError(f"find_lags_device: row lengths {La}, {Lb} outside 1..{FIND_LAG_MAX_LEN}")
+    if not 0 <= int(top_n) <= FIND_LAG_MAX_TOP:
+        raise ValueError(f"find_lags_device: top_n {top_n} outside 0..{FIND_LAG_MAX_TOP}")
+    for name, t in (("len_a", len_a), ("len_b", len_b)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.shape == (n,)):
+            raise ValueError(f"find_lags_device: {name} must be an int32 CUDA tensor [{n}]")
+    a, b = a.contiguous(), b.contiguous()
+    len_a = len_a.contiguous() if len_a is not None else None
+    len_b = len_b.contiguous() if len_b is not None else None
+    dev = a.device
+    top_n = int(top_n)
+    lag = torch.empty(n, dtype=torch.int32, device=dev)
+    peak_lag = torch.empty((n, top_n), dtype=torch.int32, device=dev)
+    peak_val = torch.empty((n, top_n), dtype=torch.float32, device=dev)
+    n_peaks = torch.empty(n, dtype=torch.int32, device=dev)
+    check(_lib.lib().ofp_find_lags(a.data_ptr(), b.data_ptr(), n, La, Lb, 1, None, None, La, Lb, _ptr(len_a),
+                                   _ptr(len_b), top_n, lag.data_ptr(), _ptr(peak_lag) if top_n else None,
+                                   _ptr(peak_val) if top_n else None, n_peaks.data_ptr(), _stream(dev)),
+          "ofp_find_lags")
+    return lag, peak_lag, peak_val, n_peaks
+
+
+def _pair_rows(a, b, device):
+    a = np.asarray(a, dtype=np.float32).reshape(-1)
+    b = np.asarray(b, dtype=np.float32).reshape(-1)
+    if a.size == 0 or b.size == 0:
+        raise ValueError("find_lag: a and b must not be empty")  # as np.correlate
+    if a.size > FIND_LAG_MAX_LEN or b.size > FIND_LAG_MAX_LEN:
+        raise ValueError(f"find_lag: rows of {a.size} and {b.size} samples; at most {FIND_LAG_MAX_LEN}")
+    dev = _dev(device)
+    _lib.require_gpu(dev.index or 0)
+    return torch.from_numpy(a).to(dev).reshape(1, -1), torch.from_numpy(b).to(dev).reshape(1, -1)
+
+
+def find_lag(a, b, device=0) -> int:
+    """multilateration.py:878-887: np.argmax(np.correlate(a, b, "full")) - (len(a) - 1), on float32 copies."""
+    ta, tb = _pair_rows(a, b, device)
+    lag, _, _, _ = find_lags_device(ta, tb)
+    return int(lag.cpu()[0])
+
+
+def find_lag_multi(a, b, top_n: int = 3, device=0):
+    """multilateration.py:890-899: the top_n peaks of scipy.signal.find_peaks over np.correlate(a, b, "full") by
+    descending value, as (lags int64, cc ** 2 float32).  Exact ties are ordered by ascending lag (numpy's argsort
+    leaves their order undefined).  A correlation with a non-finite value raises ValueError."""
+    if not 0 <= int(top_n) <= FIND_LAG_MAX_TOP:
+        raise ValueError(f"find_lag_multi: top_n {top_n} outside 0..{FIND_LAG_MAX_TOP}")
+    ta, tb = _pair_rows(a, b, device)
+    if int(top_n) == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.float32)
+    _, pl, pv, npk = find_lags_device(ta, tb, top_n)
+    k = int(npk.cpu()[0])
+    if k < 0:
+        raise ValueError("find_lag_multi: the correlation holds a non-finite value")
+    return pl.cpu().numpy()[0, :k].astype(np.int64), pv.cpu().numpy()[0, :k]
+
+
+# ---- Multilaterate (2-D) ------------------------------------------------------------------------------------
+
+class Multilaterate:
+    def __init__(self, sensor_locations, drum_diameter: float = DIAMETER, medium: str = "drumhead", sr: int = 44100,
+                 device=0):
+        """multilateration.py:578-645.  sensor_locations: (relative radius, angle) per sensor.  The lag maps (1 cm
+        grid, 2 cm tolerance at the edge, values below -samples_per_cm dropped) are built by ``ofp_lag_maps`` and
+        stay on `device`; ``lag_maps``, ``min_lags``, ``max_lags``, ``max_max_lags`` are the reference's host
+        views of them."""
+        self.radius = drum_diameter / 2
+        self.sensor_locs = [polar_to_cartesian(x[0] * self.radius, x[1]) for x in sensor_locations]
+        self.medium = medium
+        self.sr = sr
+        self.samples_per_cm = sr / speed_of_sound(100, medium=medium)
+        sensors = _sensor_array(self.sensor_locs)
+        self.device = _dev(device)
+        _lib.require_gpu(self.device.index or 0)
+        S = len(sensors)
+        r, mask_r2 = _grid_2d(drum_diameter, 1, 2)
+        self.maps_dev, self.min_dev, self.max_dev = lag_maps_device(
+            sensors, r, speed_of_sound(100, medium=medium), sr, mask_r2, floor=-self.samples_per_cm * 1,
+            device=self.device)
+        maps = self.maps_dev.cpu().numpy()
+        mn, mx = self.min_dev.cpu().numpy(), self.max_dev.cpu().numpy()
+        self.lag_maps = [{j: maps[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.max_lags = [{j: mx[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.min_lags = [{j: mn[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.max_max_lags = [np.nanmax(list(d.values())) for d in self.max_lags]
+        self.ongoing = []
+
+    def is_legal(self, first_sensor: int, later_sensor: int, lag: int) -> bool:
+        """The lag lies strictly between the extremes of the pair's lag map."""
+        return self.min_lags[first_sensor][later_sensor] < lag < self.max_lags[first_sensor][later_sensor]
+
+    def is_legal_3d(self, group, tolerance=1):
+        """multilateration.py:663-676: (col, row) of the first map cell consistent with both lags of the group
+        within `tolerance` cm, (0, 0) when there is none."""
+        sensors, onsets = group[0], group[1]
+        s = torch.tensor([[int(v) for v in sensors[:3]]], dtype=torch.int32, device=self.device)
+        o = torch.tensor([[int(v) for v in onsets[:3]]], dtype=torch.int64, device=self.device)
+        idx = legal_cells_device(self.maps_dev, s, o, tolerance * self.samples_per_cm).cpu().numpy()[0]
+        return int(idx[0]), int(idx[1])
+
+    def locate(self, sensor_index: int, onset_index: int):
+        """multilateration.py:678-711: feed one onset; returns (radius / drum radius, angle) of the hit it
+        completes, or None.  Kept as the reference has it: a group that passes is_legal is appended twice, and the
+        guess is (col, row) - radius on the grid of radius round(radius)."""
+        new_groups = []
+        for group in self.ongoing:
+            lag = onset_index - group[1][0]
+            if sensor_index not in group[0]:
+                if self.is_legal(group[0][0], sensor_index, lag):
+                    group = (group[0] + [sensor_index], group[1] + [onset_index])
+                    if len(group[0]) == 3:
+                        res = self.is_legal_3d(group)
+                        if res != (0, 0):
+                            res = self.trilaterate(group, np.array(res) - self.radius)
+                            self.ongoing = new_groups
+                            return res
+                    new_groups.append(group)
+            if lag <= self.max_max_lags[group[0][0]]:
+                new_groups.append(group)
+        new_groups.append(([sensor_index], [onset_index]))
+        self.ongoing = new_groups
+        return None
+
+    def trilaterate(self, group, initial_guess):
+        """multilateration.py:713-733: solve_trilateration (``ofp_trilaterate``) -> cartesian_to_polar(x, y,
+        radius), or None.  No sensor reordering."""
+        sensors, onsets = group[0], group[1]
+        c = speed_of_sound(100, medium=self.medium)
+        d_a1 = (onsets[1] - onsets[0]) * c / self.sr
+        d_b1 = (onsets[2] - onsets[0]) * c / self.sr
+        res = solve_trilateration(self.sensor_locs[sensors[1]], self.sensor_locs[sensors[2]],
+                                  self.sensor_locs[sensors[0]], d_a1, d_b1, initial_guess, device=self.device)
+        if res is None:
+            return None
+        return cartesian_to_polar(*res, self.radius)
+
+
+# ---- MultilateratePaired ------------------------------------------------------------------------------------
+
+PAIRED_OK, PAIRED_UNUSED, PAIRED_NO_CHANNEL = 0, -1, -2
+PAIRED_NEG_WINDOW, PAIRED_EMPTY_WINDOW, PAIRED_BAD_HIT = -5, -6, -7
+PAIRED_MAX_SENSORS = 16  # all S x S maps of ofp_lag_maps stay on the device: 16 x 16 x 0.5 MB at scale 10
+
+
+class MultilateratePaired:
+    def __init__(self, sensor_locations, drum_diameter: float = DIAMETER, scale: float = 10,
+                 medium: str = "drumhead", sr: int = 44100, device=0):
+        """multilateration.py:736-796.  The neighbour maps lag_map_2d(s_i, s_j, scale=scale, medium="drumhead")
+        for j = (i - 1) % S, (i + 1) % S are built by ``ofp_lag_maps`` and indexed once by ``ofp_vote_index``;
+        ``lag_maps`` (list of dicts) and ``res`` are the reference's host views.  2 <= S <= 16."""
+        S = len(sensor_locations)
+        if not 2 <= S <= PAIRED_MAX_SENSORS:
+            raise ValueError(f"MultilateratePaired: {S} sensors; 2..{PAIRED_MAX_SENSORS} supported")
+        self.radius = int(np.round(drum_diameter * scale / 2, 1))
+        self.sensor_locs = [polar_to_cartesian(x[0] * self.radius, x[1]) for x in sensor_locations]
+        self.scale = scale
+        self.medium = medium
+        self.sr = sr
+        self.device = _dev(device)
+        _lib.require_gpu(self.device.index or 0)
+        sensors = _sensor_array(self.sensor_locs)
+        r, mask_r2 = _grid_2d(drum_diameter, scale, 1)
+        self.side = 2 * r + 1
+        self.maps_dev, mn, mx = lag_maps_device(sensors, r, speed_of_sound(100 * scale, medium="drumhead"), sr,
+                                                mask_r2, device=self.device)
+        self.sensors_dev = torch.from_numpy(sensors).to(self.device)
+        # the reference's map (i, j) = lag_map_2d(s_i, s_j) is ofp_lag_maps' map (j, i); slot 2i + k of the index
+        # holds sensor i's neighbour (i - 1) % S (k = 0) and (i + 1) % S (k = 1)
+        self.neighbours = [((i - 1) % S, (i + 1) % S) for i in range(S)]
+        ids = [j * S + i for i in range(S) for j in self.neighbours[i]]
+        mn, mx = mn.cpu().numpy().reshape(-1)[ids], mx.cpu().numpy().reshape(-1)[ids]
+        empty = np.isnan(mn)
+        vmin = np.where(empty, 0, mn).astype(np.int64)
+        vmax = np.where(empty, 0, mx).astype(np.int64)
+        self.n_buckets = int((vmax - vmin).max()) + 1
+        cells = self.side * self.side
+        dev = self.device
+        self.map_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
+        self.vmin = torch.from_numpy(vmin.astype(np.int32)).to(dev)
+        self.starts = torch.empty((2 * S, self.n_buckets + 1), dtype=torch.int32, device=dev)
+        self.sorted_cells = torch.empty((2 * S, cells), dtype=torch.int32, device=dev)
+        bad = torch.empty(2 * S, dtype=torch.int32, device=dev)
+        check(_lib.lib().ofp_vote_index(self.maps_dev.data_ptr(), cells, self.map_ids.data_ptr(), 2 * S,
+                                        self.vmin.data_ptr(), self.n_buckets, self.starts.data_ptr(),
+                                        self.sorted_cells.data_ptr(), bad.data_ptr(), _stream(dev)), "ofp_vote_index")
+        if int(bad.sum().cpu()) != 0:
+            raise RuntimeError("MultilateratePaired: a lag map holds a non-integer value; the vote index needs "
+                               "integer maps")
+        maps = self.maps_dev.cpu().numpy()
+        self.lag_maps = [{j: maps[j, i] for j in self.neighbours[i]} for i in range(S)]
+        self.res = np.zeros_like(self.lag_maps[0][1])
+
+    def _c(self):
+        return speed_of_sound(100 * self.scale, medium=self.medium)
+
+    def locate(self, lags, i: int):
+        """multilateration.py:798-834: (radius / self.radius, angle) from the lags to the neighbours of sensor i;
+        raises TypeError where the reference does (a failed solve)."""
+        S = len(self.sensor_locs)
+        js = [(i - 1) % S, (i + 1) % S]
+        sensor_a, sensor_b, sensor_origin = self.sensor_locs[js[0]], self.sensor_locs[js[1]], self.sensor_locs[i]
+        c = self._c()
+        d_a1 = lags[0] * c / self.sr
+        d_b1 = lags[1] * c / self.sr
+        weight_a = abs(d_a1) / self.radius
+        weight_b = abs(d_b1) / self.radius
+        weight_o = abs(d_a1 + d_b1) / (2 * self.radius)
+        guess = np.array([sensor_a[0] * weight_a + sensor_b[0] * weight_b + sensor_origin[0] * weight_o,
+                          sensor_a[1] * weight_a + sensor_b[1] * weight_b + sensor_origin[1] * weight_o])
+        x, y = solve_trilateration(sensor_a, sensor_b, sensor_origin, d_a1, d_b1, guess, device=self.device)
+        return cartesian_to_polar(x, y, self.radius)
+
+    def locate_device(self, lags, first, xtol=XTOL, maxfev=MAXFEV):
+        """``locate`` for B rows at once (``ofp_paired_solve``): lags int32 CUDA [B, 2], first int32 [B] ->
+        rphi float64 [B, 2] (the polar result of the last iterate) and ier int32 [B] (1: the reference returns;
+        any other value: it raises)."""
+        if not (torch.is_tensor(lags) and lags.is_cuda and lags.dtype == torch.int32 and lags.dim() == 2
+                and lags.shape[1] == 2):
+            raise ValueError("locate_device: lags must be an int32 CUDA tensor [B, 2]")
+        B = lags.shape[0]
+        if not (torch.is_tensor(first) and first.dtype == torch.int32 and first.shape == (B,) and first.is_cuda):
+            raise ValueError(f"locate_device: first must be an int32 CUDA tensor [{B}]")
+        lags, first = lags.contiguous(), first.contiguous()
+        dev = lags.device
+        root = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        rphi = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        ier = torch.empty(B, dtype=torch.int32, device=dev)
+        check(_lib.lib().ofp_paired_solve(self.sensors_dev.data_ptr(), self.sensors_dev.shape[0], lags.data_ptr(),
+                                          first.data_ptr(), B, float(self._c()), float(self.sr), float(self.radius),
+                                          float(xtol), int(maxfev), root.data_ptr(), rphi.data_ptr(), ier.data_ptr(),
+                                          _stream(dev)), "ofp_paired_solve")
+        return rphi, ier
+
+    def _vote(self, x, hits, groups, tol, left, right, want_res=False):
+        """x float32 CUDA [n_clips, N, C]; hits = (onset int64 [B], first int32 [B], clip int32 [B] or None) or
+        groups = (groups int64 [n_clips, cap, C], n_groups or None) -> rphi, cell, status, lags (and res)."""
+        S = len(self.sensor_locs)
+        n_clips, N, C = x.shape
+        if C < S:
+            raise ValueError(f"locate_cc: {C} channels but {S} sensors")
+        if not (0 <= int(left) and int(right) >= 1 and int(left) + int(right) <= FIND_LAG_MAX_LEN):
+            raise ValueError(f"locate_cc: left {left}, right {right}: need left >= 0, right >= 1 and a window of at "
+                             f"most {FIND_LAG_MAX_LEN} samples")
+        if float(tol) < 0:
+            raise ValueError(f"locate_cc: tol {tol} < 0")
+        dev = x.device
+        L = _lib.lib()
+        if groups is not None:
+            g, n_groups = groups
+            cap = g.shape[1]
+            B = n_clips * cap
+            onset = first = clip = None
+        else:
+            onset, first, clip = hits
+            B = onset.shape[0]
+            g, n_groups, cap = None, None, 0
+        i64 = lambda n_: torch.empty(n_, dtype=torch.int64, device=dev)
+        i32 = lambda n_: torch.empty(n_, dtype=torch.int32, device=dev)
+        a_off, b_off, ln, first_out, st_in = i64(2 * B), i64(2 * B), i32(2 * B), i32(B), i32(B)
+        check(L.ofp_paired_windows(n_clips, N, C, S, _ptr(onset), _ptr(first), _ptr(clip), _ptr(g), cap,
+                                   _ptr(n_groups), B, int(left), int(right), a_off.data_ptr(), b_off.data_ptr(),
+                                   ln.data_ptr(), first_out.data_ptr(), st_in.data_ptr(), _stream(dev)),
+              "ofp_paired_windows")
+        w = int(left) + int(right)
+        lags = i32(2 * B)
+        if B:
+            check(L.ofp_find_lags(x.data_ptr(), x.data_ptr(), 2 * B, 0, 0, C, a_off.data_ptr(), b_off.data_ptr(), w, w,
+                                  ln.data_ptr(), ln.data_ptr(), 0, lags.data_ptr(), None, None, None, _stream(dev)),
+                  "ofp_find_lags")
+        cell, status = i32(B), i32(B)
+        xy = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        rphi = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        res = torch.empty((B, self.side, self.side), dtype=torch.float32, device=dev) if want_res else None
+        check(L.ofp_paired_vote(self.maps_dev.data_ptr(), self.map_ids.data_ptr(), self.starts.data_ptr(),
+                                self.sorted_cells.data_ptr(), self.vmin.data_ptr(), self.n_buckets, S, self.side,
+                                first_out.data_ptr(), lags.data_ptr(), st_in.data_ptr(), B, float(tol),
+                                float(self.radius), cell.data_ptr(), xy.data_ptr(), rphi.data_ptr(), status.data_ptr(),
+                                _ptr(res), _stream(dev)), "ofp_paired_vote")
+        return rphi, cell, status, lags.reshape(B, 2), res
+
+    def locate_cc(self, x, onset_idx: int, i: int, tol: int = 2, left: int = 0, right: int = 256):
+        """multilateration.py:836-875: the vote over the neighbour maps of sensor i with the lags find_lag gives for
+        x[onset_idx - left : onset_idx + right] ([N, C], as float32); sets ``res`` and returns
+        cartesian_to_polar of the winning cell.  Refuses onset_idx - left < 0 (the reference's slice would wrap) and
+        an empty window with ValueError.  Only the window travels to the device."""
+        xs = x.detach() if torch.is_tensor(x) else np.asarray(x)
+        if xs.ndim != 2:
+            raise ValueError(f"locate_cc: x must be [N, C], got shape {tuple(xs.shape)}")
+        N = xs.shape[0]
+        S = len(self.sensor_locs)
+        if not 0 <= int(i) < S:
+            raise ValueError(f"locate_cc: sensor {i} outside 0..{S - 1}")
+        if not (0 <= int(left) and int(right) >= 1 and int(left) + int(right) <= FIND_LAG_MAX_LEN):
+            raise ValueError(f"locate_cc: left {left}, right {right}: need left >= 0, right >= 1 and a window of at "
+                             f"most {FIND_LAG_MAX_LEN} samples")
+        if int(onset_idx) - int(left) < 0:
+            raise ValueError(f"locate_cc: onset_idx - left = {int(onset_idx) - int(left)} < 0")
+        if min(int(onset_idx) + int(right), N) - (int(onset_idx) - int(left)) < 1:
+            raise ValueError("locate_cc: empty window")  # np.correlate raises on it
+        w = xs[int(onset_idx) - int(left):min(int(onset_idx) + int(right), N)]  # the window, as the reference slices
+        w = w.to(torch.float32) if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(w, np.float32))
+        xd = w.to(self.device).contiguous().unsqueeze(0)
+        hits = (torch.tensor([int(left)], dtype=torch.int64, device=self.device),
+                torch.tensor([int(i)], dtype=torch.int32, device=self.device), None)
+        _, cell, status, _, res = self._vote(xd, hits, None, tol, left, right, want_res=True)
+        st = int(status.cpu()[0])
+        if st != PAIRED_OK:
+            raise ValueError(f"locate_cc: window refused (status {st})")
+        self.res[:] = res.cpu().numpy()[0]
+        row, col = divmod(int(cell.cpu()[0]), self.side)
+        xc = col - (self.side - 1) / 2
+        yc = (self.side - 1) / 2 - row
+        return cartesian_to_polar(xc, yc, self.radius)
+
+    def locate_cc_device(self, x, onset_idx, first, tol: int = 2, left: int = 0, right: int = 256, clip=None):
+        """``locate_cc`` for B hits at once, without host synchronisation.  x float32 CUDA [N, C] or
+        [n_clips, N, C] (channel k is sensor k), onset_idx int64 CUDA [B], first int32 [B], clip int32 [B] or None
+        (clip 0).  Returns rphi float64 [B, 2] (cartesian_to_polar of the cell), cell int32 [B] (flat index into
+        the side x side grid; 0 when no cell matches, as np.argmax returns it) and status int32 [B]: PAIRED_OK, or
+        PAIRED_NEG_WINDOW (-5, onset - left < 0), PAIRED_EMPTY_WINDOW (-6), PAIRED_BAD_HIT (-7)."""
+        x = _clips(x, "locate_cc_device")
+        B = onset_idx.shape[0] if torch.is_tensor(onset_idx) else -1
+        for name, t, dt in (("onset_idx", onset_idx, torch.int64), ("first", first, torch.int32),
+                            ("clip", clip, torch.int32)):
+            if t is None and name == "clip":
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 1 and t.shape[0] == B):
+                raise ValueError(f"locate_cc_device: {name} must be a {dt} CUDA tensor [B]")
+        hits = (onset_idx.contiguous(), first.contiguous(), clip.contiguous() if clip is not None else None)
+        rphi, cell, status, _, _ = self._vote(x, hits, None, tol, left, right)
+        return rphi, cell, status
+
+
+def _clips(x, what):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (2, 3)):
+        raise ValueError(f"{what}: x must be a float32 CUDA tensor [N, C] or [n_clips, N, C]")
+    return (x if x.dim() == 3 else x.unsqueeze(0)).contiguous()
+
+
+def locate_cc_groups_device(x, groups, n_groups, m: MultilateratePaired, tol: int = 2, left: int = 0,
+                            right: int = 256):
+    """``MultilateratePaired.locate_cc`` for every row of `detection.group_onsets_device`, without host
+    synchronisation.  x float32 CUDA [n_clips, N, C]; groups int64 [n_clips, cap_groups, C] (channel k is sensor k,
+    a negative onset is an absent channel), n_groups int64 [n_clips] or None (every row).  Per row, the first sensor
+    is the earliest channel (ties by channel) and onset_idx its onset.  Returns rphi float64
+    [n_clips, cap_groups, 2], cell int32 and status int32 [n_clips, cap_groups] as locate_cc_device, plus
+    PAIRED_UNUSED (-1, row beyond the clip's groups) and PAIRED_NO_CHANNEL (-2)."""
+    x = _clips(x, "locate_cc_groups_device")
+    if not (torch.is_tensor(groups) and groups.is_cuda and groups.dtype == torch.int64 and groups.dim() == 3):
+        raise ValueError("locate_cc_groups_device: groups must be an int64 CUDA tensor [n_clips, cap_groups, C]")
+    n_clips, cap, C = groups.shape
+    if (n_clips, C) != (x.shape[0], x.shape[2]):
+        raise ValueError(f"locate_cc_groups_device: groups {tuple(groups.shape)} do not fit x {tuple(x.shape)}")
+    if n_groups is not None and not (torch.is_tensor(n_groups) and n_groups.is_cuda and n_groups.dtype == torch.int64
+                                     and n_groups.shape == (n_clips,)):
+        raise ValueError("locate_cc_groups_device: n_groups must be an int64 CUDA tensor [n_clips]")
+    if cap == 0:
+        e = torch.empty((n_clips, 0), dtype=torch.int32, device=x.device)
+        return torch.empty((n_clips, 0, 2), dtype=torch.float64, device=x.device), e, e.clone()
+    rphi, cell, status, _, _ = m._vote(x, None, (groups.contiguous(), n_groups.contiguous() if n_groups is not None
+                                                 else None), tol, left, right)
+    return rphi.reshape(n_clips, cap, 2), cell.reshape(n_clips, cap), status.reshape(n_clips, cap)
+
+
+# ---- lag_intensity_map --------------------------------------------------------------------------------------
+
+def sound_intensity_at_source(strike_location, strike_force=STRIKE_FORCE, diameter=DIAMETER) -> float:
+    """multilateration.py:1004-1008 (a placeholder there): the strike force."""
+    return strike_force
+
+
+def vec_sub(a, b):
+    """multilateration.py:1011-1015: rows (a.x - b.x, a.y - b.y, a.z - b.z) for the points of b (x and y arrays,
+    scalar z) -> [n, 3] float64."""
+    dx = a[0] - b[0].reshape(-1)
+    dy = a[1] - b[1].reshape(-1)
+    dz = np.full_like(dx, a[2] - b[2], dtype=float)
+    return np.vstack((dx, dy, dz)).T
+
+
+def attenuate_intensity(source_loc, mic_loc, reflectivity, intensity_at_source):
+    """multilateration.py:1018-1043: intensity at mic_loc of sources on the drumhead, scaled by
+    1 + reflectivity * (1 - |cos theta|) over the distance (theta: angle to the surface normal), and theta in
+    degrees."""
+    v = vec_sub(mic_loc, source_loc)
+    dist = np.linalg.norm(v, axis=-1)
+    v /= np.linalg.norm(v, axis=-1, keepdims=True)
+    theta = np.arccos(np.dot(v, np.array([0.0, 0.0, 1.0])))
+    return intensity_at_source * (1 + reflectivity * (1 - np.abs(np.cos(theta)))) / dist, np.degrees(theta)
+
+
+def lag_intensity_map(mic_a, mic_b, reflectivity: float = 0.5, d: int = DIAMETER, sr: int = 96000,
+                      scale: float = 1, medium: str = MEDIUM, device=0):
+    """multilateration.py:1046-1101: the lag map (samples, lag_map_3d without mask) and the two signal-strength
+    maps 10 log10(attenuate_intensity) in dB, all float32 [side, side]; the lags by ``ofp_lag_maps``, the
+    strengths by ``ofp_intensity_maps`` (fp64 rounded once to float32)."""
+    mics = np.array([list(mic_a), list(mic_b)], dtype=np.float64)
+    if mics.shape != (2, 3):
+        raise ValueError(f"lag_intensity_map: microphones must be (x, y, z), got shape {mics.shape[1:]}")
+    r = int(np.round(d, 1) * scale) // 2
+    dev = _dev(device)
+    _lib.require_gpu(dev.index or 0)
+    maps, _, _ = lag_maps_device(mics[::-1], r, speed_of_sound(100 * scale, medium=medium), sr, np.inf, device=dev)
+    side = 2 * r + 1
+    out = torch.empty((2, side, side), dtype=torch.float32, device=dev)
+    m = torch.from_numpy(np.ascontiguousarray(mics)).to(dev)
+    check(_lib.lib().ofp_intensity_maps(m.data_ptr(), r, float(reflectivity), out.data_ptr(), _stream(dev)),
+          "ofp_intensity_maps")
+    out = out.cpu().numpy()
+    return maps[0, 1].cpu().numpy(), out[0], out[1]
