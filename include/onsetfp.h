@@ -717,6 +717,48 @@ int ofp_paired_solve(const double* d_sensors, int32_t S, const int32_t* d_lags, 
                      int32_t* d_ier, void* stream);
 int ofp_intensity_maps(const double* d_mics, int32_t r, double reflectivity, float* d_out, void* stream);
 
+/* ---- calibration: train_location_model, optimize_positions (calibration.py:563-754) ----------------------------
+ * One workgroup runs one whole optimisation inside one launch (full-batch forward, mean loss, early stop, backward,
+ * clip_grad_norm_ with max_norm 1, Adam with torch's defaults); the grid is the M independent problems.  fp32, no
+ * atomics, every batch reduction in a fixed order that does not depend on M.
+ * Network: n_layers Linear layers of dims [n_layers + 1], every one but the last followed by BatchNorm1d (when
+ *   batch_norm; batch statistics, running statistics with momentum 0.1) and the activation act (OFP_ACT_*).
+ *   Parameters are packed per layer as weight [out][in], bias [out] (when bias), BatchNorm weight, bias [out]; the
+ *   running statistics as mean [out], var [out] per BatchNorm.  Limits: 1..8 layers, widths 1..128, n 1..1024
+ *   (n >= 2 with BatchNorm); beyond them OFP_ERR_INVALID.
+ * ofp_fcnn_train_lds_bytes: the bytes of parameters, moments and activations one problem keeps; up to 160 KiB less
+ *   512 B they live in LDS, beyond that in d_ws (ofp_fcnn_train_workspace_bytes, 0 when the LDS is used).  -1 for
+ *   arguments outside the limits.
+ * ofp_fcnn_train: problem m reads d_x + m * x_stride [n][dims[0]] and d_y + m * y_stride [n][dims[n_layers]] (a
+ *   stride of 0 shares one batch), starts at d_p0 [M][n_params] / d_stats0 [M][n_stats], and takes its per-epoch
+ *   Adam scalars from row d_rate_idx[m] of d_rates [U][num_epochs][2] = (lr_t / (1 - 0.9^t), sqrt(1 - 0.999^t)).
+ *   loss: 0 = L1, 1 = MSE (mean).  Per epoch the loss is stored in d_loss [M][num_epochs] first; then
+ *   loss < last - eps resets the patience counter, else it rises while below patience, else the run ends before
+ *   that epoch's update.  d_epochs [M]: losses stored.  d_params / d_stats: the final state.
+ * ofp_fcnn_loss_grads: the same kernel for one epoch, leaving after the backward pass: d_loss [M], d_grads
+ *   [M][n_params] (unclipped).
+ * ofp_tdoa_fit: optimize_positions.  d_obs + m * obs_stride [n][2] observed TDoA in seconds (pairs 0-2 and 1-3),
+ *   d_sensors0 [M][4][3], d_sounds0 [M][n][2], d_c0 [M]; d_rates [U][num_epochs][4] = the step sizes of sensors,
+ *   sounds and C, then sqrt(1 - 0.999^t).  The early-stop test comes before the loss is counted: d_epochs [M] is
+ *   the number of updates, and d_loss [m][d_epochs[m]] holds the stopping epoch's loss when the run stopped.  d_sounds
+ *   [M][n][3] are the positions the last forward pass used (z = 0), as the reference returns them.  n 1..4096. */
+int64_t ofp_fcnn_train_lds_bytes(int32_t n_layers, const int32_t* dims, int32_t batch_norm, int32_t bias, int64_t n);
+int64_t ofp_fcnn_train_workspace_bytes(int32_t n_layers, const int32_t* dims, int32_t batch_norm, int32_t bias,
+                                       int64_t n, int64_t M);
+int ofp_fcnn_train(int32_t n_layers, const int32_t* dims, int32_t act, int32_t batch_norm, int32_t bias,
+                   int32_t loss, int64_t M, int64_t n, const float* d_x, int64_t x_stride, const float* d_y,
+                   int64_t y_stride, const float* d_p0, const float* d_stats0, const float* d_rates,
+                   const int32_t* d_rate_idx, int32_t num_epochs, float eps, int32_t patience, float* d_params,
+                   float* d_stats, float* d_loss, int32_t* d_epochs, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_fcnn_loss_grads(int32_t n_layers, const int32_t* dims, int32_t act, int32_t batch_norm, int32_t bias,
+                        int32_t loss, int64_t M, int64_t n, const float* d_x, int64_t x_stride, const float* d_y,
+                        int64_t y_stride, const float* d_p0, float* d_loss, float* d_grads, void* d_ws,
+                        int64_t ws_bytes, void* stream);
+int ofp_tdoa_fit(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, const float* d_sensors0,
+                 const float* d_sounds0, const float* d_c0, int32_t loss, const float* d_rates,
+                 const int32_t* d_rate_idx, int32_t num_epochs, float eps, int32_t patience, float* d_sensors,
+                 float* d_sounds, float* d_c, float* d_loss, int32_t* d_epochs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,14 @@ SIGNATURES = {
     "ofp_paired_solve": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp,
                                         _vp]),
     "ofp_intensity_maps": (ctypes.c_int, [_vp, _i32, _f64, _vp, _vp]),
+    "ofp_fcnn_train_lds_bytes": (_i64, [_i32, ctypes.POINTER(_i32), _i32, _i32, _i64]),
+    "ofp_fcnn_train_workspace_bytes": (_i64, [_i32, ctypes.POINTER(_i32), _i32, _i32, _i64, _i64]),
+    "ofp_fcnn_train": (ctypes.c_int, [_i32, ctypes.POINTER(_i32), _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp,
+                                      _i64, _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_fcnn_loss_grads": (ctypes.c_int, [_i32, ctypes.POINTER(_i32), _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64,
+                                           _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_tdoa_fit": (ctypes.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
