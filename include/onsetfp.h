@@ -653,6 +653,67 @@ int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_grou
                       int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream);
 int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int32_t c1, float* d_out, void* stream);
 
+/* ---- Multilaterate3D.locate as device code (multilateration.py:428-575) ---------------------------------------
+ * The reference's state machine with its state (`ongoing`) in device memory: one call feeds (sensor, onset, counter)
+ * and returns what locate returns.  Every quirk is kept: lags are measured from a group's first onset, the swap on
+ * a negative lag stays in force for the rest of the call, the cross-correlation step (section of the last
+ * counter - first_onset + 61 rows, median 5, diff, negative part, abs; the arithmetic of ofp_locate_section,
+ * ofp_xcorr_lag and ofp_adjust_onset) moves the group's first onset in place, an extended group is appended twice
+ * (the two entries are ONE Python object: a later in-place change of one shows in the other, which `alias` records),
+ * the third member breaks out of the loop when the first two sensors are equal, and a call that reaches trilaterate
+ * returns with `ongoing` = the groups collected so far (remove_seed only after a successful solve).
+ * Capacity: OFP_LOCS_GROUPS groups of up to OFP_LOCS_MEMBERS members; the flags are sticky and never silent. */
+#define OFP_LOCS_GROUPS 64
+#define OFP_LOCS_MEMBERS 8
+#define OFP_LOCF_GROUPS 1    /* a group was not appended: more than OFP_LOCS_GROUPS groups */
+#define OFP_LOCF_MEMBERS 2   /* a group was not extended: more than OFP_LOCS_MEMBERS members */
+#define OFP_LOCF_SECTION 4   /* a cross-correlation step was skipped: section longer than the bound or under 3 rows */
+#define OFP_LOCF_BAD_CALL 8  /* a call was ignored: sensor outside 0..S-1 or counter outside the recording */
+typedef struct ofp_locate_state {
+    int32_t n_groups;
+    int32_t flags;                                        /* OFP_LOCF_* seen so far */
+    int32_t len[OFP_LOCS_GROUPS];                         /* members per group */
+    int32_t alias[OFP_LOCS_GROUPS];                       /* 1: the same object as the group before it */
+    int32_t sensors[OFP_LOCS_GROUPS][OFP_LOCS_MEMBERS];
+    int64_t onsets[OFP_LOCS_GROUPS][OFP_LOCS_MEMBERS];
+} ofp_locate_state;
+/* the locator's tables (all device pointers, as ofp_locate_groups takes them) */
+typedef struct ofp_hop_locator {
+    const double* d_sensors;   /* [S][3] */
+    int32_t S;                 /* 3..64 */
+    const float* d_maps;       /* [S][S][2r+1][2r+1] */
+    const float* d_min;        /* [S][S] */
+    const float* d_max;
+    int32_t r;
+    double samples_per_cm, sr, c, radius, xtol;
+    int32_t maxfev;
+    const ofp_mlp* mlp;        /* 2 -> 2 network replacing the solver, or NULL; parameters are copied by a session */
+    int32_t use_audio;         /* != 0: the cross-correlation step runs (locate's rec_audio is given) */
+    int32_t max_section;       /* most rows of a section, 3..4096; a longer one sets OFP_LOCF_SECTION */
+} ofp_hop_locator;
+/* Replay: K calls through one state machine in ONE launch of one workgroup.  d_sensor [K] int32, d_onset [K],
+ * d_counter [K] int64; d_audio [n_rows][n_channels] float32 or NULL (then no cross-correlation step; with it,
+ * loc->use_audio must be set and call k sees rows [0, d_counter[k]), a section that would start before row 0 is cut
+ * there as a Python slice is).  The replay starts from an empty `ongoing`; d_state receives the final one.
+ * d_found [K] int32 (1: a position was returned), d_xy [K][2] (NaN otherwise). */
+int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset,
+                      const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
+                      ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream);
+/* The stage inside the hop graph of a session (before its first hop; the graph is captured again): after the
+ * detector, the hop's onsets sorted by absolute sample (ties in record order) are fed with counter =
+ * (hop_index + 1) * block_size until one returns a position (detect_hits, realtime/audio.py:62-74).  Rows of the
+ * current hop are read from the hop buffer, older ones from the ring, rows before sample 0 are zeros (PARITY
+ * UNPINNED: the reference's ring class is absent).  OFP_ERR_INVALID: S != channels, a detector that backtracks,
+ * a ring shorter than max_section + block_size rows, a network that is not 2 -> 2.  ofp_hop_reset clears the state. */
+int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc);
+/* The location block of the last collected hop: *status 0 none / 1 located, h_xy [2], the located group as
+ * trilaterate left it (*n_members, h_sensors / h_onsets [OFP_LOCS_MEMBERS]), *fed onsets given to the state machine,
+ * *dropped onsets of the hop after the one that located (never fed, as in the reference), *flags. */
+int ofp_hop_collect_location(ofp_hop_session* s, int32_t* status, double* h_xy, int32_t* n_members,
+                             int32_t* h_sensors, int64_t* h_onsets, int32_t* fed, int32_t* dropped, int32_t* flags);
+/* copies `ongoing` out (no hop may be in flight) */
+int ofp_hop_locator_state(ofp_hop_session* s, ofp_locate_state* h_state);
+
 /* ---- 2-D hit location: find_lag, MultilateratePaired, lag_intensity_map (multilateration.py) -------------------
  * ofp_find_lags: find_lag / find_lag_multi (:878-899) for n_rows row pairs.  Row r of a starts at
  *   d_a + (d_a_off ? d_a_off[r] : r * a_stride) and steps elem_stride floats (b likewise, same element stride), so

@@ -94,6 +94,38 @@ class HopConfig(ctypes.Structure):
     ]
 
 
+LOCS_GROUPS, LOCS_MEMBERS = 64, 8  # OFP_LOCS_GROUPS, OFP_LOCS_MEMBERS
+LOCF_GROUPS, LOCF_MEMBERS, LOCF_SECTION, LOCF_BAD_CALL = 1, 2, 4, 8
+
+
+class LocateState(ctypes.Structure):
+    _fields_ = [
+        ("n_groups", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("len", ctypes.c_int32 * LOCS_GROUPS),
+        ("alias", ctypes.c_int32 * LOCS_GROUPS),
+        ("sensors", (ctypes.c_int32 * LOCS_MEMBERS) * LOCS_GROUPS),
+        ("onsets", (ctypes.c_int64 * LOCS_MEMBERS) * LOCS_GROUPS),
+    ]
+
+
+class HopLocator(ctypes.Structure):
+    _fields_ = [
+        ("d_sensors", ctypes.c_void_p),
+        ("S", ctypes.c_int32),
+        ("d_maps", ctypes.c_void_p),
+        ("d_min", ctypes.c_void_p),
+        ("d_max", ctypes.c_void_p),
+        ("r", ctypes.c_int32),
+        ("samples_per_cm", ctypes.c_double), ("sr", ctypes.c_double), ("c", ctypes.c_double),
+        ("radius", ctypes.c_double), ("xtol", ctypes.c_double),
+        ("maxfev", ctypes.c_int32),
+        ("mlp", ctypes.c_void_p),
+        ("use_audio", ctypes.c_int32),
+        ("max_section", ctypes.c_int32),
+    ]
+
+
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _f32p_h = ctypes.POINTER(ctypes.c_float)
 _long_p = ctypes.POINTER(ctypes.c_long)
@@ -193,6 +225,13 @@ SIGNATURES = {
     "ofp_locate_groups": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
                                          _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_locate_section": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ofp_locate_stream": (ctypes.c_int, [ctypes.POINTER(HopLocator), _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp,
+                                         _vp]),
+    "ofp_hop_set_locator": (ctypes.c_int, [_vp, ctypes.POINTER(HopLocator)]),
+    "ofp_hop_collect_location": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_f64), ctypes.POINTER(_i32),
+                                                ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32),
+                                                ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "ofp_hop_locator_state": (ctypes.c_int, [_vp, ctypes.POINTER(LocateState)]),
     "ofp_find_lags": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp,
                                      _vp, _vp, _vp, _vp]),
     "ofp_vote_index": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

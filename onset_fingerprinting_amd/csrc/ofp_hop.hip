@@ -17,6 +17,11 @@
 // kernel node, k_hop_fused -- workgroup 0 runs the detector while workgroups 1..C run the spectral
 // branch, the hop is read from and the result block written to pinned host memory directly.
 //
+// With a locator attached (ofp_hop_set_locator) the hop also carries Multilaterate3D.locate (ofp_locate_dev.h): the
+// detector's workgroup (fused form) or one more kernel node after the detector (nodes form) feeds the hop's onsets,
+// sorted by sample, to the device-resident state and writes the location block next to the records.  A hop without
+// onsets takes one uniform branch on the count and touches nothing of the stage.
+//
 // A replay needs no argument update: the write cursor is a counter in device memory.  The frame the
 // spectral kernel computes for the hop that ends at sample e is bit-identical to frame (e - n_fft)/B
 // of the dense kernel (k_stft_power, hop = B) on the same stream: same tables, same FFT, same mel
@@ -29,6 +34,7 @@
 
 #include "ofp_detector.h"
 #include "ofp_fft.h"
+#include "ofp_locate_dev.h"
 #include "ofp_mlp.h"
 #include "ofp_stream_dev.h"
 
@@ -370,6 +376,93 @@ __global__ __launch_bounds__(HopCfg<F>::WGS) void k_hop_spectral(HopArgs a) {
     hop_spectral_body<F, HopCfg<F>::WGS>(a, blockIdx.x, a.ctl[0], smem);
 }
 
+// The location block of a hop in the result block (ofp_hop_collect_location)
+struct HopLocBlock {
+    int32_t status, fed, dropped, flags, n_members, pad;
+    double xy[2];
+    int32_t sens[OFP_LOCS_MEMBERS];
+    int64_t on[OFP_LOCS_MEMBERS];
+};
+
+struct HopLocArgs {
+    int enabled;
+    ofp::LocTables T;
+    ofp_locate_state* state;
+    HopLocBlock* out;
+};
+
+inline size_t hop_loc_lds(int nthreads, const ofp::LocTables& T, int B, int C) {
+    return ofp::loc_lds_bytes(nthreads, T.max_section, T.plan) + (size_t)B * C * 4;
+}
+
+// detect_hits' loop (realtime/audio.py:62-74) for one hop, by one workgroup: the hop's n records sorted by onset
+// (np.argsort; ties keep record order), each fed to locate with counter = h * B until one returns a position.  Rows
+// of the current hop come from the hop buffer (other workgroups are writing the ring during a fused launch), older
+// rows from the ring, rows before sample 0 are zeros.  h = hops pushed including this one.
+__device__ __forceinline__ void hop_locate_stage(const HopArgs& a, const HopLocArgs& la, int64_t h, int n,
+                                                 const ofp_onset* recs, unsigned char* smem) {
+    __shared__ int s_order[64];
+    __shared__ ofp::LocGroup s_located;
+    const ofp::LocTables& T = la.T;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int C = a.C, B = a.B;
+    const ofp::LocView v = ofp::loc_carve(smem, nt, T.max_section, T.plan);
+    float* hopbuf = v.tb + (T.plan.n_layers > 0 ? 16 * T.plan.st_b : 0);
+    n = n < C ? n : C;
+    __syncthreads();  // the detector is done with this LDS
+    ofp::loc_load(T, v, la.state);
+    if (T.use_audio)
+        for (int i = tid; i < B * C; i += nt) hopbuf[i] = a.hop[i];
+    if (tid == 0) {
+        for (int i = 0; i < n; ++i) {  // stable insertion argsort
+            int q = i;
+            while (q > 0 && recs[s_order[q - 1]].sample > recs[i].sample) {
+                s_order[q] = s_order[q - 1];
+                --q;
+            }
+            s_order[q] = i;
+        }
+    }
+    __syncthreads();
+    const int64_t first = (h - 1) * B, counter = h * B;
+    auto sample = [&](int64_t t, int col) -> float {
+        if (t < 0) return 0.0f;
+        if (t >= first) return hopbuf[(t - first) * C + col];
+        return a.ring[(t % a.R) * C + col];
+    };
+    int fed = 0, status = 0;
+    double xy[2] = {0.0, 0.0};
+    for (int i = 0; i < n && !status; ++i) {
+        const ofp_onset r = recs[s_order[i]];
+        status = ofp::loc_feed(T, v, r.channel, first + r.sample, counter, true, sample, xy, &s_located);
+        ++fed;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        HopLocBlock* o = la.out;
+        o->status = status;
+        o->fed = fed;
+        o->dropped = n - fed;
+        o->flags = v.L->st[v.L->cur].flags;
+        o->n_members = status ? s_located.len : 0;
+        o->xy[0] = xy[0];
+        o->xy[1] = xy[1];
+        for (int k = 0; k < OFP_LOCS_MEMBERS; ++k) {
+            o->sens[k] = status && k < s_located.len ? s_located.sens[k] : 0;
+            o->on[k] = status && k < s_located.len ? s_located.on[k] : 0;
+        }
+    }
+    ofp::loc_store(v, la.state);
+}
+
+// Nodes form: the stage as a kernel of its own after the detector node.
+__global__ __launch_bounds__(256) void k_hop_locate(HopArgs a, HopLocArgs la, const ofp_onset* recs) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t n = *a.count;
+    if (n <= 0) return;
+    hop_locate_stage(a, la, a.ctl[0], (int)(n < a.C ? n : a.C), recs, smem);
+}
+
 // The whole hop in ONE launch: workgroup 0 is the detector (the phase-split block step of
 // ofp_stream_dev.h), workgroups 1..C the spectral branch of one channel each -- the two do not depend
 // on each other, so the hop takes max(detector, spectral) instead of their sum plus three launch gaps.
@@ -380,13 +473,19 @@ struct FusedCfg {
     static constexpr int WGS = HopCfg<F>::T <= 64 ? 256 : HopCfg<F>::T;
 };
 
-template <int F>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa) {
+// LOC: the instantiation of a session with a locator; without one the kernel is the one it always was.
+template <int F, bool LOC>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int64_t done = a.ctl[0];  // hops completed before this one
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) *a.hop_index = done;
-        ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
+        if constexpr (LOC) {
+            const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
+            if (n_on > 0) hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
+        } else {
+            ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
+        }
     } else if ((int)blockIdx.x <= a.C) {
         hop_spectral_body<F, FusedCfg<F>::WGS>(a, (int)blockIdx.x - 1, done + 1, smem);
     } else {  // the onset-strength workgroup (only launched when enabled)
@@ -447,6 +546,13 @@ struct ofp_hop_session {
     int64_t pushed = 0;   // hops submitted
     bool in_flight = false;
     bool retired = true;   // the last hop's kernel is known to have left the stream (a polled completion is not that)
+    // the locator (ofp_hop_set_locator)
+    HopLocArgs largs;
+    ofp_locate_state* d_loc_state = nullptr;
+    float* d_loc_prm = nullptr;     // own copy of the locator network's parameters
+    ofp_onset* d_mirror = nullptr;  // fused form: the records in device memory
+    int64_t o_loc = 0;
+    size_t lds_loc = 0;
 };
 
 namespace {
@@ -491,11 +597,15 @@ int dispatch_strength(ofp_hop_session* s) {
 
 template <int F>
 int hop_fused(ofp_hop_session* s) {
-    if (s->lds_fused > 65536 - 20480)  // (the detector's static LDS comes on top)
-        OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hop_fused<F>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_fused));
-    hipLaunchKernelGGL(k_hop_fused<F>, dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)), dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args,
-                       s->sargs);
+    auto launch = [&](auto kernel) -> int {
+        if (s->lds_fused > 65536 - 20480)  // (the detector's static LDS comes on top)
+            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)s->lds_fused));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)), dim3(FusedCfg<F>::WGS),
+                           s->lds_fused, s->stream, s->args, s->sargs, s->largs);
+        return OFP_OK;
+    };
+    if (int rc = s->largs.enabled ? launch(k_hop_fused<F, true>) : launch(k_hop_fused<F, false>)) return rc;
     OFP_LAUNCH_CHECK("k_hop_fused");
     return OFP_OK;
 }
@@ -552,6 +662,14 @@ int enqueue_hop(ofp_hop_session* s) {
                                 reinterpret_cast<ofp_onset*>(s->d_res + s->o_rec), s->C,
                                 reinterpret_cast<int64_t*>(s->d_res + s->o_count), s->stream);
     if (rc != OFP_OK) return rc;
+    if (s->largs.enabled) {  // (before the spectral node: the ring holds the older hops only)
+        if (s->lds_loc > 65536)
+            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hop_locate),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_loc));
+        hipLaunchKernelGGL(k_hop_locate, dim3(1), dim3(256), s->lds_loc, s->stream, s->args, s->largs,
+                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
+        OFP_LAUNCH_CHECK("k_hop_locate");
+    }
     if (s->args.sg.enabled) {  // (before the spectral node: it reads ring rows the spectral node is about to overwrite
                                //  only for hops older than the ring, never the current one)
         rc = dispatch_strength(s);
@@ -569,6 +687,7 @@ int reset_state(ofp_hop_session* s) {
     OFP_HIP(hipMemsetAsync(s->d_ring, 0, (size_t)s->R * s->C * sizeof(float), s->stream));
     OFP_HIP(hipMemsetAsync(s->d_ctl, 0, 2 * sizeof(int64_t), s->stream));
     OFP_HIP(hipMemsetAsync(s->d_res, 0, (size_t)s->res_bytes, s->stream));
+    if (s->d_loc_state) OFP_HIP(hipMemsetAsync(s->d_loc_state, 0, sizeof(ofp_locate_state), s->stream));
     if (s->d_sg) {
         OFP_HIP(hipMemsetAsync(s->d_sg, 0, s->sg_floats * 4, s->stream));
         OFP_HIP(hipMemcpyAsync(s->args.sg.st, s->sg_init, 16, hipMemcpyHostToDevice, s->stream));
@@ -577,6 +696,27 @@ int reset_state(ofp_hop_session* s) {
     std::memset(s->h_res, 0, (size_t)s->res_bytes);
     s->pushed = 0;
     s->in_flight = false;
+    return OFP_OK;
+}
+
+// one un-captured pass over zeros loads every code object and sets the kernel attributes
+// (neither may happen during capture), then the state is reset and the sequence captured
+int capture_hop(ofp_hop_session* s) {
+    int rc = reset_state(s);
+    if (rc != OFP_OK) return rc;
+    if ((rc = enqueue_hop(s)) != OFP_OK) return rc;
+    OFP_HIP(hipStreamSynchronize(s->stream));
+    if ((rc = reset_state(s)) != OFP_OK) return rc;
+    if (s->exec) (void)hipGraphExecDestroy(s->exec);
+    if (s->graph) (void)hipGraphDestroy(s->graph);
+    s->exec = nullptr;
+    s->graph = nullptr;
+    OFP_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+    rc = enqueue_hop(s);
+    hipError_t ce = hipStreamEndCapture(s->stream, &s->graph);
+    if (rc != OFP_OK) return rc;
+    if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    OFP_HIP(hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
     return OFP_OK;
 }
 
@@ -590,7 +730,7 @@ int ofp_hop_destroy(ofp_hop_session* s) {
     if (s->exec) (void)hipGraphExecDestroy(s->exec);
     if (s->graph) (void)hipGraphDestroy(s->graph);
     void* dev[] = {s->d_state, s->d_hop, s->d_ring, s->d_ctl, s->d_twM, s->d_twF, s->d_win, s->d_wsym, s->d_tgw, s->d_sg, s->d_fb_i, s->d_fb_w,
-                   s->d_prm, s->d_res};
+                   s->d_prm, s->d_res, s->d_loc_state, s->d_loc_prm, s->d_mirror};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (s->h_hop) (void)hipHostFree(s->h_hop);
@@ -641,7 +781,8 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     s->o_mel = up8(s->o_logits + (int64_t)C * s->n_out * 4);
     s->o_rel = up8(s->o_mel + (int64_t)C * s->n_mels * 4);
     s->o_sg = up8(s->o_rel + (s->want_rel ? (int64_t)B * C * 4 : 0));
-    s->res_bytes = up8(s->o_sg + 16 + (cfg->strength ? 4 * (int64_t)cfg->tg_win_length : 0));
+    s->o_loc = up8(s->o_sg + 16 + (cfg->strength ? 4 * (int64_t)cfg->tg_win_length : 0));
+    s->res_bytes = up8(s->o_loc + (int64_t)sizeof(HopLocBlock));
     const int M = s->n_fft / 2;
     const int st_a = cfg->mlp ? plan.st_a : 0, st_b = cfg->mlp ? plan.st_b : 0;
     s->lds = (size_t)(M + M + 2) * 8 + (size_t)s->n_fft * 4 + (size_t)(M <= 512 ? M + M / 16 : M) * 8 + (size_t)cfg->fb_nnz * 4 +
@@ -691,6 +832,7 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     }
     HopArgs& a = s->args;
     std::memset(&a, 0, sizeof(a));
+    std::memset(&s->largs, 0, sizeof(s->largs));
     a.C = C;
     a.B = B;
     a.n_mels = s->n_mels;
@@ -784,18 +926,7 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
         }
     }
     if ((rc = dispatch_tables(s)) != OFP_OK) return fail(rc);
-    // one un-captured pass over zeros loads every code object and sets the kernel attributes
-    // (neither may happen during capture), then the state is reset and the sequence captured
-    if ((rc = reset_state(s)) != OFP_OK) return fail(rc);
-    if ((rc = enqueue_hop(s)) != OFP_OK) return fail(rc);
-    HOP_TRY(hipStreamSynchronize(s->stream));
-    if ((rc = reset_state(s)) != OFP_OK) return fail(rc);
-    HOP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    rc = enqueue_hop(s);
-    hipError_t ce = hipStreamEndCapture(s->stream, &s->graph);
-    if (rc != OFP_OK) return fail(rc);
-    HOP_TRY(ce);
-    HOP_TRY(hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
+    if ((rc = capture_hop(s)) != OFP_OK) return fail(rc);
 #undef HOP_TRY
     *out = s;
     return OFP_OK;
@@ -895,6 +1026,81 @@ int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
                           hipMemcpyDeviceToHost));
         done += run;
     }
+    return OFP_OK;
+}
+
+int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
+    OFP_REQUIRE(s && loc, "ofp_hop_set_locator: NULL argument");
+    OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "ofp_hop_set_locator: the session has already taken a hop");
+    OFP_REQUIRE(!s->largs.enabled, "ofp_hop_set_locator: the session already has a locator");
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables(loc, "ofp_hop_set_locator", &T)) return rc;
+    OFP_REQUIRE(loc->S == s->C, "ofp_hop_set_locator: %d sensors for %d channels", loc->S, s->C);
+    OFP_REQUIRE(!s->det->p.backtrack, "ofp_hop_set_locator: a detector that backtracks moves onsets behind the hop");
+    OFP_REQUIRE(!loc->use_audio || s->R >= (int64_t)loc->max_section + s->B,
+                "ofp_hop_set_locator: the ring (%lld rows) must hold the longest section (%d) and one hop (%d)",
+                (long long)s->R, loc->max_section, s->B);
+    const int threads = s->fused ? fused_threads(s->n_fft) : 256;
+    const size_t lds = hop_loc_lds(threads, T, s->B, s->C);
+    OFP_REQUIRE(lds <= 128 * 1024, "ofp_hop_set_locator: %zu bytes of LDS needed", lds);
+    if (loc->mlp) {  // the session keeps its own copy: the handle may be destroyed afterwards
+        OFP_HIP(hipMalloc(&s->d_loc_prm, (size_t)T.plan.n_params * 4));
+        OFP_HIP(hipMemcpy(s->d_loc_prm, loc->mlp->d_params, (size_t)T.plan.n_params * 4, hipMemcpyDeviceToDevice));
+        T.plan.params = s->d_loc_prm;
+    }
+    OFP_HIP(hipMalloc(&s->d_loc_state, sizeof(ofp_locate_state)));
+    OFP_HIP(hipMemset(s->d_loc_state, 0, sizeof(ofp_locate_state)));
+    s->largs.T = T;
+    s->largs.state = s->d_loc_state;
+    s->lds_loc = lds;
+    if (s->fused) {
+        OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
+        OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
+        s->sargs.mirror = s->d_mirror;
+        unsigned char* dev_res = nullptr;
+        OFP_HIP(hipHostGetDevicePointer((void**)&dev_res, s->h_res, 0));
+        s->largs.out = reinterpret_cast<HopLocBlock*>(dev_res + s->o_loc);
+        s->lds_fused = std::max(s->lds_fused, lds);
+    } else {
+        s->largs.out = reinterpret_cast<HopLocBlock*>(s->d_res + s->o_loc);
+    }
+    s->largs.enabled = 1;
+    return capture_hop(s);
+}
+
+int ofp_hop_collect_location(ofp_hop_session* s, int32_t* status, double* h_xy, int32_t* n_members,
+                             int32_t* h_sensors, int64_t* h_onsets, int32_t* fed, int32_t* dropped, int32_t* flags) {
+    OFP_REQUIRE(s, "ofp_hop_collect_location: NULL session");
+    OFP_REQUIRE(s->largs.enabled, "ofp_hop_collect_location: the session has no locator");
+    OFP_REQUIRE(!s->in_flight && s->pushed > 0, "ofp_hop_collect_location: no collected hop");
+    HopLocBlock b;
+    std::memset(&b, 0, sizeof(b));
+    int64_t count;
+    std::memcpy(&count, s->h_res + s->o_count, 8);
+    if (count > 0) std::memcpy(&b, s->h_res + s->o_loc, sizeof(b));  // a hop without onsets leaves the block alone
+    if (status) *status = b.status;
+    if (h_xy) {
+        h_xy[0] = b.xy[0];
+        h_xy[1] = b.xy[1];
+    }
+    if (n_members) *n_members = b.n_members;
+    if (h_sensors) std::memcpy(h_sensors, b.sens, sizeof(b.sens));
+    if (h_onsets) std::memcpy(h_onsets, b.on, sizeof(b.on));
+    if (fed) *fed = b.fed;
+    if (dropped) *dropped = b.dropped;
+    if (flags) *flags = b.flags;
+    return OFP_OK;
+}
+
+int ofp_hop_locator_state(ofp_hop_session* s, ofp_locate_state* h_state) {
+    OFP_REQUIRE(s && h_state, "ofp_hop_locator_state: NULL argument");
+    OFP_REQUIRE(s->largs.enabled, "ofp_hop_locator_state: the session has no locator");
+    OFP_REQUIRE(!s->in_flight, "ofp_hop_locator_state: a hop is in flight (collect it first)");
+    if (!s->retired) {
+        OFP_HIP(hipStreamSynchronize(s->stream));
+        s->retired = true;
+    }
+    OFP_HIP(hipMemcpy(h_state, s->d_loc_state, sizeof(ofp_locate_state), hipMemcpyDeviceToHost));
     return OFP_OK;
 }
 

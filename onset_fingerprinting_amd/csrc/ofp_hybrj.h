@@ -11,9 +11,9 @@
 #include <cstdint>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define OFP_HD __host__ __device__
+#define OFP_HYBRJ_HD __host__ __device__
 #else
-#define OFP_HD
+#define OFP_HYBRJ_HD
 #endif
 
 namespace ofp {
@@ -29,17 +29,17 @@ struct Tdoa {
     double o[3], a[3], b[3];
     double dda, ddb;  // delta_d_a, delta_d_b
 
-    OFP_HD static double dist(double x, double y, const double* s) {
+    OFP_HYBRJ_HD static double dist(double x, double y, const double* s) {
         const double dx = x - s[0], dy = y - s[1], dz = 0.0 - s[2];
         return sqrt(dx * dx + dy * dy + dz * dz);
     }
-    OFP_HD void f(const double* p, double* out) const {
+    OFP_HYBRJ_HD void f(const double* p, double* out) const {
         const double da = dist(p[0], p[1], a), db = dist(p[0], p[1], b), d0 = dist(p[0], p[1], o);
         out[0] = da - d0 - dda;
         out[1] = db - d0 - ddb;
     }
     // fj column-major, fj[i + N*j] = d f_i / d x_j
-    OFP_HD void jac(const double* p, double* fj) const {
+    OFP_HYBRJ_HD void jac(const double* p, double* fj) const {
         const double x = p[0], y = p[1];
         const double da = dist(x, y, a), db = dist(x, y, b), d0 = dist(x, y, o);
         fj[0 + N * 0] = (x - a[0]) / da - (x - o[0]) / d0;
@@ -49,7 +49,7 @@ struct Tdoa {
     }
 };
 
-OFP_HD inline double enorm(int n, const double* x) {
+OFP_HYBRJ_HD inline double enorm(int n, const double* x) {
     const double rdwarf = 3.834e-20, rgiant = 1.304e19;
     double s1 = 0, s2 = 0, s3 = 0, x1max = 0, x3max = 0;
     const double agiant = rgiant / (double)n;
@@ -82,7 +82,7 @@ OFP_HD inline double enorm(int n, const double* x) {
 }
 
 // qrfac without pivoting on the N x N column-major a: rdiag, acnorm (initial column norms)
-OFP_HD inline void qrfac(double* a, double* rdiag, double* acnorm) {
+OFP_HYBRJ_HD inline void qrfac(double* a, double* rdiag, double* acnorm) {
     for (int j = 0; j < N; ++j) {
         acnorm[j] = enorm(N, a + N * j);
         rdiag[j] = acnorm[j];
@@ -104,7 +104,7 @@ OFP_HD inline void qrfac(double* a, double* rdiag, double* acnorm) {
     }
 }
 
-OFP_HD inline void qform(double* q) {
+OFP_HYBRJ_HD inline void qform(double* q) {
     double wa[N];
     for (int j = 1; j < N; ++j)
         for (int i = 0; i < j; ++i) q[i + N * j] = 0.0;
@@ -126,7 +126,7 @@ OFP_HD inline void qform(double* q) {
 }
 
 // r: upper triangle packed by rows (length LR)
-OFP_HD inline void dogleg(const double* r, const double* diag, const double* qtb, double delta, double* x) {
+OFP_HYBRJ_HD inline void dogleg(const double* r, const double* diag, const double* qtb, double delta, double* x) {
     double wa1[N], wa2[N];
     int jj = N * (N + 1) / 2;  // 0-based: index of r(jj) is jj - 1 in the loop below
     for (int k = 1; k <= N; ++k) {
@@ -195,7 +195,7 @@ OFP_HD inline void dogleg(const double* r, const double* diag, const double* qtb
 }
 
 // r1updt with m = n = N; s packed by rows (length LR)
-OFP_HD inline bool r1updt(double* s, const double* u, double* v, double* w) {
+OFP_HYBRJ_HD inline bool r1updt(double* s, const double* u, double* v, double* w) {
     int jj = LR - 1;  // 0-based index of the last diagonal element
     w[N - 1] = s[jj];
     for (int nmj = 1; nmj <= N - 1; ++nmj) {
@@ -261,7 +261,7 @@ OFP_HD inline bool r1updt(double* s, const double* u, double* v, double* w) {
 }
 
 // r1mpyq: a (m x N, column-major with leading dimension lda) times the rotations in v, w
-OFP_HD inline void r1mpyq(int m, double* a, int lda, const double* v, const double* w) {
+OFP_HYBRJ_HD inline void r1mpyq(int m, double* a, int lda, const double* v, const double* w) {
     double cs = 0.0, sn = 0.0;  // a NaN rotation keeps the previous one, as in the original
     for (int nmj = 1; nmj <= N - 1; ++nmj) {
         const int j = N - 1 - nmj;
@@ -295,7 +295,7 @@ struct Result {
 };
 
 // hybrj(fcn, n=2, x, xtol, maxfev, mode=1, factor) from the starting point x0
-OFP_HD inline Result solve(const Tdoa& fn, const double* x0, double xtol, int maxfev, double factor = 100.0) {
+OFP_HYBRJ_HD inline Result solve(const Tdoa& fn, const double* x0, double xtol, int maxfev, double factor = 100.0) {
     const double p1 = 0.1, p5 = 0.5, p001 = 0.001, p0001 = 0.0001;
     Result res;
     double x[N], fvec[N], fjac[N * N], diag[N], r[LR], qtf[N], wa1[N], wa2[N], wa3[N], wa4[N];

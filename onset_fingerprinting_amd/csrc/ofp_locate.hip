@@ -13,17 +13,23 @@
 // k_locate_rows: the per-row front of ofp_locate_groups: earliest three channels, is_legal on both pairs and the
 //                legality search, one workgroup per row.
 // k_locate_solve: the back: trilaterate (or the model's output * 100) per row, one lane per row.
+// k_locate_stream: Multilaterate3D.locate itself, K calls through one device-resident state (ofp_locate_dev.h),
+//                one workgroup.
 // k_section:     Multilaterate3D.locate's cross-correlation input (multilateration.py:466-476): median filter of
 //                size 5 ('reflect') along time, first difference, non-negative values zeroed, absolute value.
 #include <cmath>
+#include <cstring>
 
 #include "ofp_common.h"
 #include "ofp_hybrj.h"
+#include "ofp_locate_dev.h"
 #include "ofp_mlp.h"
 
 namespace {
 
 using ofp::cdiv;
+using ofp::first_legal;  // ofp_locate_dev.h
+using ofp::med5;
 
 constexpr int LOC_THREADS = 256;
 
@@ -84,33 +90,6 @@ __global__ void k_lag_minmax(const float* __restrict__ maps, int64_t cells, floa
         d_min[blockIdx.x] = any ? smin[0] : __builtin_nanf("");
         d_max[blockIdx.x] = any ? smax[0] : __builtin_nanf("");
     }
-}
-
-// is_legal_3d (multilateration.py:413-426) for one group, by the whole workgroup; every thread gets the result.
-// Returns the first legal flat index (row * side + col) or -1.
-__device__ int64_t first_legal(const float* __restrict__ maps, int S, int side, int s0, int s1, int s2, double lag1,
-                               double lag2, double tol, int64_t* smin) {
-    const int64_t cells = (int64_t)side * side;
-    const float* m1 = maps + ((int64_t)s0 * S + s1) * cells;
-    const float* m2 = maps + ((int64_t)s0 * S + s2) * cells;
-    const double hi1 = lag1 + tol, lo1 = lag1 - tol, hi2 = lag2 + tol, lo2 = lag2 - tol;
-    int64_t best = cells;
-    for (int64_t k = threadIdx.x; k < cells; k += blockDim.x) {
-        const double a = (double)m1[k], b = (double)m2[k];
-        if (a < hi1 && a > lo1 && b < hi2 && b > lo2) {
-            best = k;  // k only grows within a thread: the first hit is this thread's minimum
-            break;
-        }
-    }
-    smin[threadIdx.x] = best;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s && smin[threadIdx.x + s] < smin[threadIdx.x]) smin[threadIdx.x] = smin[threadIdx.x + s];
-        __syncthreads();
-    }
-    const int64_t r = smin[0];
-    __syncthreads();
-    return r < cells ? r : -1;
 }
 
 __global__ void k_legal(const float* __restrict__ maps, int S, int side, const int32_t* __restrict__ sens,
@@ -288,20 +267,6 @@ __global__ void k_locate_solve(LocateArgs A, int64_t n_rows, const float* __rest
     status[row] = res.info;
 }
 
-__device__ __forceinline__ float med5(const float* in) {
-    float v[5];
-    for (int i = 0; i < 5; ++i) {  // insertion sort of five finite samples
-        const float x = in[i];
-        int j = i;
-        while (j > 0 && v[j - 1] > x) {
-            v[j] = v[j - 1];
-            --j;
-        }
-        v[j] = x;
-    }
-    return v[2];
-}
-
 __device__ __forceinline__ float sec_at(const float* x, int64_t n, int ld, int col, int64_t t) {
     if (t < 0) t = -t - 1;          // scipy.ndimage 'reflect': d c b a | a b c d | d c b a
     if (t >= n) t = 2 * n - t - 1;
@@ -325,7 +290,76 @@ __global__ void k_section(const float* __restrict__ x, int64_t n, int ld, int c0
     out[(int64_t)which * (n - 1) + t] = fabsf(d);
 }
 
+// The replay entry: K calls of locate through one state machine, one workgroup (ofp_locate_dev.h).
+__global__ __launch_bounds__(LOC_THREADS) void k_locate_stream(ofp::LocTables T, const int32_t* __restrict__ sensor,
+                                                               const int64_t* __restrict__ onset,
+                                                               const int64_t* __restrict__ counter, int64_t K,
+                                                               const float* __restrict__ audio, int64_t n_rows, int C,
+                                                               ofp_locate_state* state, int32_t* __restrict__ found,
+                                                               double* __restrict__ xy) {
+    extern __shared__ __align__(16) unsigned char loc_smem[];
+    const ofp::LocView v = ofp::loc_carve(loc_smem, LOC_THREADS, T.max_section, T.plan);
+    ofp::loc_load(T, v, nullptr);
+    auto sample = [&](int64_t t, int col) -> float { return t >= 0 && t < n_rows ? audio[t * C + col] : 0.0f; };
+    for (int64_t k = 0; k < K; ++k) {
+        const int s = sensor[k];
+        const int64_t cnt = counter[k];
+        double r[2] = {__builtin_nan(""), __builtin_nan("")};
+        int f = 0;
+        if (s < 0 || s >= T.S || (T.use_audio && (cnt < 0 || cnt > n_rows))) {  // uniform over the workgroup
+            __syncthreads();
+            if (threadIdx.x == 0) v.L->st[v.L->cur].flags |= OFP_LOCF_BAD_CALL;
+            __syncthreads();
+        } else {
+            f = ofp::loc_feed(T, v, s, onset[k], cnt, false, sample, r, nullptr);
+        }
+        if (threadIdx.x == 0) {
+            found[k] = f;
+            xy[2 * k] = f ? r[0] : __builtin_nan("");
+            xy[2 * k + 1] = f ? r[1] : __builtin_nan("");
+        }
+    }
+    ofp::loc_store(v, state);
+}
+
 }  // namespace
+
+int ofp_locate_tables(const ofp_hop_locator* loc, const char* who, ofp::LocTables* out) {
+    OFP_REQUIRE(loc, "%s: NULL locator", who);
+    OFP_REQUIRE(loc->S >= 3 && loc->S <= 64, "%s: need 3..64 sensors (S = %d)", who, loc->S);
+    OFP_REQUIRE(loc->r >= 0 && loc->r <= 4096, "%s: grid radius %d outside 0..4096", who, loc->r);
+    OFP_REQUIRE(loc->d_sensors && loc->d_maps && loc->d_min && loc->d_max, "%s: NULL table", who);
+    OFP_REQUIRE(loc->xtol >= 0.0 && loc->maxfev > 0, "%s: xtol must be >= 0 and maxfev > 0", who);
+    OFP_REQUIRE(loc->sr > 0.0 && loc->c > 0.0 && loc->samples_per_cm > 0.0,
+                "%s: speed of sound, sampling rate and samples per cm must be positive", who);
+    OFP_REQUIRE(!loc->use_audio || (loc->max_section >= 3 && loc->max_section <= ofp::LOC_MAX_SECTION),
+                "%s: max_section %d outside 3..%d", who, loc->max_section, ofp::LOC_MAX_SECTION);
+    ofp::LocTables& T = *out;
+    std::memset(&T, 0, sizeof(T));
+    if (loc->mlp) {
+        const MlpPlan& P = loc->mlp->plan;
+        OFP_REQUIRE(P.dims[0] == 2 && P.dims[P.n_layers] == 2,
+                    "%s: the network must map 2 lags to 2 coordinates (got %d -> %d)", who, P.dims[0],
+                    P.dims[P.n_layers]);
+        T.plan = P;
+        T.plan.params = loc->mlp->d_params;
+    }
+    T.sensors = loc->d_sensors;
+    T.S = loc->S;
+    T.maps = loc->d_maps;
+    T.mn = loc->d_min;
+    T.mx = loc->d_max;
+    T.side = 2 * loc->r + 1;
+    T.spc = loc->samples_per_cm;
+    T.sr = loc->sr;
+    T.c = loc->c;
+    T.radius = loc->radius;
+    T.xtol = loc->xtol;
+    T.maxfev = loc->maxfev;
+    T.use_audio = loc->use_audio ? 1 : 0;
+    T.max_section = loc->use_audio ? loc->max_section : 4;
+    return OFP_OK;
+}
 
 extern "C" {
 
@@ -448,6 +482,29 @@ int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int3
     hipLaunchKernelGGL(k_section, dim3((unsigned)cdiv(n - 1, LOC_THREADS), 2), dim3(LOC_THREADS), 0,
                        (hipStream_t)stream, d_x, n, ld, c0, c1, d_out);
     OFP_LAUNCH_CHECK("k_section");
+    return OFP_OK;
+}
+
+int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset,
+                      const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
+                      ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables(loc, "ofp_locate_stream", &T)) return rc;
+    OFP_REQUIRE(K >= 0, "ofp_locate_stream: negative call count");
+    OFP_REQUIRE(d_state, "ofp_locate_stream: NULL state");
+    OFP_REQUIRE((d_audio != nullptr) == (loc->use_audio != 0),
+                "ofp_locate_stream: use_audio and the recording must be given together");
+    OFP_REQUIRE(!d_audio || (n_rows >= 0 && n_channels >= loc->S),
+                "ofp_locate_stream: the recording has %d channels for %d sensors", n_channels, loc->S);
+    if (K == 0) return OFP_OK;
+    OFP_REQUIRE(d_sensor && d_onset && d_counter && d_found && d_xy, "ofp_locate_stream: NULL argument");
+    const size_t lds = ofp::loc_lds_bytes(LOC_THREADS, T.max_section, T.plan);
+    OFP_REQUIRE(lds <= 150 * 1024, "ofp_locate_stream: %zu bytes of LDS needed", lds);
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_stream), lds, attr, 32768)) return rc;
+    hipLaunchKernelGGL(k_locate_stream, dim3(1), dim3(LOC_THREADS), lds, (hipStream_t)stream, T, d_sensor, d_onset,
+                       d_counter, K, d_audio, n_rows, (int)n_channels, d_state, d_found, d_xy);
+    OFP_LAUNCH_CHECK("k_locate_stream");
     return OFP_OK;
 }
 

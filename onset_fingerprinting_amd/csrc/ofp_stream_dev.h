@@ -68,6 +68,8 @@ struct StreamArgs {
     int64_t cap;
     int64_t* count;
     int fresh_count;   // != 0: the count starts at 0 instead of *count (per-hop session: no read of the result block)
+    ofp_onset* mirror; // a second copy of the records in device memory, or NULL (per-hop session with a locator: its
+                       // records go to pinned host memory, the locate stage reads this copy)
 };
 
 // ---- phase-split form of the same block step -------------------------------------------------
@@ -129,7 +131,10 @@ __device__ __forceinline__ void seq_walk(const float* __restrict__ in, int B, in
     for (; t0 < B; ++t0) f(t0, in[t0 * C]);
 }
 
-__device__ __forceinline__ void stream_par_blocks(const StreamArgs& a, float* sbuf /* three [B][C] planes of LDS */) {
+// Returns the onset count it leaves in *a.count (the same value on every thread).  MIRROR: the records also go to
+// a.mirror (only the per-hop kernel of a session with a locator is built with it; every other caller's code is unchanged).
+template <bool MIRROR = false>
+__device__ __forceinline__ long long stream_par_blocks(const StreamArgs& a, float* sbuf /* three [B][C] planes of LDS */) {
     __shared__ int s_first[PAR_MAX_C], s_last[PAR_MAX_C];
     __shared__ float s_on[PAR_MAX_C], s_off[PAR_MAX_C];
     __shared__ double s_on0[PAR_MAX_C], s_prev[PAR_MAX_C];
@@ -298,6 +303,11 @@ __device__ __forceinline__ void stream_par_blocks(const StreamArgs& a, float* sb
                     a.records[pos].clip = 0;
                     a.records[pos].channel = c;
                     a.records[pos].sample = a.sample_base + blk * B + delta;
+                    if (MIRROR) {
+                        a.mirror[pos].clip = 0;
+                        a.mirror[pos].channel = c;
+                        a.mirror[pos].sample = a.sample_base + blk * B + delta;
+                    }
                 }
             }
         }
@@ -313,6 +323,7 @@ __device__ __forceinline__ void stream_par_blocks(const StreamArgs& a, float* sb
         (which ? s.mx : s.mn)[rc] = trk;
     }
     if (tid == 0) *a.count = base;
+    return base;
 }
 
 

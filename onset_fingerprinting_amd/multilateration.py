@@ -22,6 +22,10 @@ Same names, arguments and returns as the reference for:
   * ``lag_intensity_map`` (GPU: ``ofp_lag_maps`` and ``ofp_intensity_maps``) and its host helpers ``vec_sub``,
     ``attenuate_intensity``, ``sound_intensity_at_source``.
 
+``Multilaterate3D.locate`` also exists as device code (csrc/ofp_locate_dev.h) on a device-resident copy of ``ongoing``:
+``Multilaterate3D.locate_stream_device`` replays a stream of calls in one launch (``ofp_locate_stream``), and
+``realtime.HopSession(locator=...)`` runs it inside the hop's graph.
+
 Batched, device-resident additions: ``locate_groups_device`` locates every onset group ``group_onsets_device``
 found, in one pass without host synchronisation; ``find_lags_device``, ``MultilateratePaired.locate_cc_device`` /
 ``locate_device`` and ``locate_cc_groups_device`` do the same for the 2-D functions.
@@ -47,6 +51,7 @@ MEDIUM = "air"
 ONSET_TOL = 50
 NORM_CUTOFF = 10
 lookaround = ONSET_TOL + NORM_CUTOFF
+LOCATE_MAX_SECTION = 4096  # longest cross-correlation section of the device state machine (rows)
 
 XTOL = 0.01  # solve_trilateration*'s fsolve arguments
 MAXFEV = 20
@@ -260,6 +265,49 @@ def solve_trilateration_3d(sensor_a, sensor_b, sensor_origin, delta_d_a: float, 
     return _solve_one(sensor_a, sensor_b, sensor_origin, delta_d_a, delta_d_b, initial_guess, device)
 
 
+def longest_section(max_max_lags, block_size: int) -> int:
+    """max(max_max_lags) + block_size + lookaround + 1: the group's first onset lies at most max(max_max_lags)
+    samples before the onset fed, which lies in the hop that ends at the counter."""
+    return int(np.ceil(float(np.nanmax(max_max_lags)))) + int(block_size) + lookaround + 1
+
+
+def check_locator_model(model, what):
+    """ValueError unless `model` is None or a 2 -> 2 calibration.FCNN; host-side only (no GPU call)."""
+    if model is None:
+        return
+    if not hasattr(model, "device_mlp"):
+        raise ValueError(f"{what}: the model must be a calibration.FCNN (its ofp_mlp network)")
+    lin = [m for m in model.modules() if isinstance(m, torch.nn.Linear)]
+    if not lin or (lin[0].in_features, lin[-1].out_features) != (2, 2):
+        got = f"{lin[0].in_features} -> {lin[-1].out_features}" if lin else "no"
+        raise ValueError(f"{what}: the model maps {got} values, not 2 -> 2")
+
+
+def ongoing_list(state):
+    """A ``_lib.LocateState`` as the reference's ``ongoing``: a list of ([sensors], [onsets]).  Two entries that are
+    one Python object in the reference (an extended group is appended twice) are one object here too."""
+    out = []
+    for g in range(state.n_groups):
+        if state.alias[g] and out:
+            out.append(out[-1])
+            continue
+        n = state.len[g]
+        out.append(([int(v) for v in state.sensors[g][:n]], [int(v) for v in state.onsets[g][:n]]))
+    return out
+
+
+def check_locate_flags(flags, what):
+    """The device state machine's sticky flags are never silent."""
+    if flags & (_lib.LOCF_GROUPS | _lib.LOCF_MEMBERS):
+        raise _lib.OnsetFPError(f"{what}: the locate state overflowed ({_lib.LOCS_GROUPS} groups of up to "
+                                f"{_lib.LOCS_MEMBERS} members; flags {flags})")
+    if flags & _lib.LOCF_SECTION:
+        raise _lib.OnsetFPError(f"{what}: a cross-correlation section was longer than the bound or shorter than 3 rows "
+                                f"(flags {flags})")
+    if flags & _lib.LOCF_BAD_CALL:
+        raise _lib.OnsetFPError(f"{what}: a call was refused (sensor index or counter out of range; flags {flags})")
+
+
 # ---- Multilaterate3D ----------------------------------------------------------------------------------------
 
 class Multilaterate3D:
@@ -386,6 +434,64 @@ class Multilaterate3D:
         new_groups.append(([sensor_index], [onset_index]))
         self.ongoing = new_groups
         return None
+
+    # ---- locate on the device ------------------------------------------------------------------------------
+
+    def _device_model(self, what):
+        """The model's ofp_mlp network (None without a model); ValueError unless it is a 2 -> 2 calibration.FCNN."""
+        check_locator_model(self.model, what)
+        return self.model.device_mlp(self.device) if self.model is not None else None
+
+    def locator_struct(self, use_audio, max_section, mlp=None, xtol=XTOL, maxfev=MAXFEV):
+        """The ofp_hop_locator of this object's device tables (they must outlive every call that uses it)."""
+        loc = _lib.HopLocator()
+        loc.d_sensors, loc.S = self.sensors_dev.data_ptr(), self.sensors_dev.shape[0]
+        loc.d_maps, loc.d_min, loc.d_max = self.maps_dev.data_ptr(), self.min_dev.data_ptr(), self.max_dev.data_ptr()
+        loc.r = self.grid_radius
+        loc.samples_per_cm, loc.sr, loc.c, loc.radius = float(self.samples_per_cm), float(self.sr), float(self.c), \
+            float(self.radius)
+        loc.xtol, loc.maxfev = float(xtol), int(maxfev)
+        loc.mlp = mlp.handle if mlp is not None else None
+        loc.use_audio, loc.max_section = int(bool(use_audio)), int(max_section)
+        return loc
+
+    def locate_stream_device(self, sensors, onsets, counters, audio=None):
+        """``locate`` for a whole stream of calls in ONE launch (``ofp_locate_stream``): call k feeds
+        (sensors[k], onsets[k]) with a ring that holds ``audio[:counters[k]]`` (audio [N, C] float32, numpy or a
+        CUDA tensor; None: no cross-correlation step).  Starts from an empty state and does not touch
+        ``self.ongoing``.  Returns (found bool [K], xy float64 [K, 2] with NaN where nothing was returned, ongoing:
+        the final state as the reference's list of ([sensors], [onsets])).  Raises OnsetFPError when the state
+        overflowed (64 groups of 8 members), a section was longer than LOCATE_MAX_SECTION rows, or a call was refused
+        (the kernel checks every call: sensor outside 0..S-1, counter outside the recording)."""
+        sens = np.ascontiguousarray(sensors, dtype=np.int32).reshape(-1)
+        ons = np.ascontiguousarray(onsets, dtype=np.int64).reshape(-1)
+        cnt = np.ascontiguousarray(counters, dtype=np.int64).reshape(-1)
+        K = len(sens)
+        if not (len(ons) == K and len(cnt) == K):
+            raise ValueError(f"locate_stream_device: {K} sensors, {len(ons)} onsets, {len(cnt)} counters")
+        S = self.sensors_dev.shape[0]
+        mlp = self._device_model("locate_stream_device")
+        dev = self.device
+        ad, n_rows, n_ch, max_section = None, 0, 0, 0
+        if audio is not None:
+            ad = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+            if ad.dim() != 2 or ad.shape[1] < S:
+                raise ValueError(f"locate_stream_device: audio must be [N, C >= {S}], got {tuple(ad.shape)}")
+            ad = ad.to(dev, torch.float32).contiguous()
+            n_rows, n_ch = ad.shape
+            max_section = LOCATE_MAX_SECTION  # the counters are the caller's: any section the kernel can hold
+        loc = self.locator_struct(audio is not None, max_section, mlp)
+        to = lambda a: torch.from_numpy(a).to(dev)
+        sd, od, cd = to(sens), to(ons), to(cnt)
+        state = torch.zeros(ctypes.sizeof(_lib.LocateState), dtype=torch.uint8, device=dev)
+        found = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+        xy = torch.full((max(K, 1), 2), float("nan"), dtype=torch.float64, device=dev)
+        check(_lib.lib().ofp_locate_stream(ctypes.byref(loc), sd.data_ptr(), od.data_ptr(), cd.data_ptr(), K,
+                                           _ptr(ad), n_rows, n_ch, state.data_ptr(), found.data_ptr(), xy.data_ptr(),
+                                           _stream(dev)), "ofp_locate_stream")
+        st = _lib.LocateState.from_buffer_copy(state.cpu().numpy().tobytes())
+        check_locate_flags(st.flags, "locate_stream_device")
+        return found.cpu().numpy()[:K].astype(bool), xy.cpu().numpy()[:K], ongoing_list(st)
 
 
 # ---- batched offline locator --------------------------------------------------------------------------------

@@ -48,13 +48,40 @@ class HopSession:
     ``channels`` / ``onsets`` (absolute sample indices, as ``detect_hits`` forms them,
     audio.py:65), ``logits`` ``[n_signals, n_out]`` (None without a classifier), ``mel``
     ``[n_signals, n_mels]`` and, with ``want_rel``, the hop's relative envelope.
+
+    ``locator``: a ``multilateration.Multilaterate3D`` on the session's device.  The hop's graph then also runs
+    ``detect_hits`` (realtime/audio.py:62-74): the hop's onsets, sorted by sample, go through
+    ``Multilaterate3D.locate`` on a device-resident copy of its state until one returns a position
+    (``locate_with_audio``: with the ring as ``rec_audio``).  The result dict gains ``location`` (None or (x, y) in
+    cm, as ``locate`` returns it), ``located_group`` (None or ([sensors], [onsets]) as ``trilaterate`` left it),
+    ``fed`` (onsets given to the state machine) and ``dropped`` (onsets of the hop after the one that located: the
+    reference returns at the first hit and never feeds them).  ``ongoing`` reads the state back.  The locator's own
+    ``ongoing`` is not touched.
     """
 
     def __init__(self, n_signals, block_size=128, sr=96000, n_fft=2048, n_mels=40, classifier=None,
                  ring_seconds=60.0, want_rel=False, device=0, floor=-70.0, hipass_freq=2000.0,
                  fast_ar=(3.0, 383.0), slow_ar=(2205.0, 2205.0), on_threshold=0.5, off_threshold=0.1,
                  cooldown=1323, backtrack=False, backtrack_buffer_size=None, backtrack_smooth_size=5,
-                 onset_strength=None):
+                 onset_strength=None, locator=None, locate_with_audio=True):
+        ring_rows = max(int(round(ring_seconds * sr)), n_fft, block_size)  # realtime/config.py:45,59
+        if locator is not None:  # argument errors before any GPU call
+            from . import multilateration as ml
+            if len(locator.sensor_locs) != n_signals:
+                raise ValueError(f"HopSession: the locator has {len(locator.sensor_locs)} sensors, the session "
+                                 f"{n_signals} signals")
+            if backtrack:
+                raise ValueError("HopSession: a locator needs backtrack=False (a backtracked onset may lie behind the "
+                                 "current hop)")
+            self._max_section = ml.longest_section(locator.max_max_lags, block_size)
+            if locate_with_audio and (ring_rows < self._max_section + block_size
+                                      or self._max_section > ml.LOCATE_MAX_SECTION):
+                raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the longest section "
+                                 f"({self._max_section} rows, at most {ml.LOCATE_MAX_SECTION}) plus one hop")
+            ml.check_locator_model(locator.model, "HopSession")
+            want = device.index or 0 if isinstance(device, torch.device) else int(device)
+            if (locator.device.index or 0) != want:
+                raise ValueError(f"HopSession: the locator lives on {locator.device}, the session on device {want}")
         L = _lib.lib()
         self.n_signals, self.block_size, self.sr, self.n_fft, self.n_mels = n_signals, block_size, sr, n_fft, n_mels
         if backtrack_buffer_size is None:
@@ -70,7 +97,7 @@ class HopSession:
         self.n_out = mlp.n_out if mlp is not None else 0
         cfg = HopConfig()
         cfg.n_fft = n_fft
-        cfg.ring_samples = max(int(round(ring_seconds * sr)), n_fft, block_size)  # realtime/config.py:45,59
+        cfg.ring_samples = ring_rows
         cfg.n_mels = n_mels
         cfg.fb_lo, cfg.fb_len, cfg.fb_off, cfg.fb_w = (a.ctypes.data for a in (lo, ln, off, w))
         cfg.fb_nnz = len(w)
@@ -107,6 +134,43 @@ class HopSession:
         self._rel = np.zeros((block_size, n_signals), dtype=np.float32)
         self._sg = np.zeros(4 + (int(cfg.tg_win_length) if onset_strength is not None else 0), dtype=np.float32)
         self.current_index = 0  # audio.py:120
+        self.locator = locator
+        if locator is not None:
+            try:
+                self._loc_mlp = locator._device_model("HopSession")  # kept alive with the session
+                loc = locator.locator_struct(locate_with_audio, self._max_section, self._loc_mlp)
+                with torch.cuda.device(self.device):
+                    check(L.ofp_hop_set_locator(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator")
+            except Exception:
+                self.close()
+                raise
+            self._loc_i = [ctypes.c_int32() for _ in range(5)]  # status, n_members, fed, dropped, flags
+            self._loc_xy = (ctypes.c_double * 2)()
+            self._loc_sens = (ctypes.c_int32 * _lib.LOCS_MEMBERS)()
+            self._loc_on = (ctypes.c_int64 * _lib.LOCS_MEMBERS)()
+
+    def _location(self, out):
+        from . import multilateration as ml
+        status, n, fed, dropped, flags = self._loc_i
+        check(self._L.ofp_hop_collect_location(self.handle, ctypes.byref(status), self._loc_xy, ctypes.byref(n),
+                                               self._loc_sens, self._loc_on, ctypes.byref(fed), ctypes.byref(dropped),
+                                               ctypes.byref(flags)), "ofp_hop_collect_location")
+        ml.check_locate_flags(flags.value, "HopSession")
+        hit = status.value == 1
+        out["location"] = (np.float64(self._loc_xy[0]), np.float64(self._loc_xy[1])) if hit else None
+        out["located_group"] = (list(self._loc_sens[:n.value]), list(self._loc_on[:n.value])) if hit else None
+        out["fed"], out["dropped"] = fed.value, dropped.value
+        return out
+
+    @property
+    def ongoing(self):
+        """The device state as the reference's ``Multilaterate3D.ongoing``: a list of ([sensors], [onsets])."""
+        from . import multilateration as ml
+        if self.locator is None:
+            raise ValueError("HopSession.ongoing: the session has no locator")
+        st = _lib.LocateState()
+        check(self._L.ofp_hop_locator_state(self.handle, ctypes.byref(st)), "ofp_hop_locator_state")
+        return ml.ongoing_list(st)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -150,13 +214,19 @@ class HopSession:
                                       self._sg.ctypes.data if self.onset_strength else None), "ofp_hop_collect")
         k = min(int(self._n.value), self.n_signals)
         self.current_index += self.block_size
-        return dict(channels=self._rec["channel"][:k].astype(np.int64), onsets=self._rec["sample"][:k].copy(),
+        out = dict(channels=self._rec["channel"][:k].astype(np.int64), onsets=self._rec["sample"][:k].copy(),
                     logits=self._logits.copy() if self.n_out else None, mel=self._mel.copy(),
                     rel=self._rel.copy() if self.want_rel else None,
                     # {flux, normalised, moving max, moving mean} of recording.py:296-311
                     strength=self._sg[:4].copy() if self.onset_strength else None,
                     # recording.py:313-327 (None unless onset_strength has tg_win_length)
                     tempogram=self._sg[4:].copy() if self.onset_strength and len(self._sg) > 4 else None)
+        if self.locator is None:
+            return out
+        if k == 0:  # the stage did not run: nothing to read
+            out.update(location=None, located_group=None, fed=0, dropped=0)
+            return out
+        return self._location(out)
 
     def __call__(self, hop):
         self.submit(hop)
