@@ -389,8 +389,13 @@ int ofp_mlp_destroy(ofp_mlp* mlp);
 int64_t ofp_mlp_lds_bytes(const ofp_mlp* mlp);
 int ofp_mlp_forward(const ofp_mlp* mlp, const float* d_x, int64_t n, float* d_y, void* stream);
 
-/* Conv1d (stride 1, groups 1) + bias + activation: d_x [n][cin][w] ->
- * d_y [n][cout][wout], wout = w + 2*padding - dilation*(k-1)   (model.py:84-95) */
+/* Conv1d (any stride, any groups that divide cin and cout) + bias + activation, then the optional
+ * per-channel affine of an eval-mode BatchNorm1d, then optionally MaxPool1d(2, 2) (model.py:84-107):
+ * d_x [n][cin][w] -> d_y [n][cout][wout] with
+ *   wconv = (w + 2*padding - dilation*(k-1) - 1) / stride + 1   (integer division)
+ *   wout  = pool ? wconv / 2 : wconv                            (floor: an odd last column is dropped)
+ * OFP_ERR_INVALID: cin, cout, w or k < 1, dilation < 1, padding < 0, stride < 1, groups that do not divide
+ * cin and cout, only one of d_bn_scale / d_bn_shift, an unknown activation, wout < 1. */
 int ofp_conv1d(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w /*[cout][cin/groups][k]*/,
                const float* d_b, int32_t cout, int32_t k, int32_t padding, int32_t dilation, int32_t groups,
                int32_t stride, int32_t act, const float* d_bn_scale /*[cout] or NULL*/, const float* d_bn_shift,

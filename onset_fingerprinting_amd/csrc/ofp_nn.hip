@@ -232,7 +232,7 @@ extern "C" {
 
 int ofp_autocorr_softmax(const float* d_x, int64_t n, int32_t K, int32_t V, float* d_out, void* stream) {
     if (n == 0) return OFP_OK;
-    OFP_REQUIRE(d_x && d_out && K >= 1 && V >= 1, "ofp_autocorr_softmax: bad argument");
+    OFP_REQUIRE(d_x && d_out && K >= 1 && V >= 1 && n > 0 && n < (1ll << 31), "ofp_autocorr_softmax: bad argument");
     const size_t lds = ((size_t)K * V + 2 * V + 64) * sizeof(float);
     OFP_REQUIRE(lds <= 160 * 1024, "ofp_autocorr_softmax: K*V = %d floats do not fit the LDS", K * V);
     if (lds > 65536)
@@ -344,13 +344,18 @@ int ofp_conv1d(const float* d_x, int64_t n, int32_t cin, int32_t w, const float*
                void* stream) {
     if (n == 0) return OFP_OK;
     OFP_REQUIRE(d_x && d_w && d_y, "ofp_conv1d: NULL argument");
+    OFP_REQUIRE(n > 0 && cin >= 1 && cout >= 1 && w >= 1, "ofp_conv1d: bad sizes (n=%lld cin=%d cout=%d w=%d)",
+                (long long)n, cin, cout, w);
+    OFP_REQUIRE(k >= 1 && dilation >= 1 && padding >= 0, "ofp_conv1d: need k >= 1, dilation >= 1, padding >= 0 (k=%d "
+                "dilation=%d padding=%d)", k, dilation, padding);
     OFP_REQUIRE(groups >= 1 && cin % groups == 0 && cout % groups == 0,
                 "ofp_conv1d: groups %d must divide cin %d and cout %d", groups, cin, cout);
     OFP_REQUIRE((d_bn_scale == nullptr) == (d_bn_shift == nullptr), "ofp_conv1d: give both bn_scale and bn_shift");
     OFP_REQUIRE(stride >= 1, "ofp_conv1d: stride %d", stride);
-    int wout = w + 2 * padding - dilation * (k - 1);
-    OFP_REQUIRE(wout >= 1, "ofp_conv1d: empty output (w=%d k=%d padding=%d dilation=%d)", w, k, padding, dilation);
-    wout = (wout - 1) / stride + 1;
+    const int64_t span = (int64_t)w + 2 * (int64_t)padding - (int64_t)dilation * (k - 1);
+    OFP_REQUIRE(span >= 1 && span < (1ll << 31), "ofp_conv1d: empty or oversized output (w=%d k=%d padding=%d dilation=%d)", w, k,
+                padding, dilation);
+    int wout = (int)((span - 1) / stride + 1);
     if (pool) wout /= 2;  // MaxPool1d(kernel_size=2, stride=2), floor
     OFP_REQUIRE(wout >= 1, "ofp_conv1d: nothing left after pooling");
     OFP_REQUIRE(act >= OFP_ACT_IDENTITY && act <= OFP_ACT_TANH, "ofp_conv1d: unknown activation %d", act);

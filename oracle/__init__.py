@@ -38,6 +38,9 @@ from .spectral import (  # noqa: F401
     window_contribution_weights,
 )
 from .classifier import cccnn_forward, cnn_forward, fcnn_forward  # noqa: F401
+from . import nn_kernels  # noqa: F401
+from .nn_kernels import (attention_mean_ref, autocorr_softmax_ref, conv1d_ref, dense_ref, groupnorm1_ref,  # noqa: F401
+                         layernorm_ref)
 from .groups import find_onset_groups, group_windows  # noqa: F401
 from .xcorr import (adjust_onset, adjust_onset_rel, cross_correlation_lag, detect_onset_region,  # noqa: F401
                     filter_data, fix_onsets, lag_window, xcorr_slice)
