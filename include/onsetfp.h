@@ -334,7 +334,8 @@ int64_t ofp_detect_planar_stride(const ofp_detector* det, int64_t n_clips, int64
  * the Python layer): for each of n_frames (clip, channel, start) triples,
  * d_spec[f][n_fft/2+1] complex64 = rfft(window * pad_center(x[start : start+frame_length]))
  * with samples outside [0, n_samples) read as zero.  d_window is float32[n_fft]
- * (the zero-padded periodic Hann, data.py:627-629).  starts may be negative. */
+ * (the zero-padded periodic Hann, data.py:627-629).  starts may be negative.
+ * n_channels < 1 or a frame_length outside [1, n_fft] is OFP_ERR_INVALID (nothing is launched). */
 int ofp_stft_frames(const float* d_x, int64_t n_clips, int64_t n_samples, int32_t n_channels,
                     const int32_t* d_clip, const int32_t* d_channel, const int64_t* d_start,
                     const int64_t* d_valid_lo, const int64_t* d_valid_hi, int64_t n_frames,
@@ -349,14 +350,15 @@ int ofp_extract_frames(const float* d_x, int64_t n_samples, int32_t n_channels,
 /* ---- fingerprint: mel + dB + DCT (data.py:657-680) ------------------------------- */
 /* d_power [n_rows][n_bins] -> d_mel [n_rows][n_mels] = power @ fb^T with the sparse
  * triangular filterbank given in CSR-by-band form (band b covers bins
- * [d_fb_lo[b], d_fb_lo[b]+d_fb_len[b]) with weights d_fb_w[d_fb_off[b] ...]). */
+ * [d_fb_lo[b], d_fb_lo[b]+d_fb_len[b]) with weights d_fb_w[d_fb_off[b] ...]).
+ * n_mels outside [1, 127] or n_bins < 1 is OFP_ERR_INVALID (nothing is launched). */
 int ofp_mel(const float* d_power, int64_t n_rows, int32_t n_bins, int32_t n_mels,
             const int32_t* d_fb_lo, const int32_t* d_fb_len, const int32_t* d_fb_off,
             const float* d_fb_w, float* d_mel, void* stream);
 /* power_to_db (ref 1, amin, top_db relative to the max over the n values) then
  * DCT-II ortho over the mel axis keeping n_mfcc: d_mel [n_rows][n_mels] ->
  * d_mfcc [n_rows][n_mfcc].  d_dct is float32 [n_mfcc][n_mels].  top_db < 0: no floor.
- * d_scratch: >= 4 bytes. */
+ * d_scratch: >= 4 bytes.  n_mels < 1 or n_mfcc < 1 is OFP_ERR_INVALID (nothing is launched). */
 int ofp_mfcc(const float* d_mel, int64_t n_rows, int32_t n_mels, int32_t n_mfcc, float amin,
              float top_db, const float* d_dct, float* d_mfcc, float* d_scratch, void* stream);
 

@@ -600,6 +600,7 @@ int ofp_stft_frames(const float* d_x, int64_t n_clips, int64_t n_samples, int32_
     OFP_REQUIRE(d_x && d_clip && d_channel && d_start && d_valid_lo && d_valid_hi && d_window && d_spec,
                 "ofp_stft_frames: NULL argument");
     OFP_REQUIRE(frame_length >= 1 && frame_length <= n_fft, "frame_length %d must be in [1, n_fft]", frame_length);
+    OFP_REQUIRE(C >= 1, "ofp_stft_frames: %d channels", C);
     (void)n_clips;
     FrameArgs a;
     a.x = d_x; a.n_samples = n_samples; a.C = C; a.clip = d_clip; a.channel = d_channel; a.start = d_start;
@@ -632,6 +633,7 @@ int ofp_mel(const float* d_power, int64_t n_rows, int32_t n_bins, int32_t n_mels
             const int32_t* d_fb_len, const int32_t* d_fb_off, const float* d_fb_w, float* d_mel, void* stream) {
     if (n_rows == 0) return OFP_OK;
     OFP_REQUIRE(d_power && d_fb_lo && d_fb_len && d_fb_off && d_fb_w && d_mel, "ofp_mel: NULL argument");
+    OFP_REQUIRE(n_mels >= 1 && n_bins >= 1, "ofp_mel: %d bands on %d bins", n_mels, n_bins);
     OFP_REQUIRE(n_mels <= 127, "ofp_mel: at most 127 bands (got %d)", n_mels);
     int64_t total = n_rows * n_mels;
     unsigned grid = (unsigned)std::min<int64_t>(cdiv(total, 256), 256 * 16);
@@ -645,6 +647,7 @@ int ofp_mfcc(const float* d_mel, int64_t n_rows, int32_t n_mels, int32_t n_mfcc,
              const float* d_dct, float* d_mfcc, float* d_scratch, void* stream_) {
     if (n_rows == 0) return OFP_OK;
     OFP_REQUIRE(d_mel && d_dct && d_mfcc && d_scratch, "ofp_mfcc: NULL argument");
+    OFP_REQUIRE(n_mels >= 1 && n_mfcc >= 1, "ofp_mfcc: %d coefficients from %d bands", n_mfcc, n_mels);
     hipStream_t stream = (hipStream_t)stream_;
     OFP_HIP(hipMemsetAsync(d_scratch, 0, 4, stream));
     int64_t n = n_rows * n_mels;
