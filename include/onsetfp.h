@@ -51,6 +51,18 @@ int ofp_device_count(void);
 /* writes the gcnArchName of `device` into buf; fails unless it is gfx950 */
 int ofp_device_check(int device, char* buf, int buflen);
 
+/* Process-wide settings of the HIP runtime that the library's in-flight use depends on.  A caller that keeps
+ * several steps in flight gives every step two streams (its own and the spectral branch's); the runtime maps all
+ * streams of a process onto GPU_MAX_HW_QUEUES hardware queues (its default: 4) in submission order, so with twelve
+ * streams on four queues a short kernel of one step waits behind another step's long one.  Measured:
+ * 8 and 16 queues equal, 32 slightly slower, 4 limits three and more steps in flight.
+ *   ofp_runtime_prepare() sets GPU_MAX_HW_QUEUES=16 in the process environment (replacing any value) and returns 1.
+ * The runtime reads the variable once, at the first HIP call of the process: when the runtime is already up the
+ * function changes nothing and returns 0.  It makes no HIP call itself.  The Python package calls it at import. */
+#define OFP_RUNTIME_QUEUES_VAR "GPU_MAX_HW_QUEUES"
+#define OFP_RUNTIME_QUEUES "16"
+int ofp_runtime_prepare(void);
+
 /* ---- legacy symbols: drop-in for envelope_follower.so ---------------------------
  * Identical names, signatures and HOST-pointer semantics as envelope_follower.c:6,
  * :27 and :59, so that the reference's detection.py:517-578 can CDLL this library

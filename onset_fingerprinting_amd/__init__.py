@@ -10,3 +10,8 @@ Everything runs in hand-written HIP kernels behind the C ABI of
 ``libonsetfp.so`` (include/onsetfp.h).  There is no CPU fallback.
 """
 __all__ = ["detection", "data", "calibration", "model", "pipeline", "distributed", "synth"]
+
+from . import _lib
+
+# Before anything in this process makes a HIP call (torch.cuda included): the runtime reads GPU_MAX_HW_QUEUES once.
+_lib.runtime_prepare()

@@ -6,6 +6,7 @@ raised.  PyTorch is used only to own device memory and streams; every pointer
 handed to the library is a raw device address.
 """
 import ctypes
+import os
 import subprocess
 from pathlib import Path
 
@@ -134,6 +135,7 @@ _long_p = ctypes.POINTER(ctypes.c_long)
 SIGNATURES = {
     "ofp_abi_version": (ctypes.c_int, []),
     "ofp_last_error": (ctypes.c_char_p, []),
+    "ofp_runtime_prepare": (ctypes.c_int, []),
     "ofp_device_count": (ctypes.c_int, []),
     "ofp_device_check": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     "ar_envelope": (None, [_f32p_h, _f32p_h, _f32, _f32, ctypes.c_int, ctypes.c_int]),
@@ -279,6 +281,22 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def runtime_prepare():
+    """ofp_runtime_prepare() (include/onsetfp.h): ask the HIP runtime for the hardware queues that steps in flight need,
+    while it can still be asked -- before the first HIP call of the process.  -> 1 if the variable was set, 0 if the
+    runtime was already up (nothing changed).  os.environ is brought in line with what the C call did, so that Python
+    code and child processes started with a copy of it see the same value.  A tree that has not been built yet has
+    nothing to prepare (lib() raises at the first use)."""
+    if not LIB_PATH.exists():
+        return 0
+    done = lib().ofp_runtime_prepare()
+    if done:
+        libc_getenv = ctypes.CDLL(None).getenv
+        libc_getenv.restype, libc_getenv.argtypes = ctypes.c_char_p, [ctypes.c_char_p]
+        os.environ["GPU_MAX_HW_QUEUES"] = libc_getenv(b"GPU_MAX_HW_QUEUES").decode()
+    return done
 
 
 def check(status, what=""):

@@ -1,4 +1,8 @@
-// Status / error reporting and the three legacy symbols of envelope_follower.so.
+// Status / error reporting, the process-wide runtime settings and the three legacy symbols of envelope_follower.so.
+#include <dirent.h>
+#include <unistd.h>
+
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -125,6 +129,29 @@ struct DevBuf {
     }
 };
 
+// The HIP runtime reads its settings once, when the first HIP call of the process brings it up; from then on the
+// process holds the kernel driver's compute device open.  Looking for that descriptor makes no HIP call, so asking
+// does not start the runtime.
+bool hip_runtime_is_up() {
+    DIR* dir = opendir("/proc/self/fd");
+    if (!dir) return false;
+    bool up = false;
+    char path[64], target[64];
+    while (const dirent* e = readdir(dir)) {
+        if (e->d_name[0] == '.') continue;
+        snprintf(path, sizeof path, "/proc/self/fd/%s", e->d_name);
+        const ssize_t n = readlink(path, target, sizeof target - 1);
+        if (n <= 0) continue;
+        target[n] = 0;
+        if (std::strcmp(target, "/dev/kfd") == 0) {
+            up = true;
+            break;
+        }
+    }
+    closedir(dir);
+    return up;
+}
+
 #define LEGACY_HIP(call)                                                                      \
     do {                                                                                      \
         hipError_t e__ = (call);                                                              \
@@ -141,6 +168,11 @@ extern "C" {
 int ofp_abi_version(void) { return OFP_ABI_VERSION; }
 
 const char* ofp_last_error(void) { return ofp::err_buf(); }
+
+int ofp_runtime_prepare(void) {
+    if (hip_runtime_is_up()) return 0;  // too late: the runtime has read its settings
+    return setenv(OFP_RUNTIME_QUEUES_VAR, OFP_RUNTIME_QUEUES, 1) == 0 ? 1 : 0;
+}
 
 int ofp_device_count(void) {
     int n = 0;
