@@ -505,6 +505,7 @@ typedef struct ofp_hop_config {
 } ofp_hop_config;
 typedef struct ofp_hop_session ofp_hop_session; /* opaque */
 int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session** out);
+/* (OFP_ERR_INVALID while the session is a member of an ofp_hop_group, as for submit / push / set_locator) */
 int ofp_hop_destroy(ofp_hop_session* s);
 /* back to the state after creation (zero ring, fresh detector state, hop counter 0) */
 int ofp_hop_reset(ofp_hop_session* s);
@@ -521,6 +522,35 @@ int ofp_hop_push(ofp_hop_session* s, const float* h_hop, int64_t* n_onsets, ofp_
                  float* h_mel, float* h_rel, float* h_strength);
 /* audio[-n_rows:] of the ring buffer (oldest row first), h_out [n_rows][C]; n_rows <= ring_samples */
 int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out);
+
+/* ---- S sessions per hop period in ONE launch ---------------------------------------------------
+ * A group binds n sessions (several drums, players or streams with the same hop clock) to one captured graph whose
+ * single kernel node has a second grid dimension: row i runs member i's hop exactly as the member's own graph
+ * would -- same device code, same state, nothing shared or summed across members -- so every output is bit for bit
+ * what the stand-alone session gives.  The group owns a stream, device copies of the members' kernel arguments and
+ * the graph; the members keep their state, ring, pinned hop / result blocks and hop counters, and may join warmed
+ * up or mid-stream.
+ *   ofp_hop_group_create   OFP_ERR_INVALID (nothing is launched): n outside 1..1024, a NULL member, a member listed
+ *       twice, already in a group, with a hop in flight, or not in the fused one-kernel form (OFP_HOP_GRAPH=nodes, or
+ *       a shape too wide for it); members on different devices; members that differ in n_fft, in the channel count,
+ *       in whether the onset strength is enabled or in whether a locator is attached (these four fix the kernel and
+ *       its grid).  Block size, sample rate, detector arguments, ring length, want_rel, filterbank, classifier and
+ *       the locator's geometry and model may differ per member.
+ *   ofp_hop_group_submit   h_hops[i] is member i's hop, HOST memory [B_i][C]; one graph launch for all members.  No
+ *       member may have an uncollected hop.
+ *   ofp_hop_group_wait     returns once every member's results are published.  Then read each member with
+ *       ofp_hop_collect (required before the next submit; it no longer waits) and ofp_hop_collect_location /
+ *       ofp_hop_locator_state / ofp_hop_ring_read as for a stand-alone session.
+ *   ofp_hop_group_destroy  waits for the last launch and releases the members, which work stand-alone again (an
+ *       uncollected hop can still be collected); the sessions themselves are not destroyed.
+ * While a session is a member: ofp_hop_reset and ofp_hop_warmup still work (they first wait for the group's last
+ * launch); ofp_hop_submit, ofp_hop_push, ofp_hop_set_locator and ofp_hop_destroy return OFP_ERR_INVALID -- destroy the
+ * group first.  A group must be destroyed before any of its members or their detectors. */
+typedef struct ofp_hop_group ofp_hop_group; /* opaque */
+int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group** out);
+int ofp_hop_group_destroy(ofp_hop_group* g);
+int ofp_hop_group_submit(ofp_hop_group* g, const float* const* h_hops);
+int ofp_hop_group_wait(ofp_hop_group* g);
 
 /* ---- onset groups and their windows --------------------------------
  * find_onset_groups (detection.py:131-189) per clip, straight from the records

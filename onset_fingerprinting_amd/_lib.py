@@ -193,6 +193,10 @@ SIGNATURES = {
     "ofp_hop_collect": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
     "ofp_hop_push": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
     "ofp_hop_ring_read": (ctypes.c_int, [_vp, _i64, _vp]),
+    "ofp_hop_group_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.POINTER(_vp)]),
+    "ofp_hop_group_destroy": (ctypes.c_int, [_vp]),
+    "ofp_hop_group_submit": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "ofp_hop_group_wait": (ctypes.c_int, [_vp]),
     "ofp_autocorr_softmax": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "ofp_conv1d": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                   _i32, _vp, _vp]),

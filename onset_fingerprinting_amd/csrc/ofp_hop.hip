@@ -508,6 +508,54 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpst
     }
 }
 
+// S sessions' hops in ONE launch: grid (C + 1 + strength, S), row blockIdx.y is member blockIdx.y of an
+// ofp_hop_group.  A workgroup takes its member's three argument structs from the group's device arrays (uniform,
+// read-only addresses: scalar loads, as for kernel arguments) and runs what k_hop_fused runs for that member -- the
+// same branch on blockIdx.x, the same fences, the member's own ticket, counter and completion word.  Members share
+// nothing and no workgroup waits for another, so a grid larger than the device simply queues.  n_fft, the channel
+// count, and whether a locator / the onset strength is on fix the instantiation and gridDim.x: a group's members
+// agree on these four.  dry != 0: every workgroup returns at once (the un-captured launch at group creation that
+// loads the code and sets the dynamic-LDS attribute must not touch a member's state).
+template <int F, bool LOC>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group(const HopArgs* __restrict__ args,
+                                                                      const ofpstream::StreamArgs* __restrict__ sargs,
+                                                                      const HopLocArgs* __restrict__ largs, int dry) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (dry) return;
+    const HopArgs& a = args[blockIdx.y];
+    const int64_t done = a.ctl[0];  // hops this member completed before this one
+    if (blockIdx.x == 0) {
+        const ofpstream::StreamArgs& sa = sargs[blockIdx.y];
+        if (threadIdx.x == 0) *a.hop_index = done;
+        if constexpr (LOC) {
+            const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
+            if (n_on > 0) {
+                const HopLocArgs& la = largs[blockIdx.y];
+                hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
+            }
+        } else {
+            ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
+        }
+    } else if ((int)blockIdx.x <= a.C) {
+        hop_spectral_body<F, FusedCfg<F>::WGS>(a, (int)blockIdx.x - 1, done + 1, smem);
+    } else {
+        hop_strength_body<F, FusedCfg<F>::WGS>(a, done + 1, smem);
+    }
+    // the completion handshake of k_hop_fused, per member: gridDim.x workgroups take a ticket
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence_system();
+        const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctl + 1), 1ull);
+        if (t == gridDim.x - 1) {
+            a.ctl[1] = 0;
+            a.ctl[0] = done + 1;
+            __threadfence_system();
+            *a.done_flag = done + 1;
+        }
+    }
+}
+
 }  // namespace
 
 struct ofp_hop_session {
@@ -553,6 +601,23 @@ struct ofp_hop_session {
     ofp_onset* d_mirror = nullptr;  // fused form: the records in device memory
     int64_t o_loc = 0;
     size_t lds_loc = 0;
+    int device = 0;
+    ofp_hop_group* owner = nullptr;  // the group whose launches carry this session's hops (ofp_hop_group_create)
+};
+
+// S fused sessions served by one launch per hop period.  The members keep their state, ring, pinned blocks and
+// counters; the group owns the stream the launches go to, copies of the members' kernel arguments and the graph.
+struct ofp_hop_group {
+    std::vector<ofp_hop_session*> members;
+    int device = 0, n_fft = 0, grid_x = 0;
+    bool loc = false;
+    size_t lds = 0;
+    hipStream_t stream = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    HopArgs* d_args = nullptr;
+    ofpstream::StreamArgs* d_sargs = nullptr;
+    HopLocArgs* d_largs = nullptr;
 };
 
 namespace {
@@ -720,12 +785,100 @@ int capture_hop(ofp_hop_session* s) {
     return OFP_OK;
 }
 
+// the stream the session's last hop was launched to
+hipStream_t hop_stream(const ofp_hop_session* s) { return s->owner ? s->owner->stream : s->stream; }
+
+// The copies of ring_read / locator_state are not stream-ordered and reset / warm-up run on the session's own
+// stream: the last hop's kernel (polled, not synchronised) must have left the stream it was launched to.
+int retire_last_hop(ofp_hop_session* s) {
+    if (!s->retired) {
+        OFP_HIP(hipStreamSynchronize(hop_stream(s)));
+        s->retired = true;
+    }
+    return OFP_OK;
+}
+
+#define OFP_NOT_IN_GROUP(s, what)                                                                                  \
+    OFP_REQUIRE(!(s)->owner, what ": the session is a member of an ofp_hop_group (its hops go through "            \
+                                  "ofp_hop_group_submit; ofp_hop_group_destroy releases it)")
+
+template <int F>
+int hop_group_launch(ofp_hop_group* g, int dry) {
+    auto launch = [&](auto kernel) -> int {
+        if (dry && g->lds > 65536 - 20480)  // (the detector's static LDS comes on top)
+            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)g->lds));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g->grid_x, (unsigned)g->members.size()), dim3(FusedCfg<F>::WGS), g->lds,
+                           g->stream, g->d_args, g->d_sargs, g->d_largs, dry);
+        return OFP_OK;
+    };
+    if (int rc = g->loc ? launch(k_hop_fused_group<F, true>) : launch(k_hop_fused_group<F, false>)) return rc;
+    OFP_LAUNCH_CHECK("k_hop_fused_group");
+    return OFP_OK;
+}
+
+int dispatch_group(ofp_hop_group* g, int dry) {
+    switch (g->n_fft) {
+        case 256: return hop_group_launch<256>(g, dry);
+        case 512: return hop_group_launch<512>(g, dry);
+        case 1024: return hop_group_launch<1024>(g, dry);
+        case 2048: return hop_group_launch<2048>(g, dry);
+        case 4096: return hop_group_launch<4096>(g, dry);
+    }
+    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", g->n_fft);
+}
+
+void group_free(ofp_hop_group* g) {
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    if (g->exec) (void)hipGraphExecDestroy(g->exec);
+    if (g->graph) (void)hipGraphDestroy(g->graph);
+    if (g->d_args) (void)hipFree(g->d_args);
+    if (g->d_sargs) (void)hipFree(g->d_sargs);
+    if (g->d_largs) (void)hipFree(g->d_largs);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    delete g;
+}
+
+// the group's resources on the members' device: the argument arrays, the dry launch, the captured graph
+int group_build(ofp_hop_group* g) {
+    const size_t n = g->members.size();
+    std::vector<HopArgs> a(n);
+    std::vector<ofpstream::StreamArgs> q(n);
+    std::vector<HopLocArgs> l(n);
+    for (size_t i = 0; i < n; ++i) {
+        a[i] = g->members[i]->args;
+        q[i] = g->members[i]->sargs;
+        l[i] = g->members[i]->largs;
+    }
+    OFP_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    OFP_HIP(hipMalloc(&g->d_args, n * sizeof(HopArgs)));
+    OFP_HIP(hipMalloc(&g->d_sargs, n * sizeof(ofpstream::StreamArgs)));
+    OFP_HIP(hipMalloc(&g->d_largs, n * sizeof(HopLocArgs)));
+    OFP_HIP(hipMemcpy(g->d_args, a.data(), n * sizeof(HopArgs), hipMemcpyHostToDevice));
+    OFP_HIP(hipMemcpy(g->d_sargs, q.data(), n * sizeof(ofpstream::StreamArgs), hipMemcpyHostToDevice));
+    OFP_HIP(hipMemcpy(g->d_largs, l.data(), n * sizeof(HopLocArgs), hipMemcpyHostToDevice));
+    // a member that joins mid-stream: its last stand-alone hop must have left its own stream
+    for (ofp_hop_session* s : g->members)
+        if (int rc = retire_last_hop(s)) return rc;
+    // code loading and the kernel attribute may not happen during capture: one launch that touches nothing
+    if (int rc = dispatch_group(g, 1)) return rc;
+    OFP_HIP(hipStreamSynchronize(g->stream));
+    OFP_HIP(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = dispatch_group(g, 0);
+    const hipError_t ce = hipStreamEndCapture(g->stream, &g->graph);
+    if (rc != OFP_OK) return rc;
+    if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    OFP_HIP(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
+    return OFP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int ofp_hop_destroy(ofp_hop_session* s) {
     if (!s) return OFP_OK;
+    OFP_NOT_IN_GROUP(s, "ofp_hop_destroy");
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->exec) (void)hipGraphExecDestroy(s->exec);
     if (s->graph) (void)hipGraphDestroy(s->graph);
@@ -804,6 +957,7 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
             return ofp::fail(OFP_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e__));                      \
         }                                                                                                       \
     } while (0)
+    HOP_TRY(hipGetDevice(&s->device));
     HOP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     const int64_t sb = ofp_stream_state_bytes(det);
     HOP_TRY(hipMalloc(&s->d_state, (size_t)sb));
@@ -934,6 +1088,8 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
 
 int ofp_hop_reset(ofp_hop_session* s) {
     OFP_REQUIRE(s, "ofp_hop_reset: NULL session");
+    if (s->owner)  // (the group's launches go to the group's stream, the reset to the session's)
+        if (int rc = retire_last_hop(s)) return rc;
     return reset_state(s);
 }
 
@@ -941,6 +1097,8 @@ int ofp_hop_warmup(ofp_hop_session* s, const float* h_x, int64_t n_rows) {
     OFP_REQUIRE(s && (h_x || n_rows == 0), "ofp_hop_warmup: NULL argument");
     OFP_REQUIRE(!s->in_flight, "ofp_hop_warmup: a hop is in flight (collect it first)");
     if (n_rows <= 0) return OFP_OK;
+    if (s->owner)
+        if (int rc = retire_last_hop(s)) return rc;
     float* d = nullptr;
     OFP_HIP(hipMalloc(&d, (size_t)n_rows * s->C * 4));
     hipError_t e = hipMemcpyAsync(d, h_x, (size_t)n_rows * s->C * 4, hipMemcpyHostToDevice, s->stream);
@@ -955,6 +1113,7 @@ int ofp_hop_warmup(ofp_hop_session* s, const float* h_x, int64_t n_rows) {
 
 int ofp_hop_submit(ofp_hop_session* s, const float* h_hop) {
     OFP_REQUIRE(s && h_hop, "ofp_hop_submit: NULL argument");
+    OFP_NOT_IN_GROUP(s, "ofp_hop_submit");
     OFP_REQUIRE(!s->in_flight, "ofp_hop_submit: the previous hop has not been collected");
     std::memcpy(s->h_hop, h_hop, (size_t)s->B * s->C * sizeof(float));
     OFP_HIP(hipGraphLaunch(s->exec, s->stream));
@@ -972,7 +1131,7 @@ int ofp_hop_collect(ofp_hop_session* s, int64_t* n_onsets, ofp_onset* h_records,
         // stream synchronisation's wake-up (bounded: an error or a lost launch falls through to the sync)
         const volatile int64_t* flag = reinterpret_cast<const volatile int64_t*>(s->h_res + s->o_done);
         for (int spin = 0; spin < 2000000 && *flag != s->pushed; ++spin) __builtin_ia32_pause();
-        if (*flag != s->pushed) OFP_HIP(hipStreamSynchronize(s->stream));
+        if (*flag != s->pushed) OFP_HIP(hipStreamSynchronize(hop_stream(s)));
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         s->retired = false;  // the kernel has published its results; it may not have retired from the stream yet
     } else {
@@ -1010,11 +1169,7 @@ int ofp_hop_push(ofp_hop_session* s, const float* h_hop, int64_t* n_onsets, ofp_
 int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
     OFP_REQUIRE(s && h_out && n_rows >= 0 && n_rows <= s->R, "ofp_hop_ring_read: bad argument");
     OFP_REQUIRE(!s->in_flight, "ofp_hop_ring_read: a hop is in flight (collect it first)");
-    // the copies below are not stream-ordered: the last hop's kernel (polled, not synchronised) must have retired
-    if (!s->retired) {
-        OFP_HIP(hipStreamSynchronize(s->stream));
-        s->retired = true;
-    }
+    if (int rc = retire_last_hop(s)) return rc;
     // audio[-n_rows:] of the reference's CircularArray: the rows ending at the write cursor, oldest first
     const int64_t end = s->pushed * s->B;
     const size_t row = (size_t)s->C * 4;
@@ -1031,6 +1186,7 @@ int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
 
 int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
     OFP_REQUIRE(s && loc, "ofp_hop_set_locator: NULL argument");
+    OFP_NOT_IN_GROUP(s, "ofp_hop_set_locator");
     OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "ofp_hop_set_locator: the session has already taken a hop");
     OFP_REQUIRE(!s->largs.enabled, "ofp_hop_set_locator: the session already has a locator");
     ofp::LocTables T;
@@ -1096,11 +1252,105 @@ int ofp_hop_locator_state(ofp_hop_session* s, ofp_locate_state* h_state) {
     OFP_REQUIRE(s && h_state, "ofp_hop_locator_state: NULL argument");
     OFP_REQUIRE(s->largs.enabled, "ofp_hop_locator_state: the session has no locator");
     OFP_REQUIRE(!s->in_flight, "ofp_hop_locator_state: a hop is in flight (collect it first)");
-    if (!s->retired) {
-        OFP_HIP(hipStreamSynchronize(s->stream));
+    if (int rc = retire_last_hop(s)) return rc;
+    OFP_HIP(hipMemcpy(h_state, s->d_loc_state, sizeof(ofp_locate_state), hipMemcpyDeviceToHost));
+    return OFP_OK;
+}
+
+int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group** out) {
+    OFP_REQUIRE(sessions && out, "ofp_hop_group_create: NULL argument");
+    OFP_REQUIRE(n >= 1 && n <= 1024, "ofp_hop_group_create: 1..1024 members (got %d)", n);
+    const ofp_hop_session* f = sessions[0];
+    size_t lds = 0;
+    for (int i = 0; i < n; ++i) {
+        const ofp_hop_session* s = sessions[i];
+        OFP_REQUIRE(s, "ofp_hop_group_create: member %d is NULL", i);
+        for (int j = 0; j < i; ++j)
+            OFP_REQUIRE(sessions[j] != s, "ofp_hop_group_create: members %d and %d are the same session", j, i);
+        OFP_REQUIRE(!s->owner, "ofp_hop_group_create: member %d already belongs to a group", i);
+        OFP_REQUIRE(!s->in_flight, "ofp_hop_group_create: member %d has a hop in flight (collect it first)", i);
+        OFP_REQUIRE(s->fused, "ofp_hop_group_create: member %d runs the five-node graph (OFP_HOP_GRAPH=nodes, or a shape "
+                              "too wide for the one-kernel form); only one-kernel sessions can be grouped", i);
+        OFP_REQUIRE(s->device == f->device, "ofp_hop_group_create: member %d lives on device %d, member 0 on device %d", i,
+                    s->device, f->device);
+        OFP_REQUIRE(s->n_fft == f->n_fft, "ofp_hop_group_create: member %d has n_fft %d, member 0 has %d", i, s->n_fft,
+                    f->n_fft);
+        OFP_REQUIRE(s->C == f->C, "ofp_hop_group_create: member %d has %d channels, member 0 has %d", i, s->C, f->C);
+        OFP_REQUIRE(!s->args.sg.enabled == !f->args.sg.enabled,
+                    "ofp_hop_group_create: members 0 and %d differ in having the onset strength enabled", i);
+        OFP_REQUIRE(!s->largs.enabled == !f->largs.enabled, "ofp_hop_group_create: members 0 and %d differ in having a locator",
+                    i);
+        lds = std::max(lds, s->lds_fused);
+    }
+    ofp_hop_group* g = new (std::nothrow) ofp_hop_group();
+    if (!g) return ofp::fail(OFP_ERR_INVALID, "out of host memory");
+    g->members.assign(sessions, sessions + n);
+    g->device = f->device;
+    g->n_fft = f->n_fft;
+    g->grid_x = f->C + 1 + (f->args.sg.enabled ? 1 : 0);
+    g->loc = f->largs.enabled != 0;
+    g->lds = lds;
+    int prev = 0;
+    hipError_t e = hipGetDevice(&prev);
+    if (e == hipSuccess && prev != g->device) e = hipSetDevice(g->device);
+    int rc = e == hipSuccess ? group_build(g) : ofp::fail(OFP_ERR_HIP, "ofp_hop_group_create: %s", hipGetErrorString(e));
+    if (e == hipSuccess && prev != g->device) (void)hipSetDevice(prev);
+    if (rc != OFP_OK) {
+        group_free(g);
+        return rc;
+    }
+    for (ofp_hop_session* s : g->members) s->owner = g;
+    *out = g;
+    return OFP_OK;
+}
+
+int ofp_hop_group_destroy(ofp_hop_group* g) {
+    if (!g) return OFP_OK;
+    const hipError_t e = hipStreamSynchronize(g->stream);
+    for (ofp_hop_session* s : g->members) {
+        s->owner = nullptr;
         s->retired = true;
     }
-    OFP_HIP(hipMemcpy(h_state, s->d_loc_state, sizeof(ofp_locate_state), hipMemcpyDeviceToHost));
+    group_free(g);
+    if (e != hipSuccess) return ofp::fail(OFP_ERR_HIP, "ofp_hop_group_destroy: %s", hipGetErrorString(e));
+    return OFP_OK;
+}
+
+int ofp_hop_group_submit(ofp_hop_group* g, const float* const* h_hops) {
+    OFP_REQUIRE(g && h_hops, "ofp_hop_group_submit: NULL argument");
+    const size_t n = g->members.size();
+    for (size_t i = 0; i < n; ++i) {
+        OFP_REQUIRE(h_hops[i], "ofp_hop_group_submit: the hop of member %zu is NULL", i);
+        OFP_REQUIRE(!g->members[i]->in_flight, "ofp_hop_group_submit: the previous hop of member %zu has not been collected",
+                    i);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        ofp_hop_session* s = g->members[i];
+        std::memcpy(s->h_hop, h_hops[i], (size_t)s->B * s->C * sizeof(float));
+    }
+    OFP_HIP(hipGraphLaunch(g->exec, g->stream));
+    for (ofp_hop_session* s : g->members) {
+        s->in_flight = true;
+        s->retired = false;
+        s->pushed += 1;
+    }
+    return OFP_OK;
+}
+
+int ofp_hop_group_wait(ofp_hop_group* g) {
+    OFP_REQUIRE(g, "ofp_hop_group_wait: NULL group");
+    // the members' completion words, as ofp_hop_collect polls its own; the members of one launch finish within
+    // microseconds of each other, so the walk costs the slowest member's time, not the sum
+    for (ofp_hop_session* s : g->members) {
+        if (!s->in_flight) continue;
+        const volatile int64_t* flag = reinterpret_cast<const volatile int64_t*>(s->h_res + s->o_done);
+        for (int spin = 0; spin < 2000000 && *flag != s->pushed; ++spin) __builtin_ia32_pause();
+        if (*flag != s->pushed) {  // an error or a lost launch: the stream tells
+            OFP_HIP(hipStreamSynchronize(g->stream));
+            break;
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
     return OFP_OK;
 }
 

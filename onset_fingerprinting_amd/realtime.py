@@ -134,6 +134,7 @@ class HopSession:
         self._rel = np.zeros((block_size, n_signals), dtype=np.float32)
         self._sg = np.zeros(4 + (int(cfg.tg_win_length) if onset_strength is not None else 0), dtype=np.float32)
         self.current_index = 0  # audio.py:120
+        self._group = None  # the HopSessionGroup that carries this session's hops, if any
         self.locator = locator
         if locator is not None:
             try:
@@ -173,6 +174,8 @@ class HopSession:
         return ml.ongoing_list(st)
 
     def close(self):
+        if getattr(self, "_group", None) is not None:  # a member goes only after its group: the group's graph
+            self._group.close()                        # holds the session's device pointers
         if getattr(self, "handle", None):
             self._L.ofp_hop_destroy(self.handle)
             self.handle = None
@@ -247,3 +250,113 @@ class HopSession:
         out = np.empty((int(n), self.n_signals), dtype=np.float32)
         check(self._L.ofp_hop_ring_read(self.handle, int(n), out.ctypes.data), "ofp_hop_ring_read")
         return out
+
+
+class HopSessionGroup:
+    """S streams per hop period in ONE graph launch (``ofp_hop_group_*``): several drums, players or clients whose
+    hops arrive on the same clock.
+
+    ``sessions``: ``HopSession`` objects on one device with the same ``n_fft`` and channel count that agree on
+    having a locator and on having the onset strength; everything else (block size, ``sr``, detector arguments, ring
+    length, ``want_rel``, ``n_mels``, classifier, the locator's geometry and model) may differ.  They may be warmed
+    up or mid-stream.  Each member keeps its own state and runs the device code it runs alone, so every output is
+    bit for bit the stand-alone session's.  While grouped a member still takes ``reset()``,
+    ``init_minmax_tracker()``, ``audio()`` and ``ongoing``; calling it with a hop raises.  ``close()`` gives the
+    members back for stand-alone use (closing a member closes its group first).
+    """
+
+    def __init__(self, sessions):
+        sessions = list(sessions)
+        if not sessions:
+            raise ValueError("HopSessionGroup: no sessions")
+        for i, s in enumerate(sessions):
+            if not isinstance(s, HopSession):
+                raise TypeError(f"HopSessionGroup: member {i} is {type(s).__name__}, not a HopSession")
+            if not s.handle:
+                raise ValueError(f"HopSessionGroup: member {i} is closed")
+            if any(s is t for t in sessions[:i]):
+                raise ValueError(f"HopSessionGroup: member {i} is listed twice")
+            if s._group is not None:
+                raise ValueError(f"HopSessionGroup: member {i} already belongs to a group")
+        self._L = _lib.lib()
+        self.handle = None
+        n = len(sessions)
+        members = (ctypes.c_void_p * n)(*[s.handle.value for s in sessions])
+        h = ctypes.c_void_p()
+        # (the library checks the rest -- hop in flight, graph form, device, n_fft, channels, locator, strength --
+        #  on the host, before anything is launched)
+        check(self._L.ofp_hop_group_create(members, n, ctypes.byref(h)), "ofp_hop_group_create")
+        self.handle = h
+        self.sessions = tuple(sessions)
+        for s in sessions:
+            s._group = self
+        self._ptrs = (ctypes.c_void_p * n)()
+        b, c = sessions[0].block_size, sessions[0].n_signals
+        self._shape = (n, b, c) if all(s.block_size == b for s in sessions) else None  # hops as one [S, B, C] array
+        self._collect = [(s, (s.handle, ctypes.byref(s._n), s._rec.ctypes.data,
+                              s._logits.ctypes.data if s.n_out else None, s._mel.ctypes.data,
+                              s._rel.ctypes.data if s.want_rel else None,
+                              s._sg.ctypes.data if s.onset_strength else None)) for s in sessions]
+
+    def __len__(self):
+        return len(self.sessions)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.ofp_hop_group_destroy(self.handle)
+            self.handle = None
+            for s in self.sessions:
+                s._group = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _fill(self, hops):
+        """The members' hop pointers; the arrays they point into (kept alive by the caller of this method)."""
+        if not self.handle:
+            raise ValueError("HopSessionGroup: the group is closed")
+        if isinstance(hops, np.ndarray) and hops.ndim == 3 and self._shape is not None:
+            if hops.dtype != np.float32:  # (as HopSession._f32)
+                raise ctypes.ArgumentError(f"array must have data type float32, got {hops.dtype}")
+            if hops.shape != self._shape:
+                raise ValueError(f"expected shape {self._shape}, got {hops.shape}")
+            hops = np.ascontiguousarray(hops)
+            base, step = hops.ctypes.data, hops[0].nbytes  # (not strides[0]: numpy leaves it free when S == 1)
+            self._ptrs[:] = range(base, base + step * len(self.sessions), step)
+            return hops
+        if len(hops) != len(self.sessions):
+            raise ValueError(f"expected {len(self.sessions)} hops, got {len(hops)}")
+        keep = [s._f32(h, s.block_size) for s, h in zip(self.sessions, hops)]
+        self._ptrs[:] = [h.ctypes.data for h in keep]
+        return keep
+
+    def submit(self, hops):
+        """``hops``: ``[S, B, C]`` float32, or a sequence of S arrays ``[B_i, C]`` float32 (member i's hop)."""
+        keep = self._fill(hops)
+        check(self._L.ofp_hop_group_submit(self.handle, self._ptrs), "ofp_hop_group_submit")
+        del keep  # (the library has copied the hops into the members' pinned buffers)
+
+    def collect(self):
+        """The members' result dicts, as ``HopSession.collect`` returns them."""
+        check(self._L.ofp_hop_group_wait(self.handle), "ofp_hop_group_wait")
+        return [s.collect() for s in self.sessions]
+
+    def __call__(self, hops):
+        self.submit(hops)
+        return self.collect()
+
+    def push_raw(self, hops):
+        """`__call__` without building the result dicts (latency measurements): the S onset counts; the outputs stay
+        in the members' host arrays."""
+        self.submit(hops)
+        L = self._L
+        check(L.ofp_hop_group_wait(self.handle), "ofp_hop_group_wait")
+        counts = []
+        for s, a in self._collect:
+            check(L.ofp_hop_collect(*a), "ofp_hop_collect")
+            s.current_index += s.block_size
+            counts.append(int(s._n.value))
+        return counts
