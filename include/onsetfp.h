@@ -869,6 +869,68 @@ int ofp_tdoa_fit(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, c
                  const int32_t* d_rate_idx, int32_t num_epochs, float eps, int32_t patience, float* d_sensors,
                  float* d_sounds, float* d_c, float* d_loss, int32_t* d_epochs, void* stream);
 
+/* ---- training model.CNN (model.py:52-162, the loop of train.py) -----------------------------------------------
+ * Network: n_conv layers of Conv1d (stride 1, bias) -> activation -> BatchNorm1d (when batch_norm) -> MaxPool1d(2, 2)
+ *   (when pool), flatten, Linear to n_out values; channels[0] inputs of `width` samples, channels[i] outputs of
+ *   conv i.  Activations are [n][channels][width], as torch lays them out.  fp32 data; every sum over the batch in
+ *   fp64 with a shape fixed by the dimensions alone (no atomics: results are bitwise reproducible).
+ * Parameters are packed in state_dict order: per conv layer weight [cout][cin/groups][kernel], bias [cout], then
+ *   (when batch_norm) BatchNorm weight [cout], bias [cout]; last fc weight [n_out][channels[n_conv] * width_last],
+ *   bias [n_out].  The running statistics are packed as mean [cout], var [cout] per BatchNorm.
+ * Limits (beyond them OFP_ERR_INVALID, or -1 from the size functions): 1..3 conv layers, 1..128 channels, kernel
+ *   1..8, width 1..512, n and n_val 1..1024 (n * width >= 2 with BatchNorm), n_out 1..16, 0 < bn_momentum <= 1.
+ * ofp_cnn_train_slab: the (sample, position) pairs one workgroup of the batch reductions sums.
+ * ofp_cnn_train: fits up to num_epochs epochs of: training-mode forward of d_x [n][channels[0]][width] (batch
+ *   statistics; running statistics updated with the unbiased variance), mean loss against d_y [n][n_out] (loss 0 =
+ *   L1, 1 = MSE) into d_train_loss[epoch], backward, one torch.optim.NAdam step with row `epoch` of d_rates
+ *   [num_epochs][4] = (-lr (1 - mu_t) / (1 - mu_product_t), -lr mu_{t+1} / (1 - mu_product_t mu_{t+1}),
+ *   1 - 0.999^t, unused); then, when n_val > 0, an eval-mode forward of d_x_val on the running statistics and its
+ *   mean L1 loss into d_val_loss[epoch].  Stop rule (patience >= 0, needs n_val > 0): a validation loss that is not
+ *   below the best so far counts, a lower one resets the count; once the count has reached patience the run ends
+ *   after the first epoch at which at least min_epochs epochs are done.  d_params / d_stats are read and updated in
+ *   place; curve slots of epochs not run are left untouched; *h_epochs (host memory) = epochs run.  One epoch is a
+ *   linear chain of kernels captured once as a hipGraph and replayed (the first epoch is launched plainly); the
+ *   host looks at the stop word every 64 epochs and synchronises the stream before it returns.  `stream` must be a
+ *   created stream (capture is not possible on the null stream) unless the environment has OFP_CNN_GRAPH=nodes,
+ *   which launches the same chain without a graph.  Nothing is allocated: d_ws of ofp_cnn_train_workspace_bytes.
+ * ofp_cnn_loss_grads: one training-mode forward and backward: d_loss [1], d_grads packed like the parameters.
+ * ofp_conv1d_backward: d_dz [n][cout][wc] (wc = w + 2 padding - dilation (k - 1)) -> d_dw [cout][cin/groups][k],
+ *   d_db [cout] and, unless NULL, d_dx [n][cin][w].  ofp_batchnorm_train_forward / _backward: BatchNorm1d in training
+ *   mode on d_x [n][C][w]: d_y, the saved d_mean / d_rstd [C], running statistics updated in place; and d_dx,
+ *   d_dgamma, d_dbeta from d_dy.  ofp_nadam_step: one NAdam step of n elements with one row of the rate table. */
+typedef struct ofp_cnn_config {
+    int32_t n_conv;
+    int32_t channels[4];
+    int32_t kernel, padding, dilation, groups;
+    int32_t act, batch_norm, pool;
+    int32_t width, n_out, loss;
+    float bn_momentum;
+    double bn_eps;
+} ofp_cnn_config;
+int32_t ofp_cnn_train_slab(void);
+int64_t ofp_cnn_train_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val);
+int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                  const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                  int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                  float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                       const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                       void* stream);
+int64_t ofp_conv1d_backward_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,
+                                            int32_t padding, int32_t dilation, int32_t groups);
+int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
+                        int32_t k, int32_t padding, int32_t dilation, int32_t groups, const float* d_dz, float* d_dx,
+                        float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
+int64_t ofp_batchnorm_train_workspace_bytes(int64_t n, int32_t C, int32_t w);
+int ofp_batchnorm_train_forward(const float* d_x, int64_t n, int32_t C, int32_t w, const float* d_gamma,
+                                const float* d_beta, double eps, float momentum, float* d_running_mean,
+                                float* d_running_var, float* d_y, float* d_mean, float* d_rstd, void* d_ws,
+                                int64_t ws_bytes, void* stream);
+int ofp_batchnorm_train_backward(const float* d_x, int64_t n, int32_t C, int32_t w, const float* d_gamma,
+                                 const float* d_mean, const float* d_rstd, const float* d_dy, float* d_dx,
+                                 float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_nadam_step(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, const float* d_row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,19 @@ class HopLocator(ctypes.Structure):
     ]
 
 
+class CnnConfig(ctypes.Structure):
+    _fields_ = [
+        ("n_conv", ctypes.c_int32),
+        ("channels", ctypes.c_int32 * 4),
+        ("kernel", ctypes.c_int32), ("padding", ctypes.c_int32), ("dilation", ctypes.c_int32),
+        ("groups", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("batch_norm", ctypes.c_int32), ("pool", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("n_out", ctypes.c_int32), ("loss", ctypes.c_int32),
+        ("bn_momentum", ctypes.c_float),
+        ("bn_eps", ctypes.c_double),
+    ]
+
+
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _f32p_h = ctypes.POINTER(ctypes.c_float)
 _long_p = ctypes.POINTER(ctypes.c_long)
@@ -256,6 +269,20 @@ SIGNATURES = {
                                            _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_tdoa_fit": (ctypes.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
+    "ofp_cnn_train_slab": (_i32, []),
+    "ofp_cnn_train_workspace_bytes": (_i64, [ctypes.POINTER(CnnConfig), _i64, _i64]),
+    "ofp_cnn_train": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32,
+                                     _vp, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp]),
+    "ofp_cnn_loss_grads": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_conv1d_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "ofp_conv1d_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                           _vp, _vp, _i64, _vp]),
+    "ofp_batchnorm_train_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ofp_batchnorm_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _f64, _f32, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _i64, _vp]),
+    "ofp_batchnorm_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _i64, _vp]),
+    "ofp_nadam_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

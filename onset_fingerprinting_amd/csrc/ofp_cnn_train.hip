@@ -1,0 +1,987 @@
+// Training model.CNN on the GPU (the reference's model.py:52-162 and the loop of train.py): full-batch forward in
+// training mode, mean L1 / MSE loss, backward, NAdam, and optionally an eval-mode validation pass with Lightning's
+// early-stop rule -- one epoch is a linear chain of short kernels on one stream, captured once as a hipGraph and
+// replayed.  The epoch index (row of the rate table, slot of the loss curves) is a device counter that the chain's
+// last kernel advances, so every replay is the same graph; once the stop word is set every kernel returns at once.
+//
+// Layer order as the reference builds it: conv + bias -> activation -> BatchNorm1d -> MaxPool1d(2, 2).  Only the
+// pre-activation z [B][C][Wc] and the layer's output [B][C][Wo] are kept; the activation, the normalised value and
+// the pool's choice are recomputed from z where the backward needs them (ties take the first, an odd last column is
+// dropped and gets no gradient).
+//
+// Reductions.  No atomics anywhere.  Everything summed over the batch (BatchNorm's sums, forward and backward; the
+// convolution's weight and bias gradients) goes through one partial-slab reducer: the B * Wc (sample, position)
+// pairs of a channel are cut into slabs of kSlab pairs; a workgroup sums one slab in fp64 in an order fixed by the
+// thread index, and a second kernel adds the slabs in slab order.  The shape depends on the problem's dimensions
+// alone, so results are bitwise reproducible.  The Linear head sums over features (forward, one workgroup per
+// sample) and over samples (backward, one thread per feature and chunk of 64 samples, the chunks added in order) in
+// fp64 as well.  Convolution forward and input
+// gradient are fp32 fmaf chains of at most cin/groups * k (cout/groups * k) terms, in k_conv1d's order.
+#include "ofp_common.h"
+#include "ofp_mlp.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+namespace {
+
+constexpr int kT = 256;        // threads per workgroup
+constexpr int kSlab = 2048;    // (sample, position) pairs one workgroup sums
+constexpr int kFcChunk = 64;   // samples one thread of the Linear head's weight gradient sums
+constexpr int kMaxConv = 3;
+constexpr int kMaxCh = 128;
+constexpr int kMaxKernel = 8;
+constexpr int kMaxWidth = 512;
+constexpr int kMaxBatch = 1024;
+constexpr int kMaxOut = 16;
+constexpr int kCheckEvery = 64;  // epochs between two looks at the stop word
+
+struct Ctl {
+    int32_t epoch, stop, wait, reached;
+    float best;
+    int32_t pad[3];
+};
+
+#define OFP_CNN_STOPPED(ctl) \
+    if ((ctl) != nullptr && (ctl)->stop) return
+
+struct Conv {
+    int cin, cout, win, wc, k, pad, dil, groups;
+};
+
+// what follows the convolution: activation, BatchNorm (mode 0 none, 1 batch statistics, 2 running statistics), pool
+struct Post {
+    int C, wc, wo, act, pool, mode;
+    double eps;
+    const float* ga;
+    const float* be;
+    const float* mean;  // mode 1: saved batch mean; mode 2: running mean
+    const float* rs;    // mode 1: saved 1 / sqrt(var + eps); mode 2: running variance
+};
+
+struct Aff {
+    float mean, rstd, ga, be;
+};
+
+__device__ __forceinline__ Aff load_aff(const Post& t, int c) {
+    Aff f{0.0f, 1.0f, 1.0f, 0.0f};
+    if (t.mode == 1) {
+        f.mean = t.mean[c], f.rstd = t.rs[c], f.ga = t.ga[c], f.be = t.be[c];
+    } else if (t.mode == 2) {  // the fold of model.conv1d_forward, in double, rounded once
+        const double inv = 1.0 / sqrt((double)t.rs[c] + t.eps);
+        const double g = (double)t.ga[c];
+        f.ga = (float)(g * inv);
+        f.be = (float)((double)t.be[c] - (double)t.mean[c] * g * inv);
+    }
+    return f;
+}
+
+__device__ __forceinline__ float aff_apply(const Aff& f, int mode, float a) {
+    if (mode == 1) return ((a - f.mean) * f.rstd) * f.ga + f.be;
+    if (mode == 2) return fmaf(a, f.ga, f.be);
+    return a;
+}
+
+// d act / d z at pre-activation z (a = act(z)), as csrc/ofp_train.hip evaluates it
+__device__ __forceinline__ float act_grad(float y, float a, int act) {
+    switch (act) {
+        case OFP_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
+        case OFP_ACT_SILU: {
+            const float s = 1.0f / (1.0f + expf(-y));
+            return s * (1.0f + y * (1.0f - s));
+        }
+        case OFP_ACT_LEAKYRELU: return y > 0.0f ? 1.0f : 0.01f;
+        case OFP_ACT_ELU: return y > 0.0f ? 1.0f : expf(y);
+        case OFP_ACT_TANH: return 1.0f - a * a;
+        default: return 1.0f;
+    }
+}
+
+// sum of (a, b) over the workgroup: xor butterfly inside each wave, then the four waves in wave order
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[kT / 64]) {
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // a previous use of `red` has been read
+    if (lane == 0) red[0][wave] = a, red[1][wave] = b;
+    __syncthreads();
+    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+}
+
+__global__ __launch_bounds__(kT) void k_init(Ctl* ctl) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        *ctl = Ctl{};
+        ctl->best = INFINITY;
+    }
+}
+
+// z[s][o][p] = b[o] + sum_{ci, kk} x[s][g*cin_g + ci][p - pad + kk*dil] * w[o][ci][kk]: thread per element, the
+// arithmetic of k_conv1d (csrc/ofp_nn.hip)
+__global__ __launch_bounds__(kT) void k_conv_fwd(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ x,
+                                                 const float* __restrict__ w, const float* __restrict__ b,
+                                                 float* __restrict__ z) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * c.cout * c.wc;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int p = (int)(i % c.wc);
+        const int64_t t = i / c.wc;
+        const int o = (int)(t % c.cout);
+        const int64_t s = t / c.cout;
+        const float* xs = x + (s * c.cin + (int64_t)(o / cout_g) * cin_g) * c.win;
+        const float* ws = w + (int64_t)o * cin_g * c.k;
+        float acc = b[o];
+        for (int ci = 0; ci < cin_g; ++ci)
+            for (int kk = 0; kk < c.k; ++kk) {
+                const int q = p - c.pad + kk * c.dil;
+                if (q >= 0 && q < c.win) acc = fmaf(xs[(int64_t)ci * c.win + q], ws[ci * c.k + kk], acc);
+            }
+        z[i] = acc;
+    }
+}
+
+// BatchNorm, batch statistics: sum a, sum a^2 (a = act(z)) of one slab of one channel
+__global__ __launch_bounds__(kT) void k_bn_stats_partial(const Ctl* ctl, const float* __restrict__ z, int64_t n, int C,
+                                                         int wc, int act, double* __restrict__ partial) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    const int slab = blockIdx.x, c = blockIdx.y, nslab = gridDim.x;
+    const int pairs = (int)n * wc, q0 = slab * kSlab;  // n * wc <= 2^20: 32-bit index arithmetic
+    const int q1 = q0 + kSlab < pairs ? q0 + kSlab : pairs;
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += kT) {
+        const int s = q / wc;
+        const int p = q - s * wc;
+        const double a = (double)ofp_activate(z[((int64_t)s * C + c) * wc + p], act);
+        s1 += a;
+        s2 += a * a;
+    }
+    block_sum2(s1, s2, red);
+    if (threadIdx.x == 0) {
+        partial[((int64_t)c * nslab + slab) * 2] = s1;
+        partial[((int64_t)c * nslab + slab) * 2 + 1] = s2;
+    }
+}
+
+// slabs in slab order -> mean, 1 / sqrt(biased var + eps); running statistics with the unbiased variance
+__global__ __launch_bounds__(kT) void k_bn_stats_final(const Ctl* ctl, const double* __restrict__ partial, int nslab,
+                                                       int C, int64_t count, double eps, float mom,
+                                                       float* __restrict__ mean, float* __restrict__ rstd,
+                                                       float* __restrict__ run_mean, float* __restrict__ run_var) {
+    OFP_CNN_STOPPED(ctl);
+    const int c = blockIdx.x * kT + threadIdx.x;
+    if (c >= C) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < nslab; ++i) {
+        s1 += partial[((int64_t)c * nslab + i) * 2];
+        s2 += partial[((int64_t)c * nslab + i) * 2 + 1];
+    }
+    const double m = s1 / (double)count;
+    double var = s2 / (double)count - m * m;
+    var = var > 0.0 ? var : 0.0;
+    mean[c] = (float)m;
+    rstd[c] = (float)(1.0 / sqrt(var + eps));
+    const float unbiased = (float)(var * ((double)count / (double)(count - 1)));
+    run_mean[c] = mom * (float)m + (1.0f - mom) * run_mean[c];
+    run_var[c] = mom * unbiased + (1.0f - mom) * run_var[c];
+}
+
+// the layer's output: MaxPool(BatchNorm(act(z)))
+__global__ __launch_bounds__(kT) void k_post(const Ctl* ctl, const Post t, int64_t n, const float* __restrict__ z,
+                                             float* __restrict__ h) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * t.C * t.wo;
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int po = (int)(i % t.wo);
+        const int64_t row = i / t.wo;
+        const int c = (int)(row % t.C);
+        const Aff f = load_aff(t, c);
+        const float* zr = z + row * t.wc;
+        if (t.pool) {
+            const float y0 = aff_apply(f, t.mode, ofp_activate(zr[2 * po], t.act));
+            const float y1 = aff_apply(f, t.mode, ofp_activate(zr[2 * po + 1], t.act));
+            h[i] = y1 > y0 ? y1 : y0;
+        } else {
+            h[i] = aff_apply(f, t.mode, ofp_activate(zr[po], t.act));
+        }
+    }
+}
+
+// gradient that reaches position p of the un-pooled row: the pool hands its gradient to the larger of the pair
+// (the first on a tie); a dropped odd last column gets none
+__device__ __forceinline__ float routed_dy(const Post& t, const Aff& f, const float* zr, const float* dhr, int p) {
+    if (!t.pool) return dhr[p];
+    const int po = p >> 1;
+    if (po >= t.wo) return 0.0f;
+    const float y0 = aff_apply(f, t.mode, ofp_activate(zr[2 * po], t.act));
+    const float y1 = aff_apply(f, t.mode, ofp_activate(zr[2 * po + 1], t.act));
+    const bool second = y1 > y0;
+    return ((p & 1) != 0) == second ? dhr[po] : 0.0f;
+}
+
+// BatchNorm backward: sum dy, sum dy * xhat of one slab of one channel
+__global__ __launch_bounds__(kT) void k_bn_bwd_partial(const Ctl* ctl, const Post t, int64_t n,
+                                                       const float* __restrict__ z, const float* __restrict__ dh,
+                                                       double* __restrict__ partial) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    const int slab = blockIdx.x, c = blockIdx.y, nslab = gridDim.x;
+    const int pairs = (int)n * t.wc, q0 = slab * kSlab;
+    const int q1 = q0 + kSlab < pairs ? q0 + kSlab : pairs;
+    const Aff f = load_aff(t, c);
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += kT) {
+        const int s = q / t.wc;
+        const int p = q - s * t.wc;
+        const float* zr = z + ((int64_t)s * t.C + c) * t.wc;
+        const float dy = routed_dy(t, f, zr, dh + ((int64_t)s * t.C + c) * t.wo, p);
+        const float xh = (ofp_activate(zr[p], t.act) - f.mean) * f.rstd;
+        s1 += (double)dy;
+        s2 += (double)dy * (double)xh;
+    }
+    block_sum2(s1, s2, red);
+    if (threadIdx.x == 0) {
+        partial[((int64_t)c * nslab + slab) * 2] = s1;
+        partial[((int64_t)c * nslab + slab) * 2 + 1] = s2;
+    }
+}
+
+__global__ __launch_bounds__(kT) void k_bn_bwd_final(const Ctl* ctl, const double* __restrict__ partial, int nslab,
+                                                     int C, float* __restrict__ s12, float* __restrict__ dgamma,
+                                                     float* __restrict__ dbeta) {
+    OFP_CNN_STOPPED(ctl);
+    const int c = blockIdx.x * kT + threadIdx.x;
+    if (c >= C) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < nslab; ++i) {
+        s1 += partial[((int64_t)c * nslab + i) * 2];
+        s2 += partial[((int64_t)c * nslab + i) * 2 + 1];
+    }
+    s12[c] = (float)s1, s12[C + c] = (float)s2;
+    dbeta[c] = (float)s1, dgamma[c] = (float)s2;
+}
+
+// gradient at the pre-activation: pool routing, BatchNorm backward (needs the two sums), activation backward
+__global__ __launch_bounds__(kT) void k_dz(const Ctl* ctl, const Post t, int64_t n, const float* __restrict__ z,
+                                           const float* __restrict__ dh, const float* __restrict__ s12,
+                                           float* __restrict__ dz) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * t.C * t.wc;
+    const float inv_count = 1.0f / (float)(n * t.wc);
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int p = (int)(i % t.wc);
+        const int64_t row = i / t.wc;
+        const int c = (int)(row % t.C);
+        const Aff f = load_aff(t, c);
+        const float* zr = z + row * t.wc;
+        float d = routed_dy(t, f, zr, dh + row * t.wo, p);
+        const float a = ofp_activate(zr[p], t.act);
+        if (t.mode == 1) {
+            const float xh = (a - f.mean) * f.rstd;
+            d = (d - s12[c] * inv_count - xh * (s12[t.C + c] * inv_count)) * f.rstd * f.ga;
+        }
+        dz[i] = d * act_grad(zr[p], a, t.act);
+    }
+}
+
+// lanes per output of the weight-gradient kernel: the largest power of two <= 64 with outputs * g <= kT
+__host__ __device__ inline int lanes_per_output(int outputs) {
+    int g = 64;
+    while (g > 1 && outputs * g > kT) g >>= 1;
+    return g;
+}
+
+// dW[o][ci][kk] = sum_{s, p} dz[s][o][p] * x[s][g*cin_g + ci][p - pad + kk*dil], db[o] = sum dz: workgroup (slab, o);
+// the cin_g * k weights of channel o and its bias are the T outputs, g adjacent lanes share one output and take
+// the slab's pairs sub, sub + g, ... in ascending order, then an xor butterfly joins them
+__global__ __launch_bounds__(kT) void k_wgrad_partial(const Ctl* ctl, const Conv c, int64_t n,
+                                                      const float* __restrict__ x, const float* __restrict__ dz,
+                                                      double* __restrict__ partial) {
+    OFP_CNN_STOPPED(ctl);
+    const int slab = blockIdx.x, o = blockIdx.y, nslab = gridDim.x;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    const int T = cin_g * c.k + 1;
+    const int g = lanes_per_output(T), per = kT / g, sub = threadIdx.x & (g - 1);
+    const int pairs = (int)n * c.wc, q0 = slab * kSlab;
+    const int q1 = q0 + kSlab < pairs ? q0 + kSlab : pairs;
+    const int ch0 = (o / cout_g) * cin_g;
+    for (int base = 0; base < T; base += per) {
+        const int wi = base + threadIdx.x / g;
+        const bool valid = wi < T;
+        const int ci = wi / c.k, kk = wi - ci * c.k;
+        const bool bias = wi == T - 1;
+        const int shift = kk * c.dil - c.pad;
+        double acc = 0.0;
+        if (valid)
+            for (int q = q0 + sub; q < q1; q += g) {
+                const int s = q / c.wc;
+                const int p = q - s * c.wc;
+                const float d = dz[((int64_t)s * c.cout + o) * c.wc + p];
+                if (bias) {
+                    acc += (double)d;
+                } else {
+                    const int xi = p + shift;
+                    if (xi >= 0 && xi < c.win) acc += (double)d * (double)x[((int64_t)s * c.cin + ch0 + ci) * c.win + xi];
+                }
+            }
+        for (int off = g >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (valid && sub == 0) partial[((int64_t)o * T + wi) * nslab + slab] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kT) void k_wgrad_final(const Ctl* ctl, const double* __restrict__ partial, int nslab,
+                                                    int cout, int T, float* __restrict__ dw, float* __restrict__ db) {
+    OFP_CNN_STOPPED(ctl);
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= cout * T) return;
+    const int o = i / T, wi = i - o * T;
+    double s = 0.0;
+    for (int j = 0; j < nslab; ++j) s += partial[(int64_t)i * nslab + j];
+    if (wi == T - 1)
+        db[o] = (float)s;
+    else
+        dw[o * (T - 1) + wi] = (float)s;
+}
+
+// dx[s][ci][q] = sum_{o in ci's group, kk} dz[s][o][q + pad - kk*dil] * w[o][ci][kk]: thread per element
+__global__ __launch_bounds__(kT) void k_dgrad(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ dz,
+                                              const float* __restrict__ w, float* __restrict__ dx) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * c.cin * c.win;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int q = (int)(i % c.win);
+        const int64_t t = i / c.win;
+        const int ci = (int)(t % c.cin);
+        const int64_t s = t / c.cin;
+        const int grp = ci / cin_g, cil = ci - grp * cin_g;
+        float acc = 0.0f;
+        for (int oo = 0; oo < cout_g; ++oo) {
+            const int o = grp * cout_g + oo;
+            const float* dr = dz + (s * c.cout + o) * c.wc;
+            const float* wr = w + ((int64_t)o * cin_g + cil) * c.k;
+            for (int kk = 0; kk < c.k; ++kk) {
+                const int p = q + c.pad - kk * c.dil;
+                if (p >= 0 && p < c.wc) acc = fmaf(dr[p], wr[kk], acc);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
+// Linear head of one sample per workgroup: out = W h + b (fp64 sums over the F features), the sample's share of
+// the loss (sum over its outputs of |r| or r^2) and, when dy is given, d loss / d out
+__global__ __launch_bounds__(kT) void k_fc_fwd(const Ctl* ctl, const float* __restrict__ h, int F, int O,
+                                               const float* __restrict__ w, const float* __restrict__ b,
+                                               const float* __restrict__ y, int loss, float inv_numel,
+                                               float* __restrict__ out, float* __restrict__ dy,
+                                               double* __restrict__ part) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    const int64_t s = blockIdx.x;
+    const float* hr = h + s * F;
+    double lsum = 0.0;
+    for (int j = 0; j < O; j += 2) {
+        const bool two = j + 1 < O;
+        double a0 = 0.0, a1 = 0.0;
+        for (int f = threadIdx.x; f < F; f += kT) {
+            const double hv = (double)hr[f];
+            a0 += hv * (double)w[(int64_t)j * F + f];
+            if (two) a1 += hv * (double)w[(int64_t)(j + 1) * F + f];
+        }
+        block_sum2(a0, a1, red);
+        if (threadIdx.x == 0) {
+            for (int u = 0; u < (two ? 2 : 1); ++u) {
+                const float o = (float)((u ? a1 : a0) + (double)b[j + u]);
+                const float r = o - y[s * O + j + u];
+                out[s * O + j + u] = o;
+                if (loss == 0) {
+                    lsum += (double)fabsf(r);
+                    if (dy) dy[s * O + j + u] = r > 0.0f ? inv_numel : (r < 0.0f ? -inv_numel : 0.0f);
+                } else {
+                    lsum += (double)r * (double)r;
+                    if (dy) dy[s * O + j + u] = (2.0f * inv_numel) * r;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) part[s] = lsum;
+}
+
+// mean loss of the batch into slot `epoch` of a curve (and the head's bias gradient); for the validation loss also Lightning's early-stop rule
+// (min_delta 0): a loss that is not below the best so far counts towards patience
+__global__ __launch_bounds__(kT) void k_loss_final(Ctl* ctl, const double* __restrict__ part, int64_t n, int O,
+                                                   float* __restrict__ curve, int validation, int patience,
+                                                   const float* __restrict__ dy, float* __restrict__ db) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    if (db)  // the Linear head's bias gradient, db[j] = sum_s dy[s][j], two outputs at a time
+        for (int j = 0; j < O; j += 2) {
+            const bool two = j + 1 < O;
+            double b0 = 0.0, b1 = 0.0;
+            for (int64_t i = threadIdx.x; i < n; i += kT) {
+                b0 += (double)dy[i * O + j];
+                if (two) b1 += (double)dy[i * O + j + 1];
+            }
+            block_sum2(b0, b1, red);
+            if (threadIdx.x == 0) {
+                db[j] = (float)b0;
+                if (two) db[j + 1] = (float)b1;
+            }
+        }
+    double a = 0.0, z = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kT) a += part[i];
+    block_sum2(a, z, red);
+    if (threadIdx.x == 0) {
+        const float loss = (float)(a / (double)(n * O));
+        curve[ctl ? ctl->epoch : 0] = loss;
+        if (validation && ctl) {
+            if (loss < ctl->best) {
+                ctl->best = loss;
+                ctl->wait = 0;
+            } else {
+                ctl->wait += 1;
+            }
+            if (patience >= 0 && ctl->wait >= patience) ctl->reached = 1;
+        }
+    }
+}
+
+// dW[j][f] = sum_s dy[s][j] h[s][f], dh[s][f] = sum_j dy[s][j] W[j][f]: thread per feature and chunk of kFcChunk
+// samples (fp64, samples in ascending order); k_fc_wfinal adds the chunks in chunk order
+__global__ __launch_bounds__(kT) void k_fc_bwd(const Ctl* ctl, const float* __restrict__ h,
+                                               const float* __restrict__ dy, int64_t n, int F, int O,
+                                               const float* __restrict__ w, double* __restrict__ partial,
+                                               float* __restrict__ dh) {
+    OFP_CNN_STOPPED(ctl);
+    const int f = blockIdx.x * kT + threadIdx.x, ck = blockIdx.y;
+    if (f >= F) return;
+    double acc[kMaxOut];
+    float wj[kMaxOut];
+#pragma unroll
+    for (int j = 0; j < kMaxOut; ++j) acc[j] = 0.0, wj[j] = j < O ? w[(int64_t)j * F + f] : 0.0f;
+    const int64_t s0 = (int64_t)ck * kFcChunk, s1 = s0 + kFcChunk < n ? s0 + kFcChunk : n;
+    for (int64_t s = s0; s < s1; ++s) {
+        const float hv = h[s * F + f];
+        float d = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kMaxOut; ++j)
+            if (j < O) {
+                const float g = dy[s * O + j];
+                acc[j] += (double)g * (double)hv;
+                d = fmaf(g, wj[j], d);
+            }
+        dh[s * F + f] = d;
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxOut; ++j)
+        if (j < O) partial[((int64_t)ck * O + j) * F + f] = acc[j];
+}
+
+__global__ __launch_bounds__(kT) void k_fc_wfinal(const Ctl* ctl, const double* __restrict__ partial, int nchunk,
+                                                  int64_t OF, float* __restrict__ dw) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= OF) return;
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) s += partial[(int64_t)c * OF + i];
+    dw[i] = (float)s;
+}
+
+// torch.optim.NAdam (_single_tensor_nadam, defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay), one element per
+// thread.  row = (c1, c2, bias_correction2), denom = sqrt(v / bias_correction2) + eps, p += (c1 g + c2 m) / denom.
+// torch adds the two terms to p one after the other (two addcdiv_ calls, p rounded twice); here they are added to
+// each other first, so that p is rounded once per step.
+__global__ __launch_bounds__(kT) void k_nadam(const Ctl* ctl, const float* __restrict__ rows, float* __restrict__ p,
+                                              const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, int64_t np) {
+    OFP_CNN_STOPPED(ctl);
+    const float* row = rows + (int64_t)(ctl ? ctl->epoch : 0) * 4;
+    const float c1 = row[0], c2 = row[1], bc2 = row[2];
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < np; i += (int64_t)gridDim.x * kT) {
+        const float gr = g[i];
+        const float mo = fmaf(0.1f, gr - m[i], m[i]);
+        const float vo = v[i] * 0.999f + (0.001f * gr) * gr;
+        m[i] = mo, v[i] = vo;
+        const float denom = sqrtf(vo / bc2) + 1e-8f;
+        p[i] = p[i] + ((c1 * gr) / denom + (c2 * mo) / denom);
+    }
+}
+
+// the chain's last kernel: the epoch is over; stop once patience has run out and min_epochs are done
+__global__ __launch_bounds__(kT) void k_epoch_end(Ctl* ctl, int min_epochs) {
+    OFP_CNN_STOPPED(ctl);
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ctl->epoch += 1;
+        if (ctl->reached && ctl->epoch >= min_epochs) ctl->stop = 1;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+
+unsigned grid_for(int64_t total) {
+    const int64_t g = ofp::cdiv(total, kT);
+    return (unsigned)(g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g));
+}
+int slabs_of(int64_t pairs) { return (int)ofp::cdiv(pairs, kSlab); }
+
+int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int padding, int dilation, int groups) {
+    OFP_REQUIRE(n >= 1 && n <= kMaxBatch, "%s: batch of %lld (limit: 1..%d)", who, (long long)n, kMaxBatch);
+    OFP_REQUIRE(cin >= 1 && cin <= kMaxCh && cout >= 1 && cout <= kMaxCh, "%s: %d -> %d channels (limit: 1..%d)", who,
+                cin, cout, kMaxCh);
+    OFP_REQUIRE(w >= 1 && w <= kMaxWidth, "%s: width %d (limit: 1..%d)", who, w, kMaxWidth);
+    OFP_REQUIRE(k >= 1 && k <= kMaxKernel, "%s: kernel size %d (limit: 1..%d)", who, k, kMaxKernel);
+    OFP_REQUIRE(dilation >= 1 && dilation <= 64 && padding >= 0 && padding <= kMaxWidth,
+                "%s: dilation %d, padding %d", who, dilation, padding);
+    OFP_REQUIRE(groups >= 1 && cin % groups == 0 && cout % groups == 0, "%s: groups %d do not divide %d and %d", who,
+                groups, cin, cout);
+    OFP_REQUIRE(w + 2 * padding - dilation * (k - 1) >= 1, "%s: the convolution leaves no output column", who);
+    return OFP_OK;
+}
+
+struct Plan {
+    int L, act, bn, pool, loss, O, F, np, ns;
+    double eps;
+    float mom;
+    Conv conv[kMaxConv];
+    int wo[kMaxConv];
+    int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], rs_off[kMaxConv], fcw_off, fcb_off;
+    // work space, byte offsets
+    int64_t o_Z[kMaxConv], o_H[kMaxConv], o_out, o_dy, o_lpart, o_gh, o_gz, o_save, o_s12, o_part, o_G, o_M, o_V,
+        o_RS, o_ctl, bytes;
+};
+
+int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p) {
+    OFP_REQUIRE(c != nullptr, "cnn training: config is NULL");
+    OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "cnn training: %d conv layers (limit: 1..%d)", c->n_conv,
+                kMaxConv);
+    OFP_REQUIRE(n_val >= 0 && n_val <= kMaxBatch, "cnn training: validation batch of %lld (limit: 0..%d)",
+                (long long)n_val, kMaxBatch);
+    OFP_REQUIRE(c->act >= 0 && c->act <= OFP_ACT_TANH, "cnn training: unknown activation %d", c->act);
+    OFP_REQUIRE(c->loss == 0 || c->loss == 1, "cnn training: loss %d (0 = L1, 1 = MSE)", c->loss);
+    OFP_REQUIRE(c->n_out >= 1 && c->n_out <= kMaxOut, "cnn training: %d outputs (limit: 1..%d)", c->n_out, kMaxOut);
+    if (c->batch_norm)
+        OFP_REQUIRE(c->bn_momentum > 0.0f && c->bn_momentum <= 1.0f && c->bn_eps > 0.0,
+                    "cnn training: BatchNorm momentum %g, eps %g (a cumulative average, momentum=None, is not built)",
+                    (double)c->bn_momentum, c->bn_eps);
+    p = Plan{};
+    p.L = c->n_conv, p.act = c->act, p.bn = c->batch_norm ? 1 : 0, p.pool = c->pool ? 1 : 0, p.loss = c->loss;
+    p.O = c->n_out, p.eps = c->bn_eps, p.mom = c->bn_momentum;
+    const int64_t nmax = n > n_val ? n : n_val;
+    int width = c->width, np = 0, ns = 0;
+    int64_t max_h = 0, max_z = 0, max_part = 2;
+    for (int l = 0; l < p.L; ++l) {
+        const int cin = c->channels[l], cout = c->channels[l + 1];
+        if (int rc = check_conv("cnn training", n, cin, width, cout, c->kernel, c->padding, c->dilation, c->groups))
+            return rc;
+        Conv& v = p.conv[l];
+        v = Conv{cin, cout, width, width + 2 * c->padding - c->dilation * (c->kernel - 1), c->kernel, c->padding,
+                 c->dilation, c->groups};
+        OFP_REQUIRE(v.wc <= 2 * kMaxWidth, "cnn training: layer %d is %d wide (limit: %d)", l + 1, v.wc, 2 * kMaxWidth);
+        p.wo[l] = p.pool ? v.wc / 2 : v.wc;
+        OFP_REQUIRE(p.wo[l] >= 1, "cnn training: the pool of layer %d leaves no output column", l + 1);
+        OFP_REQUIRE(!p.bn || n * v.wc >= 2, "cnn training: BatchNorm needs more than 1 value per channel");
+        const int T = cin / c->groups * c->kernel + 1;
+        p.w_off[l] = np, np += cout * (T - 1);
+        p.b_off[l] = np, np += cout;
+        if (p.bn) {
+            p.g_off[l] = np, np += cout;
+            p.be_off[l] = np, np += cout;
+            p.rs_off[l] = ns, ns += 2 * cout;
+        }
+        const int64_t part = (int64_t)cout * T * slabs_of(n * v.wc);
+        max_part = part > max_part ? part : max_part;
+        max_h = std::max<int64_t>(max_h, nmax * cout * p.wo[l]);
+        max_z = std::max<int64_t>(max_z, nmax * cout * v.wc);
+        width = p.wo[l];
+    }
+    p.F = c->channels[p.L] * width;
+    max_part = std::max<int64_t>(max_part, ofp::cdiv(n, kFcChunk) * p.O * p.F);
+    p.fcw_off = np, np += p.O * p.F;
+    p.fcb_off = np, np += p.O;
+    p.np = np, p.ns = ns;
+    int64_t o = 0;
+    auto take = [&](int64_t bytes) {
+        const int64_t at = o;
+        o += ofp::align_up(bytes > 0 ? bytes : 1, 256);
+        return at;
+    };
+    for (int l = 0; l < p.L; ++l) {
+        p.o_Z[l] = take(nmax * p.conv[l].cout * p.conv[l].wc * 4);
+        p.o_H[l] = take(nmax * p.conv[l].cout * p.wo[l] * 4);
+    }
+    p.o_out = take(nmax * p.O * 4);
+    p.o_dy = take(nmax * p.O * 4);
+    p.o_lpart = take(nmax * 8);
+    p.o_gh = take(max_h * 4);
+    p.o_gz = take(max_z * 4);
+    p.o_save = take((int64_t)ns * 4);
+    p.o_s12 = take((int64_t)ns * 4);
+    p.o_part = take(max_part * 8);
+    p.o_G = take((int64_t)np * 4);
+    p.o_M = take((int64_t)np * 4);
+    p.o_V = take((int64_t)np * 4);
+    p.o_RS = take((int64_t)ns * 4);
+    p.o_ctl = take(sizeof(Ctl));
+    p.bytes = o;
+    return OFP_OK;
+}
+
+struct Run {
+    const Plan* p;
+    char* ws;
+    float* P;    // packed parameters
+    float* RS;   // packed running statistics
+    float* G;    // packed gradients
+    Ctl* ctl;    // NULL: a single pass, epoch 0
+    hipStream_t st;
+    template <class T>
+    T* at(int64_t off) const {
+        return reinterpret_cast<T*>(ws + off);
+    }
+};
+
+Post post_of(const Run& r, int l, int mode) {
+    const Plan& p = *r.p;
+    Post t{};
+    t.C = p.conv[l].cout, t.wc = p.conv[l].wc, t.wo = p.wo[l], t.act = p.act, t.pool = p.pool, t.mode = mode;
+    t.eps = p.eps;
+    if (mode) {
+        t.ga = r.P + p.g_off[l], t.be = r.P + p.be_off[l];
+        if (mode == 1) {
+            t.mean = r.at<float>(p.o_save) + p.rs_off[l], t.rs = t.mean + t.C;
+        } else {
+            t.mean = r.RS + p.rs_off[l], t.rs = t.mean + t.C;
+        }
+    }
+    return t;
+}
+
+// batch statistics of act(z) for one BatchNorm: saved mean / rstd, running statistics updated
+int enqueue_bn_stats(const Ctl* ctl, const float* z, int64_t n, int C, int wc, int act, double eps, float mom,
+                     double* part, float* mean, float* rstd, float* run_mean, float* run_var, hipStream_t st) {
+    const int nslab = slabs_of(n * wc);
+    hipLaunchKernelGGL(k_bn_stats_partial, dim3(nslab, C), dim3(kT), 0, st, ctl, z, n, C, wc, act, part);
+    OFP_LAUNCH_CHECK("k_bn_stats_partial");
+    hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)ofp::cdiv(C, kT)), dim3(kT), 0, st, ctl, part, nslab, C,
+                       n * wc, eps, mom, mean, rstd, run_mean, run_var);
+    OFP_LAUNCH_CHECK("k_bn_stats_final");
+    return OFP_OK;
+}
+
+// pool routing, BatchNorm backward, activation backward: dh -> dz (and d gamma, d beta)
+int enqueue_post_bwd(const Ctl* ctl, const Post& t, int64_t n, const float* z, const float* dh, double* part,
+                     float* s12, float* dgamma, float* dbeta, float* dz, hipStream_t st) {
+    if (t.mode == 1) {
+        const int nslab = slabs_of(n * t.wc);
+        hipLaunchKernelGGL(k_bn_bwd_partial, dim3(nslab, t.C), dim3(kT), 0, st, ctl, t, n, z, dh, part);
+        OFP_LAUNCH_CHECK("k_bn_bwd_partial");
+        hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)ofp::cdiv(t.C, kT)), dim3(kT), 0, st, ctl, part, nslab, t.C,
+                           s12, dgamma, dbeta);
+        OFP_LAUNCH_CHECK("k_bn_bwd_final");
+    }
+    hipLaunchKernelGGL(k_dz, dim3(grid_for(n * t.C * t.wc)), dim3(kT), 0, st, ctl, t, n, z, dh, s12, dz);
+    OFP_LAUNCH_CHECK("k_dz");
+    return OFP_OK;
+}
+
+int enqueue_conv_bwd(const Ctl* ctl, const Conv& c, int64_t n, const float* x, const float* w, const float* dz,
+                     double* part, float* dw, float* db, float* dx, hipStream_t st) {
+    const int nslab = slabs_of(n * c.wc), T = c.cin / c.groups * c.k + 1;
+    hipLaunchKernelGGL(k_wgrad_partial, dim3(nslab, c.cout), dim3(kT), 0, st, ctl, c, n, x, dz, part);
+    OFP_LAUNCH_CHECK("k_wgrad_partial");
+    hipLaunchKernelGGL(k_wgrad_final, dim3((unsigned)ofp::cdiv(c.cout * T, kT)), dim3(kT), 0, st, ctl, part, nslab,
+                       c.cout, T, dw, db);
+    OFP_LAUNCH_CHECK("k_wgrad_final");
+    if (dx) {
+        hipLaunchKernelGGL(k_dgrad, dim3(grid_for(n * c.cin * c.win)), dim3(kT), 0, st, ctl, c, n, dz, w, dx);
+        OFP_LAUNCH_CHECK("k_dgrad");
+    }
+    return OFP_OK;
+}
+
+// conv stack and head of a batch; train: batch statistics, d loss / d out kept; else running statistics, L1
+int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train) {
+    const Plan& p = *r.p;
+    const float* in = x;
+    for (int l = 0; l < p.L; ++l) {
+        const Conv& c = p.conv[l];
+        float* Z = r.at<float>(p.o_Z[l]);
+        float* H = r.at<float>(p.o_H[l]);
+        hipLaunchKernelGGL(k_conv_fwd, dim3(grid_for(n * c.cout * c.wc)), dim3(kT), 0, r.st, r.ctl, c, n, in,
+                           r.P + p.w_off[l], r.P + p.b_off[l], Z);
+        OFP_LAUNCH_CHECK("k_conv_fwd");
+        const Post t = post_of(r, l, p.bn ? (train ? 1 : 2) : 0);
+        if (p.bn && train) {
+            float* save = r.at<float>(p.o_save) + p.rs_off[l];
+            if (int rc = enqueue_bn_stats(r.ctl, Z, n, c.cout, c.wc, p.act, p.eps, p.mom, r.at<double>(p.o_part), save,
+                                          save + c.cout, r.RS + p.rs_off[l], r.RS + p.rs_off[l] + c.cout, r.st))
+                return rc;
+        }
+        hipLaunchKernelGGL(k_post, dim3(grid_for(n * c.cout * p.wo[l])), dim3(kT), 0, r.st, r.ctl, t, n, Z, H);
+        OFP_LAUNCH_CHECK("k_post");
+        in = H;
+    }
+    const float inv_numel = 1.0f / (float)(n * p.O);
+    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, in, p.F, p.O, r.P + p.fcw_off,
+                       r.P + p.fcb_off, y, train ? p.loss : 0, inv_numel, r.at<float>(p.o_out),
+                       train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart));
+    OFP_LAUNCH_CHECK("k_fc_fwd");
+    return OFP_OK;
+}
+
+int enqueue_backward(const Run& r, const float* x, int64_t n) {
+    const Plan& p = *r.p;
+    float* GH = r.at<float>(p.o_gh);
+    float* GZ = r.at<float>(p.o_gz);
+    double* part = r.at<double>(p.o_part);
+    const int nchunk = (int)ofp::cdiv(n, kFcChunk);
+    hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(p.F, kT), nchunk), dim3(kT), 0, r.st, r.ctl,
+                       r.at<float>(p.o_H[p.L - 1]), r.at<float>(p.o_dy), n, p.F, p.O, r.P + p.fcw_off, part, GH);
+    OFP_LAUNCH_CHECK("k_fc_bwd");
+    hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)p.O * p.F, kT)), dim3(kT), 0, r.st, r.ctl, part,
+                       nchunk, (int64_t)p.O * p.F, r.G + p.fcw_off);
+    OFP_LAUNCH_CHECK("k_fc_wfinal");
+    for (int l = p.L - 1; l >= 0; --l) {
+        const Post t = post_of(r, l, p.bn ? 1 : 0);
+        const float* Z = r.at<float>(p.o_Z[l]);
+        if (int rc = enqueue_post_bwd(r.ctl, t, n, Z, GH, part, r.at<float>(p.o_s12) + p.rs_off[l],
+                                      r.G + p.g_off[l], r.G + p.be_off[l], GZ, r.st))
+            return rc;
+        const float* in = l == 0 ? x : r.at<float>(p.o_H[l - 1]);
+        if (int rc = enqueue_conv_bwd(r.ctl, p.conv[l], n, in, r.P + p.w_off[l], GZ, part, r.G + p.w_off[l],
+                                      r.G + p.b_off[l], l == 0 ? nullptr : GH, r.st))
+            return rc;
+    }
+    return OFP_OK;
+}
+
+struct TrainArgs {
+    const float* x;
+    const float* y;
+    int64_t n;
+    const float* xv;
+    const float* yv;
+    int64_t nv;
+    const float* rates;
+    int min_epochs, patience;
+    float* train_loss;
+    float* val_loss;
+};
+
+int enqueue_epoch(const Run& r, const TrainArgs& a) {
+    const Plan& p = *r.p;
+    if (int rc = enqueue_forward(r, a.x, a.y, a.n, true)) return rc;
+    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.n, p.O,
+                       a.train_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
+    OFP_LAUNCH_CHECK("k_loss_final");
+    if (int rc = enqueue_backward(r, a.x, a.n)) return rc;
+    hipLaunchKernelGGL(k_nadam, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, a.rates, r.P, r.G,
+                       r.at<float>(p.o_M), r.at<float>(p.o_V), (int64_t)p.np);
+    OFP_LAUNCH_CHECK("k_nadam");
+    if (a.nv > 0) {
+        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false)) return rc;
+        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.nv, p.O,
+                           a.val_loss, 1, a.patience, (const float*)nullptr, (float*)nullptr);
+        OFP_LAUNCH_CHECK("k_loss_final");
+    }
+    hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(kT), 0, r.st, r.ctl, a.min_epochs);
+    OFP_LAUNCH_CHECK("k_epoch_end");
+    return OFP_OK;
+}
+
+int check_ws(const char* who, const void* ws, int64_t given, int64_t need) {
+    if (ws == nullptr || given < need)
+        return ofp::fail(OFP_ERR_WORKSPACE, "%s: work space of %lld bytes needed, %lld given", who, (long long)need,
+                         (long long)given);
+    return OFP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t ofp_cnn_train_slab(void) { return kSlab; }
+
+int64_t ofp_cnn_train_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val) {
+    Plan p;
+    if (make_plan(cfg, n, n_val, p)) return -1;
+    return p.bytes;
+}
+
+int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                  const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                  int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                  float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream) {
+    Plan p;
+    if (int rc = make_plan(cfg, n, n_val, p)) return rc;
+    OFP_REQUIRE(num_epochs >= 1 && min_epochs >= 0, "ofp_cnn_train: num_epochs %d, min_epochs %d", num_epochs,
+                min_epochs);
+    OFP_REQUIRE(d_x && d_y && d_rates && d_params && d_train_loss && h_epochs, "ofp_cnn_train: NULL argument");
+    OFP_REQUIRE(p.ns == 0 || d_stats, "ofp_cnn_train: BatchNorm statistics are NULL");
+    OFP_REQUIRE(n_val == 0 || (d_x_val && d_y_val && d_val_loss), "ofp_cnn_train: NULL validation argument");
+    OFP_REQUIRE(patience < 0 || n_val > 0, "ofp_cnn_train: patience needs a validation set");
+    if (int rc = check_ws("ofp_cnn_train", d_ws, ws_bytes, p.bytes)) return rc;
+    const char* mode = getenv("OFP_CNN_GRAPH");
+    const bool plain = mode != nullptr && std::strcmp(mode, "nodes") == 0;
+    hipStream_t st = (hipStream_t)stream;
+    OFP_REQUIRE(plain || st != nullptr,
+                "ofp_cnn_train: the epoch graph cannot be captured on the null stream (pass a created stream, or set "
+                "OFP_CNN_GRAPH=nodes for plain launches)");
+    Run r{&p, (char*)d_ws, d_params, d_stats, nullptr, nullptr, st};
+    r.G = r.at<float>(p.o_G);
+    r.ctl = r.at<Ctl>(p.o_ctl);
+    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, n_val > 0 ? patience : -1,
+                      d_train_loss, d_val_loss};
+    OFP_HIP(hipMemsetAsync(r.at<float>(p.o_M), 0, (size_t)p.np * 4, st));
+    OFP_HIP(hipMemsetAsync(r.at<float>(p.o_V), 0, (size_t)p.np * 4, st));
+    hipLaunchKernelGGL(k_init, dim3(1), dim3(kT), 0, st, r.ctl);
+    OFP_LAUNCH_CHECK("k_init");
+    // the first epoch is launched plainly: it loads every code object, which may not happen during capture
+    if (int rc = enqueue_epoch(r, a)) return rc;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (!plain && num_epochs > 1) {
+        OFP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue_epoch(r, a);
+        const hipError_t ce = hipStreamEndCapture(st, &graph);
+        if (rc != OFP_OK) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return rc;
+        }
+        if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (ie != hipSuccess) {
+            (void)hipGraphDestroy(graph);
+            return ofp::fail(OFP_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+        }
+    }
+    int rc = OFP_OK;
+    Ctl seen{};
+    for (int e = 1; e < num_epochs && rc == OFP_OK; ++e) {
+        if (a.patience >= 0 && e % kCheckEvery == 0) {  // has the device stopped?  (at most once per 64 epochs)
+            hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            if (he != hipSuccess) {
+                rc = ofp::fail(OFP_ERR_HIP, "ofp_cnn_train: %s", hipGetErrorString(he));
+                break;
+            }
+            if (seen.stop) break;
+        }
+        if (exec) {
+            const hipError_t he = hipGraphLaunch(exec, st);
+            if (he != hipSuccess) rc = ofp::fail(OFP_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(he));
+        } else {
+            rc = enqueue_epoch(r, a);
+        }
+    }
+    hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc != OFP_OK) return rc;
+    if (he != hipSuccess) return ofp::fail(OFP_ERR_HIP, "ofp_cnn_train: %s", hipGetErrorString(he));
+    *h_epochs = seen.epoch;
+    return OFP_OK;
+}
+
+int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                       const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                       void* stream) {
+    Plan p;
+    if (int rc = make_plan(cfg, n, 0, p)) return rc;
+    OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cnn_loss_grads: NULL argument");
+    if (int rc = check_ws("ofp_cnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
+    // the trainer's own forward and backward; the running statistics it would update are a scratch copy
+    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream};
+    r.RS = r.at<float>(p.o_RS);
+    OFP_HIP(hipMemsetAsync(r.RS, 0, (size_t)(p.ns > 0 ? p.ns : 1) * 4, r.st));
+    if (int rc = enqueue_forward(r, d_x, d_y, n, true)) return rc;
+    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, (Ctl*)nullptr, r.at<double>(p.o_lpart), n, p.O,
+                       d_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
+    OFP_LAUNCH_CHECK("k_loss_final");
+    return enqueue_backward(r, d_x, n);
+}
+
+int64_t ofp_conv1d_backward_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,
+                                            int32_t padding, int32_t dilation, int32_t groups) {
+    if (check_conv("ofp_conv1d_backward", n, cin, w, cout, k, padding, dilation, groups)) return -1;
+    const int wc = w + 2 * padding - dilation * (k - 1);
+    return (int64_t)cout * (cin / groups * k + 1) * slabs_of(n * wc) * 8;
+}
+
+int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
+                        int32_t k, int32_t padding, int32_t dilation, int32_t groups, const float* d_dz, float* d_dx,
+                        float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
+    const int64_t need = ofp_conv1d_backward_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups);
+    if (need < 0) return OFP_ERR_INVALID;
+    OFP_REQUIRE(d_x && d_w && d_dz && d_dw && d_db, "ofp_conv1d_backward: NULL argument");
+    if (int rc = check_ws("ofp_conv1d_backward", d_ws, ws_bytes, need)) return rc;
+    const Conv c{cin, cout, w, w + 2 * padding - dilation * (k - 1), k, padding, dilation, groups};
+    return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
+}
+
+int64_t ofp_batchnorm_train_workspace_bytes(int64_t n, int32_t C, int32_t w) {
+    if (n < 1 || n > kMaxBatch || C < 1 || C > kMaxCh || w < 1 || w > 2 * kMaxWidth) return -1;
+    return (int64_t)C * slabs_of(n * w) * 2 * 8 + (int64_t)C * 2 * 4;
+}
+
+namespace {
+int check_bn(const char* who, int64_t n, int32_t C, int32_t w, void* d_ws, int64_t ws_bytes) {
+    const int64_t need = ofp_batchnorm_train_workspace_bytes(n, C, w);
+    OFP_REQUIRE(need >= 0, "%s: n %lld, %d channels, width %d (limits: 1..%d, 1..%d, 1..%d)", who, (long long)n, C, w,
+                kMaxBatch, kMaxCh, 2 * kMaxWidth);
+    OFP_REQUIRE(n * w >= 2, "%s: BatchNorm needs more than 1 value per channel", who);
+    return check_ws(who, d_ws, ws_bytes, need);
+}
+}  // namespace
+
+int ofp_batchnorm_train_forward(const float* d_x, int64_t n, int32_t C, int32_t w, const float* d_gamma,
+                                const float* d_beta, double eps, float momentum, float* d_running_mean,
+                                float* d_running_var, float* d_y, float* d_mean, float* d_rstd, void* d_ws,
+                                int64_t ws_bytes, void* stream) {
+    if (int rc = check_bn("ofp_batchnorm_train_forward", n, C, w, d_ws, ws_bytes)) return rc;
+    OFP_REQUIRE(d_x && d_gamma && d_beta && d_running_mean && d_running_var && d_y && d_mean && d_rstd,
+                "ofp_batchnorm_train_forward: NULL argument");
+    OFP_REQUIRE(momentum > 0.0f && momentum <= 1.0f && eps > 0.0, "ofp_batchnorm_train_forward: momentum %g, eps %g",
+                (double)momentum, eps);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = enqueue_bn_stats(nullptr, d_x, n, C, w, OFP_ACT_IDENTITY, eps, momentum, (double*)d_ws, d_mean,
+                                  d_rstd, d_running_mean, d_running_var, st))
+        return rc;
+    Post t{};
+    t.C = C, t.wc = w, t.wo = w, t.act = OFP_ACT_IDENTITY, t.pool = 0, t.mode = 1, t.eps = eps;
+    t.ga = d_gamma, t.be = d_beta, t.mean = d_mean, t.rs = d_rstd;
+    hipLaunchKernelGGL(k_post, dim3(grid_for(n * C * w)), dim3(kT), 0, st, (const Ctl*)nullptr, t, n, d_x, d_y);
+    OFP_LAUNCH_CHECK("k_post");
+    return OFP_OK;
+}
+
+int ofp_batchnorm_train_backward(const float* d_x, int64_t n, int32_t C, int32_t w, const float* d_gamma,
+                                 const float* d_mean, const float* d_rstd, const float* d_dy, float* d_dx,
+                                 float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (int rc = check_bn("ofp_batchnorm_train_backward", n, C, w, d_ws, ws_bytes)) return rc;
+    OFP_REQUIRE(d_x && d_gamma && d_mean && d_rstd && d_dy && d_dx && d_dgamma && d_dbeta,
+                "ofp_batchnorm_train_backward: NULL argument");
+    Post t{};
+    t.C = C, t.wc = w, t.wo = w, t.act = OFP_ACT_IDENTITY, t.pool = 0, t.mode = 1;
+    t.ga = d_gamma, t.be = d_gamma /* not read by the backward */, t.mean = d_mean, t.rs = d_rstd;
+    float* s12 = reinterpret_cast<float*>((char*)d_ws + (int64_t)C * slabs_of(n * w) * 2 * 8);
+    return enqueue_post_bwd(nullptr, t, n, d_x, d_dy, (double*)d_ws, s12, d_dgamma, d_dbeta, d_dx,
+                            (hipStream_t)stream);
+}
+
+int ofp_nadam_step(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, const float* d_row, void* stream) {
+    OFP_REQUIRE(d_p && d_g && d_m && d_v && d_row && n >= 1, "ofp_nadam_step: NULL argument or n < 1");
+    hipLaunchKernelGGL(k_nadam, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, (const Ctl*)nullptr, d_row, d_p,
+                       d_g, d_m, d_v, n);
+    OFP_LAUNCH_CHECK("k_nadam");
+    return OFP_OK;
+}
+
+}  // extern "C"

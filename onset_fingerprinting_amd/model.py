@@ -6,17 +6,22 @@ so its ``state_dict`` loads unchanged.  ``forward`` is inference-only (eval sema
 BatchNorm on its running statistics) and runs as HIP kernels (csrc/ofp_nn.hip, csrc/ofp_xcorr.hip,
 csrc/ofp_rnn.hip); torch only allocates memory and makes views.  ``rnn_forward`` runs a torch
 ``nn.GRU`` / ``nn.LSTM`` / ``nn.RNN`` module (its full output sequence) on the same kernels.
-Lightning training steps and optimisers are out of scope.
+``fit_cnn`` trains a ``CNN`` in place with the recipe of its ``training_step`` / ``configure_optimizers``
+(full batch, NAdam, cosine warm restarts every 250 epochs) as one graph of HIP kernels per epoch
+(csrc/ofp_cnn_train.hip).  Training the other classes is out of scope.
 """
 import ctypes
+import functools
+from types import SimpleNamespace
 
+import numpy as np
 import torch
 from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
 from ._lib import check
-from .calibration import ACT_CODES, dense_forward
+from .calibration import ACT_CODES, _loss_code, dense_forward
 
 
 def _stream(dev):
@@ -125,6 +130,14 @@ class CNN(nn.Module):
         h = h.reshape(h.shape[0], -1)
         h = dense_forward(h, to(self.fc.weight), to(self.fc.bias), None, None, 0)
         return h if x.is_cuda else h.cpu()
+
+    def configure_optimizers(self):
+        """model.py:146-162: NAdam at ``self.lr`` and cosine warm restarts every 250 epochs, stepped once per epoch.
+        ``fit_cnn`` builds its per-epoch tables from the same two torch classes."""
+        optimizer = torch.optim.NAdam(self.parameters(), lr=self.lr)
+        scheduler = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(optimizer, 250, 1)
+        return {"optimizer": optimizer,
+                "lr_scheduler": {"scheduler": scheduler, "monitor": "val_loss", "frequency": 1}}
 
 
 def paired_xcorr(x: torch.Tensor, C: int, K: int) -> torch.Tensor:
@@ -452,3 +465,347 @@ class CNNRNN(nn.Module):
         _rnn_into(self.rnn, h, out, to)  # time axis = the conv channels
         y = attention_mean_head(out, self.attention, self.fc, to)
         return y if x.is_cuda else y.cpu()
+
+
+# ---- training model.CNN (model.py:122-162, train.py) ---------------------------------------------------------------
+CNN_TRAIN_MAX_LAYERS, CNN_TRAIN_MAX_CHANNELS, CNN_TRAIN_MAX_KERNEL = 3, 128, 8  # csrc/ofp_cnn_train.hip
+CNN_TRAIN_MAX_WIDTH, CNN_TRAIN_MAX_BATCH, CNN_TRAIN_MAX_OUT = 512, 1024, 16
+
+
+@functools.lru_cache(maxsize=256)
+def cnn_rates(lr, num_epochs):
+    """The learning rate of every epoch of CNN.configure_optimizers(): torch's own CosineAnnealingWarmRestarts(T_0 =
+    250, T_mult = 1) stepped once per epoch on a dummy parameter.  float64 [num_epochs]."""
+    p = nn.Parameter(torch.zeros(1))
+    opt = torch.optim.NAdam([p], lr=lr)
+    sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, 250, 1)
+    opt.step()
+    rates = np.empty(num_epochs, np.float64)
+    for e in range(num_epochs):
+        rates[e] = float(opt.param_groups[0]["lr"])
+        sched.step()
+    rates.setflags(write=False)
+    return rates
+
+
+def cnn_rate_table(lr, num_epochs):
+    """float64 [num_epochs][5]: lr_t, mu_t, mu_{t+1}, mu_product_t and bias_correction2_t of torch.optim.NAdam's
+    defaults (betas 0.9 / 0.999, momentum_decay 0.004), computed as _single_tensor_nadam computes them: Python
+    doubles, except the running mu_product, which torch keeps in a tensor of its scalar dtype (float32 unless the
+    default dtype is float64) and multiplies by mu_t there."""
+    rates = cnn_rates(float(lr), int(num_epochs))
+    scalar = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
+    mu_product = torch.tensor(1.0, dtype=scalar)
+    table = np.empty((num_epochs, 5), np.float64)
+    for e in range(num_epochs):
+        step = float(e + 1)
+        bias_correction2 = 1 - 0.999 ** step
+        mu = 0.9 * (1.0 - 0.5 * (0.96 ** (step * 0.004)))
+        mu_next = 0.9 * (1.0 - 0.5 * (0.96 ** ((step + 1) * 0.004)))
+        mu_product *= mu
+        table[e] = rates[e], mu, mu_next, mu_product.item(), bias_correction2
+    return table
+
+
+def cnn_step_factors(table):
+    """Rows of cnn_rate_table -> float64 [n][3]: the factor of g / denom, the factor of exp_avg / denom, and
+    bias_correction2, as _single_tensor_nadam forms them in double."""
+    lr, mu, mu_next, mu_product, bc2 = np.asarray(table, np.float64).T
+    return np.stack([-lr * (1.0 - mu) / (1.0 - mu_product), (-lr * mu_next) / (1.0 - mu_product * mu_next), bc2], 1)
+
+
+def _cnn_device_rows(lr, num_epochs):
+    """float32 [num_epochs][4] for ofp_cnn_train: cnn_step_factors rounded once, and a pad."""
+    rows = np.zeros((num_epochs, 4), np.float32)
+    rows[:, :3] = cnn_step_factors(cnn_rate_table(lr, num_epochs))
+    return rows
+
+
+def _cnn_arch(model, width=None):
+    """(CnnConfig, convs, batch norms) of a CNN for the trainer; ValueError for what it cannot run."""
+    if model.dropout.p > 0:
+        raise ValueError(f"dropout_rate {model.dropout.p} cannot be trained on the GPU: torch's dropout stream cannot "
+                         "be matched (construct the model with dropout_rate=0.0)")
+    loss = _loss_code(model.loss)
+    mods = list(model.conv_layers)
+    convs = [m for m in mods if isinstance(m, nn.Conv1d)]
+    bns = [m for m in mods if isinstance(m, nn.BatchNorm1d)]
+    pools = [m for m in mods if isinstance(m, nn.MaxPool1d)]
+    acts = [m for m in mods if not isinstance(m, (nn.Conv1d, nn.BatchNorm1d, nn.MaxPool1d))]
+    codes = set()
+    for a in acts:
+        if type(a) not in ACT_CODES:
+            raise ValueError(f"activation {type(a).__name__} has no HIP implementation")
+        codes.add(ACT_CODES[type(a)])
+    if len(acts) != len(convs) or len(codes) != 1:
+        raise ValueError("every Conv1d must be followed by one and the same activation")
+    if not 1 <= len(convs) <= CNN_TRAIN_MAX_LAYERS:
+        raise ValueError(f"{len(convs)} conv layers: the trainer's limit is 1..{CNN_TRAIN_MAX_LAYERS}")
+    if len(bns) not in (0, len(convs)) or len(pools) not in (0, len(convs)):
+        raise ValueError("BatchNorm1d / MaxPool1d must follow every Conv1d or none")
+    c0 = convs[0]
+    key = lambda m: (m.kernel_size, m.stride, m.padding, m.dilation, m.groups, m.padding_mode, m.bias is not None)
+    if any(key(m) != key(c0) for m in convs) or c0.stride != (1,) or c0.padding_mode != "zeros" or c0.bias is None \
+            or not isinstance(c0.padding[0], int):
+        raise ValueError("the Conv1d layers must share kernel size, padding, dilation and groups, with stride 1, "
+                         "zero padding and a bias")
+    if any(m.kernel_size != 2 or m.stride != 2 or m.padding != 0 or m.dilation != 1 or m.ceil_mode for m in pools):
+        raise ValueError("only MaxPool1d(kernel_size=2, stride=2) is trained")
+    for m in bns:
+        if m.momentum is None:
+            raise ValueError("BatchNorm1d(momentum=None), the cumulative average, is not trained on the GPU")
+        if not (m.affine and m.track_running_stats) or (m.eps, m.momentum) != (bns[0].eps, bns[0].momentum):
+            raise ValueError("the BatchNorm1d layers must be affine, track running statistics and share eps and "
+                             "momentum")
+    channels = [c0.in_channels] + [m.out_channels for m in convs]
+    if max(channels) > CNN_TRAIN_MAX_CHANNELS:
+        raise ValueError(f"{max(channels)} channels: the trainer's limit is {CNN_TRAIN_MAX_CHANNELS}")
+    k = c0.kernel_size[0]
+    if k > CNN_TRAIN_MAX_KERNEL:
+        raise ValueError(f"kernel size {k}: the trainer's limit is {CNN_TRAIN_MAX_KERNEL}")
+    if model.fc.out_features > CNN_TRAIN_MAX_OUT or model.fc.bias is None:
+        raise ValueError(f"the Linear head needs a bias and at most {CNN_TRAIN_MAX_OUT} outputs")
+    cfg = _lib.CnnConfig()
+    cfg.n_conv = len(convs)
+    for i, c in enumerate(channels):
+        cfg.channels[i] = c
+    cfg.kernel, cfg.padding, cfg.dilation, cfg.groups = k, c0.padding[0], c0.dilation[0], c0.groups
+    cfg.act, cfg.batch_norm, cfg.pool, cfg.loss = codes.pop(), int(bool(bns)), int(bool(pools)), loss
+    cfg.n_out = model.fc.out_features
+    cfg.bn_momentum, cfg.bn_eps = (bns[0].momentum, bns[0].eps) if bns else (0.1, 1e-5)
+    if width is not None:
+        if not 1 <= width <= CNN_TRAIN_MAX_WIDTH:
+            raise ValueError(f"window of {width} samples: the trainer's limit is 1..{CNN_TRAIN_MAX_WIDTH}")
+        cfg.width = w = width
+        for _ in convs:
+            w = w + 2 * cfg.padding - cfg.dilation * (k - 1)
+            w = w // 2 if pools else w
+            if w < 1:
+                raise ValueError(f"a window of {width} samples leaves no column after the conv layers")
+        if channels[-1] * w != model.fc.in_features:
+            raise ValueError(f"a window of {width} samples gives {channels[-1] * w} features; the model's Linear "
+                             f"expects {model.fc.in_features}")
+    return cfg, convs, bns
+
+
+def _cnn_tensors(model):
+    """[(state_dict name, tensor)] of the parameters in packing order, and the running statistics likewise."""
+    _cfg, convs, bns = _cnn_arch(model)
+    names = {id(m): n for n, m in model.conv_layers.named_children()}
+    ps, st = [], []
+    for i, conv in enumerate(convs):
+        n = "conv_layers." + names[id(conv)]
+        ps += [(n + ".weight", conv.weight), (n + ".bias", conv.bias)]
+        if bns:
+            b = "conv_layers." + names[id(bns[i])]
+            ps += [(b + ".weight", bns[i].weight), (b + ".bias", bns[i].bias)]
+            st += [(b + ".running_mean", bns[i].running_mean), (b + ".running_var", bns[i].running_var)]
+    ps += [("fc.weight", model.fc.weight), ("fc.bias", model.fc.bias)]
+    return ps, st
+
+
+def _flat(tensors, dev):
+    if not tensors:
+        return torch.zeros(1, dtype=torch.float32, device=dev)
+    return torch.cat([t.detach().reshape(-1).to(dev, torch.float32) for _n, t in tensors]).contiguous()
+
+
+def _cnn_batch(model, x, y, what="x"):
+    x, y = torch.as_tensor(x), torch.as_tensor(y)
+    if x.dim() != 3 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)}: expected [n, channels, width] and [n, outputs]")
+    if not 1 <= x.shape[0] <= CNN_TRAIN_MAX_BATCH:
+        raise ValueError(f"{x.shape[0]} windows: the trainer's limit is 1..{CNN_TRAIN_MAX_BATCH} (one full batch)")
+    cfg, _c, bns = _cnn_arch(model, int(x.shape[2]))
+    if x.shape[1] != cfg.channels[0] or y.shape[1] != cfg.n_out:
+        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)} do not fit a model of {cfg.channels[0]} "
+                         f"channels and {cfg.n_out} outputs")
+    if bns and x.shape[0] * (x.shape[2] + 2 * cfg.padding - cfg.dilation * (cfg.kernel - 1)) < 2:
+        raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
+    return x, y, cfg
+
+
+def _train_device(model, x):
+    if x.is_cuda:
+        return x.device
+    p = model.fc.weight
+    return p.device if p.is_cuda else torch.device("cuda", 0)
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+def cnn_loss_and_grads_device(model, x, y):
+    """Loss (``model.loss``) and the gradient of every parameter of a CNN for the full batch x [n, channels, width],
+    y [n, outputs], in training mode (BatchNorm on batch statistics; the module's running statistics are not
+    touched), by the trainer's own forward and backward kernels.  Returns (loss, {state_dict name: gradient}) on
+    the GPU."""
+    x, y, cfg = _cnn_batch(model, x, y)
+    dev = _train_device(model, x)
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ps, _st = _cnn_tensors(model)
+    p0 = _flat(ps, dev)
+    xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grads = torch.empty_like(p0)
+    n = int(xd.shape[0])
+    ws_bytes = int(L.ofp_cnn_train_workspace_bytes(ctypes.byref(cfg), n, 0))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ws = _workspace(ws_bytes, dev)
+    with torch.cuda.device(dev):
+        check(L.ofp_cnn_loss_grads(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(), loss.data_ptr(),
+                                   grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)), "ofp_cnn_loss_grads")
+    named, o = {}, 0
+    for name, t in ps:
+        named[name] = grads[o:o + t.numel()].reshape(t.shape)
+        o += t.numel()
+    return loss[0], named
+
+
+def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None):
+    """Train a ``CNN`` in place, as ``Trainer.fit(model, ...)`` does with the reference's recipe (model.py:122-162,
+    train.py): the whole of x [n, channels, width] / y [n, outputs] is one batch; every epoch is one training-mode
+    forward, ``model.loss`` (F.l1_loss or F.mse_loss), backward and one NAdam step at the learning rate of
+    CosineAnnealingWarmRestarts(250, 1) starting from ``model.lr``; then, with a validation set, an eval-mode forward
+    of x_val and its L1 loss (the reference's validation_step always uses F.l1_loss).  One epoch is one launch of a
+    captured graph of HIP kernels; the optimiser state starts fresh at every call, as a new Trainer's does.
+
+    Stop rule (``patience`` given; needs the validation set): Lightning's EarlyStopping(monitor="val_loss",
+    mode="min", patience=patience) with min_delta 0, restated here because Lightning is not installed: an epoch whose
+    validation loss is not below the best so far counts towards patience, a lower loss resets the count; training ends
+    after the epoch at which the count reaches patience, but not before min_epochs epochs have run.
+
+    Parameters, BatchNorm running statistics and num_batches_tracked of `model` are updated where they live (CPU or
+    GPU) and the model is left in eval mode.  Returns a record with ``train_loss`` and ``val_loss`` (or None): float32
+    GPU tensors [max_epochs], NaN beyond the epochs run; ``epochs``: epochs run; ``lrs``: float64 [epochs].
+
+    ValueError, before anything runs on the GPU: dropout_rate > 0, a loss other than F.l1_loss / F.mse_loss, an
+    activation without HIP implementation, BatchNorm1d(momentum=None), shapes beyond the limits (3 conv layers, 128
+    channels, kernel 8, window 512, batch 1024, 16 outputs)."""
+    x, y, cfg = _cnn_batch(model, x, y)
+    have_val = x_val is not None or y_val is not None
+    if have_val:
+        if x_val is None or y_val is None:
+            raise ValueError("x_val and y_val go together")
+        x_val, y_val, cfg_v = _cnn_batch(model, x_val, y_val, "x_val")
+        if cfg_v.width != cfg.width:
+            raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
+    max_epochs, min_epochs = int(max_epochs), int(min_epochs)
+    if max_epochs < 1 or min_epochs < 0:
+        raise ValueError("max_epochs must be at least 1 and min_epochs at least 0")
+    if patience is not None and (not have_val or int(patience) < 0):
+        raise ValueError("patience needs x_val / y_val and must not be negative")
+    lr = float(model.lr)
+
+    dev = _train_device(model, x)
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ps, st = _cnn_tensors(model)
+    params, stats = _flat(ps, dev), _flat(st, dev)
+    to = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    xd, yd = to(x), to(y)
+    xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
+    rows = torch.from_numpy(_cnn_device_rows(lr, max_epochs)).to(dev)
+    train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
+    val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
+    n, nv = int(xd.shape[0]), int(xv.shape[0]) if have_val else 0
+    ws_bytes = int(L.ofp_cnn_train_workspace_bytes(ctypes.byref(cfg), n, nv))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ws = _workspace(ws_bytes, dev)
+    epochs = ctypes.c_int32(0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    # the epoch graph is captured on a stream of its own (the null stream cannot be captured); the call returns
+    # after that stream has drained
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(cur)
+    with torch.cuda.device(dev):
+        check(L.ofp_cnn_train(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                              rows.data_ptr(), max_epochs, min_epochs, -1 if patience is None else int(patience),
+                              params.data_ptr(), stats.data_ptr(), train_loss.data_ptr(), ptr(val_loss),
+                              ctypes.byref(epochs), ws.data_ptr(), ws_bytes, ctypes.c_void_p(side.cuda_stream)),
+              "ofp_cnn_train")
+    cur.wait_stream(side)
+    with torch.no_grad():
+        for flat, tensors in ((params, ps), (stats, st)):
+            o = 0
+            for _name, t in tensors:
+                t.copy_(flat[o:o + t.numel()].reshape(t.shape))
+                o += t.numel()
+        for m in model.conv_layers:
+            if isinstance(m, nn.BatchNorm1d):
+                m.num_batches_tracked += epochs.value
+    model.eval()
+    return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
+                           lrs=np.array(cnn_rates(lr, max_epochs)[:epochs.value]))
+
+
+def conv1d_backward(x, weight, dz, padding, dilation, groups=1, *, dx=None, dw=None, db=None, need_dx=True):
+    """The three gradients of a stride-1 Conv1d (ofp_conv1d_backward) on float32 CUDA tensors: x [n, cin, w], weight
+    [cout, cin / groups, k], dz [n, cout, wc] -> (dx or None, dw, db); preallocated outputs may be passed."""
+    L = _lib.lib()
+    n, cin, w = x.shape
+    cout, _, k = weight.shape
+    dev = x.device
+    ws_bytes = int(L.ofp_conv1d_backward_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    if need_dx and dx is None:
+        dx = torch.empty_like(x)
+    dw = torch.empty_like(weight) if dw is None else dw
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if db is None else db
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_conv1d_backward(x.data_ptr(), n, cin, w, weight.data_ptr(), cout, k, padding, dilation, groups,
+                                dz.data_ptr(), dx.data_ptr() if need_dx else None, dw.data_ptr(), db.data_ptr(),
+                                ws.data_ptr(), ws_bytes, _stream(dev)), "ofp_conv1d_backward")
+    return (dx if need_dx else None), dw, db
+
+
+def batchnorm_train_forward(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, *, out=None):
+    """BatchNorm1d in training mode on float32 CUDA x [n, C, w]: -> (y, mean, rstd); running_mean / running_var are
+    updated in place (the variance written is the unbiased one)."""
+    L = _lib.lib()
+    n, C, w = x.shape
+    dev = x.device
+    ws_bytes = int(L.ofp_batchnorm_train_workspace_bytes(n, C, w))
+    if ws_bytes < 0:
+        raise ValueError(f"n {n}, {C} channels, width {w}: beyond the BatchNorm kernels' limits")
+    y = torch.empty_like(x) if out is None else out
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    rstd = torch.empty(C, dtype=torch.float32, device=dev)
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_batchnorm_train_forward(x.data_ptr(), n, C, w, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                        float(momentum), running_mean.data_ptr(), running_var.data_ptr(),
+                                        y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws_bytes,
+                                        _stream(dev)), "ofp_batchnorm_train_forward")
+    return y, mean, rstd
+
+
+def batchnorm_train_backward(x, gamma, mean, rstd, dy, *, out=None):
+    """Backward of batchnorm_train_forward: -> (dx, dgamma, dbeta)."""
+    L = _lib.lib()
+    n, C, w = x.shape
+    dev = x.device
+    ws_bytes = int(L.ofp_batchnorm_train_workspace_bytes(n, C, w))
+    if ws_bytes < 0:
+        raise ValueError(f"n {n}, {C} channels, width {w}: beyond the BatchNorm kernels' limits")
+    dx = torch.empty_like(x) if out is None else out
+    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_batchnorm_train_backward(x.data_ptr(), n, C, w, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                         dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                         ws.data_ptr(), ws_bytes, _stream(dev)), "ofp_batchnorm_train_backward")
+    return dx, dgamma, dbeta
+
+
+def nadam_step(p, g, m, v, row):
+    """One NAdam step in place on float32 CUDA tensors p, m, v with gradient g; row: float32 CUDA [>= 3] =
+    cnn_step_factors of the step, rounded."""
+    check(_lib.lib().ofp_nadam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
+                                    row.data_ptr(), _stream(p.device)), "ofp_nadam_step")
+    return p
