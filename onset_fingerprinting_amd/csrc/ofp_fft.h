@@ -8,6 +8,7 @@
 // one frame, so a 1024-point frame is exactly one 64-lane wavefront.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "ofp_common.h"
 
@@ -208,6 +209,20 @@ struct Cfg {
     // (k_stft_power keeps half the window, see build_half_window)
     static constexpr size_t lds_bytes_half_window = (size_t)(M + M + 2) * 8 + (size_t)(F / 2 + 4) * 4 + (size_t)FPW * MP * 8;
 };
+
+// The transform lengths the kernels are instantiated for, listed here and nowhere else:
+// f(std::integral_constant<int, F>()) for n_fft == F (f returns an OFP_* code), the refusal for any other length.
+template <class Fn>
+int with_n_fft(int n_fft, Fn f) {
+    switch (n_fft) {
+        case 256: return f(std::integral_constant<int, 256>());
+        case 512: return f(std::integral_constant<int, 512>());
+        case 1024: return f(std::integral_constant<int, 1024>());
+        case 2048: return f(std::integral_constant<int, 2048>());
+        case 4096: return f(std::integral_constant<int, 4096>());
+    }
+    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", n_fft);
+}
 
 template <int F>
 __device__ __forceinline__ void build_tables(float2* twM, float2* twF, float* win, int frame_length) {

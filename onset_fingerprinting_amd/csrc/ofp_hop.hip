@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ofp_detector.h"
@@ -62,7 +63,7 @@ struct StrengthArgs {
 
 struct HopArgs {
     StrengthArgs sg;
-    int C, B, n_mels, nnz, mean_mode;
+    int C, B, n_mels, nnz;
     int64_t R;             // rows of the ring buffer
     int64_t* ctl;          // [0] hops pushed so far (incremented by k_hop_begin), [1] spare
     const float* hop;      // [B][C] the hop just uploaded
@@ -108,6 +109,72 @@ struct HopCfg {
     static constexpr int WGS = T < 64 ? 64 : T;
 };
 
+// The dynamic LDS of the two bodies below is laid out once each, by a constructor that walks a cursor: LdsCarve hands
+// out the pointers (the body), LdsSize only adds up (ofp_hop_create).
+struct LdsCarve {
+    unsigned char* p;
+    template <class T, class N>
+    __device__ T* take(N n) {
+        T* at = reinterpret_cast<T*>(p);
+        p = reinterpret_cast<unsigned char*>(at + n);
+        return at;
+    }
+    __device__ void align16() { p = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 15) & ~(uintptr_t)15); }
+};
+struct LdsSize {
+    size_t bytes = 0;
+    template <class T, class N>
+    T* take(N n) {
+        bytes += (size_t)n * sizeof(T);
+        return nullptr;
+    }
+    void align16() { bytes += 16; }  // (room for the rounding, whatever the base)
+};
+
+template <int F>
+struct SpectralLds {
+    float2 *twM, *twF, *A;
+    float *win, *fw, *partial, *mprm, *tileA, *tileB, *hcol;
+    int32_t *flo, *flen, *foff;
+    MelSegs* segs;
+    template <class Cursor>
+    __host__ __device__ SpectralLds(Cursor& c, int nnz, int n_mels, const MlpPlan& plan, int B) {
+        constexpr int M = F / 2;
+        twM = c.template take<float2>(M);
+        twF = c.template take<float2>(M + 2);
+        win = c.template take<float>(F);
+        A = c.template take<float2>(FftBuf<M>::words);
+        fw = c.template take<float>(nnz);
+        flo = c.template take<int32_t>(n_mels);
+        flen = c.template take<int32_t>(n_mels);
+        foff = c.template take<int32_t>(n_mels);
+        c.align16();
+        segs = c.template take<MelSegs>(1);
+        partial = c.template take<float>(MEL_MAXSEG);
+        mprm = c.template take<float>((plan.n_params + 3) & ~3);
+        tileA = c.template take<float>(16 * plan.st_a);
+        tileB = c.template take<float>(16 * plan.st_b);
+        hcol = c.template take<float>(B);  // [B] this channel's column of the hop
+    }
+};
+
+template <int F>
+struct StrengthLds {
+    float2 *twM, *twF, *A;
+    float *hbuf, *red, *y, *tg;
+    template <class Cursor>
+    __host__ __device__ StrengthLds(Cursor& c, int B, int C, int tg_len) {
+        constexpr int M = F / 2;
+        twM = c.template take<float2>(M);
+        twF = c.template take<float2>(M + 2);
+        A = c.template take<float2>(FftBuf<M>::words);
+        hbuf = c.template take<float>((size_t)B * C);  // [B][C] the hop
+        red = c.template take<float>(64);              // reduction slots: one per wave, and the dB floor
+        y = c.template take<float>(tg_len);            // tempogram: [W] windowed envelope, then [W] the raw lags
+        tg = c.template take<float>(tg_len);
+    }
+};
+
 // One channel's share of a hop: ring write, Hann x trailing n_fft samples, rFFT, |X|^2, mel bands and the
 // classifier.  Executed by one workgroup of WGS lanes (WGS == T when a frame needs more than one wave:
 // the FFT passes then synchronise with workgroup barriers); h = hops pushed including this one.
@@ -115,55 +182,43 @@ template <int F, int WGS>
 __device__ __forceinline__ void hop_spectral_body(const HopArgs& a, int c, int64_t h, unsigned char* smem) {
     constexpr int M = HopCfg<F>::M, T = HopCfg<F>::T;
     static_assert(T <= 64 ? WGS >= 64 : WGS == T, "lanes of a multi-wave frame must be the whole workgroup");
-    float2* twM = reinterpret_cast<float2*>(smem);
-    float2* twF = twM + M;
-    float* win = reinterpret_cast<float*>(twF + M + 2);
-    float2* A = reinterpret_cast<float2*>(win + F);
-    float* fw = reinterpret_cast<float*>(A + FftBuf<M>::words);
-    int32_t* flo = reinterpret_cast<int32_t*>(fw + a.nnz);
-    int32_t* flen = flo + a.n_mels;
-    int32_t* foff = flen + a.n_mels;
-    MelSegs* segs = reinterpret_cast<MelSegs*>((reinterpret_cast<uintptr_t>(foff + a.n_mels) + 15) & ~(uintptr_t)15);
-    float* partial = reinterpret_cast<float*>(segs + 1);
-    float* mprm = partial + MEL_MAXSEG;
-    float* tileA = mprm + ((a.plan.n_params + 3) & ~3);
-    float* tileB = tileA + 16 * a.plan.st_a;
-    float* hcol = tileB + 16 * a.plan.st_b;  // [B] this channel's column of the hop
+    LdsCarve carve{smem};
+    const SpectralLds<F> l(carve, a.nnz, a.n_mels, a.plan, a.B);
     const int C = a.C, B = a.B;
     const int tid = threadIdx.x;
     // the hop may live in pinned host memory: every sample is fetched exactly once
-    for (int t = tid; t < B; t += WGS) hcol[t] = a.hop[(int64_t)t * C + c];
+    for (int t = tid; t < B; t += WGS) l.hcol[t] = a.hop[(int64_t)t * C + c];
     // tables, filterbank and classifier parameters: L2-resident copies -> LDS
-    for (int k = tid; k < M; k += WGS) twM[k] = a.twM[k];
-    for (int k = tid; k <= M; k += WGS) twF[k] = a.twF[k];
-    for (int n = tid; n < F; n += WGS) win[n] = a.win[n];
-    for (int i = tid; i < a.nnz; i += WGS) fw[i] = a.fw[i];
+    for (int k = tid; k < M; k += WGS) l.twM[k] = a.twM[k];
+    for (int k = tid; k <= M; k += WGS) l.twF[k] = a.twF[k];
+    for (int n = tid; n < F; n += WGS) l.win[n] = a.win[n];
+    for (int i = tid; i < a.nnz; i += WGS) l.fw[i] = a.fw[i];
     for (int i = tid; i < a.n_mels; i += WGS) {
-        flo[i] = a.flo[i];
-        flen[i] = a.flen[i];
-        foff[i] = a.foff[i];
+        l.flo[i] = a.flo[i];
+        l.flen[i] = a.flen[i];
+        l.foff[i] = a.foff[i];
     }
-    for (int i = tid; i < a.plan.n_params; i += WGS) mprm[i] = a.plan.params[i];
+    for (int i = tid; i < a.plan.n_params; i += WGS) l.mprm[i] = a.plan.params[i];
     if (a.plan.n_layers > 0)
-        for (int i = tid; i < 16 * a.plan.st_a; i += WGS) tileA[i] = 0.0f;
-    if (tid == 0) mel_build_segs(segs, a.flen, a.n_mels);
+        for (int i = tid; i < 16 * a.plan.st_a; i += WGS) l.tileA[i] = 0.0f;
+    if (tid == 0) mel_build_segs(l.segs, a.flen, a.n_mels);
     const int64_t first = (h - 1) * B;  // stream index of this hop's first sample
     __syncthreads();
     // ring-buffer write of this channel's column (realtime/audio.py:97)
-    for (int t = tid; t < B; t += WGS) a.ring[((first + t) % a.R) * C + c] = hcol[t];
+    for (int t = tid; t < B; t += WGS) a.ring[((first + t) % a.R) * C + c] = l.hcol[t];
     // trailing n_fft samples of the stream (realtime/recording.py:276: audio[-n_fft:]); samples before
     // the stream started read as the zeros the ring was created with
     const int64_t base = h * B - F;
     auto sample = [&](int64_t s) -> float {
         if (s < 0) return 0.0f;
-        if (s >= first) return hcol[s - first];
+        if (s >= first) return l.hcol[s - first];
         return a.ring[(s % a.R) * C + c];
     };
     for (int p = tid; p < M; p += WGS)
-        A[fft_pad<M>(p)] = make_float2(sample(base + 2 * p) * win[2 * p], sample(base + 2 * p + 1) * win[2 * p + 1]);
+        l.A[fft_pad<M>(p)] = make_float2(sample(base + 2 * p) * l.win[2 * p], sample(base + 2 * p + 1) * l.win[2 * p + 1]);
     __syncthreads();
     if (tid < T) {
-        cfft<M, T>(A, twM, tid);
+        cfft<M, T>(l.A, l.twM, tid);
         // the same paired power bins, LDS staging and band sums as k_stft_power (bit-identical to its frame)
         constexpr int NQ = (M / 2) / T + 1;
         float pa[NQ], pb[NQ];
@@ -171,10 +226,10 @@ __device__ __forceinline__ void hop_spectral_body(const HopArgs& a, int c, int64
         for (int q = 0; q < NQ; ++q) {
             const int pp = tid + q * T;
             pa[q] = pb[q] = 0.0f;
-            if (pp <= M / 2) rfft_power_pair<M>(A, twF, pp, pa[q], pb[q]);
+            if (pp <= M / 2) rfft_power_pair<M>(l.A, l.twF, pp, pa[q], pb[q]);
         }
         frame_sync<T>();  // every bin of the spectrum has been read
-        float* pf = reinterpret_cast<float*>(A);
+        float* pf = reinterpret_cast<float*>(l.A);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int pp = tid + q * T;
@@ -184,17 +239,17 @@ __device__ __forceinline__ void hop_spectral_body(const HopArgs& a, int c, int64
             }
         }
         frame_sync<T>();
-        mel_bands(segs, pf, fw, flo, flen, foff, a.n_mels, tid, T, partial, [] { frame_sync<T>(); },
+        mel_bands(l.segs, pf, l.fw, l.flo, l.flen, l.foff, a.n_mels, tid, T, l.partial, [] { frame_sync<T>(); },
                   [&](int b, float acc) {
                       a.mel[c * a.n_mels + b] = acc;
-                      if (a.plan.n_layers > 0) tileA[b] = acc;  // row 0 of the classifier's tile
+                      if (a.plan.n_layers > 0) l.tileA[b] = acc;  // row 0 of the classifier's tile
                   });
     }
     if (a.plan.n_layers > 0) {
         __syncthreads();
         if (tid < 64) {
             const int nout = a.plan.dims[a.plan.n_layers];
-            ofp_mlp_tile(a.plan, mprm, tileA, tileB, tid, [&](int r, int col, float v) {
+            ofp_mlp_tile(a.plan, l.mprm, l.tileA, l.tileB, tid, [&](int r, int col, float v) {
                 if (r == 0) a.logits[c * nout + col] = v;
             });
         }
@@ -207,22 +262,20 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
     constexpr int M = HopCfg<F>::M, T = HopCfg<F>::T;
     static_assert(T <= 64 ? WGS >= 64 : WGS == T, "lanes of a multi-wave frame must be the whole workgroup");
     const StrengthArgs& g = a.sg;
-    float2* twM = reinterpret_cast<float2*>(smem);
-    float2* twF = twM + M;
-    float2* A = twF + M + 2;
-    float* hbuf = reinterpret_cast<float*>(A + FftBuf<M>::words);   // [B][C] the hop
-    float* red = hbuf + (size_t)a.B * a.C;            // [WGS / 64 + 2]
+    static_assert(WGS / 64 + 2 <= 64, "one reduction slot per wave and the dB floor");
+    LdsCarve carve{smem};
+    const StrengthLds<F> l(carve, a.B, a.C, g.tg_len);
     const int C = a.C, B = a.B, tid = threadIdx.x;
-    for (int k = tid; k < M; k += WGS) twM[k] = a.twM[k];
-    for (int k = tid; k <= M; k += WGS) twF[k] = a.twF[k];
-    for (int i = tid; i < B * C; i += WGS) hbuf[i] = a.hop[i];
+    for (int k = tid; k < M; k += WGS) l.twM[k] = a.twM[k];
+    for (int k = tid; k <= M; k += WGS) l.twF[k] = a.twF[k];
+    for (int i = tid; i < B * C; i += WGS) l.hbuf[i] = a.hop[i];
     __syncthreads();
     const int64_t first = (h - 1) * B, base = h * B - F;
     auto mean_sample = [&](int64_t s) -> float {  // audio[-n_fft:].mean(-1): float32 sum in channel order, then / C
         if (s < 0) return 0.0f;
         float m = 0.0f;
         if (s >= first) {
-            for (int c = 0; c < C; ++c) m += hbuf[(s - first) * C + c];
+            for (int c = 0; c < C; ++c) m += l.hbuf[(s - first) * C + c];
         } else {
             const float* r = a.ring + (s % a.R) * C;
             for (int c = 0; c < C; ++c) m += r[c];
@@ -230,20 +283,20 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
         return m / (float)C;
     };
     for (int p = tid; p < M; p += WGS)
-        A[fft_pad<M>(p)] = make_float2(g.wsym[2 * p] * mean_sample(base + 2 * p), g.wsym[2 * p + 1] * mean_sample(base + 2 * p + 1));
+        l.A[fft_pad<M>(p)] = make_float2(g.wsym[2 * p] * mean_sample(base + 2 * p), g.wsym[2 * p + 1] * mean_sample(base + 2 * p + 1));
     __syncthreads();
     constexpr int NK = M / T + 1;
     float pw[NK], sdb[NK];
     float smax = -INFINITY;
     if (tid < T) {
-        cfft<M, T>(A, twM, tid);
+        cfft<M, T>(l.A, l.twM, tid);
 #pragma unroll
         for (int q = 0; q < NK; ++q) {
             const int k = tid + q * T;
             pw[q] = 0.0f;
             sdb[q] = -INFINITY;
             if (k <= M) {
-                const float2 X = rfft_bin<M>(A, twF, k);
+                const float2 X = rfft_bin<M>(l.A, l.twF, k);
                 pw[q] = X.x * X.x + X.y * X.y;
                 sdb[q] = 10.0f * log10f(fmaxf(1e-10f, pw[q]));   // :290
                 smax = fmaxf(smax, sdb[q]);
@@ -252,19 +305,19 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
     }
     // block maximum of the dB spectrum -> the tracked maximum (:291), floor 80 dB below it (:292-294)
     for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o));
-    if ((tid & 63) == 0) red[tid >> 6] = smax;
+    if ((tid & 63) == 0) l.red[tid >> 6] = smax;
     __syncthreads();
     if (tid == 0) {
-        float m = red[0];
-        for (int w = 1; w < (WGS + 63) / 64; ++w) m = fmaxf(m, red[w]);
+        float m = l.red[0];
+        for (int w = 1; w < (WGS + 63) / 64; ++w) m = fmaxf(m, l.red[w]);
         float ls = g.st[0];
         ls = m > ls ? m : (1.0f - g.ls_alpha) * ls + g.ls_alpha * m;
         ls = fmaxf(ls, g.ls_minmax);
         g.st[0] = ls;
-        red[WGS / 64 + 1] = ls - 80.0f;
+        l.red[WGS / 64 + 1] = ls - 80.0f;
     }
     __syncthreads();
-    const float floor_db = red[WGS / 64 + 1];
+    const float floor_db = l.red[WGS / 64 + 1];
     float fsum = 0.0f;
     if (tid < T) {
 #pragma unroll
@@ -280,11 +333,11 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
     }
     for (int o = 32; o > 0; o >>= 1) fsum += __shfl_xor(fsum, o);
     __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = fsum;
+    if ((tid & 63) == 0) l.red[tid >> 6] = fsum;
     __syncthreads();
     if (tid == 0) {
         float sum = 0.0f;
-        for (int w = 0; w < (WGS + 63) / 64; ++w) sum += red[w];
+        for (int w = 0; w < (WGS + 63) / 64; ++w) sum += l.red[w];
         const float oe = sum / (float)(M + 1);
         float mn = g.st[1], mx = g.st[2];
         mx = oe > mx ? oe : (1.0f - g.oe_alpha) * mx + g.oe_alpha * oe;   // :299 add_sample
@@ -312,15 +365,15 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
         vsum += __shfl_xor(vsum, o);
     }
     if ((tid & 63) == 0) {
-        red[tid >> 6] = vmax;
-        hbuf[tid >> 6] = vsum;
+        l.red[tid >> 6] = vmax;
+        l.hbuf[tid >> 6] = vsum;
     }
     __syncthreads();
     if (tid == 0) {
-        float m = red[0], sm = hbuf[0];
+        float m = l.red[0], sm = l.hbuf[0];
         for (int w = 1; w < (WGS + 63) / 64; ++w) {
-            m = fmaxf(m, red[w]);
-            sm += hbuf[w];
+            m = fmaxf(m, l.red[w]);
+            sm += l.hbuf[w];
         }
         g.out[2] = m;
         g.out[3] = sm / (float)g.avg_length;
@@ -332,35 +385,33 @@ __device__ __forceinline__ void hop_strength_body(const HopArgs& a, int64_t h, u
     // to the same thread: W + 1 products each.  PARITY UNPINNED like the envelope it reads.
     if (g.tg_len > 0) {
         const int W = g.tg_len;
-        float* y = red + 64;   // [W] windowed envelope, then [W] the raw lags (LDS reserved by ofp_hop_create)
-        float* tg = y + W;
         for (int i = tid; i < W; i += WGS) {
             const int64_t e = h - W + i;   // onset_env[-W + i]; entries before the stream started are the ring's zeros
-            y[i] = e >= 0 ? g.tgw[i] * g.ring[e % g.n_ring] : 0.0f;
+            l.y[i] = e >= 0 ? g.tgw[i] * g.ring[e % g.n_ring] : 0.0f;
         }
         __syncthreads();
         float mx = -INFINITY;
         for (int k = tid; 2 * k < W; k += WGS) {
             const int k2 = W - 1 - k;
             float a0 = 0.0f, a1 = 0.0f;
-            for (int i = 0; i + k < W; ++i) a0 = fmaf(y[i], y[i + k], a0);
+            for (int i = 0; i + k < W; ++i) a0 = fmaf(l.y[i], l.y[i + k], a0);
             if (k2 != k)
-                for (int i = 0; i + k2 < W; ++i) a1 = fmaf(y[i], y[i + k2], a1);
-            tg[k] = a0;
+                for (int i = 0; i + k2 < W; ++i) a1 = fmaf(l.y[i], l.y[i + k2], a1);
+            l.tg[k] = a0;
             mx = fmaxf(mx, a0);
             if (k2 != k) {
-                tg[k2] = a1;
+                l.tg[k2] = a1;
                 mx = fmaxf(mx, a1);
             }
         }
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
         __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = mx;
+        if ((tid & 63) == 0) l.red[tid >> 6] = mx;
         __syncthreads();
-        float m = red[0];
-        for (int w = 1; w < (WGS + 63) / 64; ++w) m = fmaxf(m, red[w]);
+        float m = l.red[0];
+        for (int w = 1; w < (WGS + 63) / 64; ++w) m = fmaxf(m, l.red[w]);
         const float den = m + 1e-10f;
-        for (int k = tid; k < W; k += WGS) g.out[4 + k] = tg[k] / den;
+        for (int k = tid; k < W; k += WGS) g.out[4 + k] = l.tg[k] / den;
     }
 }
 
@@ -391,10 +442,6 @@ struct HopLocArgs {
     HopLocBlock* out;
 };
 
-inline size_t hop_loc_lds(int nthreads, const ofp::LocTables& T, int B, int C) {
-    return ofp::loc_lds_bytes(nthreads, T.max_section, T.plan) + (size_t)B * C * 4;
-}
-
 // detect_hits' loop (realtime/audio.py:62-74) for one hop, by one workgroup: the hop's n records sorted by onset
 // (np.argsort; ties keep record order), each fed to locate with counter = h * B until one returns a position.  Rows
 // of the current hop come from the hop buffer (other workgroups are writing the ring during a fused launch), older
@@ -407,7 +454,7 @@ __device__ __forceinline__ void hop_locate_stage(const HopArgs& a, const HopLocA
     const int tid = threadIdx.x, nt = blockDim.x;
     const int C = a.C, B = a.B;
     const ofp::LocView v = ofp::loc_carve(smem, nt, T.max_section, T.plan);
-    float* hopbuf = v.tb + (T.plan.n_layers > 0 ? 16 * T.plan.st_b : 0);
+    float* hopbuf = v.extra;  // [B][C] the hop
     n = n < C ? n : C;
     __syncthreads();  // the detector is done with this LDS
     ofp::loc_load(T, v, la.state);
@@ -473,10 +520,12 @@ struct FusedCfg {
     static constexpr int WGS = HopCfg<F>::T <= 64 ? 256 : HopCfg<F>::T;
 };
 
+// Everything a workgroup of the fused hop does, from the read of the hop counter to the completion word; the
+// arguments are the caller's (kernel arguments or a group's device arrays), never copies.
 // LOC: the instantiation of a session with a locator; without one the kernel is the one it always was.
 template <int F, bool LOC>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la) {
-    extern __shared__ __align__(16) unsigned char smem[];
+__device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream::StreamArgs& sa, const HopLocArgs& la,
+                                               unsigned char* smem) {
     const int64_t done = a.ctl[0];  // hops completed before this one
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) *a.hop_index = done;
@@ -499,7 +548,7 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpst
     if (threadIdx.x == 0) {
         __threadfence_system();  // (orders the ticket after the barrier's view of the other waves' fences)
         const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctl + 1), 1ull);
-        if (t == gridDim.x - 1) {  // every workgroup has read ctl[0] and published its results
+        if (t == gridDim.x - 1) {  // every workgroup (gridDim.x of them) has read ctl[0] and published its results
             a.ctl[1] = 0;
             a.ctl[0] = done + 1;
             __threadfence_system();
@@ -508,52 +557,26 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpst
     }
 }
 
+template <int F, bool LOC>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    hop_fused_body<F, LOC>(a, sa, la, smem);
+}
+
 // S sessions' hops in ONE launch: grid (C + 1 + strength, S), row blockIdx.y is member blockIdx.y of an
-// ofp_hop_group.  A workgroup takes its member's three argument structs from the group's device arrays (uniform,
-// read-only addresses: scalar loads, as for kernel arguments) and runs what k_hop_fused runs for that member -- the
-// same branch on blockIdx.x, the same fences, the member's own ticket, counter and completion word.  Members share
-// nothing and no workgroup waits for another, so a grid larger than the device simply queues.  n_fft, the channel
-// count, and whether a locator / the onset strength is on fix the instantiation and gridDim.x: a group's members
-// agree on these four.  dry != 0: every workgroup returns at once (the un-captured launch at group creation that
-// loads the code and sets the dynamic-LDS attribute must not touch a member's state).
+// ofp_hop_group and runs hop_fused_body on that member's three argument structs in the group's device arrays
+// (uniform, read-only addresses: scalar loads, as for kernel arguments) -- the member's own ticket, counter and
+// completion word.  Members share nothing and no workgroup waits for another, so a grid larger than the device simply
+// queues.  n_fft, the channel count, and whether a locator / the onset strength is on fix the instantiation and
+// gridDim.x: a group's members agree on these four.  dry != 0: every workgroup returns at once (the un-captured launch
+// at group creation that loads the code and sets the dynamic-LDS attribute must not touch a member's state).
 template <int F, bool LOC>
 __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group(const HopArgs* __restrict__ args,
                                                                       const ofpstream::StreamArgs* __restrict__ sargs,
                                                                       const HopLocArgs* __restrict__ largs, int dry) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (dry) return;
-    const HopArgs& a = args[blockIdx.y];
-    const int64_t done = a.ctl[0];  // hops this member completed before this one
-    if (blockIdx.x == 0) {
-        const ofpstream::StreamArgs& sa = sargs[blockIdx.y];
-        if (threadIdx.x == 0) *a.hop_index = done;
-        if constexpr (LOC) {
-            const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
-            if (n_on > 0) {
-                const HopLocArgs& la = largs[blockIdx.y];
-                hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
-            }
-        } else {
-            ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
-        }
-    } else if ((int)blockIdx.x <= a.C) {
-        hop_spectral_body<F, FusedCfg<F>::WGS>(a, (int)blockIdx.x - 1, done + 1, smem);
-    } else {
-        hop_strength_body<F, FusedCfg<F>::WGS>(a, done + 1, smem);
-    }
-    // the completion handshake of k_hop_fused, per member: gridDim.x workgroups take a ticket
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence_system();
-        const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long*>(a.ctl + 1), 1ull);
-        if (t == gridDim.x - 1) {
-            a.ctl[1] = 0;
-            a.ctl[0] = done + 1;
-            __threadfence_system();
-            *a.done_flag = done + 1;
-        }
-    }
+    hop_fused_body<F, LOC>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], smem);
 }
 
 }  // namespace
@@ -589,6 +612,8 @@ struct ofp_hop_session {
     HopArgs args;
     ofpstream::StreamArgs sargs;  // fused form: the detector workgroup's arguments
     bool fused = false;
+    int threads = 256;  // of the workgroup that runs the detector and the locator (fused form: the fused kernel's)
+    unsigned char* res_dev = nullptr;  // the result block as the kernels address it (point_results)
     size_t lds_fused = 0;
     size_t lds = 0;
     int64_t pushed = 0;   // hops submitted
@@ -622,6 +647,8 @@ struct ofp_hop_group {
 
 namespace {
 
+// Every launch goes through ensure_dynamic_lds with a cache of its own instantiation: the attribute is set by the
+// un-captured first pass (capture_hop, group_build) and found in the cache during capture, where it may not be set.
 template <int F>
 int hop_tables(ofp_hop_session* s) {
     hipLaunchKernelGGL(k_hop_tables<F>, dim3(1), dim3(256), 0, s->stream, s->d_twM, s->d_twF, s->d_win, s->d_wsym);
@@ -631,9 +658,8 @@ int hop_tables(ofp_hop_session* s) {
 
 template <int F>
 int hop_spectral(ofp_hop_session* s) {
-    if (s->lds > 65536)
-        OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hop_spectral<F>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_spectral<F>), s->lds, attr)) return rc;
     hipLaunchKernelGGL(k_hop_spectral<F>, dim3((unsigned)s->C), dim3(HopCfg<F>::WGS), s->lds, s->stream, s->args);
     OFP_LAUNCH_CHECK("k_hop_spectral");
     return OFP_OK;
@@ -641,84 +667,32 @@ int hop_spectral(ofp_hop_session* s) {
 
 template <int F>
 int hop_strength(ofp_hop_session* s) {
-    if (s->lds_strength > 65536)
-        OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hop_strength<F>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_strength));
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_strength<F>), s->lds_strength, attr)) return rc;
     hipLaunchKernelGGL(k_hop_strength<F>, dim3(1), dim3(HopCfg<F>::WGS), s->lds_strength, s->stream, s->args);
     OFP_LAUNCH_CHECK("k_hop_strength");
     return OFP_OK;
 }
 
-int dispatch_strength(ofp_hop_session* s) {
-    switch (s->n_fft) {
-        case 256: return hop_strength<256>(s);
-        case 512: return hop_strength<512>(s);
-        case 1024: return hop_strength<1024>(s);
-        case 2048: return hop_strength<2048>(s);
-        case 4096: return hop_strength<4096>(s);
-    }
-    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", s->n_fft);
-}
+constexpr size_t FUSED_LDS_THRESHOLD = 65536 - 20480;  // (the detector's static LDS comes on top)
 
-template <int F>
+template <int F, bool LOC>
 int hop_fused(ofp_hop_session* s) {
-    auto launch = [&](auto kernel) -> int {
-        if (s->lds_fused > 65536 - 20480)  // (the detector's static LDS comes on top)
-            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)s->lds_fused));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)), dim3(FusedCfg<F>::WGS),
-                           s->lds_fused, s->stream, s->args, s->sargs, s->largs);
-        return OFP_OK;
-    };
-    if (int rc = s->largs.enabled ? launch(k_hop_fused<F, true>) : launch(k_hop_fused<F, false>)) return rc;
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused<F, LOC>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused<F, LOC>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
+                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->largs);
     OFP_LAUNCH_CHECK("k_hop_fused");
     return OFP_OK;
 }
 
-int fused_threads(int n_fft) {
-    switch (n_fft) {
-        case 2048: return FusedCfg<2048>::WGS;
-        case 4096: return FusedCfg<4096>::WGS;
-        default: return 256;
-    }
-}
-
-int dispatch_fused(ofp_hop_session* s) {
-    switch (s->n_fft) {
-        case 256: return hop_fused<256>(s);
-        case 512: return hop_fused<512>(s);
-        case 1024: return hop_fused<1024>(s);
-        case 2048: return hop_fused<2048>(s);
-        case 4096: return hop_fused<4096>(s);
-    }
-    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", s->n_fft);
-}
-
-int dispatch_tables(ofp_hop_session* s) {
-    switch (s->n_fft) {
-        case 256: return hop_tables<256>(s);
-        case 512: return hop_tables<512>(s);
-        case 1024: return hop_tables<1024>(s);
-        case 2048: return hop_tables<2048>(s);
-        case 4096: return hop_tables<4096>(s);
-    }
-    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", s->n_fft);
-}
-
-int dispatch_spectral(ofp_hop_session* s) {
-    switch (s->n_fft) {
-        case 256: return hop_spectral<256>(s);
-        case 512: return hop_spectral<512>(s);
-        case 1024: return hop_spectral<1024>(s);
-        case 2048: return hop_spectral<2048>(s);
-        case 4096: return hop_spectral<4096>(s);
-    }
-    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", s->n_fft);
-}
-
 // the per-hop sequence, enqueued on the session's stream (captured once, then replayed)
 int enqueue_hop(ofp_hop_session* s) {
-    if (s->fused) return dispatch_fused(s);  // one kernel: no copy nodes, no begin kernel
+    if (s->fused)  // one kernel: no copy nodes, no begin kernel
+        return with_n_fft(s->n_fft, [&](auto f) {
+            constexpr int F = decltype(f)::value;
+            return s->largs.enabled ? hop_fused<F, true>(s) : hop_fused<F, false>(s);
+        });
     OFP_HIP(hipMemcpyAsync(s->d_hop, s->h_hop, (size_t)s->B * s->C * sizeof(float), hipMemcpyHostToDevice, s->stream));
     hipLaunchKernelGGL(k_hop_begin, dim3(1), dim3(64), 0, s->stream, s->args);
     OFP_LAUNCH_CHECK("k_hop_begin");
@@ -728,19 +702,18 @@ int enqueue_hop(ofp_hop_session* s) {
                                 reinterpret_cast<int64_t*>(s->d_res + s->o_count), s->stream);
     if (rc != OFP_OK) return rc;
     if (s->largs.enabled) {  // (before the spectral node: the ring holds the older hops only)
-        if (s->lds_loc > 65536)
-            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hop_locate),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_loc));
+        static ofp::LdsAttrCache attr;
+        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_locate), s->lds_loc, attr)) != OFP_OK) return rc;
         hipLaunchKernelGGL(k_hop_locate, dim3(1), dim3(256), s->lds_loc, s->stream, s->args, s->largs,
                            reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
         OFP_LAUNCH_CHECK("k_hop_locate");
     }
     if (s->args.sg.enabled) {  // (before the spectral node: it reads ring rows the spectral node is about to overwrite
                                //  only for hops older than the ring, never the current one)
-        rc = dispatch_strength(s);
+        rc = with_n_fft(s->n_fft, [&](auto f) { return hop_strength<decltype(f)::value>(s); });
         if (rc != OFP_OK) return rc;
     }
-    rc = dispatch_spectral(s);
+    rc = with_n_fft(s->n_fft, [&](auto f) { return hop_spectral<decltype(f)::value>(s); });
     if (rc != OFP_OK) return rc;
     OFP_HIP(hipMemcpyAsync(s->h_res, s->d_res, (size_t)s->res_bytes, hipMemcpyDeviceToHost, s->stream));
     return OFP_OK;
@@ -764,6 +737,19 @@ int reset_state(ofp_hop_session* s) {
     return OFP_OK;
 }
 
+// What `enqueue` puts on the stream, as an instantiated graph.  The capture is ended whatever enqueue returns (a
+// stream left capturing is of no use to anyone); enqueue's result is returned only after that.
+template <class Enqueue>
+int capture_graph(hipStream_t stream, Enqueue enqueue, hipGraph_t* graph, hipGraphExec_t* exec) {
+    OFP_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    const hipError_t ce = hipStreamEndCapture(stream, graph);
+    if (rc != OFP_OK) return rc;
+    if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    OFP_HIP(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
+    return OFP_OK;
+}
+
 // one un-captured pass over zeros loads every code object and sets the kernel attributes
 // (neither may happen during capture), then the state is reset and the sequence captured
 int capture_hop(ofp_hop_session* s) {
@@ -776,13 +762,24 @@ int capture_hop(ofp_hop_session* s) {
     if (s->graph) (void)hipGraphDestroy(s->graph);
     s->exec = nullptr;
     s->graph = nullptr;
-    OFP_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    rc = enqueue_hop(s);
-    hipError_t ce = hipStreamEndCapture(s->stream, &s->graph);
-    if (rc != OFP_OK) return rc;
-    if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-    OFP_HIP(hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
-    return OFP_OK;
+    return capture_graph(s->stream, [&] { return enqueue_hop(s); }, &s->graph, &s->exec);
+}
+
+// The kernel arguments' pointers into the result block at `base`: d_res, or the mapped h_res as the device sees it
+// (fused form, which alone has the detector's arguments and the completion word).
+void point_results(ofp_hop_session* s, unsigned char* base) {
+    HopArgs& a = s->args;
+    s->res_dev = base;
+    a.logits = reinterpret_cast<float*>(base + s->o_logits);
+    a.mel = reinterpret_cast<float*>(base + s->o_mel);
+    a.count = reinterpret_cast<int64_t*>(base + s->o_count);
+    a.hop_index = reinterpret_cast<int64_t*>(base + s->o_index);
+    if (a.sg.enabled) a.sg.out = reinterpret_cast<float*>(base + s->o_sg);
+    if (base == s->d_res) return;
+    a.done_flag = reinterpret_cast<volatile int64_t*>(base + s->o_done);
+    s->sargs.rel = s->want_rel ? reinterpret_cast<float*>(base + s->o_rel) : nullptr;
+    s->sargs.records = reinterpret_cast<ofp_onset*>(base + s->o_rec);
+    s->sargs.count = a.count;
 }
 
 // the stream the session's last hop was launched to
@@ -798,34 +795,30 @@ int retire_last_hop(ofp_hop_session* s) {
     return OFP_OK;
 }
 
+// The fused kernel's last workgroup publishes the hop count after every result: poll it instead of paying the
+// stream synchronisation's wake-up.  Bounded: an error or a lost launch falls through to the synchronisation of
+// `stream` (*synced, when given, says that it came to that).
+int wait_done(const ofp_hop_session* s, hipStream_t stream, bool* synced = nullptr) {
+    const volatile int64_t* flag = reinterpret_cast<const volatile int64_t*>(s->h_res + s->o_done);
+    for (int spin = 0; spin < 2000000 && *flag != s->pushed; ++spin) __builtin_ia32_pause();
+    const bool late = *flag != s->pushed;
+    if (late) OFP_HIP(hipStreamSynchronize(stream));
+    if (synced) *synced = late;
+    return OFP_OK;
+}
+
 #define OFP_NOT_IN_GROUP(s, what)                                                                                  \
     OFP_REQUIRE(!(s)->owner, what ": the session is a member of an ofp_hop_group (its hops go through "            \
                                   "ofp_hop_group_submit; ofp_hop_group_destroy releases it)")
 
-template <int F>
+template <int F, bool LOC>
 int hop_group_launch(ofp_hop_group* g, int dry) {
-    auto launch = [&](auto kernel) -> int {
-        if (dry && g->lds > 65536 - 20480)  // (the detector's static LDS comes on top)
-            OFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)g->lds));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)g->grid_x, (unsigned)g->members.size()), dim3(FusedCfg<F>::WGS), g->lds,
-                           g->stream, g->d_args, g->d_sargs, g->d_largs, dry);
-        return OFP_OK;
-    };
-    if (int rc = g->loc ? launch(k_hop_fused_group<F, true>) : launch(k_hop_fused_group<F, false>)) return rc;
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group<F, LOC>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_group<F, LOC>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
+                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_largs, dry);
     OFP_LAUNCH_CHECK("k_hop_fused_group");
     return OFP_OK;
-}
-
-int dispatch_group(ofp_hop_group* g, int dry) {
-    switch (g->n_fft) {
-        case 256: return hop_group_launch<256>(g, dry);
-        case 512: return hop_group_launch<512>(g, dry);
-        case 1024: return hop_group_launch<1024>(g, dry);
-        case 2048: return hop_group_launch<2048>(g, dry);
-        case 4096: return hop_group_launch<4096>(g, dry);
-    }
-    return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", g->n_fft);
 }
 
 void group_free(ofp_hop_group* g) {
@@ -861,15 +854,15 @@ int group_build(ofp_hop_group* g) {
     for (ofp_hop_session* s : g->members)
         if (int rc = retire_last_hop(s)) return rc;
     // code loading and the kernel attribute may not happen during capture: one launch that touches nothing
-    if (int rc = dispatch_group(g, 1)) return rc;
+    auto launch = [&](int dry) {
+        return with_n_fft(g->n_fft, [&](auto f) {
+            constexpr int F = decltype(f)::value;
+            return g->loc ? hop_group_launch<F, true>(g, dry) : hop_group_launch<F, false>(g, dry);
+        });
+    };
+    if (int rc = launch(1)) return rc;
     OFP_HIP(hipStreamSynchronize(g->stream));
-    OFP_HIP(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = dispatch_group(g, 0);
-    const hipError_t ce = hipStreamEndCapture(g->stream, &g->graph);
-    if (rc != OFP_OK) return rc;
-    if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-    OFP_HIP(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
-    return OFP_OK;
+    return capture_graph(g->stream, [&] { return launch(0); }, &g->graph, &g->exec);
 }
 
 }  // namespace
@@ -897,8 +890,25 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     OFP_REQUIRE(det && cfg && out, "ofp_hop_create: NULL argument");
     const int C = det->p.n_channels, B = det->p.block_size;
     OFP_REQUIRE(C <= 1024, "ofp_hop_create: at most 1024 channels (got %d)", C);
-    OFP_REQUIRE(cfg->n_fft == 256 || cfg->n_fft == 512 || cfg->n_fft == 1024 || cfg->n_fft == 2048 || cfg->n_fft == 4096,
-                "n_fft %d not supported (256,512,1024,2048,4096)", cfg->n_fft);
+    MlpPlan plan;
+    std::memset(&plan, 0, sizeof(plan));
+    if (cfg->mlp) plan = cfg->mlp->plan;
+    size_t lds = 0, lds_strength = 0;  // of the spectral and the strength workgroup
+    int fused_threads = 0;
+    if (int rc = with_n_fft(cfg->n_fft, [&](auto f) {
+            constexpr int F = decltype(f)::value;
+            fused_threads = FusedCfg<F>::WGS;
+            LdsSize spectral, strength;
+            SpectralLds<F>(spectral, cfg->fb_nnz, cfg->n_mels, plan, B);
+            lds = spectral.bytes + 64;  // (sizing slack)
+            if (cfg->strength) {
+                StrengthLds<F>(strength, B, C, cfg->tg_win_length);
+                lds_strength = strength.bytes + (F > 1024 ? F / 4 : 0);  // (padding no frame above 1024 has, but
+                                                                         //  earlier versions counted: no total shrinks)
+            }
+            return OFP_OK;
+        }))
+        return rc;
     OFP_REQUIRE(cfg->ring_samples >= cfg->n_fft && cfg->ring_samples >= B,
                 "ofp_hop_create: the ring buffer (%lld rows) must hold n_fft = %d and one hop = %d samples",
                 (long long)cfg->ring_samples, cfg->n_fft, B);
@@ -916,6 +926,8 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     OFP_REQUIRE(!cfg->mlp || cfg->mlp->plan.dims[0] == cfg->n_mels,
                 "ofp_hop_create: the classifier takes %d inputs, the filterbank has %d bands",
                 cfg->mlp ? cfg->mlp->plan.dims[0] : 0, cfg->n_mels);
+    OFP_REQUIRE(lds <= 160 * 1024, "ofp_hop_create: %zu bytes of LDS needed, 160 KiB available", lds);
+    OFP_REQUIRE(lds_strength <= 160 * 1024, "ofp_hop_create: the hop (%d x %d samples) does not fit the LDS", B, C);
     ofp_hop_session* s = new (std::nothrow) ofp_hop_session();
     if (!s) return ofp::fail(OFP_ERR_INVALID, "out of host memory");
     s->det = det;
@@ -925,9 +937,6 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     s->n_mels = cfg->n_mels;
     s->R = cfg->ring_samples;
     s->want_rel = cfg->want_rel ? 1 : 0;
-    MlpPlan plan;
-    std::memset(&plan, 0, sizeof(plan));
-    if (cfg->mlp) plan = cfg->mlp->plan;
     s->n_out = cfg->mlp ? plan.dims[plan.n_layers] : 0;
     auto up8 = [](int64_t v) { return (v + 7) / 8 * 8; };
     s->o_logits = up8(s->o_rec + (int64_t)C * (int64_t)sizeof(ofp_onset));
@@ -937,18 +946,13 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     s->o_loc = up8(s->o_sg + 16 + (cfg->strength ? 4 * (int64_t)cfg->tg_win_length : 0));
     s->res_bytes = up8(s->o_loc + (int64_t)sizeof(HopLocBlock));
     const int M = s->n_fft / 2;
-    const int st_a = cfg->mlp ? plan.st_a : 0, st_b = cfg->mlp ? plan.st_b : 0;
-    s->lds = (size_t)(M + M + 2) * 8 + (size_t)s->n_fft * 4 + (size_t)(M <= 512 ? M + M / 16 : M) * 8 + (size_t)cfg->fb_nnz * 4 +
-             (size_t)3 * s->n_mels * 4 + 16 + sizeof(MelSegs) + (size_t)MEL_MAXSEG * 4 + (size_t)((plan.n_params + 3) & ~3) * 4 + (size_t)16 * (st_a + st_b) * 4 + (size_t)B * 4 + 64;
+    s->lds = lds;
+    s->lds_strength = lds_strength;
     int rc = OFP_OK;
     auto fail = [&](int code) {
         ofp_hop_destroy(s);
         return code;
     };
-    if (s->lds > 160 * 1024) {
-        ofp_hop_destroy(s);
-        return ofp::fail(OFP_ERR_INVALID, "ofp_hop_create: %zu bytes of LDS needed, 160 KiB available", s->lds);
-    }
 #define HOP_TRY(call)                                                                                           \
     do {                                                                                                        \
         hipError_t e__ = (call);                                                                                \
@@ -1003,10 +1007,6 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     a.foff = s->d_fb_i + 2 * s->n_mels;
     a.fw = s->d_fb_w;
     a.plan = plan;
-    a.logits = reinterpret_cast<float*>(s->d_res + s->o_logits);
-    a.mel = reinterpret_cast<float*>(s->d_res + s->o_mel);
-    a.count = reinterpret_cast<int64_t*>(s->d_res + s->o_count);
-    a.hop_index = reinterpret_cast<int64_t*>(s->d_res + s->o_index);
     if (cfg->strength) {
         const int bins = s->n_fft / 2 + 1;
         s->sg_floats = (size_t)bins + 4 + (size_t)cfg->strength_ring;
@@ -1024,11 +1024,9 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
         g.prev = s->d_sg;
         g.st = s->d_sg + bins;
         g.ring = s->d_sg + bins + 4;
-        g.out = reinterpret_cast<float*>(s->d_res + s->o_sg);
         s->sg_init[0] = cfg->ls_max0;
         s->sg_init[1] = cfg->oe_min0;
         s->sg_init[2] = cfg->oe_max0;
-        s->lds_strength = (size_t)(3 * M + M / 16 + 2) * 8 + (size_t)B * C * 4 + 64 * 4 + (size_t)2 * cfg->tg_win_length * 4;
         g.tg_len = cfg->tg_win_length;
         g.tgw = nullptr;
         if (cfg->tg_win_length > 0) {  // scipy.signal.windows.hann(W) (symmetric) as float32 (recording.py:250)
@@ -1039,31 +1037,23 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
             HOP_TRY(hipMemcpy(s->d_tgw, w.data(), (size_t)W * 4, hipMemcpyHostToDevice));
             g.tgw = s->d_tgw;
         }
-        if (s->lds_strength > 160 * 1024) {
-            ofp_hop_destroy(s);
-            return ofp::fail(OFP_ERR_INVALID, "ofp_hop_create: the hop (%d x %d samples) does not fit the LDS", B, C);
-        }
     }
     // Fused form (one launch per hop, hop and result block in pinned host memory) whenever the detector
     // fits one workgroup of the fused kernel; OFP_HOP_GRAPH=nodes keeps the five-node graph.
     {
         const char* mode = getenv("OFP_HOP_GRAPH");
         const size_t par_lds = (size_t)3 * B * C * sizeof(float);
-        s->fused = !(mode && mode[0] == 'n') && 2 * C <= fused_threads(s->n_fft) && C <= ofpstream::PAR_MAX_C &&
+        s->fused = !(mode && mode[0] == 'n') && 2 * C <= fused_threads && C <= ofpstream::PAR_MAX_C &&
                    par_lds <= 96 * 1024;
         s->lds_fused = std::max(std::max(s->lds, par_lds), s->lds_strength);
+        point_results(s, s->d_res);
         if (s->fused) {
+            s->threads = fused_threads;
             float* dev_hop = nullptr;
             unsigned char* dev_res = nullptr;
             HOP_TRY(hipHostGetDevicePointer((void**)&dev_hop, s->h_hop, 0));
             HOP_TRY(hipHostGetDevicePointer((void**)&dev_res, s->h_res, 0));
             a.hop = dev_hop;
-            a.logits = reinterpret_cast<float*>(dev_res + s->o_logits);
-            a.mel = reinterpret_cast<float*>(dev_res + s->o_mel);
-            a.count = reinterpret_cast<int64_t*>(dev_res + s->o_count);
-            a.hop_index = reinterpret_cast<int64_t*>(dev_res + s->o_index);
-            if (a.sg.enabled) a.sg.out = reinterpret_cast<float*>(dev_res + s->o_sg);
-            a.done_flag = reinterpret_cast<volatile int64_t*>(dev_res + s->o_done);
             ofpstream::StreamArgs& q = s->sargs;
             q = ofpstream::make_stream_args(det);
             q.state = s->d_state;
@@ -1072,14 +1062,12 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
             q.n_rows = 0;
             q.warmup = 0;
             q.sample_base = 0;
-            q.rel = s->want_rel ? reinterpret_cast<float*>(dev_res + s->o_rel) : nullptr;
-            q.records = reinterpret_cast<ofp_onset*>(dev_res + s->o_rec);
             q.cap = C;
-            q.count = a.count;
             q.fresh_count = 1;
+            point_results(s, dev_res);
         }
     }
-    if ((rc = dispatch_tables(s)) != OFP_OK) return fail(rc);
+    if ((rc = with_n_fft(s->n_fft, [&](auto f) { return hop_tables<decltype(f)::value>(s); })) != OFP_OK) return fail(rc);
     if ((rc = capture_hop(s)) != OFP_OK) return fail(rc);
 #undef HOP_TRY
     *out = s;
@@ -1127,11 +1115,7 @@ int ofp_hop_collect(ofp_hop_session* s, int64_t* n_onsets, ofp_onset* h_records,
     OFP_REQUIRE(s, "ofp_hop_collect: NULL session");
     OFP_REQUIRE(s->in_flight, "ofp_hop_collect: no hop in flight");
     if (s->fused) {
-        // the last workgroup publishes the hop count after every result: poll it instead of paying the
-        // stream synchronisation's wake-up (bounded: an error or a lost launch falls through to the sync)
-        const volatile int64_t* flag = reinterpret_cast<const volatile int64_t*>(s->h_res + s->o_done);
-        for (int spin = 0; spin < 2000000 && *flag != s->pushed; ++spin) __builtin_ia32_pause();
-        if (*flag != s->pushed) OFP_HIP(hipStreamSynchronize(hop_stream(s)));
+        if (int rc = wait_done(s, hop_stream(s))) return rc;
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         s->retired = false;  // the kernel has published its results; it may not have retired from the stream yet
     } else {
@@ -1196,32 +1180,45 @@ int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
     OFP_REQUIRE(!loc->use_audio || s->R >= (int64_t)loc->max_section + s->B,
                 "ofp_hop_set_locator: the ring (%lld rows) must hold the longest section (%d) and one hop (%d)",
                 (long long)s->R, loc->max_section, s->B);
-    const int threads = s->fused ? fused_threads(s->n_fft) : 256;
-    const size_t lds = hop_loc_lds(threads, T, s->B, s->C);
+    const size_t lds = ofp::loc_lds_bytes(s->threads, T.max_section, T.plan, (size_t)s->B * s->C * 4);  // (+ the hop rows)
     OFP_REQUIRE(lds <= 128 * 1024, "ofp_hop_set_locator: %zu bytes of LDS needed", lds);
-    if (loc->mlp) {  // the session keeps its own copy: the handle may be destroyed afterwards
-        OFP_HIP(hipMalloc(&s->d_loc_prm, (size_t)T.plan.n_params * 4));
-        OFP_HIP(hipMemcpy(s->d_loc_prm, loc->mlp->d_params, (size_t)T.plan.n_params * 4, hipMemcpyDeviceToDevice));
-        T.plan.params = s->d_loc_prm;
+    const size_t lds_fused = s->lds_fused;
+    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+        if (loc->mlp) {  // the session keeps its own copy: the handle may be destroyed afterwards
+            OFP_HIP(hipMalloc(&s->d_loc_prm, (size_t)T.plan.n_params * 4));
+            OFP_HIP(hipMemcpy(s->d_loc_prm, loc->mlp->d_params, (size_t)T.plan.n_params * 4, hipMemcpyDeviceToDevice));
+            T.plan.params = s->d_loc_prm;
+        }
+        OFP_HIP(hipMalloc(&s->d_loc_state, sizeof(ofp_locate_state)));
+        OFP_HIP(hipMemset(s->d_loc_state, 0, sizeof(ofp_locate_state)));
+        s->largs.T = T;
+        s->largs.state = s->d_loc_state;
+        s->largs.out = reinterpret_cast<HopLocBlock*>(s->res_dev + s->o_loc);
+        s->lds_loc = lds;
+        if (s->fused) {
+            OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
+            OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
+            s->sargs.mirror = s->d_mirror;
+            s->lds_fused = std::max(s->lds_fused, lds);
+        }
+        s->largs.enabled = 1;
+        return capture_hop(s);
+    };
+    const int rc = attach();
+    if (rc == OFP_OK) return OFP_OK;
+    // the session is again exactly the locator-less one it was, and a later call is accepted
+    const std::string why = ofp::err_buf();
+    void** dev[] = {(void**)&s->d_loc_prm, (void**)&s->d_loc_state, (void**)&s->d_mirror};
+    for (void** p : dev) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
     }
-    OFP_HIP(hipMalloc(&s->d_loc_state, sizeof(ofp_locate_state)));
-    OFP_HIP(hipMemset(s->d_loc_state, 0, sizeof(ofp_locate_state)));
-    s->largs.T = T;
-    s->largs.state = s->d_loc_state;
-    s->lds_loc = lds;
-    if (s->fused) {
-        OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
-        OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
-        s->sargs.mirror = s->d_mirror;
-        unsigned char* dev_res = nullptr;
-        OFP_HIP(hipHostGetDevicePointer((void**)&dev_res, s->h_res, 0));
-        s->largs.out = reinterpret_cast<HopLocBlock*>(dev_res + s->o_loc);
-        s->lds_fused = std::max(s->lds_fused, lds);
-    } else {
-        s->largs.out = reinterpret_cast<HopLocBlock*>(s->d_res + s->o_loc);
-    }
-    s->largs.enabled = 1;
-    return capture_hop(s);
+    std::memset(&s->largs, 0, sizeof(s->largs));
+    s->sargs.mirror = nullptr;
+    s->lds_fused = lds_fused;
+    s->lds_loc = 0;
+    if (!s->exec) (void)capture_hop(s);  // (the failure came after the locator-less graph had been given up)
+    return ofp::fail(rc, "%s", why.c_str());
 }
 
 int ofp_hop_collect_location(ofp_hop_session* s, int32_t* status, double* h_xy, int32_t* n_members,
@@ -1343,12 +1340,9 @@ int ofp_hop_group_wait(ofp_hop_group* g) {
     // microseconds of each other, so the walk costs the slowest member's time, not the sum
     for (ofp_hop_session* s : g->members) {
         if (!s->in_flight) continue;
-        const volatile int64_t* flag = reinterpret_cast<const volatile int64_t*>(s->h_res + s->o_done);
-        for (int spin = 0; spin < 2000000 && *flag != s->pushed; ++spin) __builtin_ia32_pause();
-        if (*flag != s->pushed) {  // an error or a lost launch: the stream tells
-            OFP_HIP(hipStreamSynchronize(g->stream));
-            break;
-        }
+        bool synced = false;
+        if (int rc = wait_done(s, g->stream, &synced)) return rc;
+        if (synced) break;  // (the whole launch has left the stream)
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     return OFP_OK;

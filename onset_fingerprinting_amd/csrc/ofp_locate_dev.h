@@ -102,12 +102,12 @@ struct LocLds {
     int32_t pad;
 };
 
-__host__ __device__ inline size_t loc_lds_bytes(int nthreads, int max_section, const MlpPlan& plan) {
+__host__ __device__ inline size_t loc_lds_bytes(int nthreads, int max_section, const MlpPlan& plan, size_t extra = 0) {
     size_t b = (sizeof(LocLds) + 15) & ~(size_t)15;
     b += (size_t)nthreads * 8;                            // first_legal's slots
     b += (size_t)2 * ((max_section + 3) & ~3) * 4;        // the two section rows
     if (plan.n_layers > 0) b += (size_t)16 * (plan.st_a + plan.st_b) * 4;
-    return b + 16;
+    return b + extra + 16;  // extra: bytes a caller keeps behind all this (LocView::extra)
 }
 
 struct LocView {
@@ -117,6 +117,7 @@ struct LocView {
     float* ys;
     float* ta;
     float* tb;
+    float* extra;  // behind the last tile: the caller's own rows (the hop of csrc/ofp_hop.hip)
 };
 
 __device__ inline LocView loc_carve(unsigned char* smem, int nthreads, int max_section, const MlpPlan& plan) {
@@ -131,6 +132,7 @@ __device__ inline LocView loc_carve(unsigned char* smem, int nthreads, int max_s
     v.ys = v.xs + ms;
     v.ta = v.ys + ms;
     v.tb = v.ta + (plan.n_layers > 0 ? 16 * plan.st_a : 0);
+    v.extra = v.tb + (plan.n_layers > 0 ? 16 * plan.st_b : 0);
     return v;
 }
 

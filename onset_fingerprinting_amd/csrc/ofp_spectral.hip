@@ -545,14 +545,9 @@ static int stft_power_impl(const float* d_x, int64_t n_clips, int64_t n_samples,
     const int64_t H = 1 + (n_samples - n_fft) / hop;
     const int64_t total = n_clips * C * H;
     OFP_REQUIRE(total < (1ll << 31), "ofp_stft_power: %lld frames in one launch (at most 2^31 - 1)", (long long)total);
-    switch (n_fft) {
-        case 256: return launch_power<256>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
-        case 512: return launch_power<512>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
-        case 1024: return launch_power<1024>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
-        case 2048: return launch_power<2048>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
-        case 4096: return launch_power<4096>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
-        default: return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", n_fft);
-    }
+    return with_n_fft(n_fft, [&](auto f) {
+        return launch_power<decltype(f)::value>(d_x, n_samples, C, hop, H, total, d_power, mf, planar, ml, stream);
+    });
 }
 
 int ofp_stft_power(const float* d_x, int64_t n_clips, int64_t n_samples, int32_t C, int32_t n_fft,
@@ -607,14 +602,7 @@ int ofp_stft_frames(const float* d_x, int64_t n_clips, int64_t n_samples, int32_
     a.valid_lo = d_valid_lo; a.valid_hi = d_valid_hi; a.n_frames = n_frames; a.frame_length = frame_length;
     a.window = d_window; a.spec = reinterpret_cast<float2*>(d_spec);
     hipStream_t stream = (hipStream_t)stream_;
-    switch (n_fft) {
-        case 256: return launch_frames<256>(a, stream);
-        case 512: return launch_frames<512>(a, stream);
-        case 1024: return launch_frames<1024>(a, stream);
-        case 2048: return launch_frames<2048>(a, stream);
-        case 4096: return launch_frames<4096>(a, stream);
-        default: return ofp::fail(OFP_ERR_INVALID, "n_fft %d not supported (256,512,1024,2048,4096)", n_fft);
-    }
+    return with_n_fft(n_fft, [&](auto f) { return launch_frames<decltype(f)::value>(a, stream); });
 }
 
 int ofp_extract_frames(const float* d_x, int64_t n_samples, int32_t C, const int64_t* d_start,

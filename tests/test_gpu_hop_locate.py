@@ -314,3 +314,54 @@ def test_refused_calls_and_long_sections_are_reported():
         m.locate_stream_device([0, 1], [5000, 5100], [5128, 11000], audio)
     found, _, ongoing = m.locate_stream_device([0, 1], [5000, 5100], [5128, 5228], audio)  # still usable
     assert not found.any() and len(ongoing) >= 1
+
+
+@pytest.mark.parametrize("form", ["fused", "nodes"])
+def test_a_refused_locator_leaves_the_session_as_it_was(form, monkeypatch):
+    """ofp_hop_set_locator refuses a locator whose network does not fit the workgroup's LDS (an argument check).  The
+    session is still the locator-less one it was, then accepts a valid locator and gives the reference's positions
+    and state hop by hop -- read through the C ABI, as HopSession does for a session created with `locator=`."""
+    import ctypes
+
+    from onset_fingerprinting_amd import _lib, calibration
+    from onset_fingerprinting_amd import multilateration as ml
+    monkeypatch.setenv("OFP_HOP_GRAPH", form)
+    case, mode = "rt3_fast3", "audio"
+    g = g25()
+    sess, m, audio, B = session(case, locator=False)
+    torch.manual_seed(5)
+    wide = calibration.FCNN(2, 2, hidden_layers=[1024, 1024])  # two tiles of 16 x 1025 floats: 128 KiB and a bit
+    wide.eval()
+    m_wide = ml.Multilaterate3D(**json.loads(str(g[f"{case}/args"]))["layout"], model=wide)
+    section = ml.longest_section(m.max_max_lags, B)
+    mlp = m_wide._device_model("test")
+    L = _lib.lib()
+    with torch.cuda.device(sess.device):
+        rc = L.ofp_hop_set_locator(sess.handle, ctypes.byref(m_wide.locator_struct(True, section, mlp)))
+    assert rc != 0 and "bytes of LDS needed" in L.ofp_last_error().decode()
+    assert "location" not in sess(audio[:B])  # still a session without a locator ...
+    sess.reset()
+    with torch.cuda.device(sess.device):  # ... that takes one
+        _lib.check(L.ofp_hop_set_locator(sess.handle, ctypes.byref(m.locator_struct(True, section))),
+                   "ofp_hop_set_locator")
+    hops = {int(h): k for k, h in enumerate(g[f"{case}/hops"])}
+    status, fed, dropped = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    xy, state, located = (ctypes.c_double * 2)(), _lib.LocateState(), 0
+    for h in range(len(audio) // B):
+        r = sess(audio[h * B:(h + 1) * B])
+        k = hops.get(h)
+        if k is None:
+            assert len(r["onsets"]) == 0, h
+            continue
+        n = int(g[f"{case}/n_onsets"][k])
+        assert np.array_equal(r["channels"], g[f"{case}/channels"][k, :n]), h
+        assert np.array_equal(r["onsets"], g[f"{case}/onsets"][k, :n]), h
+        _lib.check(L.ofp_hop_collect_location(sess.handle, ctypes.byref(status), xy, None, None, None,
+                                              ctypes.byref(fed), ctypes.byref(dropped), None), "collect_location")
+        same_location((xy[0], xy[1]) if status.value == 1 else None, g[f"{case}/{mode}/res"][k], h)
+        assert fed.value == g[f"{case}/{mode}/fed"][k] and dropped.value == g[f"{case}/{mode}/dropped"][k], h
+        _lib.check(L.ofp_hop_locator_state(sess.handle, ctypes.byref(state)), "locator_state")
+        assert plain(ml.ongoing_list(state)) == golden_ongoing(g, case, mode, k), h
+        located += status.value == 1
+    assert located == int(g[f"{case}/{mode}/res"][:, 0].sum()) >= 10
+    sess.close()

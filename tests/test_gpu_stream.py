@@ -77,6 +77,10 @@ def check_spectral(got, mel_ref, log_ref):
     # the reference's own realtime setup: 3 ch @ 96 kHz, hop 128, N_FFT 2048 (realtime/config.py:15,24,36,53)
     # with the detector arguments of realtime/audio.py:39-52
     dict(C=3, B=128, sr=96000, F=2048, seconds=2.1, kw="realtime"),
+    # the largest frame, the only one whose workgroup needs more than 64 KiB of dynamic LDS (the top of the LDS
+    # layouts and the kernels' raised limit): 300 hops, so that the 64-hop frame has left the zero prefix and the
+    # ring (two frames and a bit, not a multiple of the hop) has wrapped; hits every 30 ms for a dozen onsets
+    dict(C=2, B=64, sr=48000, F=4096, seconds=0.4, kw={}, period=0.03, ring_rows=2 * 4096 + 17),
 ])
 @pytest.mark.parametrize("graph", ["fused", "nodes"])
 def test_hop_session_matches_the_oracle_hop_by_hop(cfg, graph, monkeypatch):
@@ -89,16 +93,20 @@ def test_hop_session_matches_the_oracle_hop_by_hop(cfg, graph, monkeypatch):
     from onset_fingerprinting_amd.pipeline import seeded_fcnn
     C, B, sr, F = cfg["C"], cfg["B"], cfg["sr"], cfg["F"]
     kw = dict(realtime.REALTIME_DETECTOR_KWARGS) if cfg["kw"] == "realtime" else {}
-    x = synth.drum_hits(C, cfg["seconds"], sr, seed=4, period=0.23)
+    x = synth.drum_hits(C, cfg["seconds"], sr, seed=4, period=cfg.get("period", 0.23))
     clf = seeded_fcnn(40, 8)
-    sess = realtime.HopSession(C, B, sr=sr, n_fft=F, n_mels=40, classifier=clf, want_rel=True, **kw)
+    ring = dict(ring_seconds=cfg["ring_rows"] / sr) if "ring_rows" in cfg else {}
+    sess = realtime.HopSession(C, B, sr=sr, n_fft=F, n_mels=40, classifier=clf, want_rel=True, **ring, **kw)
     okw = {k: v for k, v in kw.items()}
     odet = oracle.OracleDetector(C, B, sr=sr, **okw)
     warm = x[: int(0.1 * sr)]
     sess.init_minmax_tracker(warm)
     odet.init_minmax_tracker(warm)
     got, exp, nb = replay(sess, odet, x, B)
-    assert nb * B >= 2 * sr  # at least two seconds, hop by hop
+    if "ring_rows" not in cfg:
+        assert nb * B >= 2 * sr  # the two stated configurations: at least two seconds, hop by hop
+    else:
+        assert sess.ring_samples == cfg["ring_rows"] and nb * B > 2 * sess.ring_samples >= 4 * F
     assert len(exp["on"]) > 5
     assert got["ch"] == exp["ch"] and got["on"] == exp["on"]
     assert np.array_equal(bits(np.concatenate(got["rel"])), bits(np.concatenate(exp["rel"])))
@@ -196,6 +204,13 @@ def test_phase_split_block_kernel_equals_the_one_lane_per_channel_kernel(kw, mon
     assert np.array_equal(bits(outs[1][0][: k * B]), bits(exp))
 
 
+STRENGTH_SHAPES = [
+    dict(C=3, B=128, sr=96000, F=2048, seconds=0.6, min_hops=400, kw="realtime"),
+    # the strength workgroup's largest layout: the 4096-point frame, the tempogram rows behind the reduction slots
+    dict(C=2, B=64, sr=48000, F=4096, seconds=0.4, min_hops=250, kw={}, tg_win_length=48),
+]
+
+
 @pytest.mark.parametrize("graph", ["fused", "nodes"])
 def test_per_hop_onset_strength_matches_the_oracle_restatement(graph, monkeypatch):
     """N1, second half (realtime/recording.py:273-311): channel-mean frame, dB flux, tracked normalisation,
@@ -204,21 +219,27 @@ def test_per_hop_onset_strength_matches_the_oracle_restatement(graph, monkeypatc
     same assumption at 1e-4 relative (+ 1e-6 absolute for values that are differences of dB terms)."""
     from onset_fingerprinting_amd import realtime
     monkeypatch.setenv("OFP_HOP_GRAPH", graph)
-    C, B, sr, F = 3, 128, 96000, 2048
-    x = synth.drum_hits(C, 0.6, sr, seed=31, period=0.09)
-    sess = realtime.HopSession(C, B, sr=sr, n_fft=F, ring_seconds=1.0, onset_strength=dict(max_length=12, avg_length=40, ring=64),
-                               **realtime.REALTIME_DETECTOR_KWARGS)
-    ref = oracle.HopStrength(F, C, 12, 40, 64)
-    worst = 0.0
-    for i in range(len(x) // B):
-        hop = np.ascontiguousarray(x[i * B:(i + 1) * B])
-        got = sess(hop)["strength"]
-        want = ref(hop)
-        err = np.abs(got - want) / (np.abs(want) + 1e-2)   # (flux values are means of dB differences of O(1))
-        worst = max(worst, float(err.max()))
-        assert err.max() < RTOL, (i, got, want)
-    assert worst > 0 and len(x) // B > 400
-    sess.close()
+    for shape in STRENGTH_SHAPES:
+        C, B, sr, F, W = shape["C"], shape["B"], shape["sr"], shape["F"], shape.get("tg_win_length", 0)
+        kw = dict(realtime.REALTIME_DETECTOR_KWARGS) if shape["kw"] == "realtime" else {}
+        tg = dict(tg_win_length=W) if W else {}
+        x = synth.drum_hits(C, shape["seconds"], sr, seed=31, period=0.09)
+        sess = realtime.HopSession(C, B, sr=sr, n_fft=F, ring_seconds=1.0,
+                                   onset_strength=dict(max_length=12, avg_length=40, ring=64, **tg), **kw)
+        ref = oracle.HopStrength(F, C, 12, 40, 64, **tg)
+        worst = 0.0
+        for i in range(len(x) // B):
+            hop = np.ascontiguousarray(x[i * B:(i + 1) * B])
+            r = sess(hop)
+            got = r["strength"]
+            want = ref(hop)
+            err = np.abs(got - want) / (np.abs(want) + 1e-2)   # (flux values are means of dB differences of O(1))
+            worst = max(worst, float(err.max()))
+            assert err.max() < RTOL, (i, got, want)
+            if W:  # as test_per_hop_tempogram_matches_the_reference_expression checks it
+                assert r["tempogram"].shape == (W,) and np.abs(r["tempogram"] - ref.tempogram()).max() < RTOL, i
+        assert worst > 0 and len(x) // B > shape["min_hops"]
+        sess.close()
 
 
 @pytest.mark.parametrize("graph", ["fused", "nodes"])
