@@ -931,6 +931,80 @@ int ofp_batchnorm_train_backward(const float* d_x, int64_t n, int32_t C, int32_t
                                  float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream);
 int ofp_nadam_step(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, const float* d_row, void* stream);
 
+/* ---- training model.CCCNN / model.LCCCNN (csrc/ofp_cccnn_train.hip) ------------------------------------------------
+ * The reference's recipe (model.py:443-629, train.py): the whole training set is one batch; one epoch is a forward,
+ *   the mean loss, a backward and one torch.optim.SGD step (momentum, weight decay on every parameter, dampening 0,
+ *   no Nesterov) at the learning rate d_rates[epoch].  The conv stack sees items: group = 0 makes every (window,
+ *   sensor) pair an item with one input channel (n * sensors items, layer l has layer_sizes[l] channels), group = 1
+ *   makes every window an item with `sensors` input channels and a convolution of `sensors` groups (layer l has
+ *   sensors * layer_sizes[l] channels).  Per layer: Conv1d (kernels[l], strides[l], shared padding / dilation) + bias,
+ *   activation `act`, GroupNorm(1, channels) over the whole item when `norm`, MaxPool1d(2, 2) when `pool`.  Head, per
+ *   (window, sensor) with maps f [K][V], K = layer_sizes[n_conv - 1]: cc[j] = sum_k sum_i f_k[i + j - (V - 1)]
+ *   f_k[i], p = softmax(cc) over the 2V - 1 lags, out = fc(p of all sensors).  GroupNorm keeps no running
+ *   statistics: the validation forward is the same forward.
+ * Parameters are packed in state_dict order: per conv layer weight [cout][cin/groups][kernel], bias [cout], then
+ *   (when norm) GroupNorm weight [cout], bias [cout]; last fc weight [n_out][sensors * (2V - 1)], bias [n_out].
+ * Limits (beyond them OFP_ERR_INVALID, or -1 from the size functions): 1..8 conv layers, kernel 1..64, stride 1..4,
+ *   1..64 channels per layer (sensors * layer_sizes[l] when grouped), width 1..512 (no layer wider than 1024), n and
+ *   n_val 1..1024 with n * sensors <= 4096, n_out 1..16, ofp_autocorr_softmax_lds_bytes(K, V) <= 160 KiB, every layer
+ *   leaves at least one column.
+ * ofp_cccnn_train: as ofp_cnn_train (d_train_loss / d_val_loss [num_epochs], the stop rule, *h_epochs, one captured
+ *   graph per epoch with the first epoch launched plainly, the stop word looked at every 64 epochs, a created
+ *   stream); d_rates is float [num_epochs]; OFP_CCCNN_GRAPH=nodes launches the same chain without a graph.  The
+ *   validation loss is always L1.  The momentum buffer starts fresh at every call.  Nothing is allocated: d_ws of
+ *   ofp_cccnn_train_workspace_bytes.
+ * ofp_cccnn_loss_grads: one forward and backward: d_loss [1], d_grads packed like the parameters.
+ * ofp_conv1d_backward_strided: ofp_conv1d_backward with a stride; wc = (w + 2 padding - dilation (k - 1) - 1) /
+ *   stride + 1; n 1..4096, channels 1..64, k 1..64, stride 1..4, w 1..1024.
+ * ofp_groupnorm1_train_forward: GroupNorm(1, K) (+ MaxPool1d(2, 2)) of d_x [n][K][V] -> d_y [n][K][V or V/2] and the
+ *   saved d_mean / d_rstd [n] (fp64 sums over the item's K V values, biased variance).  _backward: d_dy (shaped like
+ *   d_y) -> d_dx [n][K][V], d_dgamma / d_dbeta [K]; the pool hands its gradient to the larger of a pair (the first
+ *   on a tie), an odd last column gets none.  d_ws of ofp_groupnorm1_train_workspace_bytes.
+ * ofp_autocorr_softmax_backward: d_f [items][K][V] (items = windows * C, sensor fastest), the forward's d_p
+ *   [items][2V - 1], d_dout [windows][O], d_wfc [O][C * (2V - 1)] -> d_df [items][K][V].
+ * ofp_sgd_step: g' = g + weight_decay p; buf = g' when `first`, else momentum buf + g'; p -= d_lr[0] buf. */
+typedef struct ofp_cccnn_config {
+    int32_t n_conv;
+    int32_t sensors;
+    int32_t layer_sizes[8];
+    int32_t kernels[8];
+    int32_t strides[8];
+    int32_t padding, dilation, group;
+    int32_t act, norm, pool;
+    int32_t width, n_out, loss;
+    float momentum, weight_decay;
+    double gn_eps;
+} ofp_cccnn_config;
+int64_t ofp_cccnn_train_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val);
+int ofp_cccnn_train(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                    const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                    int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss, float* d_val_loss,
+                    int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_cccnn_loss_grads(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                         const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                         void* stream);
+int64_t ofp_conv1d_backward_strided_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,
+                                                    int32_t padding, int32_t dilation, int32_t groups,
+                                                    int32_t stride);
+int ofp_conv1d_backward_strided(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
+                                int32_t k, int32_t padding, int32_t dilation, int32_t groups, int32_t stride,
+                                const float* d_dz, float* d_dx, float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes,
+                                void* stream);
+int64_t ofp_groupnorm1_train_workspace_bytes(int64_t n, int32_t K, int32_t V);
+int ofp_groupnorm1_train_forward(const float* d_x, int64_t n, int32_t K, int32_t V, const float* d_gamma,
+                                 const float* d_beta, double eps, int32_t pool, float* d_y, float* d_mean,
+                                 float* d_rstd, void* stream);
+int ofp_groupnorm1_train_backward(const float* d_x, int64_t n, int32_t K, int32_t V, const float* d_gamma,
+                                  const float* d_beta, const float* d_mean, const float* d_rstd, int32_t pool,
+                                  const float* d_dy, float* d_dx, float* d_dgamma, float* d_dbeta, void* d_ws,
+                                  int64_t ws_bytes, void* stream);
+int64_t ofp_autocorr_softmax_lds_bytes(int32_t K, int32_t V);
+int ofp_autocorr_softmax_backward(const float* d_f, const float* d_p, const float* d_dout, const float* d_wfc,
+                                  int64_t items, int32_t C, int32_t K, int32_t V, int32_t O, float* d_df,
+                                  void* stream);
+int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const float* d_lr, int32_t first,
+                 float momentum, float weight_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

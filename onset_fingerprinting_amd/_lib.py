@@ -140,6 +140,21 @@ class CnnConfig(ctypes.Structure):
     ]
 
 
+class CccnnConfig(ctypes.Structure):
+    _fields_ = [
+        ("n_conv", ctypes.c_int32),
+        ("sensors", ctypes.c_int32),
+        ("layer_sizes", ctypes.c_int32 * 8),
+        ("kernels", ctypes.c_int32 * 8),
+        ("strides", ctypes.c_int32 * 8),
+        ("padding", ctypes.c_int32), ("dilation", ctypes.c_int32), ("group", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("norm", ctypes.c_int32), ("pool", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("n_out", ctypes.c_int32), ("loss", ctypes.c_int32),
+        ("momentum", ctypes.c_float), ("weight_decay", ctypes.c_float),
+        ("gn_eps", ctypes.c_double),
+    ]
+
+
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _f32p_h = ctypes.POINTER(ctypes.c_float)
 _long_p = ctypes.POINTER(ctypes.c_long)
@@ -283,6 +298,21 @@ SIGNATURES = {
     "ofp_batchnorm_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                     _i64, _vp]),
     "ofp_nadam_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ofp_cccnn_train_workspace_bytes": (_i64, [ctypes.POINTER(CccnnConfig), _i64, _i64]),
+    "ofp_cccnn_train": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32,
+                                       _i32, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp]),
+    "ofp_cccnn_loss_grads": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                            _vp]),
+    "ofp_conv1d_backward_strided_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "ofp_conv1d_backward_strided": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                   _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_groupnorm1_train_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ofp_groupnorm1_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "ofp_groupnorm1_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                     _vp, _vp, _i64, _vp]),
+    "ofp_autocorr_softmax_lds_bytes": (_i64, [_i32, _i32]),
+    "ofp_autocorr_softmax_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "ofp_sgd_step": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp]),
 }
 
 _lib = None

@@ -17,8 +17,7 @@
 // sample) and over samples (backward, one thread per feature and chunk of 64 samples, the chunks added in order) in
 // fp64 as well.  Convolution forward and input
 // gradient are fp32 fmaf chains of at most cin/groups * k (cout/groups * k) terms, in k_conv1d's order.
-#include "ofp_common.h"
-#include "ofp_mlp.h"
+#include "ofp_train_chain.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,29 +26,11 @@
 
 namespace {
 
-constexpr int kT = 256;        // threads per workgroup
-constexpr int kSlab = 2048;    // (sample, position) pairs one workgroup sums
-constexpr int kFcChunk = 64;   // samples one thread of the Linear head's weight gradient sums
 constexpr int kMaxConv = 3;
 constexpr int kMaxCh = 128;
 constexpr int kMaxKernel = 8;
 constexpr int kMaxWidth = 512;
 constexpr int kMaxBatch = 1024;
-constexpr int kMaxOut = 16;
-constexpr int kCheckEvery = 64;  // epochs between two looks at the stop word
-
-struct Ctl {
-    int32_t epoch, stop, wait, reached;
-    float best;
-    int32_t pad[3];
-};
-
-#define OFP_CNN_STOPPED(ctl) \
-    if ((ctl) != nullptr && (ctl)->stop) return
-
-struct Conv {
-    int cin, cout, win, wc, k, pad, dil, groups;
-};
 
 // what follows the convolution: activation, BatchNorm (mode 0 none, 1 batch statistics, 2 running statistics), pool
 struct Post {
@@ -84,66 +65,6 @@ __device__ __forceinline__ float aff_apply(const Aff& f, int mode, float a) {
     return a;
 }
 
-// d act / d z at pre-activation z (a = act(z)), as csrc/ofp_train.hip evaluates it
-__device__ __forceinline__ float act_grad(float y, float a, int act) {
-    switch (act) {
-        case OFP_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
-        case OFP_ACT_SILU: {
-            const float s = 1.0f / (1.0f + expf(-y));
-            return s * (1.0f + y * (1.0f - s));
-        }
-        case OFP_ACT_LEAKYRELU: return y > 0.0f ? 1.0f : 0.01f;
-        case OFP_ACT_ELU: return y > 0.0f ? 1.0f : expf(y);
-        case OFP_ACT_TANH: return 1.0f - a * a;
-        default: return 1.0f;
-    }
-}
-
-// sum of (a, b) over the workgroup: xor butterfly inside each wave, then the four waves in wave order
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[kT / 64]) {
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();  // a previous use of `red` has been read
-    if (lane == 0) red[0][wave] = a, red[1][wave] = b;
-    __syncthreads();
-    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-}
-
-__global__ __launch_bounds__(kT) void k_init(Ctl* ctl) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        *ctl = Ctl{};
-        ctl->best = INFINITY;
-    }
-}
-
-// z[s][o][p] = b[o] + sum_{ci, kk} x[s][g*cin_g + ci][p - pad + kk*dil] * w[o][ci][kk]: thread per element, the
-// arithmetic of k_conv1d (csrc/ofp_nn.hip)
-__global__ __launch_bounds__(kT) void k_conv_fwd(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ x,
-                                                 const float* __restrict__ w, const float* __restrict__ b,
-                                                 float* __restrict__ z) {
-    OFP_CNN_STOPPED(ctl);
-    const int64_t total = n * c.cout * c.wc;
-    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
-    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
-        const int p = (int)(i % c.wc);
-        const int64_t t = i / c.wc;
-        const int o = (int)(t % c.cout);
-        const int64_t s = t / c.cout;
-        const float* xs = x + (s * c.cin + (int64_t)(o / cout_g) * cin_g) * c.win;
-        const float* ws = w + (int64_t)o * cin_g * c.k;
-        float acc = b[o];
-        for (int ci = 0; ci < cin_g; ++ci)
-            for (int kk = 0; kk < c.k; ++kk) {
-                const int q = p - c.pad + kk * c.dil;
-                if (q >= 0 && q < c.win) acc = fmaf(xs[(int64_t)ci * c.win + q], ws[ci * c.k + kk], acc);
-            }
-        z[i] = acc;
-    }
-}
 
 // BatchNorm, batch statistics: sum a, sum a^2 (a = act(z)) of one slab of one channel
 __global__ __launch_bounds__(kT) void k_bn_stats_partial(const Ctl* ctl, const float* __restrict__ z, int64_t n, int C,
@@ -289,210 +210,6 @@ __global__ __launch_bounds__(kT) void k_dz(const Ctl* ctl, const Post t, int64_t
     }
 }
 
-// lanes per output of the weight-gradient kernel: the largest power of two <= 64 with outputs * g <= kT
-__host__ __device__ inline int lanes_per_output(int outputs) {
-    int g = 64;
-    while (g > 1 && outputs * g > kT) g >>= 1;
-    return g;
-}
-
-// dW[o][ci][kk] = sum_{s, p} dz[s][o][p] * x[s][g*cin_g + ci][p - pad + kk*dil], db[o] = sum dz: workgroup (slab, o);
-// the cin_g * k weights of channel o and its bias are the T outputs, g adjacent lanes share one output and take
-// the slab's pairs sub, sub + g, ... in ascending order, then an xor butterfly joins them
-__global__ __launch_bounds__(kT) void k_wgrad_partial(const Ctl* ctl, const Conv c, int64_t n,
-                                                      const float* __restrict__ x, const float* __restrict__ dz,
-                                                      double* __restrict__ partial) {
-    OFP_CNN_STOPPED(ctl);
-    const int slab = blockIdx.x, o = blockIdx.y, nslab = gridDim.x;
-    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
-    const int T = cin_g * c.k + 1;
-    const int g = lanes_per_output(T), per = kT / g, sub = threadIdx.x & (g - 1);
-    const int pairs = (int)n * c.wc, q0 = slab * kSlab;
-    const int q1 = q0 + kSlab < pairs ? q0 + kSlab : pairs;
-    const int ch0 = (o / cout_g) * cin_g;
-    for (int base = 0; base < T; base += per) {
-        const int wi = base + threadIdx.x / g;
-        const bool valid = wi < T;
-        const int ci = wi / c.k, kk = wi - ci * c.k;
-        const bool bias = wi == T - 1;
-        const int shift = kk * c.dil - c.pad;
-        double acc = 0.0;
-        if (valid)
-            for (int q = q0 + sub; q < q1; q += g) {
-                const int s = q / c.wc;
-                const int p = q - s * c.wc;
-                const float d = dz[((int64_t)s * c.cout + o) * c.wc + p];
-                if (bias) {
-                    acc += (double)d;
-                } else {
-                    const int xi = p + shift;
-                    if (xi >= 0 && xi < c.win) acc += (double)d * (double)x[((int64_t)s * c.cin + ch0 + ci) * c.win + xi];
-                }
-            }
-        for (int off = g >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (valid && sub == 0) partial[((int64_t)o * T + wi) * nslab + slab] = acc;
-    }
-}
-
-__global__ __launch_bounds__(kT) void k_wgrad_final(const Ctl* ctl, const double* __restrict__ partial, int nslab,
-                                                    int cout, int T, float* __restrict__ dw, float* __restrict__ db) {
-    OFP_CNN_STOPPED(ctl);
-    const int i = blockIdx.x * kT + threadIdx.x;
-    if (i >= cout * T) return;
-    const int o = i / T, wi = i - o * T;
-    double s = 0.0;
-    for (int j = 0; j < nslab; ++j) s += partial[(int64_t)i * nslab + j];
-    if (wi == T - 1)
-        db[o] = (float)s;
-    else
-        dw[o * (T - 1) + wi] = (float)s;
-}
-
-// dx[s][ci][q] = sum_{o in ci's group, kk} dz[s][o][q + pad - kk*dil] * w[o][ci][kk]: thread per element
-__global__ __launch_bounds__(kT) void k_dgrad(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ dz,
-                                              const float* __restrict__ w, float* __restrict__ dx) {
-    OFP_CNN_STOPPED(ctl);
-    const int64_t total = n * c.cin * c.win;
-    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
-    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
-        const int q = (int)(i % c.win);
-        const int64_t t = i / c.win;
-        const int ci = (int)(t % c.cin);
-        const int64_t s = t / c.cin;
-        const int grp = ci / cin_g, cil = ci - grp * cin_g;
-        float acc = 0.0f;
-        for (int oo = 0; oo < cout_g; ++oo) {
-            const int o = grp * cout_g + oo;
-            const float* dr = dz + (s * c.cout + o) * c.wc;
-            const float* wr = w + ((int64_t)o * cin_g + cil) * c.k;
-            for (int kk = 0; kk < c.k; ++kk) {
-                const int p = q + c.pad - kk * c.dil;
-                if (p >= 0 && p < c.wc) acc = fmaf(dr[p], wr[kk], acc);
-            }
-        }
-        dx[i] = acc;
-    }
-}
-
-// Linear head of one sample per workgroup: out = W h + b (fp64 sums over the F features), the sample's share of
-// the loss (sum over its outputs of |r| or r^2) and, when dy is given, d loss / d out
-__global__ __launch_bounds__(kT) void k_fc_fwd(const Ctl* ctl, const float* __restrict__ h, int F, int O,
-                                               const float* __restrict__ w, const float* __restrict__ b,
-                                               const float* __restrict__ y, int loss, float inv_numel,
-                                               float* __restrict__ out, float* __restrict__ dy,
-                                               double* __restrict__ part) {
-    OFP_CNN_STOPPED(ctl);
-    __shared__ double red[2][kT / 64];
-    const int64_t s = blockIdx.x;
-    const float* hr = h + s * F;
-    double lsum = 0.0;
-    for (int j = 0; j < O; j += 2) {
-        const bool two = j + 1 < O;
-        double a0 = 0.0, a1 = 0.0;
-        for (int f = threadIdx.x; f < F; f += kT) {
-            const double hv = (double)hr[f];
-            a0 += hv * (double)w[(int64_t)j * F + f];
-            if (two) a1 += hv * (double)w[(int64_t)(j + 1) * F + f];
-        }
-        block_sum2(a0, a1, red);
-        if (threadIdx.x == 0) {
-            for (int u = 0; u < (two ? 2 : 1); ++u) {
-                const float o = (float)((u ? a1 : a0) + (double)b[j + u]);
-                const float r = o - y[s * O + j + u];
-                out[s * O + j + u] = o;
-                if (loss == 0) {
-                    lsum += (double)fabsf(r);
-                    if (dy) dy[s * O + j + u] = r > 0.0f ? inv_numel : (r < 0.0f ? -inv_numel : 0.0f);
-                } else {
-                    lsum += (double)r * (double)r;
-                    if (dy) dy[s * O + j + u] = (2.0f * inv_numel) * r;
-                }
-            }
-        }
-    }
-    if (threadIdx.x == 0) part[s] = lsum;
-}
-
-// mean loss of the batch into slot `epoch` of a curve (and the head's bias gradient); for the validation loss also Lightning's early-stop rule
-// (min_delta 0): a loss that is not below the best so far counts towards patience
-__global__ __launch_bounds__(kT) void k_loss_final(Ctl* ctl, const double* __restrict__ part, int64_t n, int O,
-                                                   float* __restrict__ curve, int validation, int patience,
-                                                   const float* __restrict__ dy, float* __restrict__ db) {
-    OFP_CNN_STOPPED(ctl);
-    __shared__ double red[2][kT / 64];
-    if (db)  // the Linear head's bias gradient, db[j] = sum_s dy[s][j], two outputs at a time
-        for (int j = 0; j < O; j += 2) {
-            const bool two = j + 1 < O;
-            double b0 = 0.0, b1 = 0.0;
-            for (int64_t i = threadIdx.x; i < n; i += kT) {
-                b0 += (double)dy[i * O + j];
-                if (two) b1 += (double)dy[i * O + j + 1];
-            }
-            block_sum2(b0, b1, red);
-            if (threadIdx.x == 0) {
-                db[j] = (float)b0;
-                if (two) db[j + 1] = (float)b1;
-            }
-        }
-    double a = 0.0, z = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += kT) a += part[i];
-    block_sum2(a, z, red);
-    if (threadIdx.x == 0) {
-        const float loss = (float)(a / (double)(n * O));
-        curve[ctl ? ctl->epoch : 0] = loss;
-        if (validation && ctl) {
-            if (loss < ctl->best) {
-                ctl->best = loss;
-                ctl->wait = 0;
-            } else {
-                ctl->wait += 1;
-            }
-            if (patience >= 0 && ctl->wait >= patience) ctl->reached = 1;
-        }
-    }
-}
-
-// dW[j][f] = sum_s dy[s][j] h[s][f], dh[s][f] = sum_j dy[s][j] W[j][f]: thread per feature and chunk of kFcChunk
-// samples (fp64, samples in ascending order); k_fc_wfinal adds the chunks in chunk order
-__global__ __launch_bounds__(kT) void k_fc_bwd(const Ctl* ctl, const float* __restrict__ h,
-                                               const float* __restrict__ dy, int64_t n, int F, int O,
-                                               const float* __restrict__ w, double* __restrict__ partial,
-                                               float* __restrict__ dh) {
-    OFP_CNN_STOPPED(ctl);
-    const int f = blockIdx.x * kT + threadIdx.x, ck = blockIdx.y;
-    if (f >= F) return;
-    double acc[kMaxOut];
-    float wj[kMaxOut];
-#pragma unroll
-    for (int j = 0; j < kMaxOut; ++j) acc[j] = 0.0, wj[j] = j < O ? w[(int64_t)j * F + f] : 0.0f;
-    const int64_t s0 = (int64_t)ck * kFcChunk, s1 = s0 + kFcChunk < n ? s0 + kFcChunk : n;
-    for (int64_t s = s0; s < s1; ++s) {
-        const float hv = h[s * F + f];
-        float d = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kMaxOut; ++j)
-            if (j < O) {
-                const float g = dy[s * O + j];
-                acc[j] += (double)g * (double)hv;
-                d = fmaf(g, wj[j], d);
-            }
-        dh[s * F + f] = d;
-    }
-#pragma unroll
-    for (int j = 0; j < kMaxOut; ++j)
-        if (j < O) partial[((int64_t)ck * O + j) * F + f] = acc[j];
-}
-
-__global__ __launch_bounds__(kT) void k_fc_wfinal(const Ctl* ctl, const double* __restrict__ partial, int nchunk,
-                                                  int64_t OF, float* __restrict__ dw) {
-    OFP_CNN_STOPPED(ctl);
-    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= OF) return;
-    double s = 0.0;
-    for (int c = 0; c < nchunk; ++c) s += partial[(int64_t)c * OF + i];
-    dw[i] = (float)s;
-}
-
 // torch.optim.NAdam (_single_tensor_nadam, defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay), one element per
 // thread.  row = (c1, c2, bias_correction2), denom = sqrt(v / bias_correction2) + eps, p += (c1 g + c2 m) / denom.
 // torch adds the two terms to p one after the other (two addcdiv_ calls, p rounded twice); here they are added to
@@ -513,22 +230,8 @@ __global__ __launch_bounds__(kT) void k_nadam(const Ctl* ctl, const float* __res
     }
 }
 
-// the chain's last kernel: the epoch is over; stop once patience has run out and min_epochs are done
-__global__ __launch_bounds__(kT) void k_epoch_end(Ctl* ctl, int min_epochs) {
-    OFP_CNN_STOPPED(ctl);
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        ctl->epoch += 1;
-        if (ctl->reached && ctl->epoch >= min_epochs) ctl->stop = 1;
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-unsigned grid_for(int64_t total) {
-    const int64_t g = ofp::cdiv(total, kT);
-    return (unsigned)(g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g));
-}
-int slabs_of(int64_t pairs) { return (int)ofp::cdiv(pairs, kSlab); }
 
 int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int padding, int dilation, int groups) {
     OFP_REQUIRE(n >= 1 && n <= kMaxBatch, "%s: batch of %lld (limit: 1..%d)", who, (long long)n, kMaxBatch);
@@ -581,7 +284,7 @@ int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p) {
             return rc;
         Conv& v = p.conv[l];
         v = Conv{cin, cout, width, width + 2 * c->padding - c->dilation * (c->kernel - 1), c->kernel, c->padding,
-                 c->dilation, c->groups};
+                 c->dilation, c->groups, 1};
         OFP_REQUIRE(v.wc <= 2 * kMaxWidth, "cnn training: layer %d is %d wide (limit: %d)", l + 1, v.wc, 2 * kMaxWidth);
         p.wo[l] = p.pool ? v.wc / 2 : v.wc;
         OFP_REQUIRE(p.wo[l] >= 1, "cnn training: the pool of layer %d leaves no output column", l + 1);
@@ -690,20 +393,6 @@ int enqueue_post_bwd(const Ctl* ctl, const Post& t, int64_t n, const float* z, c
     return OFP_OK;
 }
 
-int enqueue_conv_bwd(const Ctl* ctl, const Conv& c, int64_t n, const float* x, const float* w, const float* dz,
-                     double* part, float* dw, float* db, float* dx, hipStream_t st) {
-    const int nslab = slabs_of(n * c.wc), T = c.cin / c.groups * c.k + 1;
-    hipLaunchKernelGGL(k_wgrad_partial, dim3(nslab, c.cout), dim3(kT), 0, st, ctl, c, n, x, dz, part);
-    OFP_LAUNCH_CHECK("k_wgrad_partial");
-    hipLaunchKernelGGL(k_wgrad_final, dim3((unsigned)ofp::cdiv(c.cout * T, kT)), dim3(kT), 0, st, ctl, part, nslab,
-                       c.cout, T, dw, db);
-    OFP_LAUNCH_CHECK("k_wgrad_final");
-    if (dx) {
-        hipLaunchKernelGGL(k_dgrad, dim3(grid_for(n * c.cin * c.win)), dim3(kT), 0, st, ctl, c, n, dz, w, dx);
-        OFP_LAUNCH_CHECK("k_dgrad");
-    }
-    return OFP_OK;
-}
 
 // conv stack and head of a batch; train: batch statistics, d loss / d out kept; else running statistics, L1
 int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train) {
@@ -795,12 +484,6 @@ int enqueue_epoch(const Run& r, const TrainArgs& a) {
     return OFP_OK;
 }
 
-int check_ws(const char* who, const void* ws, int64_t given, int64_t need) {
-    if (ws == nullptr || given < need)
-        return ofp::fail(OFP_ERR_WORKSPACE, "%s: work space of %lld bytes needed, %lld given", who, (long long)need,
-                         (long long)given);
-    return OFP_OK;
-}
 
 }  // namespace
 
@@ -922,7 +605,7 @@ int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, con
     if (need < 0) return OFP_ERR_INVALID;
     OFP_REQUIRE(d_x && d_w && d_dz && d_dw && d_db, "ofp_conv1d_backward: NULL argument");
     if (int rc = check_ws("ofp_conv1d_backward", d_ws, ws_bytes, need)) return rc;
-    const Conv c{cin, cout, w, w + 2 * padding - dilation * (k - 1), k, padding, dilation, groups};
+    const Conv c{cin, cout, w, w + 2 * padding - dilation * (k - 1), k, padding, dilation, groups, 1};
     return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
 }
 

@@ -1,0 +1,341 @@
+// Device code and launch helpers shared by the two epoch-graph trainers (csrc/ofp_cnn_train.hip, csrc/ofp_cccnn_train.hip):
+// the control block of a run, the partial-slab reducer's shape, the convolution's forward and three gradients (any
+// stride), the Linear head with its loss, and the chain's first and last kernels.  Everything here is file-local
+// (anonymous namespace): each trainer compiles its own copy.
+#pragma once
+#include "ofp_common.h"
+#include "ofp_mlp.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kT = 256;        // threads per workgroup
+constexpr int kSlab = 2048;    // (sample, position) pairs one workgroup sums
+constexpr int kFcChunk = 64;   // samples one thread of the Linear head's weight gradient sums
+constexpr int kMaxOut = 16;
+constexpr int kCheckEvery = 64;  // epochs between two looks at the stop word
+
+struct Ctl {
+    int32_t epoch, stop, wait, reached;
+    float best;
+    int32_t pad[3];
+};
+
+#define OFP_CNN_STOPPED(ctl) \
+    if ((ctl) != nullptr && (ctl)->stop) return
+
+struct Conv {
+    int cin, cout, win, wc, k, pad, dil, groups, stride;  // wc = (win + 2 pad - dil (k - 1) - 1) / stride + 1
+};
+
+// d act / d z at pre-activation z (a = act(z)), as csrc/ofp_train.hip evaluates it
+__device__ __forceinline__ float act_grad(float y, float a, int act) {
+    switch (act) {
+        case OFP_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
+        case OFP_ACT_SILU: {
+            const float s = 1.0f / (1.0f + expf(-y));
+            return s * (1.0f + y * (1.0f - s));
+        }
+        case OFP_ACT_LEAKYRELU: return y > 0.0f ? 1.0f : 0.01f;
+        case OFP_ACT_ELU: return y > 0.0f ? 1.0f : expf(y);
+        case OFP_ACT_TANH: return 1.0f - a * a;
+        default: return 1.0f;
+    }
+}
+
+// sum of (a, b) over the workgroup: xor butterfly inside each wave, then the four waves in wave order
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[kT / 64]) {
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();  // a previous use of `red` has been read
+    if (lane == 0) red[0][wave] = a, red[1][wave] = b;
+    __syncthreads();
+    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+}
+
+__global__ __launch_bounds__(kT) void k_init(Ctl* ctl) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        *ctl = Ctl{};
+        ctl->best = INFINITY;
+    }
+}
+
+// z[s][o][p] = b[o] + sum_{ci, kk} x[s][g*cin_g + ci][p*stride - pad + kk*dil] * w[o][ci][kk]: thread per element, the
+// arithmetic of k_conv1d (csrc/ofp_nn.hip)
+__global__ __launch_bounds__(kT) void k_conv_fwd(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ x,
+                                                 const float* __restrict__ w, const float* __restrict__ b,
+                                                 float* __restrict__ z) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * c.cout * c.wc;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int p = (int)(i % c.wc);
+        const int64_t t = i / c.wc;
+        const int o = (int)(t % c.cout);
+        const int64_t s = t / c.cout;
+        const float* xs = x + (s * c.cin + (int64_t)(o / cout_g) * cin_g) * c.win;
+        const float* ws = w + (int64_t)o * cin_g * c.k;
+        float acc = b[o];
+        for (int ci = 0; ci < cin_g; ++ci)
+            for (int kk = 0; kk < c.k; ++kk) {
+                const int q = p * c.stride - c.pad + kk * c.dil;
+                if (q >= 0 && q < c.win) acc = fmaf(xs[(int64_t)ci * c.win + q], ws[ci * c.k + kk], acc);
+            }
+        z[i] = acc;
+    }
+}
+
+// lanes per output of the weight-gradient kernel: the largest power of two <= 64 with outputs * g <= kT
+__host__ __device__ inline int lanes_per_output(int outputs) {
+    int g = 64;
+    while (g > 1 && outputs * g > kT) g >>= 1;
+    return g;
+}
+
+// dW[o][ci][kk] = sum_{s, p} dz[s][o][p] * x[s][g*cin_g + ci][p*stride - pad + kk*dil], db[o] = sum dz: workgroup (slab, o);
+// the cin_g * k weights of channel o and its bias are the T outputs, g adjacent lanes share one output and take
+// the slab's pairs sub, sub + g, ... in ascending order, then an xor butterfly joins them
+__global__ __launch_bounds__(kT) void k_wgrad_partial(const Ctl* ctl, const Conv c, int64_t n,
+                                                      const float* __restrict__ x, const float* __restrict__ dz,
+                                                      double* __restrict__ partial) {
+    OFP_CNN_STOPPED(ctl);
+    const int slab = blockIdx.x, o = blockIdx.y, nslab = gridDim.x;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    const int T = cin_g * c.k + 1;
+    const int g = lanes_per_output(T), per = kT / g, sub = threadIdx.x & (g - 1);
+    const int pairs = (int)n * c.wc, q0 = slab * kSlab;
+    const int q1 = q0 + kSlab < pairs ? q0 + kSlab : pairs;
+    const int ch0 = (o / cout_g) * cin_g;
+    for (int base = 0; base < T; base += per) {
+        const int wi = base + threadIdx.x / g;
+        const bool valid = wi < T;
+        const int ci = wi / c.k, kk = wi - ci * c.k;
+        const bool bias = wi == T - 1;
+        const int shift = kk * c.dil - c.pad;
+        double acc = 0.0;
+        if (valid)
+            for (int q = q0 + sub; q < q1; q += g) {
+                const int s = q / c.wc;
+                const int p = q - s * c.wc;
+                const float d = dz[((int64_t)s * c.cout + o) * c.wc + p];
+                if (bias) {
+                    acc += (double)d;
+                } else {
+                    const int xi = p * c.stride + shift;
+                    if (xi >= 0 && xi < c.win) acc += (double)d * (double)x[((int64_t)s * c.cin + ch0 + ci) * c.win + xi];
+                }
+            }
+        for (int off = g >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (valid && sub == 0) partial[((int64_t)o * T + wi) * nslab + slab] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kT) void k_wgrad_final(const Ctl* ctl, const double* __restrict__ partial, int nslab,
+                                                    int cout, int T, float* __restrict__ dw, float* __restrict__ db) {
+    OFP_CNN_STOPPED(ctl);
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= cout * T) return;
+    const int o = i / T, wi = i - o * T;
+    double s = 0.0;
+    for (int j = 0; j < nslab; ++j) s += partial[(int64_t)i * nslab + j];
+    if (wi == T - 1)
+        db[o] = (float)s;
+    else
+        dw[o * (T - 1) + wi] = (float)s;
+}
+
+// dx[s][ci][q] = sum_{o in ci's group, kk} dz[s][o][p] * w[o][ci][kk] over the p with p*stride = q + pad - kk*dil:
+// thread per element
+__global__ __launch_bounds__(kT) void k_dgrad(const Ctl* ctl, const Conv c, int64_t n, const float* __restrict__ dz,
+                                              const float* __restrict__ w, float* __restrict__ dx) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t total = n * c.cin * c.win;
+    const int cin_g = c.cin / c.groups, cout_g = c.cout / c.groups;
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const int q = (int)(i % c.win);
+        const int64_t t = i / c.win;
+        const int ci = (int)(t % c.cin);
+        const int64_t s = t / c.cin;
+        const int grp = ci / cin_g, cil = ci - grp * cin_g;
+        float acc = 0.0f;
+        for (int oo = 0; oo < cout_g; ++oo) {
+            const int o = grp * cout_g + oo;
+            const float* dr = dz + (s * c.cout + o) * c.wc;
+            const float* wr = w + ((int64_t)o * cin_g + cil) * c.k;
+            for (int kk = 0; kk < c.k; ++kk) {
+                int p = q + c.pad - kk * c.dil;
+                if (c.stride > 1) {
+                    if (p < 0 || p % c.stride) continue;
+                    p /= c.stride;
+                }
+                if (p >= 0 && p < c.wc) acc = fmaf(dr[p], wr[kk], acc);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
+// Linear head of one sample per workgroup: out = W h + b (fp64 sums over the F features), the sample's share of
+// the loss (sum over its outputs of |r| or r^2) and, when dy is given, d loss / d out
+__global__ __launch_bounds__(kT) void k_fc_fwd(const Ctl* ctl, const float* __restrict__ h, int F, int O,
+                                               const float* __restrict__ w, const float* __restrict__ b,
+                                               const float* __restrict__ y, int loss, float inv_numel,
+                                               float* __restrict__ out, float* __restrict__ dy,
+                                               double* __restrict__ part) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    const int64_t s = blockIdx.x;
+    const float* hr = h + s * F;
+    double lsum = 0.0;
+    for (int j = 0; j < O; j += 2) {
+        const bool two = j + 1 < O;
+        double a0 = 0.0, a1 = 0.0;
+        for (int f = threadIdx.x; f < F; f += kT) {
+            const double hv = (double)hr[f];
+            a0 += hv * (double)w[(int64_t)j * F + f];
+            if (two) a1 += hv * (double)w[(int64_t)(j + 1) * F + f];
+        }
+        block_sum2(a0, a1, red);
+        if (threadIdx.x == 0) {
+            for (int u = 0; u < (two ? 2 : 1); ++u) {
+                const float o = (float)((u ? a1 : a0) + (double)b[j + u]);
+                const float r = o - y[s * O + j + u];
+                out[s * O + j + u] = o;
+                if (loss == 0) {
+                    lsum += (double)fabsf(r);
+                    if (dy) dy[s * O + j + u] = r > 0.0f ? inv_numel : (r < 0.0f ? -inv_numel : 0.0f);
+                } else {
+                    lsum += (double)r * (double)r;
+                    if (dy) dy[s * O + j + u] = (2.0f * inv_numel) * r;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) part[s] = lsum;
+}
+
+// mean loss of the batch into slot `epoch` of a curve (and the head's bias gradient); for the validation loss also Lightning's early-stop rule
+// (min_delta 0): a loss that is not below the best so far counts towards patience
+__global__ __launch_bounds__(kT) void k_loss_final(Ctl* ctl, const double* __restrict__ part, int64_t n, int O,
+                                                   float* __restrict__ curve, int validation, int patience,
+                                                   const float* __restrict__ dy, float* __restrict__ db) {
+    OFP_CNN_STOPPED(ctl);
+    __shared__ double red[2][kT / 64];
+    if (db)  // the Linear head's bias gradient, db[j] = sum_s dy[s][j], two outputs at a time
+        for (int j = 0; j < O; j += 2) {
+            const bool two = j + 1 < O;
+            double b0 = 0.0, b1 = 0.0;
+            for (int64_t i = threadIdx.x; i < n; i += kT) {
+                b0 += (double)dy[i * O + j];
+                if (two) b1 += (double)dy[i * O + j + 1];
+            }
+            block_sum2(b0, b1, red);
+            if (threadIdx.x == 0) {
+                db[j] = (float)b0;
+                if (two) db[j + 1] = (float)b1;
+            }
+        }
+    double a = 0.0, z = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kT) a += part[i];
+    block_sum2(a, z, red);
+    if (threadIdx.x == 0) {
+        const float loss = (float)(a / (double)(n * O));
+        curve[ctl ? ctl->epoch : 0] = loss;
+        if (validation && ctl) {
+            if (loss < ctl->best) {
+                ctl->best = loss;
+                ctl->wait = 0;
+            } else {
+                ctl->wait += 1;
+            }
+            if (patience >= 0 && ctl->wait >= patience) ctl->reached = 1;
+        }
+    }
+}
+
+// dW[j][f] = sum_s dy[s][j] h[s][f], dh[s][f] = sum_j dy[s][j] W[j][f]: thread per feature and chunk of kFcChunk
+// samples (fp64, samples in ascending order); k_fc_wfinal adds the chunks in chunk order
+__global__ __launch_bounds__(kT) void k_fc_bwd(const Ctl* ctl, const float* __restrict__ h,
+                                               const float* __restrict__ dy, int64_t n, int F, int O,
+                                               const float* __restrict__ w, double* __restrict__ partial,
+                                               float* __restrict__ dh) {
+    OFP_CNN_STOPPED(ctl);
+    const int f = blockIdx.x * kT + threadIdx.x, ck = blockIdx.y;
+    if (f >= F) return;
+    double acc[kMaxOut];
+    float wj[kMaxOut];
+#pragma unroll
+    for (int j = 0; j < kMaxOut; ++j) acc[j] = 0.0, wj[j] = j < O ? w[(int64_t)j * F + f] : 0.0f;
+    const int64_t s0 = (int64_t)ck * kFcChunk, s1 = s0 + kFcChunk < n ? s0 + kFcChunk : n;
+    for (int64_t s = s0; s < s1; ++s) {
+        const float hv = h[s * F + f];
+        float d = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kMaxOut; ++j)
+            if (j < O) {
+                const float g = dy[s * O + j];
+                acc[j] += (double)g * (double)hv;
+                d = fmaf(g, wj[j], d);
+            }
+        dh[s * F + f] = d;
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxOut; ++j)
+        if (j < O) partial[((int64_t)ck * O + j) * F + f] = acc[j];
+}
+
+__global__ __launch_bounds__(kT) void k_fc_wfinal(const Ctl* ctl, const double* __restrict__ partial, int nchunk,
+                                                  int64_t OF, float* __restrict__ dw) {
+    OFP_CNN_STOPPED(ctl);
+    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= OF) return;
+    double s = 0.0;
+    for (int c = 0; c < nchunk; ++c) s += partial[(int64_t)c * OF + i];
+    dw[i] = (float)s;
+}
+
+// the chain's last kernel: the epoch is over; stop once patience has run out and min_epochs are done
+__global__ __launch_bounds__(kT) void k_epoch_end(Ctl* ctl, int min_epochs) {
+    OFP_CNN_STOPPED(ctl);
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ctl->epoch += 1;
+        if (ctl->reached && ctl->epoch >= min_epochs) ctl->stop = 1;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+
+unsigned grid_for(int64_t total) {
+    const int64_t g = ofp::cdiv(total, kT);
+    return (unsigned)(g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g));
+}
+int slabs_of(int64_t pairs) { return (int)ofp::cdiv(pairs, kSlab); }
+
+int enqueue_conv_bwd(const Ctl* ctl, const Conv& c, int64_t n, const float* x, const float* w, const float* dz,
+                     double* part, float* dw, float* db, float* dx, hipStream_t st) {
+    const int nslab = slabs_of(n * c.wc), T = c.cin / c.groups * c.k + 1;
+    hipLaunchKernelGGL(k_wgrad_partial, dim3(nslab, c.cout), dim3(kT), 0, st, ctl, c, n, x, dz, part);
+    OFP_LAUNCH_CHECK("k_wgrad_partial");
+    hipLaunchKernelGGL(k_wgrad_final, dim3((unsigned)ofp::cdiv(c.cout * T, kT)), dim3(kT), 0, st, ctl, part, nslab,
+                       c.cout, T, dw, db);
+    OFP_LAUNCH_CHECK("k_wgrad_final");
+    if (dx) {
+        hipLaunchKernelGGL(k_dgrad, dim3(grid_for(n * c.cin * c.win)), dim3(kT), 0, st, ctl, c, n, dz, w, dx);
+        OFP_LAUNCH_CHECK("k_dgrad");
+    }
+    return OFP_OK;
+}
+
+int check_ws(const char* who, const void* ws, int64_t given, int64_t need) {
+    if (ws == nullptr || given < need)
+        return ofp::fail(OFP_ERR_WORKSPACE, "%s: work space of %lld bytes needed, %lld given", who, (long long)need,
+                         (long long)given);
+    return OFP_OK;
+}
+
+}  // namespace

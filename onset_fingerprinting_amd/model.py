@@ -8,7 +8,10 @@ csrc/ofp_rnn.hip); torch only allocates memory and makes views.  ``rnn_forward``
 ``nn.GRU`` / ``nn.LSTM`` / ``nn.RNN`` module (its full output sequence) on the same kernels.
 ``fit_cnn`` trains a ``CNN`` in place with the recipe of its ``training_step`` / ``configure_optimizers``
 (full batch, NAdam, cosine warm restarts every 250 epochs) as one graph of HIP kernels per epoch
-(csrc/ofp_cnn_train.hip).  Training the other classes is out of scope.
+(csrc/ofp_cnn_train.hip).  ``fit_lcccnn`` trains an ``LCCCNN`` in place with the recipe of its own ``training_step`` /
+``configure_optimizers`` (full batch, SGD with momentum 0.8 and weight decay 1e-3 at 100 x ``lr``, cosine annealing over
+100 epochs) the same way (csrc/ofp_cccnn_train.hip).  Training the recurrent classes is out of scope (DESIGN.md
+section 7).
 """
 import ctypes
 import functools
@@ -221,8 +224,9 @@ class CCCNN(nn.Module):
 
 
 class LCCCNN(nn.Module):
-    """``model.LCCCNN`` (model.py:541-580): the training wrapper around CCCNN; inference only here.
-    Parameter names (``model.conv_layers.conv{i}``, ``model.fc``) follow the reference."""
+    """``model.LCCCNN`` (model.py:541-629): the training wrapper around CCCNN.  Parameter names
+    (``model.conv_layers.conv{i}``, ``model.fc``) follow the reference.  ``forward`` is the HIP inference pass of
+    ``CCCNN``; ``fit_lcccnn`` trains the module with the recipe of ``configure_optimizers`` on the GPU."""
 
     def __init__(self, input_size: int, output_size: int, channels: int = 3, layer_sizes=[8, 16], kernel_sizes=3,
                  strides=1, dropout_rate: float = 0.5, batch_norm=False, pool=False, padding=1, dilation=1,
@@ -235,6 +239,19 @@ class LCCCNN(nn.Module):
 
     def forward(self, x):
         return self.model(x)
+
+    def configure_optimizers(self):
+        """model.py:606-629: SGD at 100 x ``self.lr`` with momentum 0.8 and weight decay 1e-3 on every parameter, and
+        CosineAnnealingLR(T_max = 100), stepped once per epoch.  ``fit_lcccnn`` takes its per-epoch rates from the
+        same two torch classes."""
+        optimizer = torch.optim.SGD(self.parameters(), lr=self.lr * 100, momentum=LCCCNN_MOMENTUM,
+                                    weight_decay=LCCCNN_WEIGHT_DECAY)
+        scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, 100)
+        return {"optimizer": optimizer,
+                "lr_scheduler": {"scheduler": scheduler, "monitor": "val_loss", "frequency": 1}}
+
+
+LCCCNN_MOMENTUM, LCCCNN_WEIGHT_DECAY = 0.8, 1e-3  # model.py:608-614
 
 
 # ---- recurrent models (model.py:168-440) ---------------------------------------------------------------------------
@@ -808,4 +825,336 @@ def nadam_step(p, g, m, v, row):
     cnn_step_factors of the step, rounded."""
     check(_lib.lib().ofp_nadam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
                                     row.data_ptr(), _stream(p.device)), "ofp_nadam_step")
+    return p
+
+
+# ---- training model.LCCCNN (model.py:541-629, train.py) ------------------------------------------------------------
+CCCNN_TRAIN_MAX_LAYERS, CCCNN_TRAIN_MAX_CHANNELS, CCCNN_TRAIN_MAX_KERNEL = 8, 64, 64  # csrc/ofp_cccnn_train.hip
+CCCNN_TRAIN_MAX_STRIDE, CCCNN_TRAIN_MAX_WIDTH, CCCNN_TRAIN_MAX_BATCH = 4, 512, 1024
+CCCNN_TRAIN_MAX_ITEMS, CCCNN_TRAIN_MAX_OUT, CCCNN_TRAIN_MAX_LDS = 4096, 16, 160 * 1024
+
+
+def cccnn_head_lds_bytes(K, V):
+    """LDS the correlation head's training kernels need for K maps of V columns (maps, two rows of 2V - 1 lags and
+    64 words of scratch, float32)."""
+    return (K * V + 2 * (2 * V - 1) + 64) * 4
+
+
+@functools.lru_cache(maxsize=256)
+def lcccnn_rates(lr, num_epochs):
+    """The learning rate of every epoch of LCCCNN.configure_optimizers() for ``model.lr == lr``: torch's own SGD at
+    100 x lr and CosineAnnealingLR(T_max = 100) stepped once per epoch on a dummy parameter (the rate reaches 0 at
+    epoch 100 and rises again after it).  float64 [num_epochs]."""
+    p = nn.Parameter(torch.zeros(1))
+    opt = torch.optim.SGD([p], lr=lr * 100, momentum=LCCCNN_MOMENTUM, weight_decay=LCCCNN_WEIGHT_DECAY)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, 100)
+    opt.step()
+    rates = np.empty(num_epochs, np.float64)
+    for e in range(num_epochs):
+        rates[e] = float(opt.param_groups[0]["lr"])
+        sched.step()
+    rates.setflags(write=False)
+    return rates
+
+
+def _cccnn_net(model):
+    if not isinstance(model, LCCCNN):
+        raise ValueError(f"{type(model).__name__} is not an LCCCNN (the loss and the learning rate live there)")
+    return model.model
+
+
+def _cccnn_arch(model, width=None):
+    """(CccnnConfig, convs, group norms) of an LCCCNN for the trainer; ValueError for what it cannot run."""
+    net = _cccnn_net(model)
+    if net.dropout.p > 0:
+        raise ValueError(f"dropout_rate {net.dropout.p} cannot be trained on the GPU: torch's dropout stream cannot "
+                         "be matched (construct the model with dropout_rate=0.0)")
+    loss = _loss_code(model.loss)
+    mods = list(net.conv_layers)
+    convs = [m for m in mods if isinstance(m, nn.Conv1d)]
+    gns = [m for m in mods if isinstance(m, nn.GroupNorm)]
+    pools = [m for m in mods if isinstance(m, nn.MaxPool1d)]
+    acts = [m for m in mods if not isinstance(m, (nn.Conv1d, nn.GroupNorm, nn.MaxPool1d))]
+    codes = set()
+    for a in acts:
+        if type(a) not in ACT_CODES:
+            raise ValueError(f"activation {type(a).__name__} has no HIP implementation")
+        codes.add(ACT_CODES[type(a)])
+    if not 1 <= len(convs) <= CCCNN_TRAIN_MAX_LAYERS:
+        raise ValueError(f"{len(convs)} conv layers: the trainer's limit is 1..{CCCNN_TRAIN_MAX_LAYERS}")
+    if len(acts) != len(convs) or len(codes) != 1:
+        raise ValueError("every Conv1d must be followed by one and the same activation")
+    if len(gns) not in (0, len(convs)) or len(pools) not in (0, len(convs)):
+        raise ValueError("GroupNorm / MaxPool1d must follow every Conv1d or none")
+    C = net.channels
+    groups = C if net.group else 1
+    c0 = convs[0]
+    key = lambda m: (m.padding, m.dilation, m.groups, m.padding_mode, m.bias is not None)
+    if any(key(m) != key(c0) for m in convs) or c0.groups != groups or c0.in_channels != groups \
+            or c0.padding_mode != "zeros" or c0.bias is None or not isinstance(c0.padding[0], int):
+        raise ValueError("the Conv1d layers must share padding and dilation, with zero padding, a bias and one group "
+                         "per sensor channel (group=True) or a single input channel (group=False)")
+    if any(m.kernel_size != 2 or m.stride != 2 or m.padding != 0 or m.dilation != 1 or m.ceil_mode for m in pools):
+        raise ValueError("only MaxPool1d(kernel_size=2, stride=2) is trained")
+    for m in gns:
+        if m.num_groups != 1 or not m.affine or m.eps != gns[0].eps:
+            raise ValueError("the GroupNorm layers must have one group, be affine and share eps")
+    for i, m in enumerate(convs):
+        k, st = m.kernel_size[0], m.stride[0]
+        if k > CCCNN_TRAIN_MAX_KERNEL:
+            raise ValueError(f"kernel size {k} of layer {i + 1}: the trainer's limit is {CCCNN_TRAIN_MAX_KERNEL}")
+        if st > CCCNN_TRAIN_MAX_STRIDE:
+            raise ValueError(f"stride {st} of layer {i + 1}: the trainer's limit is {CCCNN_TRAIN_MAX_STRIDE}")
+        if m.out_channels > CCCNN_TRAIN_MAX_CHANNELS or m.out_channels % groups:
+            raise ValueError(f"{m.out_channels} channels in layer {i + 1}: the trainer's limit is "
+                             f"{CCCNN_TRAIN_MAX_CHANNELS} (layer size x sensor channels when grouped)")
+        if i and m.in_channels != convs[i - 1].out_channels:
+            raise ValueError("the Conv1d layers do not form a chain")
+    if net.fc.out_features > CCCNN_TRAIN_MAX_OUT or net.fc.bias is None:
+        raise ValueError(f"the Linear head needs a bias and at most {CCCNN_TRAIN_MAX_OUT} outputs")
+    cfg = _lib.CccnnConfig()
+    cfg.n_conv, cfg.sensors = len(convs), C
+    for i, m in enumerate(convs):
+        cfg.layer_sizes[i], cfg.kernels[i], cfg.strides[i] = m.out_channels // groups, m.kernel_size[0], m.stride[0]
+    cfg.padding, cfg.dilation, cfg.group = c0.padding[0], c0.dilation[0], int(bool(net.group))
+    cfg.act, cfg.norm, cfg.pool, cfg.loss = codes.pop(), int(bool(gns)), int(bool(pools)), loss
+    cfg.n_out = net.fc.out_features
+    cfg.momentum, cfg.weight_decay = LCCCNN_MOMENTUM, LCCCNN_WEIGHT_DECAY
+    cfg.gn_eps = gns[0].eps if gns else 1e-5
+    if width is not None:
+        if not 1 <= width <= CCCNN_TRAIN_MAX_WIDTH:
+            raise ValueError(f"window of {width} samples: the trainer's limit is 1..{CCCNN_TRAIN_MAX_WIDTH}")
+        cfg.width = w = width
+        for i, m in enumerate(convs):
+            span = w + 2 * cfg.padding - cfg.dilation * (m.kernel_size[0] - 1)
+            w = (span - 1) // m.stride[0] + 1 if span >= 1 else 0
+            w = w // 2 if pools else w
+            if w < 1:
+                raise ValueError(f"a window of {width} samples leaves no column after conv layer {i + 1}")
+            if w > 2 * CCCNN_TRAIN_MAX_WIDTH:
+                raise ValueError(f"layer {i + 1} is {w} wide: the trainer's limit is {2 * CCCNN_TRAIN_MAX_WIDTH}")
+        K = cfg.layer_sizes[len(convs) - 1]
+        if cccnn_head_lds_bytes(K, w) > CCCNN_TRAIN_MAX_LDS:
+            raise ValueError(f"the head's {K} maps of {w} columns need {cccnn_head_lds_bytes(K, w)} bytes of LDS: the "
+                             f"limit is {CCCNN_TRAIN_MAX_LDS}")
+        if C * (2 * w - 1) != net.fc.in_features:
+            raise ValueError(f"a window of {width} samples gives {C * (2 * w - 1)} features; the model's Linear "
+                             f"expects {net.fc.in_features}")
+    return cfg, convs, gns
+
+
+def _cccnn_tensors(model):
+    """[(state_dict name, tensor)] of an LCCCNN's parameters in packing order."""
+    _cfg, convs, gns = _cccnn_arch(model)
+    net = model.model
+    names = {id(m): n for n, m in net.conv_layers.named_children()}
+    ps = []
+    for i, conv in enumerate(convs):
+        n = "model.conv_layers." + names[id(conv)]
+        ps += [(n + ".weight", conv.weight), (n + ".bias", conv.bias)]
+        if gns:
+            b = "model.conv_layers." + names[id(gns[i])]
+            ps += [(b + ".weight", gns[i].weight), (b + ".bias", gns[i].bias)]
+    ps += [("model.fc.weight", net.fc.weight), ("model.fc.bias", net.fc.bias)]
+    return ps
+
+
+def _cccnn_batch(model, x, y, what="x"):
+    x, y = torch.as_tensor(x), torch.as_tensor(y)
+    if x.dim() != 3 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)}: expected [n, channels, width] and [n, outputs]")
+    C = _cccnn_net(model).channels
+    if not 1 <= x.shape[0] <= CCCNN_TRAIN_MAX_BATCH or x.shape[0] * C > CCCNN_TRAIN_MAX_ITEMS:
+        raise ValueError(f"{x.shape[0]} windows of {C} channels: the trainer's limits are 1..{CCCNN_TRAIN_MAX_BATCH} "
+                         f"windows and {CCCNN_TRAIN_MAX_ITEMS} (window, channel) pairs (one full batch)")
+    cfg, _c, _g = _cccnn_arch(model, int(x.shape[2]))
+    if x.shape[1] != C or y.shape[1] != cfg.n_out:
+        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)} do not fit a model of {C} channels and "
+                         f"{cfg.n_out} outputs")
+    return x, y, cfg
+
+
+def cccnn_loss_and_grads_device(model, x, y):
+    """Loss (``model.loss``) and the gradient of every parameter of an LCCCNN for the full batch x [n, channels,
+    width], y [n, outputs], by the trainer's own forward and backward kernels.  Returns (loss, {state_dict name:
+    gradient}) on the GPU."""
+    x, y, cfg = _cccnn_batch(model, x, y)
+    dev = _train_device(model.model, x)
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ps = _cccnn_tensors(model)
+    p0 = _flat(ps, dev)
+    xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grads = torch.empty_like(p0)
+    n = int(xd.shape[0])
+    ws_bytes = int(L.ofp_cccnn_train_workspace_bytes(ctypes.byref(cfg), n, 0))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ws = _workspace(ws_bytes, dev)
+    with torch.cuda.device(dev):
+        check(L.ofp_cccnn_loss_grads(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
+                                     loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)),
+              "ofp_cccnn_loss_grads")
+    named, o = {}, 0
+    for name, t in ps:
+        named[name] = grads[o:o + t.numel()].reshape(t.shape)
+        o += t.numel()
+    return loss[0], named
+
+
+def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None):
+    """Train an ``LCCCNN`` in place, as ``Trainer.fit(model, ...)`` does with the reference's recipe (model.py:541-629,
+    train.py): the whole of x [n, channels, width] / y [n, outputs] is one batch; every epoch is one forward,
+    ``model.loss`` (F.l1_loss or F.mse_loss), backward and one SGD step (momentum 0.8, weight decay 1e-3 on every
+    parameter, dampening 0, no Nesterov) at the learning rate of CosineAnnealingLR(100) starting from 100 x
+    ``model.lr``; then, with a validation set, a forward of x_val and its L1 loss (the reference's validation_step
+    always uses F.l1_loss).  GroupNorm keeps no running statistics, so both forwards are the same computation.  One
+    epoch is one launch of a captured graph of HIP kernels; the optimiser state starts fresh at every call, as a new
+    Trainer's does.
+
+    Stop rule (``patience`` given; needs the validation set): Lightning's EarlyStopping(monitor="val_loss",
+    mode="min", patience=patience) with min_delta 0, restated here because Lightning is not installed: an epoch whose
+    validation loss is not below the best so far counts towards patience, a lower loss resets the count; training ends
+    after the epoch at which the count reaches patience, but not before min_epochs epochs have run.
+
+    The parameters of `model` are updated where they live (CPU or GPU) and the model is left in eval mode.  Returns a
+    record with ``train_loss`` and ``val_loss`` (or None): float32 GPU tensors [max_epochs], NaN beyond the epochs
+    run; ``epochs``: epochs run; ``lrs``: float64 [epochs].
+
+    ValueError, before anything runs on the GPU: dropout_rate > 0, a loss other than F.l1_loss / F.mse_loss, an
+    activation without HIP implementation, shapes beyond the limits: 1..8 conv layers, kernel size 64, stride 4, 64
+    channels per layer (layer size x sensor channels when group=True), window 512, 1024 windows and 4096 (window,
+    sensor) pairs, 16 outputs, a head of K maps x V columns with cccnn_head_lds_bytes(K, V) <= 160 KiB, and every
+    layer must leave at least one column."""
+    x, y, cfg = _cccnn_batch(model, x, y)
+    have_val = x_val is not None or y_val is not None
+    if have_val:
+        if x_val is None or y_val is None:
+            raise ValueError("x_val and y_val go together")
+        x_val, y_val, cfg_v = _cccnn_batch(model, x_val, y_val, "x_val")
+        if cfg_v.width != cfg.width:
+            raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
+    max_epochs, min_epochs = int(max_epochs), int(min_epochs)
+    if max_epochs < 1 or min_epochs < 0:
+        raise ValueError("max_epochs must be at least 1 and min_epochs at least 0")
+    if patience is not None and (not have_val or int(patience) < 0):
+        raise ValueError("patience needs x_val / y_val and must not be negative")
+    lr = float(model.lr)
+
+    dev = _train_device(model.model, x)
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ps = _cccnn_tensors(model)
+    params = _flat(ps, dev)
+    to = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    xd, yd = to(x), to(y)
+    xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
+    rates = torch.from_numpy(np.asarray(lcccnn_rates(lr, max_epochs), np.float32)).to(dev)
+    train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
+    val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
+    n, nv = int(xd.shape[0]), int(xv.shape[0]) if have_val else 0
+    ws_bytes = int(L.ofp_cccnn_train_workspace_bytes(ctypes.byref(cfg), n, nv))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ws = _workspace(ws_bytes, dev)
+    epochs = ctypes.c_int32(0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    # the epoch graph is captured on a stream of its own (the null stream cannot be captured); the call returns
+    # after that stream has drained
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(cur)
+    with torch.cuda.device(dev):
+        check(L.ofp_cccnn_train(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                                rates.data_ptr(), max_epochs, min_epochs, -1 if patience is None else int(patience),
+                                params.data_ptr(), train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs),
+                                ws.data_ptr(), ws_bytes, ctypes.c_void_p(side.cuda_stream)), "ofp_cccnn_train")
+    cur.wait_stream(side)
+    with torch.no_grad():
+        o = 0
+        for _name, t in ps:
+            t.copy_(params[o:o + t.numel()].reshape(t.shape))
+            o += t.numel()
+    model.eval()
+    return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
+                           lrs=np.array(lcccnn_rates(lr, max_epochs)[:epochs.value]))
+
+
+def conv1d_backward_strided(x, weight, dz, padding, dilation, groups=1, stride=1, *, dx=None, dw=None, db=None,
+                            need_dx=True):
+    """conv1d_backward for any stride (ofp_conv1d_backward_strided): dz [n, cout, wc] with wc = (w + 2 padding -
+    dilation (k - 1) - 1) // stride + 1 -> (dx or None, dw, db)."""
+    L = _lib.lib()
+    n, cin, w = x.shape
+    cout, _, k = weight.shape
+    dev = x.device
+    ws_bytes = int(L.ofp_conv1d_backward_strided_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups,
+                                                                 stride))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    if need_dx and dx is None:
+        dx = torch.empty_like(x)
+    dw = torch.empty_like(weight) if dw is None else dw
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if db is None else db
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_conv1d_backward_strided(x.data_ptr(), n, cin, w, weight.data_ptr(), cout, k, padding, dilation,
+                                        groups, stride, dz.data_ptr(), dx.data_ptr() if need_dx else None,
+                                        dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)),
+          "ofp_conv1d_backward_strided")
+    return (dx if need_dx else None), dw, db
+
+
+def groupnorm1_train_forward(x, gamma, beta, eps=1e-5, pool=False, *, out=None):
+    """nn.GroupNorm(1, K) (+ MaxPool1d(2, 2)) on float32 CUDA x [n, K, V], keeping what the backward needs:
+    -> (y, mean [n], rstd [n])."""
+    L = _lib.lib()
+    n, K, V = x.shape
+    dev = x.device
+    y = torch.empty((n, K, V // 2 if pool else V), dtype=torch.float32, device=dev) if out is None else out
+    mean = torch.empty(n, dtype=torch.float32, device=dev)
+    rstd = torch.empty(n, dtype=torch.float32, device=dev)
+    check(L.ofp_groupnorm1_train_forward(x.data_ptr(), n, K, V, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                         int(bool(pool)), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                         _stream(dev)), "ofp_groupnorm1_train_forward")
+    return y, mean, rstd
+
+
+def groupnorm1_train_backward(x, gamma, beta, mean, rstd, dy, pool=False, *, out=None):
+    """Backward of groupnorm1_train_forward: dy shaped like its y -> (dx [n, K, V], dgamma [K], dbeta [K])."""
+    L = _lib.lib()
+    n, K, V = x.shape
+    dev = x.device
+    ws_bytes = int(L.ofp_groupnorm1_train_workspace_bytes(n, K, V))
+    if ws_bytes < 0:
+        raise ValueError(f"{n} items, {K} channels, width {V}: beyond the GroupNorm kernels' limits")
+    dx = torch.empty_like(x) if out is None else out
+    dgamma = torch.empty(K, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(K, dtype=torch.float32, device=dev)
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_groupnorm1_train_backward(x.data_ptr(), n, K, V, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+                                          rstd.data_ptr(), int(bool(pool)), dy.data_ptr(), dx.data_ptr(),
+                                          dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws_bytes,
+                                          _stream(dev)), "ofp_groupnorm1_train_backward")
+    return dx, dgamma, dbeta
+
+
+def autocorr_softmax_backward(feat, probs, dout, fc_weight, channels, *, out=None):
+    """Backward of the correlation head and the Linear behind it: feat [n * channels, K, V], probs = the forward's
+    autocorr_softmax(feat), dout [n, O] = d loss / d out, fc_weight [O, channels * (2V - 1)] -> d loss / d feat."""
+    items, K, V = feat.shape
+    df = torch.empty_like(feat) if out is None else out
+    check(_lib.lib().ofp_autocorr_softmax_backward(feat.data_ptr(), probs.data_ptr(), dout.data_ptr(),
+                                                   fc_weight.data_ptr(), items, channels, K, V, dout.shape[1],
+                                                   df.data_ptr(), _stream(feat.device)),
+          "ofp_autocorr_softmax_backward")
+    return df
+
+
+def sgd_step(p, g, buf, lr, first, momentum=LCCCNN_MOMENTUM, weight_decay=LCCCNN_WEIGHT_DECAY):
+    """One torch.optim.SGD step (dampening 0, no Nesterov) in place on float32 CUDA tensors p and buf with gradient g;
+    lr: float32 CUDA [>= 1]; first: the momentum buffer is initialised with the gradient."""
+    check(_lib.lib().ofp_sgd_step(p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), lr.data_ptr(),
+                                  int(bool(first)), float(momentum), float(weight_decay), _stream(p.device)),
+          "ofp_sgd_step")
     return p
