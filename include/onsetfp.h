@@ -1005,6 +1005,67 @@ int ofp_autocorr_softmax_backward(const float* d_f, const float* d_p, const floa
 int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const float* d_lr, int32_t first,
                  float momentum, float weight_decay, void* stream);
 
+/* ---- the trainers' random stream: dropout and per-epoch shift augmentation (csrc/ofp_train_random.h) ---------------
+ * Both trainers can regularise as the reference's train.py does: a dropout in front of the Linear head, and training
+ *   windows cut anew every epoch, each shifted by up to +-max_shift samples.  torch's random stream cannot be
+ *   reproduced; this is a documented stream of the library's own, and the user opts in by naming a seed.
+ * Generator: Philox4x32 with 10 rounds (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85;
+ *   round: p0 = M0 c0, p1 = M1 c2, c' = (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0)), then the key is bumped).
+ *   Key (seed & 0xffffffff, seed >> 32).  Counter (index / 4, site, epoch, 0), output word index % 4.  The epoch is the
+ *   0-based epoch of the run, read on the device from the run's control block, so every replay of the epoch graph
+ *   draws anew with no argument changed; ofp_*_loss_grads_random and the stand-alone forms take it as `epoch`.
+ * Site 0, dropout: index = s F + f over the features [n][F] that feed the Linear head; dropped iff word <
+ *   (uint32)(dropout_p 2^32); kept values are multiplied by (float)(1 / (1 - dropout_p)), dropped ones are 0; the
+ *   backward does the same to the gradient.  0 <= dropout_p < 1; 0 launches nothing.  The validation forward has none.
+ * Site 1, shifts: index = item; shift = ((word (2 max_shift + 1)) >> 32) - max_shift.  With n_extractions > 0 the
+ *   trainer ignores d_x and first gathers, every epoch, x[j][c][t] = d_audio[d_starts[j % n_onsets] + shift_j + t][c]
+ *   for the n = n_extractions * n_onsets items (item j = r * n_onsets + i is extraction r of onset i; d_y [n] is tiled
+ *   to match by the caller) from the interleaved audio [audio_len][audio_channels]; d_starts [n_onsets] int64 is the
+ *   hit's minimum onset less pre_samples.  The caller rules out windows that leave the audio (such rows read as 0).
+ *   n_extractions = 0: no window source, d_x is used as it is.
+ * ofp_*_train_random / ofp_*_loss_grads_random / ofp_*_train_random_workspace_bytes: the functions without
+ *   `_random`, which they are with random = NULL, plus these options (ofp_*_loss_grads_random takes no window source).
+ * ofp_philox4x32: d_counters [n][4], d_keys [n][2] -> d_out [n][4].  ofp_dropout_mask: d_mask [n][F] of 0 and
+ *   (float)(1 / (1 - p)).  ofp_shift_windows: d_shifts [n] (or NULL) and d_windows [n][channels][width], n =
+ *   n_extractions * n_onsets.  All three run the device code of the epoch graphs. */
+typedef struct ofp_train_random {
+    uint64_t seed;
+    double dropout_p;
+    int32_t epoch;          /* used where there is no control block */
+    int32_t max_shift;
+    int32_t n_extractions;  /* 0: no window source */
+    int32_t audio_channels;
+    const float* d_audio;
+    int64_t audio_len;
+    const int64_t* d_starts;
+    int64_t n_onsets;
+} ofp_train_random;
+int64_t ofp_cnn_train_random_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
+                                             const ofp_train_random* random);
+int ofp_cnn_train_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                         const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                         int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                         float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                         const ofp_train_random* random);
+int ofp_cnn_loss_grads_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                              const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                              void* stream, const ofp_train_random* random);
+int64_t ofp_cccnn_train_random_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
+                                               const ofp_train_random* random);
+int ofp_cccnn_train_random(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                           const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                           int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
+                           float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                           const ofp_train_random* random);
+int ofp_cccnn_loss_grads_random(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                                const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                                void* stream, const ofp_train_random* random);
+int ofp_philox4x32(const uint32_t* d_counters, const uint32_t* d_keys, int64_t n, uint32_t* d_out, void* stream);
+int ofp_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t F, double p, float* d_mask, void* stream);
+int ofp_shift_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_t audio_len, int32_t channels,
+                      const int64_t* d_starts, int64_t n_onsets, int32_t n_extractions, int32_t max_shift,
+                      int32_t width, int32_t* d_shifts, float* d_windows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

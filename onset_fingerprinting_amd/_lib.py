@@ -155,6 +155,19 @@ class CccnnConfig(ctypes.Structure):
     ]
 
 
+class TrainRandom(ctypes.Structure):
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("dropout_p", ctypes.c_double),
+        ("epoch", ctypes.c_int32), ("max_shift", ctypes.c_int32), ("n_extractions", ctypes.c_int32),
+        ("audio_channels", ctypes.c_int32),
+        ("d_audio", ctypes.c_void_p),
+        ("audio_len", ctypes.c_int64),
+        ("d_starts", ctypes.c_void_p),
+        ("n_onsets", ctypes.c_int64),
+    ]
+
+
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _f32p_h = ctypes.POINTER(ctypes.c_float)
 _long_p = ctypes.POINTER(ctypes.c_long)
@@ -313,6 +326,24 @@ SIGNATURES = {
     "ofp_autocorr_softmax_lds_bytes": (_i64, [_i32, _i32]),
     "ofp_autocorr_softmax_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ofp_sgd_step": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp]),
+    "ofp_cnn_train_random_workspace_bytes": (_i64, [ctypes.POINTER(CnnConfig), _i64, _i64,
+                                                    ctypes.POINTER(TrainRandom)]),
+    "ofp_cnn_train_random": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32,
+                                            _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                            ctypes.POINTER(TrainRandom)]),
+    "ofp_cnn_loss_grads_random": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                 _vp, ctypes.POINTER(TrainRandom)]),
+    "ofp_cccnn_train_random_workspace_bytes": (_i64, [ctypes.POINTER(CccnnConfig), _i64, _i64,
+                                                      ctypes.POINTER(TrainRandom)]),
+    "ofp_cccnn_train_random": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                              _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                              ctypes.POINTER(TrainRandom)]),
+    "ofp_cccnn_loss_grads_random": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _i64, _vp, ctypes.POINTER(TrainRandom)]),
+    "ofp_philox4x32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "ofp_dropout_mask": (ctypes.c_int, [ctypes.c_uint64, _i32, _i64, _i32, _f64, _vp, _vp]),
+    "ofp_shift_windows": (ctypes.c_int, [ctypes.c_uint64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
+                                         _vp, _vp]),
 }
 
 _lib = None

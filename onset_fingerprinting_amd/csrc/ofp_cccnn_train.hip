@@ -2,7 +2,9 @@
 // forward, mean L1 / MSE loss, backward through the correlation head, SGD with momentum and weight decay, and
 // optionally a validation pass with Lightning's early-stop rule.  As in csrc/ofp_cnn_train.hip one epoch is a linear
 // chain of short kernels on one stream, captured once as a hipGraph and replayed; the epoch index is a device counter
-// and once the stop word is set every kernel returns at once.
+// and once the stop word is set every kernel returns at once.  With random options (ofp_cccnn_train_random) the
+// epoch's windows come from k_shift_windows and the head's p goes through k_dropout_fwd in front of the Linear
+// (csrc/ofp_train_random.h), as in csrc/ofp_cnn_train.hip.
 //
 // The conv stack works on items: with group = 0 every (sample, sensor) pair is an item with 1 input channel (the
 // shared stack), with group = 1 every sample is an item with `sensors` input channels and a grouped convolution.
@@ -17,7 +19,7 @@
 // p . dp) are one workgroup's fp64 sums in an order fixed by the thread index.  Sums over the batch (GroupNorm's
 // d gamma / d beta, the convolution's weight and bias gradients, the Linear head's) go through the partial-slab
 // reducer of ofp_train_chain.h.  Results are bitwise reproducible.
-#include "ofp_train_chain.h"
+#include "ofp_train_random.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -244,11 +246,13 @@ __global__ __launch_bounds__(kT) void k_head_fwd(const Ctl* ctl, const float* __
 // Backward of the head for item (b, c) = (item / C, item % C): dp[j] = sum_o dout[b][o] Wfc[o][c L + j] (fmaf chain
 // over o), dot = sum_j p[j] dp[j] (fp64, fixed order), dcc[j] = p[j] (dp[j] - dot) (the difference in fp64: dp and
 // dot may nearly cancel), g[s] = dcc[V-1+s] + dcc[V-1-s], df_k[m] = sum_i g[i - m] f_k[i] (over i = 0 .. V-1 in
-// fp64, rounded once; the lag 0 carries 2 dcc[V-1]).  LDS: maps [K V], dcc [L], g [L].
+// fp64, rounded once; the lag 0 carries 2 dcc[V-1]).  LDS: maps [K V], dcc [L], g [L].  With kGiven the item's dp is
+// read from `dpin` [items][L] instead (k_fc_bwd's d h, the same fmaf chain, after k_dropout_bwd has gone over it).
+template <bool kGiven>
 __global__ __launch_bounds__(kT) void k_head_bwd(const Ctl* ctl, const float* __restrict__ x,
                                                  const float* __restrict__ prob, const float* __restrict__ dout,
                                                  const float* __restrict__ wfc, int C, int K, int V, int O,
-                                                 float* __restrict__ df) {
+                                                 float* __restrict__ df, const float* __restrict__ dpin) {
     OFP_CNN_STOPPED(ctl);
     extern __shared__ float sm[];
     __shared__ double red[2][kT / 64];
@@ -265,7 +269,10 @@ __global__ __launch_bounds__(kT) void k_head_bwd(const Ctl* ctl, const float* __
     double dot = 0.0, none = 0.0;
     for (int j = threadIdx.x; j < L; j += kT) {
         float dp = 0.0f;
-        for (int o = 0; o < O; ++o) dp = fmaf(dout[b * O + o], wfc[((int64_t)o * C + c) * L + j], dp);
+        if (kGiven)
+            dp = dpin[item * (int64_t)L + j];
+        else
+            for (int o = 0; o < O; ++o) dp = fmaf(dout[b * O + o], wfc[((int64_t)o * C + c) * L + j], dp);
         dcc[j] = dp;
         dot += (double)pr[j] * (double)dp;
     }
@@ -306,7 +313,7 @@ __global__ __launch_bounds__(kT) void k_sgd(const Ctl* ctl, const float* __restr
 
 size_t head_lds(int K, int V) { return ((size_t)K * V + 2 * (size_t)(2 * V - 1) + 64) * sizeof(float); }
 
-ofp::LdsAttrCache g_fwd_attr, g_bwd_attr;
+ofp::LdsAttrCache g_fwd_attr, g_bwd_attr, g_bwd_given_attr;
 
 int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int padding, int dilation, int groups,
                int stride) {
@@ -337,11 +344,11 @@ struct Plan {
     int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], fcw_off, fcb_off;
     // work space, byte offsets
     int64_t o_Z[kMaxConv], o_H[kMaxConv], o_stat[kMaxConv], o_P, o_out, o_dy, o_lpart, o_gh, o_gz, o_part, o_G, o_B,
-        o_ctl, bytes;
+        o_ctl, o_HD, o_DP, o_X, bytes;  // o_HD: the dropped p, o_DP: its gradient; o_X: the epoch's shifted windows
     int64_t items(int64_t n) const { return group ? n : n * C; }
 };
 
-int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p) {
+int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd = Random{}) {
     const char* who = "cccnn training";
     OFP_REQUIRE(c != nullptr, "%s: config is NULL", who);
     OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "%s: %d conv layers (limit: 1..%d)", who, c->n_conv, kMaxConv);
@@ -428,6 +435,8 @@ int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p) {
     p.o_G = take((int64_t)np * 4);
     p.o_B = take((int64_t)np * 4);
     p.o_ctl = take(sizeof(Ctl));
+    if (rnd.drop) p.o_HD = take(n * p.F * 4), p.o_DP = take(n * p.F * 4);
+    if (rnd.windows) p.o_X = take(n * p.C * c->width * 4);
     p.bytes = o;
     return OFP_OK;
 }
@@ -437,8 +446,9 @@ struct Run {
     char* ws;
     float* P;   // packed parameters
     float* G;   // packed gradients
-    Ctl* ctl;   // NULL: a single pass, epoch 0
+    Ctl* ctl;   // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
     hipStream_t st;
+    Random rnd;  // dropout in front of the Linear head and the window source; both off by default
     template <class T>
     T* at(int64_t off) const {
         return reinterpret_cast<T*>(ws + off);
@@ -494,10 +504,20 @@ int enqueue_head_fwd(const Ctl* ctl, const float* f, int64_t items, int K, int V
 }
 
 int enqueue_head_bwd(const Ctl* ctl, const float* f, const float* prob, const float* dout, const float* wfc,
-                     int64_t items, int C, int K, int V, int O, float* df, hipStream_t st) {
+                     int64_t items, int C, int K, int V, int O, float* df, hipStream_t st,
+                     const float* dpin = nullptr) {
     const size_t lds = head_lds(K, V);
-    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_head_bwd), lds, g_bwd_attr)) return rc;
-    hipLaunchKernelGGL(k_head_bwd, dim3((unsigned)items), dim3(kT), lds, st, ctl, f, prob, dout, wfc, C, K, V, O, df);
+    if (dpin != nullptr) {
+        if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_head_bwd<true>), lds, g_bwd_given_attr))
+            return rc;
+        hipLaunchKernelGGL(k_head_bwd<true>, dim3((unsigned)items), dim3(kT), lds, st, ctl, f, prob, dout, wfc, C, K,
+                           V, O, df, dpin);
+    } else {
+        if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_head_bwd<false>), lds, g_bwd_attr))
+            return rc;
+        hipLaunchKernelGGL(k_head_bwd<false>, dim3((unsigned)items), dim3(kT), lds, st, ctl, f, prob, dout, wfc, C, K,
+                           V, O, df, dpin);
+    }
     OFP_LAUNCH_CHECK("k_head_bwd");
     return OFP_OK;
 }
@@ -518,8 +538,13 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
     }
     float* prob = r.at<float>(p.o_P);
     if (int rc = enqueue_head_fwd(r.ctl, in, n * p.C, p.K, p.V, prob, r.st)) return rc;
+    const float* feat = prob;  // k_head_bwd needs the undropped p: the dropped copy has a buffer of its own
+    if (train && r.rnd.drop) {
+        if (int rc = enqueue_dropout_fwd(r.ctl, r.rnd, prob, r.at<float>(p.o_HD), n * p.F, r.st)) return rc;
+        feat = r.at<float>(p.o_HD);
+    }
     const float inv_numel = 1.0f / (float)(n * p.O);
-    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, prob, p.F, p.O, r.P + p.fcw_off,
+    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, feat, p.F, p.O, r.P + p.fcw_off,
                        r.P + p.fcb_off, y, train ? p.loss : 0, inv_numel, r.at<float>(p.o_out),
                        train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart));
     OFP_LAUNCH_CHECK("k_fc_fwd");
@@ -534,14 +559,19 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     double* part = r.at<double>(p.o_part);
     const int nchunk = (int)ofp::cdiv(n, kFcChunk);
     // the Linear head's weight gradient; the d p it also writes is not used (k_head_bwd forms its own, per item)
+    // unless there is a dropout: then it is masked in place and k_head_bwd takes it
+    float* DP = r.rnd.drop ? r.at<float>(p.o_DP) : nullptr;
     hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(p.F, kT), nchunk), dim3(kT), 0, r.st, r.ctl,
-                       r.at<float>(p.o_P), r.at<float>(p.o_dy), n, p.F, p.O, r.P + p.fcw_off, part, GH);
+                       r.at<float>(r.rnd.drop ? p.o_HD : p.o_P), r.at<float>(p.o_dy), n, p.F, p.O, r.P + p.fcw_off,
+                       part, DP ? DP : GH);
     OFP_LAUNCH_CHECK("k_fc_bwd");
     hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)p.O * p.F, kT)), dim3(kT), 0, r.st, r.ctl, part,
                        nchunk, (int64_t)p.O * p.F, r.G + p.fcw_off);
     OFP_LAUNCH_CHECK("k_fc_wfinal");
+    if (DP)
+        if (int rc = enqueue_dropout_bwd(r.ctl, r.rnd, DP, n * p.F, r.st)) return rc;
     if (int rc = enqueue_head_bwd(r.ctl, r.at<float>(p.o_H[p.L - 1]), r.at<float>(p.o_P), r.at<float>(p.o_dy),
-                                  r.P + p.fcw_off, n * p.C, p.C, p.K, p.V, p.O, GH, r.st))
+                                  r.P + p.fcw_off, n * p.C, p.C, p.K, p.V, p.O, GH, r.st, DP))
         return rc;
     for (int l = p.L - 1; l >= 0; --l) {
         const float* Z = r.at<float>(p.o_Z[l]);
@@ -572,6 +602,8 @@ struct TrainArgs {
 
 int enqueue_epoch(const Run& r, const TrainArgs& a) {
     const Plan& p = *r.p;
+    if (r.rnd.windows)  // a.x is the work space's window buffer
+        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.at<float>(p.o_X), nullptr, r.st)) return rc;
     if (int rc = enqueue_forward(r, a.x, a.y, a.n, true)) return rc;
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.n, p.O,
                        a.train_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
@@ -596,8 +628,15 @@ int enqueue_epoch(const Run& r, const TrainArgs& a) {
 extern "C" {
 
 int64_t ofp_cccnn_train_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val) {
+    return ofp_cccnn_train_random_workspace_bytes(cfg, n, n_val, nullptr);
+}
+
+int64_t ofp_cccnn_train_random_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
+                                               const ofp_train_random* random) {
     Plan p;
-    if (make_plan(cfg, n, n_val, p)) return -1;
+    Random rnd;
+    if (cfg == nullptr || make_random("cccnn training", random, n, cfg->sensors, cfg->width, true, rnd)) return -1;
+    if (make_plan(cfg, n, n_val, p, rnd)) return -1;
     return p.bytes;
 }
 
@@ -605,8 +644,22 @@ int ofp_cccnn_train(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, co
                     const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
                     int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss, float* d_val_loss,
                     int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream) {
+    return ofp_cccnn_train_random(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs,
+                                  patience, d_params, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream,
+                                  nullptr);
+}
+
+int ofp_cccnn_train_random(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                           const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                           int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
+                           float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                           const ofp_train_random* random) {
     Plan p;
-    if (int rc = make_plan(cfg, n, n_val, p)) return rc;
+    Random rnd;
+    OFP_REQUIRE(cfg != nullptr, "cccnn training: config is NULL");
+    if (int rc = make_random("ofp_cccnn_train", random, n, cfg->sensors, cfg->width, true, rnd)) return rc;
+    if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
+    if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
     OFP_REQUIRE(num_epochs >= 1 && min_epochs >= 0, "ofp_cccnn_train: num_epochs %d, min_epochs %d", num_epochs,
                 min_epochs);
     OFP_REQUIRE(d_x && d_y && d_rates && d_params && d_train_loss && h_epochs, "ofp_cccnn_train: NULL argument");
@@ -619,7 +672,7 @@ int ofp_cccnn_train(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, co
     OFP_REQUIRE(plain || st != nullptr,
                 "ofp_cccnn_train: the epoch graph cannot be captured on the null stream (pass a created stream, or "
                 "set OFP_CCCNN_GRAPH=nodes for plain launches)");
-    Run r{&p, (char*)d_ws, d_params, nullptr, nullptr, st};
+    Run r{&p, (char*)d_ws, d_params, nullptr, nullptr, st, rnd};
     r.G = r.at<float>(p.o_G);
     r.ctl = r.at<Ctl>(p.o_ctl);
     const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, n_val > 0 ? patience : -1,
@@ -679,11 +732,19 @@ int ofp_cccnn_train(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, co
 int ofp_cccnn_loss_grads(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
                          const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
                          void* stream) {
+    return ofp_cccnn_loss_grads_random(cfg, n, d_x, d_y, d_params, d_loss, d_grads, d_ws, ws_bytes, stream, nullptr);
+}
+
+int ofp_cccnn_loss_grads_random(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                                const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                                void* stream, const ofp_train_random* random) {
     Plan p;
-    if (int rc = make_plan(cfg, n, 0, p)) return rc;
+    Random rnd;
+    if (int rc = make_random("ofp_cccnn_loss_grads", random, n, 0, 0, false, rnd)) return rc;
+    if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cccnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cccnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
-    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream};
+    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream, rnd};
     if (int rc = enqueue_forward(r, d_x, d_y, n, true)) return rc;
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, (Ctl*)nullptr, r.at<double>(p.o_lpart), n, p.O,
                        d_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);

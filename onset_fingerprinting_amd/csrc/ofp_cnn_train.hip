@@ -3,6 +3,9 @@
 // early-stop rule -- one epoch is a linear chain of short kernels on one stream, captured once as a hipGraph and
 // replayed.  The epoch index (row of the rate table, slot of the loss curves) is a device counter that the chain's
 // last kernel advances, so every replay is the same graph; once the stop word is set every kernel returns at once.
+// With random options (ofp_cnn_train_random; csrc/ofp_train_random.h) the same counter drives a counter-based random
+// stream: the epoch's windows are cut from resident audio by k_shift_windows, the chain's first kernel, and the
+// features in front of the Linear head go through k_dropout_fwd (their gradient through k_dropout_bwd).
 //
 // Layer order as the reference builds it: conv + bias -> activation -> BatchNorm1d -> MaxPool1d(2, 2).  Only the
 // pre-activation z [B][C][Wc] and the layer's output [B][C][Wo] are kept; the activation, the normalised value and
@@ -17,7 +20,7 @@
 // sample) and over samples (backward, one thread per feature and chunk of 64 samples, the chunks added in order) in
 // fp64 as well.  Convolution forward and input
 // gradient are fp32 fmaf chains of at most cin/groups * k (cout/groups * k) terms, in k_conv1d's order.
-#include "ofp_train_chain.h"
+#include "ofp_train_random.h"
 
 #include <algorithm>
 #include <cmath>
@@ -230,6 +233,16 @@ __global__ __launch_bounds__(kT) void k_nadam(const Ctl* ctl, const float* __res
     }
 }
 
+// the generator alone (ofp_philox4x32): counters [n][4], keys [n][2] -> words [n][4]
+__global__ __launch_bounds__(kT) void k_philox(const uint32_t* __restrict__ counters, const uint32_t* __restrict__ keys,
+                                               int64_t n, uint32_t* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kT) {
+        const uint32_t* c = counters + i * 4;
+        const Words d = philox4x32_10(c[0], c[1], c[2], c[3], keys[i * 2], keys[i * 2 + 1]);
+        for (int u = 0; u < 4; ++u) out[i * 4 + u] = d.w[u];
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 
 
@@ -256,10 +269,10 @@ struct Plan {
     int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], rs_off[kMaxConv], fcw_off, fcb_off;
     // work space, byte offsets
     int64_t o_Z[kMaxConv], o_H[kMaxConv], o_out, o_dy, o_lpart, o_gh, o_gz, o_save, o_s12, o_part, o_G, o_M, o_V,
-        o_RS, o_ctl, bytes;
+        o_RS, o_ctl, o_HD, o_X, bytes;  // o_HD: the dropped features; o_X: the epoch's shifted windows
 };
 
-int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p) {
+int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd = Random{}) {
     OFP_REQUIRE(c != nullptr, "cnn training: config is NULL");
     OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "cnn training: %d conv layers (limit: 1..%d)", c->n_conv,
                 kMaxConv);
@@ -331,6 +344,8 @@ int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p) {
     p.o_V = take((int64_t)np * 4);
     p.o_RS = take((int64_t)ns * 4);
     p.o_ctl = take(sizeof(Ctl));
+    if (rnd.drop) p.o_HD = take(n * p.F * 4);
+    if (rnd.windows) p.o_X = take(n * c->channels[0] * c->width * 4);
     p.bytes = o;
     return OFP_OK;
 }
@@ -341,8 +356,9 @@ struct Run {
     float* P;    // packed parameters
     float* RS;   // packed running statistics
     float* G;    // packed gradients
-    Ctl* ctl;    // NULL: a single pass, epoch 0
+    Ctl* ctl;    // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
     hipStream_t st;
+    Random rnd;  // dropout in front of the Linear head and the window source; both off by default
     template <class T>
     T* at(int64_t off) const {
         return reinterpret_cast<T*>(ws + off);
@@ -416,6 +432,11 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
         OFP_LAUNCH_CHECK("k_post");
         in = H;
     }
+    if (train && r.rnd.drop) {
+        float* HD = r.at<float>(p.o_HD);
+        if (int rc = enqueue_dropout_fwd(r.ctl, r.rnd, in, HD, n * p.F, r.st)) return rc;
+        in = HD;
+    }
     const float inv_numel = 1.0f / (float)(n * p.O);
     hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, in, p.F, p.O, r.P + p.fcw_off,
                        r.P + p.fcb_off, y, train ? p.loss : 0, inv_numel, r.at<float>(p.o_out),
@@ -431,11 +452,14 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     double* part = r.at<double>(p.o_part);
     const int nchunk = (int)ofp::cdiv(n, kFcChunk);
     hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(p.F, kT), nchunk), dim3(kT), 0, r.st, r.ctl,
-                       r.at<float>(p.o_H[p.L - 1]), r.at<float>(p.o_dy), n, p.F, p.O, r.P + p.fcw_off, part, GH);
+                       r.at<float>(r.rnd.drop ? p.o_HD : p.o_H[p.L - 1]), r.at<float>(p.o_dy), n, p.F, p.O,
+                       r.P + p.fcw_off, part, GH);
     OFP_LAUNCH_CHECK("k_fc_bwd");
     hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)p.O * p.F, kT)), dim3(kT), 0, r.st, r.ctl, part,
                        nchunk, (int64_t)p.O * p.F, r.G + p.fcw_off);
     OFP_LAUNCH_CHECK("k_fc_wfinal");
+    if (r.rnd.drop)
+        if (int rc = enqueue_dropout_bwd(r.ctl, r.rnd, GH, n * p.F, r.st)) return rc;
     for (int l = p.L - 1; l >= 0; --l) {
         const Post t = post_of(r, l, p.bn ? 1 : 0);
         const float* Z = r.at<float>(p.o_Z[l]);
@@ -465,6 +489,8 @@ struct TrainArgs {
 
 int enqueue_epoch(const Run& r, const TrainArgs& a) {
     const Plan& p = *r.p;
+    if (r.rnd.windows)  // a.x is the work space's window buffer
+        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.at<float>(p.o_X), nullptr, r.st)) return rc;
     if (int rc = enqueue_forward(r, a.x, a.y, a.n, true)) return rc;
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.n, p.O,
                        a.train_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
@@ -492,8 +518,15 @@ extern "C" {
 int32_t ofp_cnn_train_slab(void) { return kSlab; }
 
 int64_t ofp_cnn_train_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val) {
+    return ofp_cnn_train_random_workspace_bytes(cfg, n, n_val, nullptr);
+}
+
+int64_t ofp_cnn_train_random_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
+                                             const ofp_train_random* random) {
     Plan p;
-    if (make_plan(cfg, n, n_val, p)) return -1;
+    Random rnd;
+    if (cfg == nullptr || make_random("cnn training", random, n, cfg->channels[0], cfg->width, true, rnd)) return -1;
+    if (make_plan(cfg, n, n_val, p, rnd)) return -1;
     return p.bytes;
 }
 
@@ -501,8 +534,22 @@ int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const 
                   const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
                   int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
                   float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream) {
+    return ofp_cnn_train_random(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs, patience,
+                                d_params, d_stats, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream,
+                                nullptr);
+}
+
+int ofp_cnn_train_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                         const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                         int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                         float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                         const ofp_train_random* random) {
     Plan p;
-    if (int rc = make_plan(cfg, n, n_val, p)) return rc;
+    Random rnd;
+    OFP_REQUIRE(cfg != nullptr, "cnn training: config is NULL");
+    if (int rc = make_random("ofp_cnn_train", random, n, cfg->channels[0], cfg->width, true, rnd)) return rc;
+    if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
+    if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
     OFP_REQUIRE(num_epochs >= 1 && min_epochs >= 0, "ofp_cnn_train: num_epochs %d, min_epochs %d", num_epochs,
                 min_epochs);
     OFP_REQUIRE(d_x && d_y && d_rates && d_params && d_train_loss && h_epochs, "ofp_cnn_train: NULL argument");
@@ -516,7 +563,7 @@ int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const 
     OFP_REQUIRE(plain || st != nullptr,
                 "ofp_cnn_train: the epoch graph cannot be captured on the null stream (pass a created stream, or set "
                 "OFP_CNN_GRAPH=nodes for plain launches)");
-    Run r{&p, (char*)d_ws, d_params, d_stats, nullptr, nullptr, st};
+    Run r{&p, (char*)d_ws, d_params, d_stats, nullptr, nullptr, st, rnd};
     r.G = r.at<float>(p.o_G);
     r.ctl = r.at<Ctl>(p.o_ctl);
     const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, n_val > 0 ? patience : -1,
@@ -576,12 +623,20 @@ int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const 
 int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
                        const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
                        void* stream) {
+    return ofp_cnn_loss_grads_random(cfg, n, d_x, d_y, d_params, d_loss, d_grads, d_ws, ws_bytes, stream, nullptr);
+}
+
+int ofp_cnn_loss_grads_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                              const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                              void* stream, const ofp_train_random* random) {
     Plan p;
-    if (int rc = make_plan(cfg, n, 0, p)) return rc;
+    Random rnd;
+    if (int rc = make_random("ofp_cnn_loss_grads", random, n, 0, 0, false, rnd)) return rc;
+    if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
     // the trainer's own forward and backward; the running statistics it would update are a scratch copy
-    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream};
+    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream, rnd};
     r.RS = r.at<float>(p.o_RS);
     OFP_HIP(hipMemsetAsync(r.RS, 0, (size_t)(p.ns > 0 ? p.ns : 1) * 4, r.st));
     if (int rc = enqueue_forward(r, d_x, d_y, n, true)) return rc;
@@ -665,6 +720,41 @@ int ofp_nadam_step(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t
                        d_g, d_m, d_v, n);
     OFP_LAUNCH_CHECK("k_nadam");
     return OFP_OK;
+}
+
+// ---- the random stream alone (csrc/ofp_train_random.h), by the kernels the two epoch graphs run -------------------------
+
+int ofp_philox4x32(const uint32_t* d_counters, const uint32_t* d_keys, int64_t n, uint32_t* d_out, void* stream) {
+    OFP_REQUIRE(d_counters && d_keys && d_out && n >= 1, "ofp_philox4x32: NULL argument or n < 1");
+    hipLaunchKernelGGL(k_philox, dim3(grid_for(n)), dim3(kT), 0, (hipStream_t)stream, d_counters, d_keys, n, d_out);
+    OFP_LAUNCH_CHECK("k_philox");
+    return OFP_OK;
+}
+
+int ofp_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t F, double p, float* d_mask, void* stream) {
+    OFP_REQUIRE(d_mask && n >= 1 && F >= 1 && n * F <= ((int64_t)1 << 32),
+                "ofp_dropout_mask: NULL mask, or n %lld x F %d outside 1..2^32 elements", (long long)n, F);
+    ofp_train_random o{};
+    o.seed = seed, o.epoch = epoch, o.dropout_p = p;
+    Random r;
+    if (int rc = make_random("ofp_dropout_mask", &o, n, 0, 0, false, r)) return rc;
+    return enqueue_dropout_fwd(nullptr, r, nullptr, d_mask, n * F, (hipStream_t)stream);
+}
+
+int ofp_shift_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_t audio_len, int32_t channels,
+                      const int64_t* d_starts, int64_t n_onsets, int32_t n_extractions, int32_t max_shift,
+                      int32_t width, int32_t* d_shifts, float* d_windows, void* stream) {
+    OFP_REQUIRE(d_windows && channels >= 1 && width >= 1 && n_extractions >= 1 && n_onsets >= 1 &&
+                    n_onsets * n_extractions <= (1 << 20),
+                "ofp_shift_windows: NULL windows, or %d channels, width %d, %lld onsets x %d extractions", channels,
+                width, (long long)n_onsets, n_extractions);
+    ofp_train_random o{};
+    o.seed = seed, o.epoch = epoch, o.max_shift = max_shift, o.n_extractions = n_extractions;
+    o.audio_channels = channels, o.d_audio = d_audio, o.audio_len = audio_len, o.d_starts = d_starts;
+    o.n_onsets = n_onsets;
+    Random r;
+    if (int rc = make_random("ofp_shift_windows", &o, n_onsets * n_extractions, channels, width, true, r)) return rc;
+    return enqueue_shift_windows(nullptr, r, d_windows, d_shifts, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,8 +5,10 @@ hot-path functions of the reference's ``onset_fingerprinting/data.py``
 batched forms the pipeline uses.  All arithmetic on sample data runs in the HIP
 kernels of ``csrc/ofp_spectral.hip``; there is no CPU path.
 
-Datasets (POSD/MCPOSD), augmentation and json/wav parsing are out of scope
-(SURVEY.md section 2).
+Datasets (POSD/MCPOSD), stretch augmentation inside the trainers and json/wav
+parsing are out of scope; ``ShiftedWindows`` is the window
+source with per-epoch shift augmentation that ``model.fit_cnn`` /
+``model.fit_lcccnn`` take in place of ``x``.
 """
 import ctypes
 
@@ -448,3 +450,78 @@ class FastFrameExtractor:
             shifts = torch.randint(-self.max_shift, self.max_shift + 1, (len(self._onsets),), device=self.device)
             return self._frames(self._onsets - (self.pre_samples - shifts.cpu().numpy()))
         return self.frames
+
+
+def check_seed(seed):
+    """The seed of the trainers' random stream (include/onsetfp.h): an int in [0, 2**64)."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed!r}: an integer with 0 <= seed < 2**64 is needed")
+    return int(seed)
+
+
+class ShiftedWindows:
+    """A window source for ``model.fit_cnn`` / ``model.fit_lcccnn`` in place of ``x``: what the reference's
+    ``MCPOSD.from_file(..., w, pre_samp, max_shift, n_extractions)`` feeds its trainer.  Every hit gives
+    ``n_extractions`` windows of ``frame_length`` samples that start at its minimum onset less ``pre_samples``, each
+    shifted by up to +-``max_shift`` samples, and -- as ``FastFrameExtractor.__call__`` draws its shifts anew at every
+    ``__getitem__`` -- the shifts change with the epoch.  They come from this package's own stream (Philox4x32-10 keyed
+    by the seed, counter (item / 4, 1, epoch, 0); include/onsetfp.h), not from torch's: the trainer's epoch graph cuts
+    the windows from the audio itself as its first kernel.
+
+    ``audio`` [N, C] or [N] is copied to HBM at the first use and kept there.  Item ``j = r * n_onsets + i`` is
+    extraction ``r`` of onset ``i``, MCPOSD's concatenation order; ``y`` [n_onsets, outputs] is tiled to match by the
+    fit functions.  ``IndexError`` at construction if any shift could take a window out of the audio."""
+
+    def __init__(self, audio, onsets, frame_length, pre_samples=0, max_shift=0, n_extractions=1, device=0):
+        self.frame_length, self.pre_samples = int(frame_length), int(pre_samples)
+        self.max_shift, self.n_extractions = int(max_shift), int(n_extractions)
+        if self.frame_length < 1 or self.max_shift < 0 or self.n_extractions < 1:
+            raise ValueError("frame_length and n_extractions must be at least 1 and max_shift at least 0")
+        a = np.ascontiguousarray(audio, dtype=np.float32)
+        if a.ndim not in (1, 2):
+            raise ValueError(f"audio {a.shape}: expected [N, C] or [N]")
+        self._one_d = a.ndim == 1
+        self._audio = a[:, None] if self._one_d else a
+        onsets = np.asarray(onsets, dtype=np.int64)
+        self.starts = np.ascontiguousarray((onsets.min(1) if onsets.ndim == 2 else onsets) - self.pre_samples)
+        if self.starts.ndim != 1 or len(self.starts) < 1:
+            raise ValueError("onsets: expected [n_onsets] or [n_onsets, sensors], at least one")
+        if self.starts.min() - self.max_shift < 0 or \
+                self.starts.max() + self.max_shift + self.frame_length > self._audio.shape[0]:
+            raise IndexError("frame outside the audio array")
+        self.device = device
+        self.n_onsets, self.channels = len(self.starts), self._audio.shape[1]
+        self.n = self.n_onsets * self.n_extractions
+        self._resident = None
+
+    def resident(self):
+        """(audio, starts) on the GPU: float32 [N, C] and int64 [n_onsets]."""
+        if self._resident is None:
+            dev = _device(self.device)
+            self._resident = (torch.from_numpy(self._audio).to(dev).contiguous(), torch.from_numpy(self.starts).to(dev))
+        return self._resident
+
+    def _cut(self, seed, epoch):
+        if self.max_shift > 0 and seed is None:
+            raise ValueError("max_shift > 0 needs a seed")
+        seed = 0 if seed is None else check_seed(seed)
+        if int(epoch) < 0:
+            raise ValueError("epoch must not be negative")
+        x, st = self.resident()
+        shifts = torch.empty(self.n, dtype=torch.int32, device=x.device)
+        out = torch.empty((self.n, self.channels, self.frame_length), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(_lib.lib().ofp_shift_windows(seed, int(epoch), x.data_ptr(), x.shape[0], self.channels, st.data_ptr(),
+                                               self.n_onsets, self.n_extractions, self.max_shift, self.frame_length,
+                                               shifts.data_ptr(), out.data_ptr(), _stream(x.device)),
+                  "ofp_shift_windows")
+        return shifts, out
+
+    def shifts(self, seed=None, epoch=0):
+        """int32 GPU tensor [n]: the shifts the epoch graph uses at `epoch` of a fit with `seed`."""
+        return self._cut(seed, epoch)[0]
+
+    def windows(self, seed=None, epoch=0):
+        """float32 GPU tensor [n, C, W] ([n, W] for 1-D audio): the training batch of that epoch."""
+        out = self._cut(seed, epoch)[1]
+        return out[:, 0, :] if self._one_d else out

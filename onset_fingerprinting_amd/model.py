@@ -10,8 +10,9 @@ csrc/ofp_rnn.hip); torch only allocates memory and makes views.  ``rnn_forward``
 (full batch, NAdam, cosine warm restarts every 250 epochs) as one graph of HIP kernels per epoch
 (csrc/ofp_cnn_train.hip).  ``fit_lcccnn`` trains an ``LCCCNN`` in place with the recipe of its own ``training_step`` /
 ``configure_optimizers`` (full batch, SGD with momentum 0.8 and weight decay 1e-3 at 100 x ``lr``, cosine annealing over
-100 epochs) the same way (csrc/ofp_cccnn_train.hip).  Training the recurrent classes is out of scope (DESIGN.md
-section 7).
+100 epochs) the same way (csrc/ofp_cccnn_train.hip).  With ``seed=`` both apply the model's dropout and, given a
+``data.ShiftedWindows``, cut shifted training windows anew every epoch, from this package's own random stream
+(csrc/ofp_train_random.h).  Training the recurrent classes is out of scope.
 """
 import ctypes
 import functools
@@ -25,6 +26,7 @@ from torch.nn import functional as F
 from . import _lib
 from ._lib import check
 from .calibration import ACT_CODES, _loss_code, dense_forward
+from .data import ShiftedWindows, check_seed
 
 
 def _stream(dev):
@@ -538,11 +540,62 @@ def _cnn_device_rows(lr, num_epochs):
     return rows
 
 
-def _cnn_arch(model, width=None):
+def _check_dropout(p, seed):
+    """The trainers' dropout is this package's own stream (include/onsetfp.h) and needs the user's seed."""
+    if seed is not None:
+        check_seed(seed)
+    if not 0 <= p < 1:
+        raise ValueError(f"dropout_rate {p}: the trainer needs 0 <= dropout_rate < 1")
+    if p > 0 and seed is None:
+        raise ValueError(f"dropout_rate {p} cannot be trained on the GPU: torch's dropout stream cannot "
+                         "be matched (construct the model with dropout_rate=0.0, or pass seed= for this package's "
+                         "own dropout stream)")
+
+
+def _train_random(p, seed, epoch=0, source=None):
+    """(_lib.TrainRandom or None, what it points to): the random options of a trainer call.  None when nothing is
+    random (no dropout, no window source): the call is then the one without options."""
+    if (seed is None or p == 0) and source is None:
+        return None, None
+    if int(epoch) < 0:
+        raise ValueError("epoch must not be negative")
+    r = _lib.TrainRandom()
+    r.epoch = int(epoch)
+    if seed is not None:
+        r.seed, r.dropout_p = int(seed), float(p)
+    keep = None
+    if source is not None:
+        keep = audio, starts = source.resident()
+        r.max_shift, r.n_extractions, r.audio_channels = source.max_shift, source.n_extractions, source.channels
+        r.d_audio, r.audio_len, r.d_starts, r.n_onsets = audio.data_ptr(), audio.shape[0], starts.data_ptr(), \
+            source.n_onsets
+    return r, keep
+
+
+def _batch_of(x, y, what):
+    """(x, y, (n, channels, width)) of a batch; x may be a data.ShiftedWindows, whose y [n_onsets, outputs] is tiled."""
+    if isinstance(x, ShiftedWindows):
+        if what != "x":
+            raise ValueError("a window source cannot be x_val: the validation forward takes the windows themselves")
+        y = torch.as_tensor(y)
+        if y.dim() != 2 or y.shape[0] != x.n_onsets:
+            raise ValueError(f"y {tuple(y.shape)}: expected [{x.n_onsets}, outputs], one row per onset of the window "
+                             "source")
+        return x, y.repeat(x.n_extractions, 1), (x.n, x.channels, x.frame_length)
+    x, y = torch.as_tensor(x), torch.as_tensor(y)
+    if x.dim() != 3 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)}: expected [n, channels, width] and [n, outputs]")
+    return x, y, tuple(int(d) for d in x.shape)
+
+
+def _check_source(x, seed):
+    if isinstance(x, ShiftedWindows) and x.max_shift > 0 and seed is None:
+        raise ValueError("a window source with max_shift > 0 needs seed=")
+
+
+def _cnn_arch(model, width=None, seed=None):
     """(CnnConfig, convs, batch norms) of a CNN for the trainer; ValueError for what it cannot run."""
-    if model.dropout.p > 0:
-        raise ValueError(f"dropout_rate {model.dropout.p} cannot be trained on the GPU: torch's dropout stream cannot "
-                         "be matched (construct the model with dropout_rate=0.0)")
+    _check_dropout(model.dropout.p, seed)
     loss = _loss_code(model.loss)
     mods = list(model.conv_layers)
     convs = [m for m in mods if isinstance(m, nn.Conv1d)]
@@ -605,9 +658,9 @@ def _cnn_arch(model, width=None):
     return cfg, convs, bns
 
 
-def _cnn_tensors(model):
+def _cnn_tensors(model, seed=None):
     """[(state_dict name, tensor)] of the parameters in packing order, and the running statistics likewise."""
-    _cfg, convs, bns = _cnn_arch(model)
+    _cfg, convs, bns = _cnn_arch(model, seed=seed)
     names = {id(m): n for n, m in model.conv_layers.named_children()}
     ps, st = [], []
     for i, conv in enumerate(convs):
@@ -627,22 +680,22 @@ def _flat(tensors, dev):
     return torch.cat([t.detach().reshape(-1).to(dev, torch.float32) for _n, t in tensors]).contiguous()
 
 
-def _cnn_batch(model, x, y, what="x"):
-    x, y = torch.as_tensor(x), torch.as_tensor(y)
-    if x.dim() != 3 or y.dim() != 2 or x.shape[0] != y.shape[0]:
-        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)}: expected [n, channels, width] and [n, outputs]")
-    if not 1 <= x.shape[0] <= CNN_TRAIN_MAX_BATCH:
-        raise ValueError(f"{x.shape[0]} windows: the trainer's limit is 1..{CNN_TRAIN_MAX_BATCH} (one full batch)")
-    cfg, _c, bns = _cnn_arch(model, int(x.shape[2]))
-    if x.shape[1] != cfg.channels[0] or y.shape[1] != cfg.n_out:
-        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)} do not fit a model of {cfg.channels[0]} "
+def _cnn_batch(model, x, y, what="x", seed=None):
+    x, y, shape = _batch_of(x, y, what)
+    if not 1 <= shape[0] <= CNN_TRAIN_MAX_BATCH:
+        raise ValueError(f"{shape[0]} windows: the trainer's limit is 1..{CNN_TRAIN_MAX_BATCH} (one full batch)")
+    cfg, _c, bns = _cnn_arch(model, shape[2], seed)
+    if shape[1] != cfg.channels[0] or y.shape[1] != cfg.n_out:
+        raise ValueError(f"{what} {shape} / y {tuple(y.shape)} do not fit a model of {cfg.channels[0]} "
                          f"channels and {cfg.n_out} outputs")
-    if bns and x.shape[0] * (x.shape[2] + 2 * cfg.padding - cfg.dilation * (cfg.kernel - 1)) < 2:
+    if bns and shape[0] * (shape[2] + 2 * cfg.padding - cfg.dilation * (cfg.kernel - 1)) < 2:
         raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
     return x, y, cfg
 
 
 def _train_device(model, x):
+    if isinstance(x, ShiftedWindows):
+        return x.resident()[0].device
     if x.is_cuda:
         return x.device
     p = model.fc.weight
@@ -653,28 +706,32 @@ def _workspace(nbytes, dev):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
-def cnn_loss_and_grads_device(model, x, y):
+def cnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
     """Loss (``model.loss``) and the gradient of every parameter of a CNN for the full batch x [n, channels, width],
     y [n, outputs], in training mode (BatchNorm on batch statistics; the module's running statistics are not
-    touched), by the trainer's own forward and backward kernels.  Returns (loss, {state_dict name: gradient}) on
-    the GPU."""
-    x, y, cfg = _cnn_batch(model, x, y)
+    touched), by the trainer's own forward and backward kernels.  With a seed the model's dropout is applied as
+    epoch `epoch` of ``fit_cnn(..., seed=seed)`` applies it (``dropout_mask_device``).  Returns (loss, {state_dict
+    name: gradient}) on the GPU."""
+    x, y, cfg = _cnn_batch(model, x, y, seed=seed)
+    rnd, _keep = _train_random(model.dropout.p, seed, epoch)
     dev = _train_device(model, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
-    ps, _st = _cnn_tensors(model)
+    ps, _st = _cnn_tensors(model, seed)
     p0 = _flat(ps, dev)
     xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     grads = torch.empty_like(p0)
     n = int(xd.shape[0])
-    ws_bytes = int(L.ofp_cnn_train_workspace_bytes(ctypes.byref(cfg), n, 0))
+    rp = ctypes.byref(rnd) if rnd is not None else None
+    ws_bytes = int(L.ofp_cnn_train_random_workspace_bytes(ctypes.byref(cfg), n, 0, rp))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
     with torch.cuda.device(dev):
-        check(L.ofp_cnn_loss_grads(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(), loss.data_ptr(),
-                                   grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)), "ofp_cnn_loss_grads")
+        check(L.ofp_cnn_loss_grads_random(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
+                                          loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev),
+                                          rp), "ofp_cnn_loss_grads")
     named, o = {}, 0
     for name, t in ps:
         named[name] = grads[o:o + t.numel()].reshape(t.shape)
@@ -682,7 +739,7 @@ def cnn_loss_and_grads_device(model, x, y):
     return loss[0], named
 
 
-def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None):
+def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
     """Train a ``CNN`` in place, as ``Trainer.fit(model, ...)`` does with the reference's recipe (model.py:122-162,
     train.py): the whole of x [n, channels, width] / y [n, outputs] is one batch; every epoch is one training-mode
     forward, ``model.loss`` (F.l1_loss or F.mse_loss), backward and one NAdam step at the learning rate of
@@ -697,17 +754,27 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
 
     Parameters, BatchNorm running statistics and num_batches_tracked of `model` are updated where they live (CPU or
     GPU) and the model is left in eval mode.  Returns a record with ``train_loss`` and ``val_loss`` (or None): float32
-    GPU tensors [max_epochs], NaN beyond the epochs run; ``epochs``: epochs run; ``lrs``: float64 [epochs].
+    GPU tensors [max_epochs], NaN beyond the epochs run; ``epochs``: epochs run; ``lrs``: float64 [epochs]; ``seed``.
 
-    ValueError, before anything runs on the GPU: dropout_rate > 0, a loss other than F.l1_loss / F.mse_loss, an
+    ``seed`` (an int in [0, 2**64)) opts into this package's own random stream (Philox4x32-10 keyed by the seed and
+    counted by epoch and element; include/onsetfp.h), which is not torch's: ``model.dropout`` is then applied to the
+    features in front of ``fc`` in the training forward, with a new mask every epoch (``dropout_mask_device`` returns
+    the mask of any epoch); the validation forward is eval mode and has none.  ``x`` may be a ``data.ShiftedWindows``:
+    the epoch graph then cuts the training windows from its audio as its first kernel, shifted anew every epoch, and
+    ``y`` is [n_onsets, outputs] (tiled over the extractions); with ``max_shift > 0`` that needs the seed too.
+
+    ValueError, before anything runs on the GPU: dropout_rate > 0 without a seed, dropout_rate >= 1, a seed out of
+    range, a window source as x_val or with other rows in y than onsets, a loss other than F.l1_loss / F.mse_loss, an
     activation without HIP implementation, BatchNorm1d(momentum=None), shapes beyond the limits (3 conv layers, 128
     channels, kernel 8, window 512, batch 1024, 16 outputs)."""
-    x, y, cfg = _cnn_batch(model, x, y)
+    x, y, cfg = _cnn_batch(model, x, y, seed=seed)
+    _check_source(x, seed)
+    source = x if isinstance(x, ShiftedWindows) else None
     have_val = x_val is not None or y_val is not None
     if have_val:
         if x_val is None or y_val is None:
             raise ValueError("x_val and y_val go together")
-        x_val, y_val, cfg_v = _cnn_batch(model, x_val, y_val, "x_val")
+        x_val, y_val, cfg_v = _cnn_batch(model, x_val, y_val, "x_val", seed)
         if cfg_v.width != cfg.width:
             raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
     max_epochs, min_epochs = int(max_epochs), int(min_epochs)
@@ -720,16 +787,18 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
     dev = _train_device(model, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
-    ps, st = _cnn_tensors(model)
+    ps, st = _cnn_tensors(model, seed)
     params, stats = _flat(ps, dev), _flat(st, dev)
     to = lambda t: t.detach().to(dev, torch.float32).contiguous()
-    xd, yd = to(x), to(y)
+    xd, yd = (None if source else to(x)), to(y)
+    rnd, _keep = _train_random(model.dropout.p, seed, 0, source)
+    rp = ctypes.byref(rnd) if rnd is not None else None
     xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
     rows = torch.from_numpy(_cnn_device_rows(lr, max_epochs)).to(dev)
     train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
     val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
-    n, nv = int(xd.shape[0]), int(xv.shape[0]) if have_val else 0
-    ws_bytes = int(L.ofp_cnn_train_workspace_bytes(ctypes.byref(cfg), n, nv))
+    n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
+    ws_bytes = int(L.ofp_cnn_train_random_workspace_bytes(ctypes.byref(cfg), n, nv, rp))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
@@ -741,11 +810,11 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
     side = torch.cuda.Stream(dev)
     side.wait_stream(cur)
     with torch.cuda.device(dev):
-        check(L.ofp_cnn_train(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), nv, ptr(xv), ptr(yv),
-                              rows.data_ptr(), max_epochs, min_epochs, -1 if patience is None else int(patience),
-                              params.data_ptr(), stats.data_ptr(), train_loss.data_ptr(), ptr(val_loss),
-                              ctypes.byref(epochs), ws.data_ptr(), ws_bytes, ctypes.c_void_p(side.cuda_stream)),
-              "ofp_cnn_train")
+        check(L.ofp_cnn_train_random(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                                     rows.data_ptr(), max_epochs, min_epochs,
+                                     -1 if patience is None else int(patience), params.data_ptr(), stats.data_ptr(),
+                                     train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(),
+                                     ws_bytes, ctypes.c_void_p(side.cuda_stream), rp), "ofp_cnn_train")
     cur.wait_stream(side)
     with torch.no_grad():
         for flat, tensors in ((params, ps), (stats, st)):
@@ -758,7 +827,30 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
                 m.num_batches_tracked += epochs.value
     model.eval()
     return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
-                           lrs=np.array(cnn_rates(lr, max_epochs)[:epochs.value]))
+                           lrs=np.array(cnn_rates(lr, max_epochs)[:epochs.value]), seed=seed)
+
+
+def dropout_mask_device(seed, epoch, n, features, p, device=0, *, out=None):
+    """The dropout mask of epoch `epoch` of a fit with `seed`: float32 GPU tensor [n, features] of 0 (dropped) and
+    float32(1 / (1 - p)) (kept), by the kernel the epoch graph runs (``ofp_dropout_mask``).  ``out``: a contiguous
+    float32 GPU tensor [n, features] to write into."""
+    seed = check_seed(seed)
+    n, features = int(n), int(features)
+    if not 0 <= p < 1 or n < 1 or features < 1 or int(epoch) < 0:
+        raise ValueError("dropout_mask_device needs 0 <= p < 1, n >= 1, features >= 1 and epoch >= 0")
+    if out is not None:
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (n, features)):
+            raise ValueError("out must be a contiguous float32 GPU tensor [n, features]")
+        dev = out.device
+    else:
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    _lib.require_gpu(dev.index or 0)
+    if out is None:
+        out = torch.empty((n, features), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().ofp_dropout_mask(seed, int(epoch), n, features, float(p), out.data_ptr(), _stream(dev)),
+              "ofp_dropout_mask")
+    return out
 
 
 def conv1d_backward(x, weight, dz, padding, dilation, groups=1, *, dx=None, dw=None, db=None, need_dx=True):
@@ -863,12 +955,10 @@ def _cccnn_net(model):
     return model.model
 
 
-def _cccnn_arch(model, width=None):
+def _cccnn_arch(model, width=None, seed=None):
     """(CccnnConfig, convs, group norms) of an LCCCNN for the trainer; ValueError for what it cannot run."""
     net = _cccnn_net(model)
-    if net.dropout.p > 0:
-        raise ValueError(f"dropout_rate {net.dropout.p} cannot be trained on the GPU: torch's dropout stream cannot "
-                         "be matched (construct the model with dropout_rate=0.0)")
+    _check_dropout(net.dropout.p, seed)
     loss = _loss_code(model.loss)
     mods = list(net.conv_layers)
     convs = [m for m in mods if isinstance(m, nn.Conv1d)]
@@ -943,9 +1033,9 @@ def _cccnn_arch(model, width=None):
     return cfg, convs, gns
 
 
-def _cccnn_tensors(model):
+def _cccnn_tensors(model, seed=None):
     """[(state_dict name, tensor)] of an LCCCNN's parameters in packing order."""
-    _cfg, convs, gns = _cccnn_arch(model)
+    _cfg, convs, gns = _cccnn_arch(model, seed=seed)
     net = model.model
     names = {id(m): n for n, m in net.conv_layers.named_children()}
     ps = []
@@ -959,43 +1049,44 @@ def _cccnn_tensors(model):
     return ps
 
 
-def _cccnn_batch(model, x, y, what="x"):
-    x, y = torch.as_tensor(x), torch.as_tensor(y)
-    if x.dim() != 3 or y.dim() != 2 or x.shape[0] != y.shape[0]:
-        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)}: expected [n, channels, width] and [n, outputs]")
+def _cccnn_batch(model, x, y, what="x", seed=None):
+    x, y, shape = _batch_of(x, y, what)
     C = _cccnn_net(model).channels
-    if not 1 <= x.shape[0] <= CCCNN_TRAIN_MAX_BATCH or x.shape[0] * C > CCCNN_TRAIN_MAX_ITEMS:
-        raise ValueError(f"{x.shape[0]} windows of {C} channels: the trainer's limits are 1..{CCCNN_TRAIN_MAX_BATCH} "
+    if not 1 <= shape[0] <= CCCNN_TRAIN_MAX_BATCH or shape[0] * C > CCCNN_TRAIN_MAX_ITEMS:
+        raise ValueError(f"{shape[0]} windows of {C} channels: the trainer's limits are 1..{CCCNN_TRAIN_MAX_BATCH} "
                          f"windows and {CCCNN_TRAIN_MAX_ITEMS} (window, channel) pairs (one full batch)")
-    cfg, _c, _g = _cccnn_arch(model, int(x.shape[2]))
-    if x.shape[1] != C or y.shape[1] != cfg.n_out:
-        raise ValueError(f"{what} {tuple(x.shape)} / y {tuple(y.shape)} do not fit a model of {C} channels and "
+    cfg, _c, _g = _cccnn_arch(model, shape[2], seed)
+    if shape[1] != C or y.shape[1] != cfg.n_out:
+        raise ValueError(f"{what} {shape} / y {tuple(y.shape)} do not fit a model of {C} channels and "
                          f"{cfg.n_out} outputs")
     return x, y, cfg
 
 
-def cccnn_loss_and_grads_device(model, x, y):
+def cccnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
     """Loss (``model.loss``) and the gradient of every parameter of an LCCCNN for the full batch x [n, channels,
-    width], y [n, outputs], by the trainer's own forward and backward kernels.  Returns (loss, {state_dict name:
+    width], y [n, outputs], by the trainer's own forward and backward kernels.  With a seed the model's dropout is
+    applied as epoch `epoch` of ``fit_lcccnn(..., seed=seed)`` applies it.  Returns (loss, {state_dict name:
     gradient}) on the GPU."""
-    x, y, cfg = _cccnn_batch(model, x, y)
+    x, y, cfg = _cccnn_batch(model, x, y, seed=seed)
+    rnd, _keep = _train_random(model.model.dropout.p, seed, epoch)
     dev = _train_device(model.model, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
-    ps = _cccnn_tensors(model)
+    ps = _cccnn_tensors(model, seed)
     p0 = _flat(ps, dev)
     xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     grads = torch.empty_like(p0)
     n = int(xd.shape[0])
-    ws_bytes = int(L.ofp_cccnn_train_workspace_bytes(ctypes.byref(cfg), n, 0))
+    rp = ctypes.byref(rnd) if rnd is not None else None
+    ws_bytes = int(L.ofp_cccnn_train_random_workspace_bytes(ctypes.byref(cfg), n, 0, rp))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
     with torch.cuda.device(dev):
-        check(L.ofp_cccnn_loss_grads(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
-                                     loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)),
-              "ofp_cccnn_loss_grads")
+        check(L.ofp_cccnn_loss_grads_random(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
+                                            loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev),
+                                            rp), "ofp_cccnn_loss_grads")
     named, o = {}, 0
     for name, t in ps:
         named[name] = grads[o:o + t.numel()].reshape(t.shape)
@@ -1003,7 +1094,7 @@ def cccnn_loss_and_grads_device(model, x, y):
     return loss[0], named
 
 
-def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None):
+def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
     """Train an ``LCCCNN`` in place, as ``Trainer.fit(model, ...)`` does with the reference's recipe (model.py:541-629,
     train.py): the whole of x [n, channels, width] / y [n, outputs] is one batch; every epoch is one forward,
     ``model.loss`` (F.l1_loss or F.mse_loss), backward and one SGD step (momentum 0.8, weight decay 1e-3 on every
@@ -1020,19 +1111,27 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
 
     The parameters of `model` are updated where they live (CPU or GPU) and the model is left in eval mode.  Returns a
     record with ``train_loss`` and ``val_loss`` (or None): float32 GPU tensors [max_epochs], NaN beyond the epochs
-    run; ``epochs``: epochs run; ``lrs``: float64 [epochs].
+    run; ``epochs``: epochs run; ``lrs``: float64 [epochs]; ``seed``.
 
-    ValueError, before anything runs on the GPU: dropout_rate > 0, a loss other than F.l1_loss / F.mse_loss, an
+    ``seed`` and a ``data.ShiftedWindows`` as ``x`` work as in ``fit_cnn``: the seed opts into this package's own
+    random stream, with which the net's dropout is applied to the head's softmax values in front of ``fc`` in the
+    training forward (a new mask every epoch, none in the validation forward), and the window source makes the epoch
+    graph cut its training windows from the resident audio, shifted anew every epoch.
+
+    ValueError, before anything runs on the GPU: dropout_rate > 0 without a seed, dropout_rate >= 1, a seed out of
+    range, a window source as x_val or with other rows in y than onsets, a loss other than F.l1_loss / F.mse_loss, an
     activation without HIP implementation, shapes beyond the limits: 1..8 conv layers, kernel size 64, stride 4, 64
     channels per layer (layer size x sensor channels when group=True), window 512, 1024 windows and 4096 (window,
     sensor) pairs, 16 outputs, a head of K maps x V columns with cccnn_head_lds_bytes(K, V) <= 160 KiB, and every
     layer must leave at least one column."""
-    x, y, cfg = _cccnn_batch(model, x, y)
+    x, y, cfg = _cccnn_batch(model, x, y, seed=seed)
+    _check_source(x, seed)
+    source = x if isinstance(x, ShiftedWindows) else None
     have_val = x_val is not None or y_val is not None
     if have_val:
         if x_val is None or y_val is None:
             raise ValueError("x_val and y_val go together")
-        x_val, y_val, cfg_v = _cccnn_batch(model, x_val, y_val, "x_val")
+        x_val, y_val, cfg_v = _cccnn_batch(model, x_val, y_val, "x_val", seed)
         if cfg_v.width != cfg.width:
             raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
     max_epochs, min_epochs = int(max_epochs), int(min_epochs)
@@ -1045,16 +1144,18 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
     dev = _train_device(model.model, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
-    ps = _cccnn_tensors(model)
+    ps = _cccnn_tensors(model, seed)
     params = _flat(ps, dev)
     to = lambda t: t.detach().to(dev, torch.float32).contiguous()
-    xd, yd = to(x), to(y)
+    xd, yd = (None if source else to(x)), to(y)
+    rnd, _keep = _train_random(model.model.dropout.p, seed, 0, source)
+    rp = ctypes.byref(rnd) if rnd is not None else None
     xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
     rates = torch.from_numpy(np.asarray(lcccnn_rates(lr, max_epochs), np.float32)).to(dev)
     train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
     val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
-    n, nv = int(xd.shape[0]), int(xv.shape[0]) if have_val else 0
-    ws_bytes = int(L.ofp_cccnn_train_workspace_bytes(ctypes.byref(cfg), n, nv))
+    n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
+    ws_bytes = int(L.ofp_cccnn_train_random_workspace_bytes(ctypes.byref(cfg), n, nv, rp))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
@@ -1066,10 +1167,11 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
     side = torch.cuda.Stream(dev)
     side.wait_stream(cur)
     with torch.cuda.device(dev):
-        check(L.ofp_cccnn_train(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), nv, ptr(xv), ptr(yv),
-                                rates.data_ptr(), max_epochs, min_epochs, -1 if patience is None else int(patience),
-                                params.data_ptr(), train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs),
-                                ws.data_ptr(), ws_bytes, ctypes.c_void_p(side.cuda_stream)), "ofp_cccnn_train")
+        check(L.ofp_cccnn_train_random(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                                       rates.data_ptr(), max_epochs, min_epochs,
+                                       -1 if patience is None else int(patience), params.data_ptr(),
+                                       train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(),
+                                       ws_bytes, ctypes.c_void_p(side.cuda_stream), rp), "ofp_cccnn_train")
     cur.wait_stream(side)
     with torch.no_grad():
         o = 0
@@ -1078,7 +1180,7 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
             o += t.numel()
     model.eval()
     return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
-                           lrs=np.array(lcccnn_rates(lr, max_epochs)[:epochs.value]))
+                           lrs=np.array(lcccnn_rates(lr, max_epochs)[:epochs.value]), seed=seed)
 
 
 def conv1d_backward_strided(x, weight, dz, padding, dilation, groups=1, stride=1, *, dx=None, dw=None, db=None,

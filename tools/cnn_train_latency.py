@@ -8,7 +8,16 @@ optimiser and scheduler of configure_optimizers(), one full batch per epoch.
 Both run in this one process, alternating, `rounds` times.  A measurement is the host clock around `epochs` epochs
 that end in a device synchronise, divided by the epochs; fit_cnn's figure therefore includes everything a call does
 (packing the parameters, the rate table, capturing the graph, copying the result back).  Each round reports the p50
-of `reps` such measurements per side, after one untimed warm-up call of each.  One JSON line per shape."""
+of `reps` such measurements per side, after one untimed warm-up call of each.  One JSON line per shape.
+
+    python tools/cnn_train_latency.py --random [--modes p0 p0.5 p0.5_shift] [--repo OTHER_TREE]
+
+measures what the trainer's own random stream costs at the default architecture (default_bn_B620): fit_cnn with
+dropout_rate 0 (the chain without any of the new kernels), with dropout_rate 0.5 and a seed (k_dropout_fwd and
+k_dropout_bwd per epoch), and with that plus a data.ShiftedWindows source of 155 onsets x 4 extractions shifted by up
+to 16 samples (k_shift_windows as well), alternating over `rounds` rounds in this one process.  `--repo` imports the
+package from another built tree (a checkout of the parent commit, which has only the p0 mode), so that both can be
+measured in one visit to the GPU."""
 import argparse
 import json
 import statistics
@@ -17,6 +26,8 @@ import time
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[1]
+if "--repo" in sys.argv:
+    REPO = Path(sys.argv[sys.argv.index("--repo") + 1]).resolve()
 sys.path.insert(0, str(REPO))
 
 SHAPES = {
@@ -27,26 +38,46 @@ SHAPES = {
 WIDTH, CHANNELS = 264, 4
 
 
-def make(cfg):
+RANDOM_SHAPE, RANDOM_MODES = "default_bn_B620", ("p0", "p0.5", "p0.5_shift")
+MAX_SHIFT, EXTRACTIONS, SEED = 16, 4, 1  # train.py: MCPOSD.from_file(..., w, pre_samp, 16, 4)
+
+
+def make(cfg, dropout_rate=0.0):
     import torch
 
     from onset_fingerprinting_amd import model
     torch.manual_seed(0)
-    m = model.CNN(WIDTH, 2, CHANNELS, cfg["layer_sizes"], cfg["kernel_size"], dropout_rate=0.0, batch_norm=True,
-                  padding=cfg["padding"]).cuda()
+    m = model.CNN(WIDTH, 2, CHANNELS, cfg["layer_sizes"], cfg["kernel_size"], dropout_rate=dropout_rate,
+                  batch_norm=True, padding=cfg["padding"]).cuda()
     gen = torch.Generator().manual_seed(1)
     x = torch.randn(cfg["n"], CHANNELS, WIDTH, generator=gen).cuda()
     y = (torch.rand(cfg["n"], 2, generator=gen) - 0.5).cuda()
     return m, x, y
 
 
-def ours(m, x, y, epochs):
+def window_source(n, channels, width):
+    """(data.ShiftedWindows of n / EXTRACTIONS onsets in seeded noise, y [onsets, 2])."""
+    import numpy as np
+    import torch
+
+    from onset_fingerprinting_amd import data
+    onsets_n = n // EXTRACTIONS
+    assert onsets_n * EXTRACTIONS == n
+    gap = width + 2 * MAX_SHIFT + 8
+    rng = np.random.default_rng(1)
+    audio = rng.standard_normal((gap * (onsets_n + 1), channels)).astype(np.float32)
+    onsets = gap * (1 + np.arange(onsets_n))
+    src = data.ShiftedWindows(audio, onsets, width, pre_samples=8, max_shift=MAX_SHIFT, n_extractions=EXTRACTIONS)
+    return src, torch.from_numpy((rng.random((onsets_n, 2)) - 0.5).astype(np.float32)).cuda()
+
+
+def ours(m, x, y, epochs, **kw):
     import torch
 
     from onset_fingerprinting_amd import model
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    fit = model.fit_cnn(m, x, y, max_epochs=epochs)
+    fit = model.fit_cnn(m, x, y, max_epochs=epochs, **kw)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert fit.epochs == epochs
@@ -70,13 +101,52 @@ def torch_loop(m, x, y, epochs):
     return (time.perf_counter() - t0) / epochs
 
 
+def random_modes(args):
+    """One JSON line: p50 us per epoch of every mode in every round, the modes alternating inside a round."""
+    import copy
+
+    import torch
+    cfg = SHAPES[RANDOM_SHAPE]
+    E = cfg["epochs"]
+    run = {}
+    for mode in args.modes:
+        start, x, y = make(cfg, 0.0 if mode == "p0" else 0.5)
+        kw = {} if mode == "p0" else dict(seed=SEED)
+        if mode.endswith("_shift"):
+            x, y = window_source(cfg["n"], CHANNELS, WIDTH)
+        run[mode] = lambda start=start, x=x, y=y, kw=kw: ours(copy.deepcopy(start), x, y, E, **kw)
+    for fn in run.values():
+        fn()
+    rounds = []
+    for _ in range(args.rounds):
+        samples = {mode: [] for mode in run}
+        for _rep in range(args.reps):
+            for mode, fn in run.items():
+                samples[mode].append(fn())
+        rounds.append({mode: round(statistics.median(v) * 1e6, 2) for mode, v in samples.items()})
+    rec = dict(tool="cnn_train_latency --random", tree=str(REPO.name), shape=RANDOM_SHAPE, n=cfg["n"],
+               layer_sizes=cfg["layer_sizes"], width=WIDTH, channels=CHANNELS, batch_norm=True, max_shift=MAX_SHIFT,
+               n_extractions=EXTRACTIONS, epochs_per_measurement=E, reps=args.reps, p50_us_per_epoch=rounds,
+               device=torch.cuda.get_device_name(0))
+    print(json.dumps(rec), flush=True)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
+    ap.add_argument("--random", action="store_true", help="the cost of dropout and shifted windows (see above)")
+    ap.add_argument("--modes", nargs="*", default=list(RANDOM_MODES), choices=RANDOM_MODES)
+    ap.add_argument("--repo", default=None, help="import the package from this built tree")
     args = ap.parse_args()
+    if args.random:
+        return random_modes(args)
     import copy
 
     import torch
