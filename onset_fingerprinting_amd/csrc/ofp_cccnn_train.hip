@@ -22,8 +22,6 @@
 #include "ofp_train_random.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 namespace {
 
@@ -331,11 +329,7 @@ int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int 
     return OFP_OK;
 }
 
-int conv_width(int w, int k, int padding, int dilation, int stride) {
-    return (w + 2 * padding - dilation * (k - 1) - 1) / stride + 1;
-}
-
-struct Plan {
+struct Plan : WsPlan {
     int L, act, norm, pool, loss, O, C, K, V, F, np, group;
     double eps;
     float mom, wd;
@@ -344,7 +338,7 @@ struct Plan {
     int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], fcw_off, fcb_off;
     // work space, byte offsets
     int64_t o_Z[kMaxConv], o_H[kMaxConv], o_stat[kMaxConv], o_P, o_out, o_dy, o_lpart, o_gh, o_gz, o_part, o_G, o_B,
-        o_ctl, o_HD, o_DP, o_X, bytes;  // o_HD: the dropped p, o_DP: its gradient; o_X: the epoch's shifted windows
+        o_ctl, o_HD, o_DP, o_X;  // o_HD: the dropped p, o_DP: its gradient; o_X: the epoch's shifted windows
     int64_t items(int64_t n) const { return group ? n : n * C; }
 };
 
@@ -414,45 +408,33 @@ int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, cons
     p.fcw_off = np, np += p.O * p.F;
     p.fcb_off = np, np += p.O;
     p.np = np;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t at = o;
-        o += ofp::align_up(bytes > 0 ? bytes : 1, 256);
-        return at;
-    };
     for (int l = 0; l < p.L; ++l) {
-        p.o_Z[l] = take(itmax * p.conv[l].cout * p.conv[l].wc * 4);
-        p.o_H[l] = take(itmax * p.conv[l].cout * p.wo[l] * 4);
-        p.o_stat[l] = take(itmax * 2 * 4);
+        p.o_Z[l] = p.take(itmax * p.conv[l].cout * p.conv[l].wc * 4);
+        p.o_H[l] = p.take(itmax * p.conv[l].cout * p.wo[l] * 4);
+        p.o_stat[l] = p.take(itmax * 2 * 4);
     }
-    p.o_P = take(nmax * p.F * 4);
-    p.o_out = take(nmax * p.O * 4);
-    p.o_dy = take(nmax * p.O * 4);
-    p.o_lpart = take(nmax * 8);
-    p.o_gh = take(max_h * 4);
-    p.o_gz = take(max_z * 4);
-    p.o_part = take(max_part * 8);
-    p.o_G = take((int64_t)np * 4);
-    p.o_B = take((int64_t)np * 4);
-    p.o_ctl = take(sizeof(Ctl));
-    if (rnd.drop) p.o_HD = take(n * p.F * 4), p.o_DP = take(n * p.F * 4);
-    if (rnd.windows) p.o_X = take(n * p.C * c->width * 4);
-    p.bytes = o;
+    p.o_P = p.take(nmax * p.F * 4);
+    p.o_out = p.take(nmax * p.O * 4);
+    p.o_dy = p.take(nmax * p.O * 4);
+    p.o_lpart = p.take(nmax * 8);
+    p.o_gh = p.take(max_h * 4);
+    p.o_gz = p.take(max_z * 4);
+    p.o_part = p.take(max_part * 8);
+    p.o_G = p.take((int64_t)np * 4);
+    p.o_B = p.take((int64_t)np * 4);
+    p.o_ctl = p.take(sizeof(Ctl));
+    if (rnd.drop) p.o_HD = p.take(n * p.F * 4), p.o_DP = p.take(n * p.F * 4);
+    if (rnd.windows) p.o_X = p.take(n * p.C * c->width * 4);
     return OFP_OK;
 }
 
-struct Run {
+struct Run : WsRun {
     const Plan* p;
-    char* ws;
     float* P;   // packed parameters
     float* G;   // packed gradients
     Ctl* ctl;   // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
     hipStream_t st;
     Random rnd;  // dropout in front of the Linear head and the window source; both off by default
-    template <class T>
-    T* at(int64_t off) const {
-        return reinterpret_cast<T*>(ws + off);
-    }
 };
 
 Norm norm_of(const Run& r, int l) {
@@ -587,39 +569,11 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     return OFP_OK;
 }
 
-struct TrainArgs {
-    const float* x;
-    const float* y;
-    int64_t n;
-    const float* xv;
-    const float* yv;
-    int64_t nv;
-    const float* rates;
-    int min_epochs, patience;
-    float* train_loss;
-    float* val_loss;
-};
-
-int enqueue_epoch(const Run& r, const TrainArgs& a) {
+int enqueue_step(const Run& r, const float* rates) {
     const Plan& p = *r.p;
-    if (r.rnd.windows)  // a.x is the work space's window buffer
-        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.at<float>(p.o_X), nullptr, r.st)) return rc;
-    if (int rc = enqueue_forward(r, a.x, a.y, a.n, true)) return rc;
-    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.n, p.O,
-                       a.train_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
-    OFP_LAUNCH_CHECK("k_loss_final");
-    if (int rc = enqueue_backward(r, a.x, a.n)) return rc;
-    hipLaunchKernelGGL(k_sgd, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, a.rates, 0, p.mom, p.wd, r.P, r.G,
+    hipLaunchKernelGGL(k_sgd, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, rates, 0, p.mom, p.wd, r.P, r.G,
                        r.at<float>(p.o_B), (int64_t)p.np);
     OFP_LAUNCH_CHECK("k_sgd");
-    if (a.nv > 0) {
-        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false)) return rc;
-        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.nv, p.O,
-                           a.val_loss, 1, a.patience, (const float*)nullptr, (float*)nullptr);
-        OFP_LAUNCH_CHECK("k_loss_final");
-    }
-    hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(kT), 0, r.st, r.ctl, a.min_epochs);
-    OFP_LAUNCH_CHECK("k_epoch_end");
     return OFP_OK;
 }
 
@@ -660,73 +614,20 @@ int ofp_cccnn_train_random(const ofp_cccnn_config* cfg, int64_t n, const float* 
     if (int rc = make_random("ofp_cccnn_train", random, n, cfg->sensors, cfg->width, true, rnd)) return rc;
     if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
     if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
-    OFP_REQUIRE(num_epochs >= 1 && min_epochs >= 0, "ofp_cccnn_train: num_epochs %d, min_epochs %d", num_epochs,
-                min_epochs);
-    OFP_REQUIRE(d_x && d_y && d_rates && d_params && d_train_loss && h_epochs, "ofp_cccnn_train: NULL argument");
-    OFP_REQUIRE(n_val == 0 || (d_x_val && d_y_val && d_val_loss), "ofp_cccnn_train: NULL validation argument");
-    OFP_REQUIRE(patience < 0 || n_val > 0, "ofp_cccnn_train: patience needs a validation set");
+    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
+    if (int rc = check_train("ofp_cccnn_train", a, num_epochs, d_params, h_epochs)) return rc;
     if (int rc = check_ws("ofp_cccnn_train", d_ws, ws_bytes, p.bytes)) return rc;
-    const char* mode = getenv("OFP_CCCNN_GRAPH");
-    const bool plain = mode != nullptr && std::strcmp(mode, "nodes") == 0;
     hipStream_t st = (hipStream_t)stream;
-    OFP_REQUIRE(plain || st != nullptr,
-                "ofp_cccnn_train: the epoch graph cannot be captured on the null stream (pass a created stream, or "
-                "set OFP_CCCNN_GRAPH=nodes for plain launches)");
-    Run r{&p, (char*)d_ws, d_params, nullptr, nullptr, st, rnd};
+    Run r{{(char*)d_ws}, &p, d_params, nullptr, nullptr, st, rnd};
     r.G = r.at<float>(p.o_G);
     r.ctl = r.at<Ctl>(p.o_ctl);
-    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, n_val > 0 ? patience : -1,
-                      d_train_loss, d_val_loss};
-    OFP_HIP(hipMemsetAsync(r.at<float>(p.o_B), 0, (size_t)p.np * 4, st));
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(kT), 0, st, r.ctl);
-    OFP_LAUNCH_CHECK("k_init");
-    // the first epoch is launched plainly: it loads every code object and sets the head kernels' LDS size, neither of
-    // which may happen during capture
-    if (int rc = enqueue_epoch(r, a)) return rc;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (!plain && num_epochs > 1) {
-        OFP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_epoch(r, a);
-        const hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (rc != OFP_OK) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            return ofp::fail(OFP_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-        }
-    }
-    int rc = OFP_OK;
-    Ctl seen{};
-    for (int e = 1; e < num_epochs && rc == OFP_OK; ++e) {
-        if (a.patience >= 0 && e % kCheckEvery == 0) {  // has the device stopped?  (at most once per 64 epochs)
-            hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);
-            if (he != hipSuccess) {
-                rc = ofp::fail(OFP_ERR_HIP, "ofp_cccnn_train: %s", hipGetErrorString(he));
-                break;
-            }
-            if (seen.stop) break;
-        }
-        if (exec) {
-            const hipError_t he = hipGraphLaunch(exec, st);
-            if (he != hipSuccess) rc = ofp::fail(OFP_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(he));
-        } else {
-            rc = enqueue_epoch(r, a);
-        }
-    }
-    hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc != OFP_OK) return rc;
-    if (he != hipSuccess) return ofp::fail(OFP_ERR_HIP, "ofp_cccnn_train: %s", hipGetErrorString(he));
-    *h_epochs = seen.epoch;
-    return OFP_OK;
+    return run_epochs(
+        "ofp_cccnn_train", "OFP_CCCNN_GRAPH", st, r.ctl, num_epochs, patience, h_epochs,
+        [&] {
+            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_B), 0, (size_t)p.np * 4, st));
+            return OFP_OK;
+        },
+        [&] { return enqueue_epoch(r, a); });
 }
 
 int ofp_cccnn_loss_grads(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
@@ -744,33 +645,25 @@ int ofp_cccnn_loss_grads_random(const ofp_cccnn_config* cfg, int64_t n, const fl
     if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cccnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cccnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
-    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream, rnd};
-    if (int rc = enqueue_forward(r, d_x, d_y, n, true)) return rc;
-    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, (Ctl*)nullptr, r.at<double>(p.o_lpart), n, p.O,
-                       d_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
-    OFP_LAUNCH_CHECK("k_loss_final");
-    return enqueue_backward(r, d_x, n);
+    Run r{{(char*)d_ws}, &p, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream, rnd};
+    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
 }
 
 int64_t ofp_conv1d_backward_strided_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,
                                                     int32_t padding, int32_t dilation, int32_t groups,
                                                     int32_t stride) {
     if (check_conv("ofp_conv1d_backward_strided", n, cin, w, cout, k, padding, dilation, groups, stride)) return -1;
-    const int wc = conv_width(w, k, padding, dilation, stride);
-    return (int64_t)cout * (cin / groups * k + 1) * slabs_of(n * wc) * 8;
+    return conv_bwd_bytes(n, cin, w, cout, k, padding, dilation, groups, stride);
 }
 
 int ofp_conv1d_backward_strided(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
                                 int32_t k, int32_t padding, int32_t dilation, int32_t groups, int32_t stride,
                                 const float* d_dz, float* d_dx, float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes,
                                 void* stream) {
-    const int64_t need =
-        ofp_conv1d_backward_strided_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups, stride);
-    if (need < 0) return OFP_ERR_INVALID;
-    OFP_REQUIRE(d_x && d_w && d_dz && d_dw && d_db, "ofp_conv1d_backward_strided: NULL argument");
-    if (int rc = check_ws("ofp_conv1d_backward_strided", d_ws, ws_bytes, need)) return rc;
-    const Conv c{cin, cout, w, conv_width(w, k, padding, dilation, stride), k, padding, dilation, groups, stride};
-    return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
+    return conv_bwd_alone(
+        "ofp_conv1d_backward_strided",
+        ofp_conv1d_backward_strided_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups, stride), d_x, n, cin,
+        w, d_w, cout, k, padding, dilation, groups, stride, d_dz, d_dx, d_dw, d_db, d_ws, ws_bytes, stream);
 }
 
 int64_t ofp_groupnorm1_train_workspace_bytes(int64_t n, int32_t K, int32_t V) {

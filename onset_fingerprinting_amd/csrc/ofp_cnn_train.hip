@@ -24,8 +24,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 
 namespace {
 
@@ -260,7 +258,7 @@ int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int 
     return OFP_OK;
 }
 
-struct Plan {
+struct Plan : WsPlan {
     int L, act, bn, pool, loss, O, F, np, ns;
     double eps;
     float mom;
@@ -269,7 +267,7 @@ struct Plan {
     int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], rs_off[kMaxConv], fcw_off, fcb_off;
     // work space, byte offsets
     int64_t o_Z[kMaxConv], o_H[kMaxConv], o_out, o_dy, o_lpart, o_gh, o_gz, o_save, o_s12, o_part, o_G, o_M, o_V,
-        o_RS, o_ctl, o_HD, o_X, bytes;  // o_HD: the dropped features; o_X: the epoch's shifted windows
+        o_RS, o_ctl, o_HD, o_X;  // o_HD: the dropped features; o_X: the epoch's shifted windows
 };
 
 int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd = Random{}) {
@@ -321,48 +319,36 @@ int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const 
     p.fcw_off = np, np += p.O * p.F;
     p.fcb_off = np, np += p.O;
     p.np = np, p.ns = ns;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t at = o;
-        o += ofp::align_up(bytes > 0 ? bytes : 1, 256);
-        return at;
-    };
     for (int l = 0; l < p.L; ++l) {
-        p.o_Z[l] = take(nmax * p.conv[l].cout * p.conv[l].wc * 4);
-        p.o_H[l] = take(nmax * p.conv[l].cout * p.wo[l] * 4);
+        p.o_Z[l] = p.take(nmax * p.conv[l].cout * p.conv[l].wc * 4);
+        p.o_H[l] = p.take(nmax * p.conv[l].cout * p.wo[l] * 4);
     }
-    p.o_out = take(nmax * p.O * 4);
-    p.o_dy = take(nmax * p.O * 4);
-    p.o_lpart = take(nmax * 8);
-    p.o_gh = take(max_h * 4);
-    p.o_gz = take(max_z * 4);
-    p.o_save = take((int64_t)ns * 4);
-    p.o_s12 = take((int64_t)ns * 4);
-    p.o_part = take(max_part * 8);
-    p.o_G = take((int64_t)np * 4);
-    p.o_M = take((int64_t)np * 4);
-    p.o_V = take((int64_t)np * 4);
-    p.o_RS = take((int64_t)ns * 4);
-    p.o_ctl = take(sizeof(Ctl));
-    if (rnd.drop) p.o_HD = take(n * p.F * 4);
-    if (rnd.windows) p.o_X = take(n * c->channels[0] * c->width * 4);
-    p.bytes = o;
+    p.o_out = p.take(nmax * p.O * 4);
+    p.o_dy = p.take(nmax * p.O * 4);
+    p.o_lpart = p.take(nmax * 8);
+    p.o_gh = p.take(max_h * 4);
+    p.o_gz = p.take(max_z * 4);
+    p.o_save = p.take((int64_t)ns * 4);
+    p.o_s12 = p.take((int64_t)ns * 4);
+    p.o_part = p.take(max_part * 8);
+    p.o_G = p.take((int64_t)np * 4);
+    p.o_M = p.take((int64_t)np * 4);
+    p.o_V = p.take((int64_t)np * 4);
+    p.o_RS = p.take((int64_t)ns * 4);
+    p.o_ctl = p.take(sizeof(Ctl));
+    if (rnd.drop) p.o_HD = p.take(n * p.F * 4);
+    if (rnd.windows) p.o_X = p.take(n * c->channels[0] * c->width * 4);
     return OFP_OK;
 }
 
-struct Run {
+struct Run : WsRun {
     const Plan* p;
-    char* ws;
     float* P;    // packed parameters
     float* RS;   // packed running statistics
     float* G;    // packed gradients
     Ctl* ctl;    // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
     hipStream_t st;
     Random rnd;  // dropout in front of the Linear head and the window source; both off by default
-    template <class T>
-    T* at(int64_t off) const {
-        return reinterpret_cast<T*>(ws + off);
-    }
 };
 
 Post post_of(const Run& r, int l, int mode) {
@@ -474,42 +460,13 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     return OFP_OK;
 }
 
-struct TrainArgs {
-    const float* x;
-    const float* y;
-    int64_t n;
-    const float* xv;
-    const float* yv;
-    int64_t nv;
-    const float* rates;
-    int min_epochs, patience;
-    float* train_loss;
-    float* val_loss;
-};
-
-int enqueue_epoch(const Run& r, const TrainArgs& a) {
+int enqueue_step(const Run& r, const float* rows) {
     const Plan& p = *r.p;
-    if (r.rnd.windows)  // a.x is the work space's window buffer
-        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.at<float>(p.o_X), nullptr, r.st)) return rc;
-    if (int rc = enqueue_forward(r, a.x, a.y, a.n, true)) return rc;
-    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.n, p.O,
-                       a.train_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
-    OFP_LAUNCH_CHECK("k_loss_final");
-    if (int rc = enqueue_backward(r, a.x, a.n)) return rc;
-    hipLaunchKernelGGL(k_nadam, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, a.rates, r.P, r.G,
-                       r.at<float>(p.o_M), r.at<float>(p.o_V), (int64_t)p.np);
+    hipLaunchKernelGGL(k_nadam, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, rows, r.P, r.G, r.at<float>(p.o_M),
+                       r.at<float>(p.o_V), (int64_t)p.np);
     OFP_LAUNCH_CHECK("k_nadam");
-    if (a.nv > 0) {
-        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false)) return rc;
-        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.at<double>(p.o_lpart), a.nv, p.O,
-                           a.val_loss, 1, a.patience, (const float*)nullptr, (float*)nullptr);
-        OFP_LAUNCH_CHECK("k_loss_final");
-    }
-    hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(kT), 0, r.st, r.ctl, a.min_epochs);
-    OFP_LAUNCH_CHECK("k_epoch_end");
     return OFP_OK;
 }
-
 
 }  // namespace
 
@@ -550,74 +507,22 @@ int ofp_cnn_train_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x,
     if (int rc = make_random("ofp_cnn_train", random, n, cfg->channels[0], cfg->width, true, rnd)) return rc;
     if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
     if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
-    OFP_REQUIRE(num_epochs >= 1 && min_epochs >= 0, "ofp_cnn_train: num_epochs %d, min_epochs %d", num_epochs,
-                min_epochs);
-    OFP_REQUIRE(d_x && d_y && d_rates && d_params && d_train_loss && h_epochs, "ofp_cnn_train: NULL argument");
+    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
+    if (int rc = check_train("ofp_cnn_train", a, num_epochs, d_params, h_epochs)) return rc;
     OFP_REQUIRE(p.ns == 0 || d_stats, "ofp_cnn_train: BatchNorm statistics are NULL");
-    OFP_REQUIRE(n_val == 0 || (d_x_val && d_y_val && d_val_loss), "ofp_cnn_train: NULL validation argument");
-    OFP_REQUIRE(patience < 0 || n_val > 0, "ofp_cnn_train: patience needs a validation set");
     if (int rc = check_ws("ofp_cnn_train", d_ws, ws_bytes, p.bytes)) return rc;
-    const char* mode = getenv("OFP_CNN_GRAPH");
-    const bool plain = mode != nullptr && std::strcmp(mode, "nodes") == 0;
     hipStream_t st = (hipStream_t)stream;
-    OFP_REQUIRE(plain || st != nullptr,
-                "ofp_cnn_train: the epoch graph cannot be captured on the null stream (pass a created stream, or set "
-                "OFP_CNN_GRAPH=nodes for plain launches)");
-    Run r{&p, (char*)d_ws, d_params, d_stats, nullptr, nullptr, st, rnd};
+    Run r{{(char*)d_ws}, &p, d_params, d_stats, nullptr, nullptr, st, rnd};
     r.G = r.at<float>(p.o_G);
     r.ctl = r.at<Ctl>(p.o_ctl);
-    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, n_val > 0 ? patience : -1,
-                      d_train_loss, d_val_loss};
-    OFP_HIP(hipMemsetAsync(r.at<float>(p.o_M), 0, (size_t)p.np * 4, st));
-    OFP_HIP(hipMemsetAsync(r.at<float>(p.o_V), 0, (size_t)p.np * 4, st));
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(kT), 0, st, r.ctl);
-    OFP_LAUNCH_CHECK("k_init");
-    // the first epoch is launched plainly: it loads every code object, which may not happen during capture
-    if (int rc = enqueue_epoch(r, a)) return rc;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (!plain && num_epochs > 1) {
-        OFP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_epoch(r, a);
-        const hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (rc != OFP_OK) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            return ofp::fail(OFP_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-        }
-    }
-    int rc = OFP_OK;
-    Ctl seen{};
-    for (int e = 1; e < num_epochs && rc == OFP_OK; ++e) {
-        if (a.patience >= 0 && e % kCheckEvery == 0) {  // has the device stopped?  (at most once per 64 epochs)
-            hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);
-            if (he != hipSuccess) {
-                rc = ofp::fail(OFP_ERR_HIP, "ofp_cnn_train: %s", hipGetErrorString(he));
-                break;
-            }
-            if (seen.stop) break;
-        }
-        if (exec) {
-            const hipError_t he = hipGraphLaunch(exec, st);
-            if (he != hipSuccess) rc = ofp::fail(OFP_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(he));
-        } else {
-            rc = enqueue_epoch(r, a);
-        }
-    }
-    hipError_t he = hipMemcpyAsync(&seen, r.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc != OFP_OK) return rc;
-    if (he != hipSuccess) return ofp::fail(OFP_ERR_HIP, "ofp_cnn_train: %s", hipGetErrorString(he));
-    *h_epochs = seen.epoch;
-    return OFP_OK;
+    return run_epochs(
+        "ofp_cnn_train", "OFP_CNN_GRAPH", st, r.ctl, num_epochs, patience, h_epochs,
+        [&] {
+            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_M), 0, (size_t)p.np * 4, st));
+            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_V), 0, (size_t)p.np * 4, st));
+            return OFP_OK;
+        },
+        [&] { return enqueue_epoch(r, a); });
 }
 
 int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
@@ -636,32 +541,25 @@ int ofp_cnn_loss_grads_random(const ofp_cnn_config* cfg, int64_t n, const float*
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
     // the trainer's own forward and backward; the running statistics it would update are a scratch copy
-    Run r{&p, (char*)d_ws, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream, rnd};
+    Run r{{(char*)d_ws}, &p, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream, rnd};
     r.RS = r.at<float>(p.o_RS);
     OFP_HIP(hipMemsetAsync(r.RS, 0, (size_t)(p.ns > 0 ? p.ns : 1) * 4, r.st));
-    if (int rc = enqueue_forward(r, d_x, d_y, n, true)) return rc;
-    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, (Ctl*)nullptr, r.at<double>(p.o_lpart), n, p.O,
-                       d_loss, 0, -1, r.at<float>(p.o_dy), r.G + p.fcb_off);
-    OFP_LAUNCH_CHECK("k_loss_final");
-    return enqueue_backward(r, d_x, n);
+    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
 }
 
 int64_t ofp_conv1d_backward_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,
                                             int32_t padding, int32_t dilation, int32_t groups) {
     if (check_conv("ofp_conv1d_backward", n, cin, w, cout, k, padding, dilation, groups)) return -1;
-    const int wc = w + 2 * padding - dilation * (k - 1);
-    return (int64_t)cout * (cin / groups * k + 1) * slabs_of(n * wc) * 8;
+    return conv_bwd_bytes(n, cin, w, cout, k, padding, dilation, groups, 1);
 }
 
 int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
                         int32_t k, int32_t padding, int32_t dilation, int32_t groups, const float* d_dz, float* d_dx,
                         float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
-    const int64_t need = ofp_conv1d_backward_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups);
-    if (need < 0) return OFP_ERR_INVALID;
-    OFP_REQUIRE(d_x && d_w && d_dz && d_dw && d_db, "ofp_conv1d_backward: NULL argument");
-    if (int rc = check_ws("ofp_conv1d_backward", d_ws, ws_bytes, need)) return rc;
-    const Conv c{cin, cout, w, w + 2 * padding - dilation * (k - 1), k, padding, dilation, groups, 1};
-    return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
+    return conv_bwd_alone("ofp_conv1d_backward",
+                          ofp_conv1d_backward_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups), d_x, n,
+                          cin, w, d_w, cout, k, padding, dilation, groups, 1, d_dz, d_dx, d_dw, d_db, d_ws, ws_bytes,
+                          stream);
 }
 
 int64_t ofp_batchnorm_train_workspace_bytes(int64_t n, int32_t C, int32_t w) {

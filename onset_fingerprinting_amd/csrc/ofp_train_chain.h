@@ -1,12 +1,15 @@
 // Device code and launch helpers shared by the two epoch-graph trainers (csrc/ofp_cnn_train.hip, csrc/ofp_cccnn_train.hip):
 // the control block of a run, the partial-slab reducer's shape, the convolution's forward and three gradients (any
-// stride), the Linear head with its loss, and the chain's first and last kernels.  Everything here is file-local
-// (anonymous namespace): each trainer compiles its own copy.
+// stride), the Linear head with its loss, and the chain's first and last kernels; on the host the work space's base,
+// the checks both trainers make, one epoch, and the driver that captures it as a graph and replays it.  Everything here
+// is file-local (anonymous namespace): each trainer compiles its own copy.
 #pragma once
 #include "ofp_common.h"
 #include "ofp_mlp.h"
 
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -335,6 +338,167 @@ int check_ws(const char* who, const void* ws, int64_t given, int64_t need) {
     if (ws == nullptr || given < need)
         return ofp::fail(OFP_ERR_WORKSPACE, "%s: work space of %lld bytes needed, %lld given", who, (long long)need,
                          (long long)given);
+    return OFP_OK;
+}
+
+int conv_width(int w, int k, int padding, int dilation, int stride) {
+    return (w + 2 * padding - dilation * (k - 1) - 1) / stride + 1;
+}
+
+// The stand-alone convolution backward of both trainers (ofp_conv1d_backward, ofp_conv1d_backward_strided): `need` is
+// what the entry's own _workspace_bytes returns for the same shape, negative when its limits do not hold.
+int64_t conv_bwd_bytes(int64_t n, int cin, int w, int cout, int k, int padding, int dilation, int groups, int stride) {
+    return (int64_t)cout * (cin / groups * k + 1) * slabs_of(n * conv_width(w, k, padding, dilation, stride)) * 8;
+}
+
+int conv_bwd_alone(const char* who, int64_t need, const float* d_x, int64_t n, int cin, int w, const float* d_w,
+                   int cout, int k, int padding, int dilation, int groups, int stride, const float* d_dz, float* d_dx,
+                   float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (need < 0) return OFP_ERR_INVALID;
+    OFP_REQUIRE(d_x && d_w && d_dz && d_dw && d_db, "%s: NULL argument", who);
+    if (int rc = check_ws(who, d_ws, ws_bytes, need)) return rc;
+    const Conv c{cin, cout, w, conv_width(w, k, padding, dilation, stride), k, padding, dilation, groups, stride};
+    return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
+}
+
+// ---- one epoch and its driver ---------------------------------------------------------------------------------------
+// A trainer derives its Plan from WsPlan and its Run from WsRun and defines enqueue_forward(r, x, y, n, train),
+// enqueue_backward(r, x, n) and enqueue_step(r, rates), its optimiser, for its own Run; the templates below find them
+// by the Run they are called with.  Of the Run they read p, G, ctl, st and rnd (csrc/ofp_train_random.h), of the
+// Plan O, fcb_off, o_lpart, o_dy and o_X.
+
+// base of a Plan: the byte offsets of the work space's blocks come from a bump allocator
+struct WsPlan {
+    int64_t bytes;  // taken so far; in the end the work space's size
+    int64_t take(int64_t n) {
+        const int64_t at = bytes;
+        bytes += ofp::align_up(n > 0 ? n : 1, 256);
+        return at;
+    }
+};
+
+// base of a Run: the work space itself
+struct WsRun {
+    char* ws;
+    template <class T>
+    T* at(int64_t off) const {
+        return reinterpret_cast<T*>(ws + off);
+    }
+};
+
+struct TrainArgs {
+    const float* x;
+    const float* y;
+    int64_t n;
+    const float* xv;
+    const float* yv;
+    int64_t nv;
+    const float* rates;
+    int min_epochs, patience;
+    float* train_loss;
+    float* val_loss;
+};
+
+int check_train(const char* who, const TrainArgs& a, int num_epochs, const float* params, const int32_t* h_epochs) {
+    OFP_REQUIRE(num_epochs >= 1 && a.min_epochs >= 0, "%s: num_epochs %d, min_epochs %d", who, num_epochs,
+                a.min_epochs);
+    OFP_REQUIRE(a.x && a.y && a.rates && params && a.train_loss && h_epochs, "%s: NULL argument", who);
+    OFP_REQUIRE(a.nv == 0 || (a.xv && a.yv && a.val_loss), "%s: NULL validation argument", who);
+    OFP_REQUIRE(a.patience < 0 || a.nv > 0, "%s: patience needs a validation set", who);
+    return OFP_OK;
+}
+
+// training forward, the batch's mean loss into `loss` (slot `epoch` of it inside a run) and backward
+template <class Run>
+int enqueue_loss_grads(const Run& r, const float* x, const float* y, int64_t n, float* loss) {
+    const auto& p = *r.p;
+    if (int rc = enqueue_forward(r, x, y, n, true)) return rc;
+    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.template at<double>(p.o_lpart), n, p.O, loss,
+                       0, -1, r.template at<float>(p.o_dy), r.G + p.fcb_off);
+    OFP_LAUNCH_CHECK("k_loss_final");
+    return enqueue_backward(r, x, n);
+}
+
+template <class Run>
+int enqueue_epoch(const Run& r, const TrainArgs& a) {
+    const auto& p = *r.p;
+    if (r.rnd.windows)  // a.x is the work space's window buffer
+        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.template at<float>(p.o_X), nullptr, r.st)) return rc;
+    if (int rc = enqueue_loss_grads(r, a.x, a.y, a.n, a.train_loss)) return rc;
+    if (int rc = enqueue_step(r, a.rates)) return rc;
+    if (a.nv > 0) {
+        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false)) return rc;
+        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.template at<double>(p.o_lpart), a.nv,
+                           p.O, a.val_loss, 1, a.patience, (const float*)nullptr, (float*)nullptr);
+        OFP_LAUNCH_CHECK("k_loss_final");
+    }
+    hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(kT), 0, r.st, r.ctl, a.min_epochs);
+    OFP_LAUNCH_CHECK("k_epoch_end");
+    return OFP_OK;
+}
+
+// the captured epoch and its executable form: freed on every way out of run_epochs
+struct EpochGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    ~EpochGraph() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+};
+
+// Up to num_epochs epochs on `st`: the first launched plainly, the others as replays of its captured graph (plain
+// launches too when the environment has `env`=nodes), until the device's stop word is seen; the epochs run go to
+// *h_epochs.  `reset` enqueues the zeroing of the optimiser's state, `epoch` one epoch.
+template <class Reset, class Epoch>
+int run_epochs(const char* who, const char* env, hipStream_t st, Ctl* ctl, int num_epochs, int patience,
+               int32_t* h_epochs, Reset reset, Epoch epoch) {
+    const char* mode = getenv(env);
+    const bool plain = mode != nullptr && std::strcmp(mode, "nodes") == 0;
+    OFP_REQUIRE(plain || st != nullptr,
+                "%s: the epoch graph cannot be captured on the null stream (pass a created stream, or set %s=nodes for "
+                "plain launches)",
+                who, env);
+    if (int rc = reset()) return rc;
+    hipLaunchKernelGGL(k_init, dim3(1), dim3(kT), 0, st, ctl);
+    OFP_LAUNCH_CHECK("k_init");
+    // the first epoch is launched plainly: it loads every code object and sets the LDS size of kernels that need more
+    // than the default (the LCCCNN's head), neither of which may happen during capture
+    if (int rc = epoch()) return rc;
+    EpochGraph g;
+    if (!plain && num_epochs > 1) {
+        OFP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        const int rc = epoch();
+        const hipError_t ce = hipStreamEndCapture(st, &g.graph);
+        if (rc != OFP_OK) return rc;
+        if (ce != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+        if (ie != hipSuccess) return ofp::fail(OFP_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+    }
+    int rc = OFP_OK;
+    Ctl seen{};
+    for (int e = 1; e < num_epochs && rc == OFP_OK; ++e) {
+        if (patience >= 0 && e % kCheckEvery == 0) {  // has the device stopped?  (at most once per 64 epochs)
+            hipError_t he = hipMemcpyAsync(&seen, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            if (he != hipSuccess) {
+                rc = ofp::fail(OFP_ERR_HIP, "%s: %s", who, hipGetErrorString(he));
+                break;
+            }
+            if (seen.stop) break;
+        }
+        if (g.exec) {
+            const hipError_t he = hipGraphLaunch(g.exec, st);
+            if (he != hipSuccess) rc = ofp::fail(OFP_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(he));
+        } else {
+            rc = epoch();
+        }
+    }
+    hipError_t he = hipMemcpyAsync(&seen, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (rc != OFP_OK) return rc;
+    if (he != hipSuccess) return ofp::fail(OFP_ERR_HIP, "%s: %s", who, hipGetErrorString(he));
+    *h_epochs = seen.epoch;
     return OFP_OK;
 }
 

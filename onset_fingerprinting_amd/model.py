@@ -706,37 +706,131 @@ def _workspace(nbytes, dev):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
 
 
-def cnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
-    """Loss (``model.loss``) and the gradient of every parameter of a CNN for the full batch x [n, channels, width],
-    y [n, outputs], in training mode (BatchNorm on batch statistics; the module's running statistics are not
-    touched), by the trainer's own forward and backward kernels.  With a seed the model's dropout is applied as
-    epoch `epoch` of ``fit_cnn(..., seed=seed)`` applies it (``dropout_mask_device``).  Returns (loss, {state_dict
-    name: gradient}) on the GPU."""
-    x, y, cfg = _cnn_batch(model, x, y, seed=seed)
-    rnd, _keep = _train_random(model.dropout.p, seed, epoch)
-    dev = _train_device(model, x)
+def _split(flat, tensors, copy=False):
+    """The pieces of a flat tensor that belong to a (name, tensor) list: copied into the tensors, or {name: view}."""
+    named, o = {}, 0
+    for name, t in tensors:
+        piece = flat[o:o + t.numel()].reshape(t.shape)
+        o += t.numel()
+        if copy:
+            t.copy_(piece)
+        else:
+            named[name] = piece
+    return named
+
+
+def _loss_and_grads(spec, model, x, y, seed, epoch):
+    """cnn_loss_and_grads_device / cccnn_loss_and_grads_device; `spec` is _CNN or _LCCCNN."""
+    x, y, cfg = spec.batch(model, x, y, seed=seed)
+    net = spec.net(model)
+    rnd, _keep = _train_random(net.dropout.p, seed, epoch)
+    dev = _train_device(net, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
-    ps, _st = _cnn_tensors(model, seed)
+    ps, _st = spec.tensors(model, seed)
     p0 = _flat(ps, dev)
     xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     grads = torch.empty_like(p0)
     n = int(xd.shape[0])
     rp = ctypes.byref(rnd) if rnd is not None else None
-    ws_bytes = int(L.ofp_cnn_train_random_workspace_bytes(ctypes.byref(cfg), n, 0, rp))
+    ws_bytes = int(getattr(L, spec.c_workspace)(ctypes.byref(cfg), n, 0, rp))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
     with torch.cuda.device(dev):
-        check(L.ofp_cnn_loss_grads_random(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
-                                          loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev),
-                                          rp), "ofp_cnn_loss_grads")
-    named, o = {}, 0
-    for name, t in ps:
-        named[name] = grads[o:o + t.numel()].reshape(t.shape)
-        o += t.numel()
-    return loss[0], named
+        check(getattr(L, spec.c_grads + "_random")(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
+                                                   loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                   _stream(dev), rp), spec.c_grads)
+    return loss[0], _split(grads, ps)
+
+
+def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed):
+    """fit_cnn / fit_lcccnn; `spec` is _CNN or _LCCCNN."""
+    x, y, cfg = spec.batch(model, x, y, seed=seed)
+    _check_source(x, seed)
+    source = x if isinstance(x, ShiftedWindows) else None
+    have_val = x_val is not None or y_val is not None
+    if have_val:
+        if x_val is None or y_val is None:
+            raise ValueError("x_val and y_val go together")
+        x_val, y_val, cfg_v = spec.batch(model, x_val, y_val, "x_val", seed)
+        if cfg_v.width != cfg.width:
+            raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
+    max_epochs, min_epochs = int(max_epochs), int(min_epochs)
+    if max_epochs < 1 or min_epochs < 0:
+        raise ValueError("max_epochs must be at least 1 and min_epochs at least 0")
+    if patience is not None and (not have_val or int(patience) < 0):
+        raise ValueError("patience needs x_val / y_val and must not be negative")
+    lr = float(model.lr)
+
+    net = spec.net(model)
+    dev = _train_device(net, x)
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ps, st = spec.tensors(model, seed)
+    params = _flat(ps, dev)
+    stats = (_flat(st, dev),) if spec.stats else ()
+    to = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    xd, yd = (None if source else to(x)), to(y)
+    rnd, _keep = _train_random(net.dropout.p, seed, 0, source)
+    rp = ctypes.byref(rnd) if rnd is not None else None
+    xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
+    rates = torch.from_numpy(spec.device_rates(lr, max_epochs)).to(dev)
+    train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
+    val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
+    n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
+    ws_bytes = int(getattr(L, spec.c_workspace)(ctypes.byref(cfg), n, nv, rp))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ws = _workspace(ws_bytes, dev)
+    epochs = ctypes.c_int32(0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    # the epoch graph is captured on a stream of its own (the null stream cannot be captured); the call returns
+    # after that stream has drained
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(cur)
+    with torch.cuda.device(dev):
+        check(getattr(L, spec.c_train + "_random")(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                                                   rates.data_ptr(), max_epochs, min_epochs,
+                                                   -1 if patience is None else int(patience), params.data_ptr(),
+                                                   *(t.data_ptr() for t in stats), train_loss.data_ptr(),
+                                                   ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(), ws_bytes,
+                                                   ctypes.c_void_p(side.cuda_stream), rp), spec.c_train)
+    cur.wait_stream(side)
+    with torch.no_grad():
+        _split(params, ps, copy=True)
+        if spec.stats:
+            _split(stats[0], st, copy=True)
+        spec.after_fit(model, epochs.value)
+    model.eval()
+    return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
+                           lrs=np.array(spec.rates(lr, max_epochs)[:epochs.value]), seed=seed)
+
+
+def _cnn_count_batches(model, epochs):
+    for m in model.conv_layers:
+        if isinstance(m, nn.BatchNorm1d):
+            m.num_batches_tracked += epochs
+
+
+# What differs between the two trainable models, for _fit and _loss_and_grads: the batch checker, the (name, tensor)
+# lists (parameters, running statistics), the module that carries `dropout` and `fc`, the rate table sent to the device
+# and the rates returned, the C entries, whether the train entry takes d_stats, and what is left to do after a fit.
+_CNN = SimpleNamespace(
+    batch=_cnn_batch, tensors=_cnn_tensors, net=lambda model: model, device_rates=_cnn_device_rows, rates=cnn_rates,
+    c_workspace="ofp_cnn_train_random_workspace_bytes", c_train="ofp_cnn_train", c_grads="ofp_cnn_loss_grads",
+    stats=True, after_fit=_cnn_count_batches)
+
+
+def cnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
+    """Loss (``model.loss``) and the gradient of every parameter of a CNN for the full batch x [n, channels, width],
+    y [n, outputs], in training mode (BatchNorm on batch statistics; the module's running statistics are not
+    touched), by the trainer's own forward and backward kernels.  With a seed the model's dropout is applied as
+    epoch `epoch` of ``fit_cnn(..., seed=seed)`` applies it (``dropout_mask_device``).  Returns (loss, {state_dict
+    name: gradient}) on the GPU."""
+    return _loss_and_grads(_CNN, model, x, y, seed, epoch)
 
 
 def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
@@ -767,67 +861,7 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
     range, a window source as x_val or with other rows in y than onsets, a loss other than F.l1_loss / F.mse_loss, an
     activation without HIP implementation, BatchNorm1d(momentum=None), shapes beyond the limits (3 conv layers, 128
     channels, kernel 8, window 512, batch 1024, 16 outputs)."""
-    x, y, cfg = _cnn_batch(model, x, y, seed=seed)
-    _check_source(x, seed)
-    source = x if isinstance(x, ShiftedWindows) else None
-    have_val = x_val is not None or y_val is not None
-    if have_val:
-        if x_val is None or y_val is None:
-            raise ValueError("x_val and y_val go together")
-        x_val, y_val, cfg_v = _cnn_batch(model, x_val, y_val, "x_val", seed)
-        if cfg_v.width != cfg.width:
-            raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
-    max_epochs, min_epochs = int(max_epochs), int(min_epochs)
-    if max_epochs < 1 or min_epochs < 0:
-        raise ValueError("max_epochs must be at least 1 and min_epochs at least 0")
-    if patience is not None and (not have_val or int(patience) < 0):
-        raise ValueError("patience needs x_val / y_val and must not be negative")
-    lr = float(model.lr)
-
-    dev = _train_device(model, x)
-    _lib.require_gpu(dev.index or 0)
-    L = _lib.lib()
-    ps, st = _cnn_tensors(model, seed)
-    params, stats = _flat(ps, dev), _flat(st, dev)
-    to = lambda t: t.detach().to(dev, torch.float32).contiguous()
-    xd, yd = (None if source else to(x)), to(y)
-    rnd, _keep = _train_random(model.dropout.p, seed, 0, source)
-    rp = ctypes.byref(rnd) if rnd is not None else None
-    xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
-    rows = torch.from_numpy(_cnn_device_rows(lr, max_epochs)).to(dev)
-    train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
-    val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
-    n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
-    ws_bytes = int(L.ofp_cnn_train_random_workspace_bytes(ctypes.byref(cfg), n, nv, rp))
-    if ws_bytes < 0:
-        raise ValueError(_lib.last_error())
-    ws = _workspace(ws_bytes, dev)
-    epochs = ctypes.c_int32(0)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    # the epoch graph is captured on a stream of its own (the null stream cannot be captured); the call returns
-    # after that stream has drained
-    cur = torch.cuda.current_stream(dev)
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(cur)
-    with torch.cuda.device(dev):
-        check(L.ofp_cnn_train_random(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
-                                     rows.data_ptr(), max_epochs, min_epochs,
-                                     -1 if patience is None else int(patience), params.data_ptr(), stats.data_ptr(),
-                                     train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(),
-                                     ws_bytes, ctypes.c_void_p(side.cuda_stream), rp), "ofp_cnn_train")
-    cur.wait_stream(side)
-    with torch.no_grad():
-        for flat, tensors in ((params, ps), (stats, st)):
-            o = 0
-            for _name, t in tensors:
-                t.copy_(flat[o:o + t.numel()].reshape(t.shape))
-                o += t.numel()
-        for m in model.conv_layers:
-            if isinstance(m, nn.BatchNorm1d):
-                m.num_batches_tracked += epochs.value
-    model.eval()
-    return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
-                           lrs=np.array(cnn_rates(lr, max_epochs)[:epochs.value]), seed=seed)
+    return _fit(_CNN, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed)
 
 
 def dropout_mask_device(seed, epoch, n, features, p, device=0, *, out=None):
@@ -1062,36 +1096,19 @@ def _cccnn_batch(model, x, y, what="x", seed=None):
     return x, y, cfg
 
 
+_LCCCNN = SimpleNamespace(
+    batch=_cccnn_batch, tensors=lambda model, seed: (_cccnn_tensors(model, seed), []), net=lambda model: model.model,
+    device_rates=lambda lr, num_epochs: np.asarray(lcccnn_rates(lr, num_epochs), np.float32), rates=lcccnn_rates,
+    c_workspace="ofp_cccnn_train_random_workspace_bytes", c_train="ofp_cccnn_train", c_grads="ofp_cccnn_loss_grads",
+    stats=False, after_fit=lambda model, epochs: None)
+
+
 def cccnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
     """Loss (``model.loss``) and the gradient of every parameter of an LCCCNN for the full batch x [n, channels,
     width], y [n, outputs], by the trainer's own forward and backward kernels.  With a seed the model's dropout is
     applied as epoch `epoch` of ``fit_lcccnn(..., seed=seed)`` applies it.  Returns (loss, {state_dict name:
     gradient}) on the GPU."""
-    x, y, cfg = _cccnn_batch(model, x, y, seed=seed)
-    rnd, _keep = _train_random(model.model.dropout.p, seed, epoch)
-    dev = _train_device(model.model, x)
-    _lib.require_gpu(dev.index or 0)
-    L = _lib.lib()
-    ps = _cccnn_tensors(model, seed)
-    p0 = _flat(ps, dev)
-    xd, yd = x.detach().to(dev, torch.float32).contiguous(), y.detach().to(dev, torch.float32).contiguous()
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    grads = torch.empty_like(p0)
-    n = int(xd.shape[0])
-    rp = ctypes.byref(rnd) if rnd is not None else None
-    ws_bytes = int(L.ofp_cccnn_train_random_workspace_bytes(ctypes.byref(cfg), n, 0, rp))
-    if ws_bytes < 0:
-        raise ValueError(_lib.last_error())
-    ws = _workspace(ws_bytes, dev)
-    with torch.cuda.device(dev):
-        check(L.ofp_cccnn_loss_grads_random(ctypes.byref(cfg), n, xd.data_ptr(), yd.data_ptr(), p0.data_ptr(),
-                                            loss.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev),
-                                            rp), "ofp_cccnn_loss_grads")
-    named, o = {}, 0
-    for name, t in ps:
-        named[name] = grads[o:o + t.numel()].reshape(t.shape)
-        o += t.numel()
-    return loss[0], named
+    return _loss_and_grads(_LCCCNN, model, x, y, seed, epoch)
 
 
 def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
@@ -1124,63 +1141,7 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
     channels per layer (layer size x sensor channels when group=True), window 512, 1024 windows and 4096 (window,
     sensor) pairs, 16 outputs, a head of K maps x V columns with cccnn_head_lds_bytes(K, V) <= 160 KiB, and every
     layer must leave at least one column."""
-    x, y, cfg = _cccnn_batch(model, x, y, seed=seed)
-    _check_source(x, seed)
-    source = x if isinstance(x, ShiftedWindows) else None
-    have_val = x_val is not None or y_val is not None
-    if have_val:
-        if x_val is None or y_val is None:
-            raise ValueError("x_val and y_val go together")
-        x_val, y_val, cfg_v = _cccnn_batch(model, x_val, y_val, "x_val", seed)
-        if cfg_v.width != cfg.width:
-            raise ValueError(f"x_val is {cfg_v.width} samples wide, x {cfg.width}")
-    max_epochs, min_epochs = int(max_epochs), int(min_epochs)
-    if max_epochs < 1 or min_epochs < 0:
-        raise ValueError("max_epochs must be at least 1 and min_epochs at least 0")
-    if patience is not None and (not have_val or int(patience) < 0):
-        raise ValueError("patience needs x_val / y_val and must not be negative")
-    lr = float(model.lr)
-
-    dev = _train_device(model.model, x)
-    _lib.require_gpu(dev.index or 0)
-    L = _lib.lib()
-    ps = _cccnn_tensors(model, seed)
-    params = _flat(ps, dev)
-    to = lambda t: t.detach().to(dev, torch.float32).contiguous()
-    xd, yd = (None if source else to(x)), to(y)
-    rnd, _keep = _train_random(model.model.dropout.p, seed, 0, source)
-    rp = ctypes.byref(rnd) if rnd is not None else None
-    xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
-    rates = torch.from_numpy(np.asarray(lcccnn_rates(lr, max_epochs), np.float32)).to(dev)
-    train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
-    val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
-    n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
-    ws_bytes = int(L.ofp_cccnn_train_random_workspace_bytes(ctypes.byref(cfg), n, nv, rp))
-    if ws_bytes < 0:
-        raise ValueError(_lib.last_error())
-    ws = _workspace(ws_bytes, dev)
-    epochs = ctypes.c_int32(0)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    # the epoch graph is captured on a stream of its own (the null stream cannot be captured); the call returns
-    # after that stream has drained
-    cur = torch.cuda.current_stream(dev)
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(cur)
-    with torch.cuda.device(dev):
-        check(L.ofp_cccnn_train_random(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
-                                       rates.data_ptr(), max_epochs, min_epochs,
-                                       -1 if patience is None else int(patience), params.data_ptr(),
-                                       train_loss.data_ptr(), ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(),
-                                       ws_bytes, ctypes.c_void_p(side.cuda_stream), rp), "ofp_cccnn_train")
-    cur.wait_stream(side)
-    with torch.no_grad():
-        o = 0
-        for _name, t in ps:
-            t.copy_(params[o:o + t.numel()].reshape(t.shape))
-            o += t.numel()
-    model.eval()
-    return SimpleNamespace(train_loss=train_loss, val_loss=val_loss, epochs=int(epochs.value),
-                           lrs=np.array(lcccnn_rates(lr, max_epochs)[:epochs.value]), seed=seed)
+    return _fit(_LCCCNN, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed)
 
 
 def conv1d_backward_strided(x, weight, dz, padding, dilation, groups=1, stride=1, *, dx=None, dw=None, db=None,

@@ -391,6 +391,30 @@ def test_determinism_and_graph_against_plain_launches(g, monkeypatch):
         assert torch.equal(a.val_loss.view(torch.int32), b.val_loss.view(torch.int32))
 
 
+_five = {}
+
+
+@pytest.mark.parametrize("E", [1, 2])
+def test_a_short_run_is_the_start_of_a_longer_one(g, E):
+    """The epoch driver's short paths: max_epochs = 1 captures no graph at all, max_epochs = 2 captures one and replays
+    it once.  The rate of epoch e depends on e alone (model.cnn_rate_table), not on max_epochs, so the losses of
+    either run are the first of a 5-epoch run, bit for bit."""
+    from onset_fingerprinting_amd import model
+    _cfg, start, x, y, val = load_case(g, STOP)
+
+    def run(epochs):
+        fit = model.fit_cnn(copy.deepcopy(start).cuda(), x.cuda(), y.cuda(), x_val=val[0].cuda(),
+                            y_val=val[1].cuda(), max_epochs=epochs)
+        assert fit.epochs == epochs
+        return fit
+
+    if not _five:
+        _five["fit"] = run(5)
+    long, short = _five["fit"], run(E)
+    assert torch.equal(short.train_loss[:E].view(torch.int32), long.train_loss[:E].view(torch.int32))
+    assert torch.equal(short.val_loss[:E].view(torch.int32), long.val_loss[:E].view(torch.int32))
+
+
 def test_in_place_semantics(g):
     from onset_fingerprinting_amd import model
     cfg, m, x, y, _val = load_case(g, "l1_silu_bn")
