@@ -184,8 +184,17 @@ __device__ __forceinline__ void walk(const float* ip, float* op, int64_t n, int&
 // floats of LDS owned by the wave.
 constexpr int WL_PITCH = 36;  // 32 + 4 floats: 16-byte rows, banks spread
 template <class F, class D>
-__device__ __forceinline__ void walk_lines_to(const float* ip, int64_t n, F& f, float* tile, D&& dst_of) {
-    // dst_of(b): where the lane's batch b (32 steps) goes, or NULL for a batch without output
+__device__ __forceinline__ void walk_lines_to(const float* in0, const float* ip, int64_t n, F& f, float* tile, float* base, D&& dst_of) {
+    // dst_of(b): where the lane's batch b (32 steps) goes, as an element offset from `base`, or < 0 for a batch without
+    // output.  `base` is the same for the whole wave and comes straight from a kernel argument: the row owners hand
+    // OFFSETS round, so the address of a cooperative store is base + offset and stays a global one.  (A pointer rebuilt
+    // from two shuffled halves belongs to no address space the compiler can name: the stores became flat_store, and
+    // with a flat access pending every wait for a load is vmcnt(0) -- the other set's prefetch and the previous batch's
+    // stores drained twice per batch.)
+    // in0: 32 readable floats, the same for the whole wave (the start of the input array).  A lane that has run out of
+    // batches while others of its wave go on loads those instead of skipping its loads: loads under a branch are not
+    // counted either (the compiler must assume they were not issued, and the wait for this set's last values became
+    // vmcnt(0) again, draining the other set).  The lanes without work all read the one line.
     const int lane = threadIdx.x & 63;
     const int64_t nb = n >> 5;
     int64_t nbmax = nb;
@@ -193,11 +202,11 @@ __device__ __forceinline__ void walk_lines_to(const float* ip, int64_t n, F& f, 
     const float4* q = reinterpret_cast<const float4*>(ip);
     float4 A[8], Bv[8];
     auto load = [&](float4 (&v)[8], int64_t b) {
-        if (b < nb) {
+        const bool have = b < nb;
+        const float4* const p = have ? q : reinterpret_cast<const float4*>(in0);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = q[i];
-            q += 8;
-        }
+        for (int i = 0; i < 8; ++i) v[i] = p[i];
+        q += have ? 8 : 0;
         __builtin_amdgcn_sched_barrier(0);
     };
     auto run = [&](const float4 (&v)[8], int64_t b) {
@@ -210,19 +219,19 @@ __device__ __forceinline__ void walk_lines_to(const float* ip, int64_t n, F& f, 
                 *reinterpret_cast<float4*>(&tile[lane * WL_PITCH + 4 * i]) = o;
             }
         }
+        // (one wave per workgroup; at this scope hipcc puts no wait on vector memory into the batch loop, only lgkmcnt)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        float* const mine = have ? dst_of(b) : nullptr;
-        const unsigned long long hv = __ballot(mine != nullptr);
-        const int64_t my = reinterpret_cast<int64_t>(mine);
+        const int64_t my = have ? dst_of(b) : -1;
+        const unsigned long long hv = __ballot(my >= 0);
         // store j: the lines of lanes 8 j .. 8 j + 7; this lane writes piece lane & 7 of lane 8 j + (lane >> 3)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int owner = 8 * j + (lane >> 3);
             const int lo = __shfl((int)my, owner), hi = __shfl((int)(my >> 32), owner);
             if ((hv >> owner) & 1ull) {
-                float* dst = reinterpret_cast<float*>(((int64_t)hi << 32) | (uint32_t)lo) + 4 * (lane & 7);
+                float* dst = base + (((int64_t)hi << 32) | (uint32_t)lo) + 4 * (lane & 7);
                 *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(&tile[owner * WL_PITCH + 4 * (lane & 7)]);
             }
         }
@@ -238,8 +247,8 @@ __device__ __forceinline__ void walk_lines_to(const float* ip, int64_t n, F& f, 
     if (b < nbmax) run(A, b);
 }
 template <class F>
-__device__ __forceinline__ void walk_lines(const float* ip, float* op, int64_t n, F& f, float* tile) {
-    walk_lines_to(ip, n, f, tile, [op](int64_t b) { return op + 32 * b; });
+__device__ __forceinline__ void walk_lines(const float* in0, const float* ip, float* base, int64_t off, int64_t n, F& f, float* tile) {
+    walk_lines_to(in0, ip, n, f, tile, base, [off](int64_t b) { return off + 32 * b; });
 }
 
 // ---------------------------------------------------------------------------
@@ -759,7 +768,7 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
         for (int64_t i = 1; i < a.S; ++i) {  // (the same trip count for the whole wave)
             const int64_t k = k0 + i;
             const bool on = live && k < a.n_chunks;
-            walk_lines(xs + (on ? (k - 1) * a.L : 0), os + (on ? (k - 1) * a.L : 0), on ? a.L : 0, s, tile);
+            walk_lines(a.xdb, xs + (on ? (k - 1) * a.L : 0), a.dif, chain * a.g.U + (on ? (k - 1) * a.L : 0), on ? a.L : 0, s, tile);
             if (on) {
                 used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.yf);
                 used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.ys);
@@ -827,7 +836,7 @@ __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_t
     ArStep s{ofp_u2f(i0), ofp_u2f(i1), a.fa, a.fr, a.sa, a.sr};
     if (LINES) {  // the whole wave stays together (walk_lines); lanes with nothing to do lend their stores
         if (!__any(act)) return;
-        walk_lines(a.xdb + chain * a.g.U + start, a.dif + chain * a.g.U + start, act ? end - start : 0, s, tile);
+        walk_lines(a.xdb, a.xdb + chain * a.g.U + start, a.dif, chain * a.g.U + start, act ? end - start : 0, s, tile);
     } else {
         if (!act) return;
         int norem = -1;
@@ -1974,16 +1983,16 @@ __global__ __launch_bounds__(64) void k_hp_run_lines(HpCand a, int64_t n_threads
     int trips = act ? q1 - q0 : 0;
     for (int o = 32; o > 0; o >>= 1) trips = max(trips, __shfl_xor(trips, o));
     const float* xs = st.xt + chain * st.g.Nv;
-    float* os = st.out + chain * st.g.U;
+    const int64_t os = chain * st.g.U;  // (element offset in st.out)
     const Geom g = st.g;
     for (int it = 0; it < trips; ++it) {
         const int q = q0 + it;
         const bool on = act && q < q1 && joined < 0;
         const int64_t t0 = on ? (pieces ? min(start + q * Ls, end) : start) : 0;
         const int64_t t1 = on ? ((!pieces || q == a.S - 1) ? end : min(start + (q + 1) * Ls, end)) : 0;
-        walk_lines_to(xs + t0, t1 - t0, s, tile, [&](int64_t b) -> float* {
+        walk_lines_to(st.xt, xs + t0, t1 - t0, s, tile, st.out, [&](int64_t b) -> int64_t {
             const int64_t u = hp_dst(g, t0 + 32 * b);  // (a batch lies inside one of the three regions of the stream)
-            return u >= 0 ? os + u : nullptr;
+            return u >= 0 ? os + u : -1;
         });
         if (on && whole && q + 1 < q1) {
             const uint32_t z0 = ofp_f2u(s.z[0]), z1 = ofp_f2u(s.z[1]), z2 = ofp_f2u(s.z[2]), z3 = ofp_f2u(s.z[3]);

@@ -101,8 +101,14 @@ __global__ __launch_bounds__(Cfg<F>::WG) __attribute__((amdgpu_waves_per_eu(F ==
     const int sub = threadIdx.x / T;  // frame slot within the workgroup
     const int tid = threadIdx.x % T;
     float2* A = bufs + (size_t)sub * G::MP;
-    // segment table of the band sums (ofp_fft.h: mel_bands) and one array of partial sums per frame slot
-    MelSegs* segs = reinterpret_cast<MelSegs*>((reinterpret_cast<uintptr_t>(foff + mf.n_mels) + 15) & ~(uintptr_t)15);
+    // segment table of the band sums (ofp_fft.h: mel_bands) and one array of partial sums per frame slot.  The regions
+    // behind the filterbank are laid out as BYTE OFFSETS from smem (16-byte aligned): a pointer rounded up as an integer
+    // address belongs to no address space the compiler can name, and everything derived from it (segs, partial, the
+    // classifier's parameters, tiles and frame indices) was read and written with flat instructions -- through the
+    // vector-memory path, each followed by a full memory wait that also drained the frame's power stores and the next
+    // frame's samples.
+    auto lds_off = [&](const void* p) { return (uint32_t)(reinterpret_cast<const unsigned char*>(p) - smem); };
+    MelSegs* segs = reinterpret_cast<MelSegs*>(smem + ((lds_off(foff + mf.n_mels) + 15u) & ~15u));
     float* partial = reinterpret_cast<float*>(segs + 1) + (size_t)sub * mf.seg_stride;
     if (mf.on && threadIdx.x == 0) mel_build_segs(segs, mf.len, mf.n_mels);
     // classifier epilogue: parameters, one tile A and 16 frame indices per tile group
@@ -115,8 +121,8 @@ __global__ __launch_bounds__(Cfg<F>::WG) __attribute__((amdgpu_waves_per_eu(F ==
         const int grp_id = threadIdx.x / TC::TG;
         float* tiles = mprm + ((ml.plan.n_params + 3) & ~3);
         tileA = tiles + (size_t)grp_id * 16 * ml.plan.st_a;
-        rowf = reinterpret_cast<long long*>((reinterpret_cast<uintptr_t>(tiles + (size_t)TC::NGRP * 16 * ml.plan.st_a) + 7) &
-                                            ~(uintptr_t)7) + grp_id * 16;
+        rowf = reinterpret_cast<long long*>(smem + ((lds_off(tiles + (size_t)TC::NGRP * 16 * ml.plan.st_a) + 7u) & ~7u)) +
+               grp_id * 16;
         tileB = reinterpret_cast<float*>(bufs + (size_t)grp_id * TC::FG * G::MP);
         for (int i = threadIdx.x; i < ml.plan.n_params; i += blockDim.x) mprm[i] = ml.plan.params[i];
         if ((threadIdx.x % TC::TG) < 16) rowf[threadIdx.x % TC::TG] = -1;
