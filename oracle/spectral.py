@@ -166,13 +166,14 @@ def cspec_to_mfcc(S, sr, fmin=0, fmax=None, n_mels=40, n_mfcc=14):
 def fourier_resample(x, num):
     """scipy.signal.resample (real input, time domain, no window) restated with explicit DFT sums in fp64:
     keep the bins up to the Nyquist of the shorter length (doubling / halving that bin when the length is
-    even, as scipy does), synthesise `num` samples, scale by num / len(x).  x [Nx] -> [num]."""
+    even, as scipy does), synthesise `num` samples, scale by num / len(x).  x [Nx] -> [num].  The products k n and k m
+    are reduced modulo the length as integers before the phase is formed, so every twiddle is within a few ulp."""
     x = np.asarray(x, dtype=np.float64)
     Nx = len(x)
     N = min(num, Nx)
     K = N // 2
     n = np.arange(Nx)
-    Y = np.array([np.sum(x * np.exp(-2j * np.pi * k * n / Nx)) for k in range(K + 1)])
+    Y = np.array([np.sum(x * np.exp(-2j * np.pi * ((k * n) % Nx) / Nx)) for k in range(K + 1)])
     if N % 2 == 0:
         if num < Nx:
             Y[K] *= 2.0
@@ -181,7 +182,7 @@ def fourier_resample(x, num):
     m = np.arange(num)
     y = np.full(num, Y[0].real)
     for k in range(1, K + 1):
-        e = np.exp(2j * np.pi * k * m / num)
+        e = np.exp(2j * np.pi * ((k * m) % num) / num)
         y += (Y[k] * e).real * (1.0 if 2 * k == num else 2.0)
     return y / num * (num / Nx)
 
