@@ -89,7 +89,7 @@ __host__ __device__ inline int64_t u_src_planar(const Geom& g, int64_t u) { retu
 // then be congruent to ip modulo 16 bytes).  EV: the functor wants a per-step event
 // (`rem` counts steps to the next event; rem < 0 disables) -- used by the tracker to
 // emit its state at block ends without a per-step branch in the common batch.
-template <int PB4, int OUT, bool EV, bool DEEP = false, class F>
+template <int PB4, int OUT, bool EV, class F>
 __device__ __forceinline__ void walk(const float* ip, float* op, int64_t n, int& rem, F& f) {
     auto one = [&](float x) {
         float o = f(x);
@@ -135,35 +135,16 @@ __device__ __forceinline__ void walk(const float* ip, float* op, int64_t n, int&
         batch(v);
         __builtin_amdgcn_sched_barrier(0);
     };
-    if (DEEP) {
-        // three register sets: two batches of loads are in flight while the third is consumed
-        // (for the light steps, whose batch is shorter than one HBM round trip)
-        float4 A[PB4], Bv[PB4], Cv[PB4];
-        if (nb >= 2 * PB4) {
-            load(A);
-            load(Bv);
+    float4 A[PB4], Bv[PB4];
+    if (nb >= PB4) {
+        load(A);
+        nb -= PB4;
+        while (nb >= 2 * PB4) {
+            load(Bv); run(A);
+            load(A); run(Bv);
             nb -= 2 * PB4;
-            while (nb >= 3 * PB4) {
-                load(Cv); run(A);
-                load(A); run(Bv);
-                load(Bv); run(Cv);
-                nb -= 3 * PB4;
-            }
-            run(A);
-            run(Bv);
         }
-    } else {
-        float4 A[PB4], Bv[PB4];
-        if (nb >= PB4) {
-            load(A);
-            nb -= PB4;
-            while (nb >= 2 * PB4) {
-                load(Bv); run(A);
-                load(A); run(Bv);
-                nb -= 2 * PB4;
-            }
-            run(A);
-        }
+        run(A);
     }
     while (nb > 0) {  // leftover whole float4s
         const float4 v = *q++;
@@ -351,6 +332,9 @@ struct HpStep {
         return y;
     }
     __device__ void event() {}
+    // the state as a work list carries it (HpRuns::z)
+    __device__ void set(const float4& v) { z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w; }
+    __device__ float4 get() const { return make_float4(z[0], z[1], z[2], z[3]); }
 };
 
 // ofp_ar_step for both followers (two independent chains: their operations interleave)
@@ -547,6 +531,88 @@ __global__ __launch_bounds__(256) void k_transpose_in(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// chunk-Jacobi bookkeeping, written once for the follower and the tracker stage.
+//
+// Lane decoding, once per layout.  k is the lane's chunk -- or, for the speculative runs, its group of S chunks -- of
+// the n a chain has; chain = clip * C + c.  Planar: k fastest, neighbouring lanes do equal work.  Interleaved: channel
+// fastest, the lanes of a row's channels are neighbours (walk_il).  live: false for a lane beyond the list that stays
+// with its wave (walk_lines); it decodes to chunk 0 of chain 0, whose addresses exist.
+struct LaneAt {
+    int64_t clip, chain, k;
+    int c;
+    // the chunk's flag in dirty[] and its pair of words in used[] / end[], whatever the order of the lanes
+    __device__ __forceinline__ int64_t did(int64_t n_chunks) const { return chain * n_chunks + k; }
+    __device__ __forceinline__ int64_t sidx(int64_t n_chunks) const { return did(n_chunks) * 2; }
+};
+__device__ __forceinline__ int64_t state_idx(int64_t chain, int64_t n_chunks, int64_t k) { return (chain * n_chunks + k) * 2; }
+__device__ __forceinline__ LaneAt lane_planar(int64_t id, int64_t n, int C, bool live = true) {
+    LaneAt l;
+    l.k = live ? id % n : 0;
+    l.chain = live ? id / n : 0;
+    l.clip = l.chain / C;
+    l.c = (int)(l.chain % C);
+    return l;
+}
+template <int CH>
+__device__ __forceinline__ LaneAt lane_il(int64_t id, int64_t n) {
+    LaneAt l;
+    l.c = (int)(id % CH);
+    const int64_t r = id / CH;
+    l.k = r % n;
+    l.clip = r / n;
+    l.chain = l.clip * CH + l.c;
+    return l;
+}
+// a state pair (or one word of it) into used[] / end[]
+__device__ __forceinline__ void put_state(uint32_t* arr, int64_t sidx, float s0, float s1) {
+    arr[sidx] = ofp_f2u(s0);
+    arr[sidx + 1] = ofp_f2u(s1);
+}
+__device__ __forceinline__ void put_state(uint32_t* arr, int64_t sidx, float s) { arr[sidx] = ofp_f2u(s); }
+
+// the chunk's end state stands: the pass hands its W words on unchanged
+template <int W>
+__device__ __forceinline__ void keep_end(const uint32_t* end_prev, uint32_t* end_next, int64_t sidx) {
+#pragma unroll
+    for (int w = 0; w < W; ++w, ++sidx) end_next[sidx] = end_prev[sidx];
+}
+
+// The start rule of a chunk pass, for a lane that owns the W words at sidx (the pair, or one word of it: the chunk
+// before then has that word two places down all the same).  Load used[]; pass 0 runs from it.  A verifying pass keeps
+// chunk 0 (it starts from the true state) and a chunk whose start equals, bitwise, the end of the chunk before and
+// that no light pass marked dirty (has_dirty: the lane's word has such a flag); every other chunk is repaired: it
+// starts from that end, which becomes its used[], its dirty flag is cleared and it is counted.
+// -> whether the lane runs its chunk, from st[].
+template <int W>
+__device__ __forceinline__ bool chunk_pass_start(int pass, int64_t k, int64_t sidx, const uint32_t* end_prev,
+                                                 uint32_t* end_next, uint32_t* used, bool has_dirty, uint8_t* dirty,
+                                                 int* changed, uint32_t (&st)[W]) {
+#pragma unroll
+    for (int w = 0; w < W; ++w) st[w] = used[sidx + w];
+    if (pass == 0) return true;
+    uint32_t p[W];
+    bool keep = k == 0;
+    if (!keep) {
+        keep = true;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            p[w] = end_prev[sidx - 2 + w];
+            keep = keep && p[w] == st[w];
+        }
+        if (has_dirty && *dirty != 0) keep = false;  // a light pass changed this chunk's starting max
+    }
+    if (keep) {
+        keep_end<W>(end_prev, end_next, sidx);
+        return false;
+    }
+    if (has_dirty) *dirty = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) used[sidx + w] = st[w] = p[w];
+    atomicAdd(changed, 1);
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // follower stage (chunk-Jacobi).  thread = (clip, chunk, channel)
 struct ArArgs {
     Geom g;
@@ -578,11 +644,9 @@ __global__ __launch_bounds__(64) void k_ar_coarse(ArArgs a, int64_t n_threads, u
     OFP_LATENCY_BOUND_KERNEL();
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int64_t k = id % a.n_chunks;       // chunk fastest: neighbouring lanes do equal work
-    const int64_t chain = id / a.n_chunks;   // clip*C + c
-    const int64_t ws = max<int64_t>(k * a.L - a.W, 0);
-    const int64_t sidx = (chain * a.n_chunks + k) * 2;
-    const float* xs = a.xdb + chain * a.g.U;
+    const LaneAt ln = lane_planar(id, a.n_chunks, a.g.C);
+    const int64_t ws = max<int64_t>(ln.k * a.L - a.W, 0);
+    const float* xs = a.xdb + ln.chain * a.g.U;
     ArCoarse cs{a.floor_db, a.floor_db, a.fa, a.fr, a.sa, a.sr};  // true initial state (:697-702)
     if (ws > 0) {
         const int64_t t0 = max<int64_t>(ws - a.Wc, 0);
@@ -590,8 +654,7 @@ __global__ __launch_bounds__(64) void k_ar_coarse(ArArgs a, int64_t n_threads, u
         int norem = -1;
         walk<16, 0, false>(xs + t0, nullptr, ws - t0, norem, cs);
     }
-    used[sidx] = ofp_f2u(cs.yf);
-    used[sidx + 1] = ofp_f2u(cs.ys);
+    put_state(used, ln.sidx(a.n_chunks), cs.yf, cs.ys);
 }
 
 // Guess for a SYMMETRIC slow follower (attack == release, the reference's default 2205/2205):
@@ -659,14 +722,14 @@ __global__ __launch_bounds__(64) void k_ar_sym_combine(ArArgs a, const double* _
         for (int i = lane; i < nb; i += 64) {
             const int64_t k = b0 + i + shift;  // the chunk whose warm-up starts at this boundary
             if (k < a.n_chunks) {
-                const int64_t sidx = (chain * a.n_chunks + k) * 2;
+                const int64_t sidx = state_idx(chain, a.n_chunks, k);
                 used[sidx] = ofp_f2u(a.floor_db);
                 used[sidx + 1] = ofp_f2u(b0 + i > 0 ? ss[i] : a.floor_db);
             }
         }
     }
     for (int64_t k = lane; k < min(shift, a.n_chunks); k += 64) {  // warm-up starts at sample 0: true state
-        const int64_t sidx = (chain * a.n_chunks + k) * 2;
+        const int64_t sidx = state_idx(chain, a.n_chunks, k);
         used[sidx] = ofp_f2u(a.floor_db);
         used[sidx + 1] = ofp_f2u(a.floor_db);
     }
@@ -676,17 +739,15 @@ __global__ __launch_bounds__(64) void k_ar_warm(ArArgs a, int64_t n_threads, uin
     OFP_LATENCY_BOUND_KERNEL();
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int64_t k = id % a.n_chunks;
-    const int64_t chain = id / a.n_chunks;
-    const int64_t start = k * a.L;
+    const LaneAt ln = lane_planar(id, a.n_chunks, a.g.C);
+    const int64_t start = ln.k * a.L;
     const int64_t ws = max<int64_t>(start - a.W, 0);
-    const int64_t sidx = (chain * a.n_chunks + k) * 2;
-    const float* xs = a.xdb + chain * a.g.U;
+    const int64_t sidx = ln.sidx(a.n_chunks);
+    const float* xs = a.xdb + ln.chain * a.g.U;
     ArStep s{ofp_u2f(used[sidx]), ofp_u2f(used[sidx + 1]), a.fa, a.fr, a.sa, a.sr};
     int norem = -1;
     walk<8, 0, false>(xs + ws, nullptr, start - ws, norem, s);
-    used[sidx] = ofp_f2u(s.yf);
-    used[sidx + 1] = ofp_f2u(s.ys);
+    put_state(used, sidx, s.yf, s.ys);
 }
 
 // The same warm-up with the followers as separate lanes (symmetric-guess path): the slow one walks
@@ -704,30 +765,29 @@ __global__ __launch_bounds__(64) void k_ar_warm2(ArArgs a, int64_t n_threads, ui
     const bool fast = blockIdx.x >= half;
     const int64_t id = ((int64_t)blockIdx.x - (fast ? half : 0)) * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int64_t n_groups = cdiv(a.n_chunks, a.S);
-    const int64_t g = id % n_groups;
-    const int64_t chain = id / n_groups;
-    const int64_t k0 = g * a.S;
+    const LaneAt ln = lane_planar(id, cdiv(a.n_chunks, a.S), a.g.C);  // (k: the group)
+    const int64_t chain = ln.chain;
+    const int64_t k0 = ln.k * a.S;
     const int64_t start = k0 * a.L;
     const float* xs = a.xdb + chain * a.g.U;
     int norem = -1;
     if (!fast) {
         const int64_t ws = max<int64_t>(start - a.W, 0);
-        ArOne s{ofp_u2f(used[(chain * a.n_chunks + k0) * 2 + 1]), a.sa, a.sr};  // closed-form guess at the run's start
+        ArOne s{ofp_u2f(used[state_idx(chain, a.n_chunks, k0) + 1]), a.sa, a.sr};  // closed-form guess at the run's start
         walk<8, 0, false>(xs + ws, nullptr, start - ws, norem, s);
-        used[(chain * a.n_chunks + k0) * 2 + 1] = ofp_f2u(s.y);
+        put_state(used, state_idx(chain, a.n_chunks, k0) + 1, s.y);
         for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
             walk<8, 0, false>(xs + (k - 1) * a.L, nullptr, a.L, norem, s);
-            used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.y);
+            put_state(used, state_idx(chain, a.n_chunks, k) + 1, s.y);
         }
     } else {
         const int64_t ws = max<int64_t>(start - min(a.W, a.Wf), 0);
         ArOne s{a.floor_db, a.fa, a.fr};  // the true state at sample 0 (:697-702), a guess elsewhere
         walk<8, 0, false>(xs + ws, nullptr, start - ws, norem, s);
-        used[(chain * a.n_chunks + k0) * 2] = ofp_f2u(s.y);
+        put_state(used, state_idx(chain, a.n_chunks, k0), s.y);
         for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
             walk<8, 0, false>(xs + (k - 1) * a.L, nullptr, a.L, norem, s);
-            used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.y);
+            put_state(used, state_idx(chain, a.n_chunks, k), s.y);
         }
     }
 }
@@ -748,20 +808,18 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = id < n_threads;
     if (!LINES && !live) return;
-    const int64_t n_groups = cdiv(a.n_chunks, a.S);
-    const int64_t g = live ? id % n_groups : 0;
-    const int64_t chain = live ? id / n_groups : 0;
-    const int64_t k0 = g * a.S;
+    const LaneAt ln = lane_planar(id, cdiv(a.n_chunks, a.S), a.g.C, live);  // (k: the group)
+    const int64_t chain = ln.chain;
+    const int64_t k0 = ln.k * a.S;
     const int64_t start = k0 * a.L;
     const float* xs = a.xdb + chain * a.g.U;
     int norem = -1;
     const int64_t ws = max<int64_t>(start - a.W, 0);
-    const int64_t s0 = (chain * a.n_chunks + k0) * 2;
+    const int64_t s0 = state_idx(chain, a.n_chunks, k0);
     ArStep s{a.floor_db, live ? ofp_u2f(used[s0 + 1]) : 0.0f, a.fa, a.fr, a.sa, a.sr};  // floor / closed-form guess at the run's start
     if (live) {
         walk<8, 0, false>(xs + ws, nullptr, start - ws, norem, s);
-        used[s0] = ofp_f2u(s.yf);
-        used[s0 + 1] = ofp_f2u(s.ys);
+        put_state(used, s0, s.yf, s.ys);
     }
     float* os = a.dif + chain * a.g.U;
     if (LINES) {
@@ -770,10 +828,8 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
             const bool on = live && k < a.n_chunks;
             walk_lines(a.xdb, xs + (on ? (k - 1) * a.L : 0), a.dif, chain * a.g.U + (on ? (k - 1) * a.L : 0), on ? a.L : 0, s, tile);
             if (on) {
-                used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.yf);
-                used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.ys);
-                end0[(chain * a.n_chunks + k - 1) * 2] = ofp_f2u(s.yf);
-                end0[(chain * a.n_chunks + k - 1) * 2 + 1] = ofp_f2u(s.ys);
+                put_state(used, state_idx(chain, a.n_chunks, k), s.yf, s.ys);
+                put_state(end0, (chain * a.n_chunks + k - 1) * 2, s.yf, s.ys);
             }
         }
         return;
@@ -781,12 +837,8 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
     for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
         if (a.through) walk<8, 4, false>(xs + (k - 1) * a.L, os + (k - 1) * a.L, a.L, norem, s);
         else walk<8, 0, false>(xs + (k - 1) * a.L, nullptr, a.L, norem, s);
-        used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.yf);
-        used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.ys);
-        if (a.through) {
-            end0[(chain * a.n_chunks + k - 1) * 2] = ofp_f2u(s.yf);
-            end0[(chain * a.n_chunks + k - 1) * 2 + 1] = ofp_f2u(s.ys);
-        }
+        put_state(used, state_idx(chain, a.n_chunks, k), s.yf, s.ys);
+        if (a.through) put_state(end0, (chain * a.n_chunks + k - 1) * 2, s.yf, s.ys);
     }
 }
 
@@ -802,38 +854,15 @@ __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_t
     __shared__ float tile[LINES ? 64 * WL_PITCH : 1];
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool act = id < n_threads;
-    const int64_t k = act ? id % a.n_chunks : 0;
-    const int64_t chain = act ? id / a.n_chunks : 0;
+    const LaneAt ln = lane_planar(id, a.n_chunks, a.g.C, act);
+    const int64_t k = ln.k, chain = ln.chain;
     const int64_t start = k * a.L;
     const int64_t end = min(start + a.L, a.g.U);
-    const int64_t sidx = (chain * a.n_chunks + k) * 2;
+    const int64_t sidx = ln.sidx(a.n_chunks);
     if (act && pass == 0 && a.through && chunk_walked(k, a.S, a.n_chunks)) act = false;  // k_ar_warm_both has been through it
-    uint32_t i0 = 0, i1 = 0;
-    if (act) {
-        i0 = used[sidx];
-        i1 = used[sidx + 1];
-        if (pass > 0) {
-            if (k == 0) {
-                end_next[sidx] = end_prev[sidx];
-                end_next[sidx + 1] = end_prev[sidx + 1];
-                act = false;
-            } else {
-                const uint32_t p0 = end_prev[sidx - 2], p1 = end_prev[sidx - 1];
-                if (p0 == i0 && p1 == i1) {
-                    end_next[sidx] = end_prev[sidx];
-                    end_next[sidx + 1] = end_prev[sidx + 1];
-                    act = false;
-                } else {
-                    i0 = p0;
-                    i1 = p1;
-                    used[sidx] = i0;
-                    used[sidx + 1] = i1;
-                    atomicAdd(changed, 1);
-                }
-            }
-        }
-    }
-    ArStep s{ofp_u2f(i0), ofp_u2f(i1), a.fa, a.fr, a.sa, a.sr};
+    uint32_t st[2] = {0, 0};
+    if (act) act = chunk_pass_start<2>(pass, k, sidx, end_prev, end_next, used, false, nullptr, changed, st);
+    ArStep s{ofp_u2f(st[0]), ofp_u2f(st[1]), a.fa, a.fr, a.sa, a.sr};
     if (LINES) {  // the whole wave stays together (walk_lines); lanes with nothing to do lend their stores
         if (!__any(act)) return;
         walk_lines(a.xdb, a.xdb + chain * a.g.U + start, a.dif, chain * a.g.U + start, act ? end - start : 0, s, tile);
@@ -842,10 +871,7 @@ __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_t
         int norem = -1;
         walk<8, 4, false>(a.xdb + chain * a.g.U + start, a.dif + chain * a.g.U + start, end - start, norem, s);
     }
-    if (act) {
-        end_next[sidx] = ofp_f2u(s.yf);
-        end_next[sidx + 1] = ofp_f2u(s.ys);
-    }
+    if (act) put_state(end_next, sidx, s.yf, s.ys);
 }
 
 // ---------------------------------------------------------------------------
@@ -859,7 +885,7 @@ struct MmArgs {
     float* thr_mx;
     float alpha_min, alpha_max, ialpha_min, ialpha_max, minmin, min0, max0;
     int64_t nb, L, W, n_chunks;
-    uint8_t* dirty;  // [chains][n_chunks] chunk must be run again although its start matches (k_mm_sweep)
+    uint8_t* dirty;  // [chains][n_chunks] chunk must be run again although its start matches (k_mm_maxpass)
     int64_t n_chains;
     int64_t S;  // span of k_mm_warm2: chunks one speculative run walks through after its warm-up
     int through;  // k_mm_warm_il left the per-block outputs and the end states of the chunks it walked through (all but
@@ -877,6 +903,30 @@ struct MmArgs {
 //               used[k], pass j >= 1 re-runs chunks whose used[k] != end[k-1] bitwise.
 constexpr int64_t MM_WARM_FULL = 12288;
 
+// What the stage's kernels share.
+// Block-end output of a walk that starts at stream position `start` of (clip, c), C channels: rem = steps to the first
+// block end of the MAIN part at or after `start` (events are disabled while rem < 0, i.e. never here: the count simply
+// runs through the warm part); -> where that block's state goes in thr_mn / thr_mx ([clips][nb][C]).
+__device__ __forceinline__ int64_t mm_block_end(const MmArgs& a, int64_t clip, int c, int C, int64_t start, int& rem) {
+    const int64_t m = start - a.g.n_wb;  // position in the main part (negative: still warm part)
+    int64_t j = 0;
+    if (m >= 0) {
+        j = m / a.g.B;
+        rem = (int)(a.g.B - 1 - (m - j * a.g.B));
+    } else {
+        rem = (int)min<int64_t>(-m + a.g.B - 1, 0x7fffffff);
+    }
+    return (clip * a.nb + j) * C + c;
+}
+// the pair step from (mn, mx), C channels; no block-end output until mm_step_out says where it goes
+__device__ __forceinline__ MmStep mm_step(const MmArgs& a, float mn, float mx, int C, int* rem) {
+    return MmStep{mn, mx, a.minmin, v2f{a.ialpha_min, a.ialpha_max}, v2f{a.alpha_min, a.alpha_max}, nullptr, nullptr, C, a.g.B, rem};
+}
+__device__ __forceinline__ void mm_step_out(MmStep& s, const MmArgs& a, int64_t oi) {
+    s.pmn = a.thr_mn + oi;
+    s.pmx = a.thr_mx + oi;
+}
+
 // Speculative warm-up: the two recurrences are independent, so the max runs its whole window alone
 // (first half of the grid) WHILE the min runs its short one alone (second half), each at the speed
 // of a one-word step.
@@ -888,10 +938,9 @@ __global__ __launch_bounds__(64) void k_mm_warm2(MmArgs a, int64_t n_threads, ui
     const bool is_min = blockIdx.x >= half;
     const int64_t id = ((int64_t)blockIdx.x - (is_min ? half : 0)) * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int64_t n_groups = cdiv(a.n_chunks, a.S);
-    const int64_t g = id % n_groups;
-    const int64_t chain = id / n_groups;
-    const int64_t k0 = g * a.S;
+    const LaneAt ln = lane_planar(id, cdiv(a.n_chunks, a.S), a.g.C);  // (k: the group)
+    const int64_t chain = ln.chain;
+    const int64_t k0 = ln.k * a.S;
     const int64_t start = k0 * a.L;
     const float* rs = a.rel + chain * a.g.U;
     int norem = -1;
@@ -899,19 +948,19 @@ __global__ __launch_bounds__(64) void k_mm_warm2(MmArgs a, int64_t n_threads, ui
         const int64_t ws = max<int64_t>(start - a.W, 0);
         MaxStep mo{ws > 0 ? 0.0f : a.max0, a.ialpha_max, a.alpha_max};  // guessed from below
         walk<16, 0, false>(rs + ws, nullptr, start - ws, norem, mo);
-        used[(chain * a.n_chunks + k0) * 2 + 1] = ofp_f2u(mo.mx);
+        put_state(used, state_idx(chain, a.n_chunks, k0) + 1, mo.mx);
         for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
             walk<16, 0, false>(rs + (k - 1) * a.L, nullptr, a.L, norem, mo);
-            used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(mo.mx);
+            put_state(used, state_idx(chain, a.n_chunks, k) + 1, mo.mx);
         }
     } else {
         const int64_t ws = max(max<int64_t>(start - a.W, 0), start - MM_WARM_FULL);
         MinStep mi{ws > 0 ? __builtin_inff() : a.min0, a.ialpha_min, a.alpha_min, a.minmin};  // from above
         walk<16, 0, false>(rs + ws, nullptr, start - ws, norem, mi);
-        used[(chain * a.n_chunks + k0) * 2] = ofp_f2u(mi.mn);
+        put_state(used, state_idx(chain, a.n_chunks, k0), mi.mn);
         for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
             walk<16, 0, false>(rs + (k - 1) * a.L, nullptr, a.L, norem, mi);
-            used[(chain * a.n_chunks + k) * 2] = ofp_f2u(mi.mn);
+            put_state(used, state_idx(chain, a.n_chunks, k), mi.mn);
         }
     }
 }
@@ -951,21 +1000,9 @@ __global__ __launch_bounds__(64) void k_mm_chunk(MmArgs a, int pass, int64_t n_t
         atomicAdd(changed, 1);
     }
     const int C = a.g.C;
-    const int64_t clip = chain / C;
-    const int c = (int)(chain % C);
-    // steps to the first block end of the MAIN part at or after `start` (events are disabled
-    // while rem < 0, i.e. never here: the count simply runs through the warm part)
     int rem;
-    const int64_t m = start - a.g.n_wb;  // position in the main part (negative: still warm part)
-    int64_t j = 0;
-    if (m >= 0) {
-        j = m / a.g.B;
-        rem = (int)(a.g.B - 1 - (m - j * a.g.B));
-    } else {
-        rem = (int)min<int64_t>(-m + a.g.B - 1, 0x7fffffff);
-    }
+    const int64_t oi = mm_block_end(a, chain / C, (int)(chain % C), C, start, rem);
     const float* rs = a.rel + chain * a.g.U + start;
-    const int64_t oi = (clip * a.nb + j) * C + c;
     if (is_min) {
         MinStepEv s{ofp_u2f(i0), a.ialpha_min, a.alpha_min, a.minmin, a.thr_mn + oi, C, a.g.B, &rem};
         walk<8, 0, true>(rs, nullptr, end - start, rem, s);
@@ -980,6 +1017,83 @@ __global__ __launch_bounds__(64) void k_mm_chunk(MmArgs a, int pass, int64_t n_t
 // The same two kernels with the min and the max in ONE lane (MmStep, the 2-wide packed step): the throughput
 // setting.  A saturated launch pays for the bytes it moves, and the separate lanes read every line of the stream
 // twice, at different times; the pair costs no more instructions than the two one-word walks together.
+//
+// They exist for two sources, and with the source goes the order of the lanes.  MmPlanar: the planar copy of `rel`,
+// lane = (chain, chunk).  MmIl<CH> (throughput setting, C = CH with a `rel` output): the INTERLEAVED envelope, the rows
+// the caller gets, lane = (clip, chunk, channel), channel fastest (walk_il) -- the planar copy of `rel` is then never
+// written (one pass over the stream less per call).  A source decodes its lane and walks stream positions [u0, u1) of
+// the lane's series through a step; PB4 is the batch of the planar walk (the interleaved one always takes 32 steps).
+struct MmPlanar {
+    static constexpr bool THROUGH = false;  // the speculative runs of this side leave no pass-0 output
+    const LaneAt ln;
+    const int C;
+    const float* const rs;  // the lane's series
+    const int64_t did;      // the chunk's flag in dirty[]: the lane's own index
+    __device__ __forceinline__ MmPlanar(const MmArgs& a, int64_t id, int64_t n)
+        : ln(lane_planar(id, n, a.g.C)), C(a.g.C), rs(a.rel + ln.chain * a.g.U), did(id) {}
+    template <int PB4, bool EV, class F>
+    __device__ __forceinline__ void run(const MmArgs&, int64_t u0, int64_t u1, int& rem, F& f) const {
+        walk<PB4, 0, EV>(rs + u0, nullptr, u1 - u0, rem, f);
+    }
+};
+struct IlSrc {
+    const float* p0;
+    int64_t n0;
+    const float* p1;
+    int64_t n1;
+};
+// stream positions [u0, u1) of (clip, c): warm-up rows first, main rows after n_wb
+__device__ __forceinline__ IlSrc mm_il_range(const MmArgs& a, int64_t clip, int c, int64_t u0, int64_t u1) {
+    const int64_t nw = a.g.n_wb, C = a.g.C;
+    IlSrc s;
+    s.n0 = max<int64_t>(min(u1, nw) - u0, 0);
+    s.p0 = a.rel_warm + (clip * nw + min(u0, nw)) * C + c;
+    s.n1 = (u1 - u0) - s.n0;
+    s.p1 = a.rel_il + (clip * a.g.Nm + (max(u0, nw) - nw)) * C + c;
+    return s;
+}
+template <int CH>
+struct MmIl {
+    static constexpr bool THROUGH = true;
+    const LaneAt ln;
+    static constexpr int C = CH;
+    const int64_t did;  // the chunk's flag in dirty[]
+    __device__ __forceinline__ MmIl(const MmArgs&, int64_t id, int64_t n) : ln(lane_il<CH>(id, n)), did(ln.did(n)) {}
+    template <int PB4, bool EV, class F>
+    __device__ __forceinline__ void run(const MmArgs& a, int64_t u0, int64_t u1, int& rem, F& f) const {
+        const IlSrc q = mm_il_range(a, ln.clip, ln.c, u0, u1);
+        walk_il2<CH, 32, EV>(q.p0, q.n0, q.p1, q.n1, rem, f);
+    }
+};
+
+// Chunk with threshold output at the block ends of the MAIN part (see k_mm_chunk).
+template <class SRC>
+__device__ __forceinline__ void mm_chunk_body(const MmArgs& a, int pass, int64_t id, const uint32_t* end_prev,
+                                              uint32_t* end_next, uint32_t* used, int* changed) {
+    const SRC src(a, id, a.n_chunks);
+    const LaneAt& ln = src.ln;
+    const int C = src.C;
+    const int64_t start = ln.k * a.L;
+    const int64_t end = min(start + a.L, a.g.U);
+    const int64_t sidx = ln.sidx(a.n_chunks);
+    if (SRC::THROUGH && pass == 0 && a.through && chunk_walked(ln.k, a.S, a.n_chunks)) return;  // the warm-up has been through it
+    uint32_t st[2];
+    if (!chunk_pass_start<2>(pass, ln.k, sidx, end_prev, end_next, used, true, a.dirty + src.did, changed, st)) return;
+    int rem;
+    const int64_t oi = mm_block_end(a, ln.clip, ln.c, C, start, rem);
+    MmStep s = mm_step(a, ofp_u2f(st[0]), ofp_u2f(st[1]), C, &rem);
+    mm_step_out(s, a, oi);
+    src.template run<8, true>(a, start, end, rem, s);
+    put_state(end_next, sidx, s.mn, s.mx);
+}
+
+// The max coalesces only where the true max is reset, so a stretch without a reset (a loud hit
+// followed by seconds of quieter ones) leaves every chunk start inside it wrong after the
+// speculative warm-up, and the repair then advances ONE chunk per pass.  The max recurrence does
+// not involve the min, so once a pass has found something to repair the host switches to LIGHT
+// passes: the same verify-and-repair rule applied to the max alone (11 ns per step instead of the
+// full step, eight passes per host round trip), which marks the chunks it corrects dirty; the full
+// passes that follow run those again and remain the verification.
 __global__ __launch_bounds__(64) void k_mm_warm_both(MmArgs a, int64_t n_threads, uint32_t* __restrict__ used) {
     OFP_LATENCY_BOUND_KERNEL();
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -996,12 +1110,10 @@ __global__ __launch_bounds__(64) void k_mm_warm_both(MmArgs a, int64_t n_threads
     MmStep s{ws > 0 ? __builtin_inff() : a.min0, ws > 0 ? 0.0f : a.max0, a.minmin, v2f{a.ialpha_min, a.ialpha_max},
              v2f{a.alpha_min, a.alpha_max}, nullptr, nullptr, 0, 0, nullptr};
     walk<8, 0, false>(rs + ws, nullptr, start - ws, norem, s);
-    used[(chain * a.n_chunks + k0) * 2] = ofp_f2u(s.mn);
-    used[(chain * a.n_chunks + k0) * 2 + 1] = ofp_f2u(s.mx);
+    put_state(used, state_idx(chain, a.n_chunks, k0), s.mn, s.mx);
     for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
         walk<8, 0, false>(rs + (k - 1) * a.L, nullptr, a.L, norem, s);
-        used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.mn);
-        used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.mx);
+        put_state(used, state_idx(chain, a.n_chunks, k), s.mn, s.mx);
     }
 }
 
@@ -1013,59 +1125,9 @@ __global__ __launch_bounds__(64) void k_mm_chunk_both(MmArgs a, int pass, int64_
     if (gate && *gate == 0) return;  // (see k_ar_chunk)
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int64_t k = id % a.n_chunks;
-    const int64_t chain = id / a.n_chunks;
-    const int64_t start = k * a.L;
-    const int64_t end = min(start + a.L, a.g.U);
-    const int64_t sidx = (chain * a.n_chunks + k) * 2;
-    uint32_t i0 = used[sidx], i1 = used[sidx + 1];
-    if (pass > 0) {
-        if (k == 0) {
-            end_next[sidx] = end_prev[sidx];
-            end_next[sidx + 1] = end_prev[sidx + 1];
-            return;
-        }
-        const uint32_t p0 = end_prev[sidx - 2], p1 = end_prev[sidx - 1];
-        const bool redo = a.dirty[id] != 0;  // a light pass changed this chunk's starting max
-        if (p0 == i0 && p1 == i1 && !redo) {
-            end_next[sidx] = end_prev[sidx];
-            end_next[sidx + 1] = end_prev[sidx + 1];
-            return;
-        }
-        a.dirty[id] = 0;
-        i0 = p0;
-        i1 = p1;
-        used[sidx] = i0;
-        used[sidx + 1] = i1;
-        atomicAdd(changed, 1);
-    }
-    const int C = a.g.C;
-    const int64_t clip = chain / C;
-    const int c = (int)(chain % C);
-    int rem;
-    const int64_t m = start - a.g.n_wb;  // position in the main part (negative: still warm part)
-    int64_t j = 0;
-    if (m >= 0) {
-        j = m / a.g.B;
-        rem = (int)(a.g.B - 1 - (m - j * a.g.B));
-    } else {
-        rem = (int)min<int64_t>(-m + a.g.B - 1, 0x7fffffff);
-    }
-    const int64_t oi = (clip * a.nb + j) * C + c;
-    MmStep s{ofp_u2f(i0), ofp_u2f(i1), a.minmin, v2f{a.ialpha_min, a.ialpha_max}, v2f{a.alpha_min, a.alpha_max},
-             a.thr_mn + oi, a.thr_mx + oi, C, a.g.B, &rem};
-    walk<8, 0, true>(a.rel + chain * a.g.U + start, nullptr, end - start, rem, s);
-    end_next[sidx] = ofp_f2u(s.mn);
-    end_next[sidx + 1] = ofp_f2u(s.mx);
+    mm_chunk_body<MmPlanar>(a, pass, id, end_prev, end_next, used, changed);
 }
 
-// The max coalesces only where the true max is reset, so a stretch without a reset (a loud hit
-// followed by seconds of quieter ones) leaves every chunk start inside it wrong after the
-// speculative warm-up, and the repair then advances ONE chunk per pass.  The max recurrence does
-// not involve the min, so once a pass has found something to repair the host switches to LIGHT
-// passes: the same verify-and-repair rule applied to the max alone (11 ns per step instead of the
-// full step, eight passes per host round trip), which marks the chunks it corrects dirty; the full
-// passes that follow run those again and remain the verification.
 __global__ __launch_bounds__(64) void k_mm_maxpass(MmArgs a, int64_t n_threads, const uint32_t* __restrict__ end_prev,
                                                    uint32_t* __restrict__ end_next, uint32_t* __restrict__ used,
                                                    int* changed, const int* gate) {
@@ -1092,26 +1154,6 @@ __global__ __launch_bounds__(64) void k_mm_maxpass(MmArgs a, int64_t n_threads, 
     atomicAdd(changed, 1);
 }
 
-// ---- the tracker on the INTERLEAVED envelope (throughput setting, C = 4 or 8 with a `rel` output): the three kernels
-// above with lane = (clip, chunk, channel), channel fastest, reading the rows the caller gets (walk_il) -- the planar
-// copy of `rel` is then never written (one pass over the stream less per call).
-struct IlSrc {
-    const float* p0;
-    int64_t n0;
-    const float* p1;
-    int64_t n1;
-};
-// stream positions [u0, u1) of (clip, c): warm-up rows first, main rows after n_wb
-__device__ __forceinline__ IlSrc mm_il_range(const MmArgs& a, int64_t clip, int c, int64_t u0, int64_t u1) {
-    const int64_t nw = a.g.n_wb, C = a.g.C;
-    IlSrc s;
-    s.n0 = max<int64_t>(min(u1, nw) - u0, 0);
-    s.p0 = a.rel_warm + (clip * nw + min(u0, nw)) * C + c;
-    s.n1 = (u1 - u0) - s.n0;
-    s.p1 = a.rel_il + (clip * a.g.Nm + (max(u0, nw) - nw)) * C + c;
-    return s;
-}
-
 template <int CH>
 __global__ __launch_bounds__(64) void k_mm_warm_il(MmArgs a, int64_t n_threads, uint32_t* __restrict__ used,
                                                    uint32_t* __restrict__ end0) {
@@ -1123,42 +1165,24 @@ __global__ __launch_bounds__(64) void k_mm_warm_il(MmArgs a, int64_t n_threads, 
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
     const int64_t n_groups = cdiv(a.n_chunks, a.S);
-    const int c = (int)(id % CH);
-    const int64_t r = id / CH;
-    const int64_t g = r % n_groups;
-    const int64_t clip = r / n_groups;
-    const int64_t chain = clip * CH + c;
-    const int64_t k0 = g * a.S;
+    const LaneAt ln = lane_il<CH>(id, n_groups);  // (k: the group)
+    const int c = ln.c;
+    const int64_t clip = ln.clip, chain = ln.chain;
+    const int64_t k0 = ln.k * a.S;
     const int64_t start = k0 * a.L;
     int rem = -1;  // (no events during the warm-up)
     const int64_t ws = max<int64_t>(start - a.W, 0);
-    MmStep s{ws > 0 ? __builtin_inff() : a.min0, ws > 0 ? 0.0f : a.max0, a.minmin, v2f{a.ialpha_min, a.ialpha_max},
-             v2f{a.alpha_min, a.alpha_max}, nullptr, nullptr, CH, a.g.B, &rem};
+    MmStep s = mm_step(a, ws > 0 ? __builtin_inff() : a.min0, ws > 0 ? 0.0f : a.max0, CH, &rem);
     IlSrc q = mm_il_range(a, clip, c, ws, start);
     walk_il2<CH, 32, true>(q.p0, q.n0, q.p1, q.n1, rem, s);
-    used[(chain * a.n_chunks + k0) * 2] = ofp_f2u(s.mn);
-    used[(chain * a.n_chunks + k0) * 2 + 1] = ofp_f2u(s.mx);
-    if (a.through) {  // block-end output from chunk k0 on (as in k_mm_chunk_il)
-        const int64_t m = start - a.g.n_wb;
-        int64_t j = 0;
-        if (m >= 0) {
-            j = m / a.g.B;
-            rem = (int)(a.g.B - 1 - (m - j * a.g.B));
-        } else {
-            rem = (int)min<int64_t>(-m + a.g.B - 1, 0x7fffffff);
-        }
-        const int64_t oi = (clip * a.nb + j) * CH + c;
-        s.pmn = a.thr_mn + oi;
-        s.pmx = a.thr_mx + oi;
-    }
+    put_state(used, state_idx(chain, a.n_chunks, k0), s.mn, s.mx);
+    if (a.through) mm_step_out(s, a, mm_block_end(a, clip, c, CH, start, rem));  // block-end output from chunk k0 on
     for (int64_t k = k0 + 1; k < min(k0 + a.S, a.n_chunks); ++k) {
         q = mm_il_range(a, clip, c, (k - 1) * a.L, k * a.L);
         walk_il2<CH, 32, true>(q.p0, q.n0, q.p1, q.n1, rem, s);
-        used[(chain * a.n_chunks + k) * 2] = ofp_f2u(s.mn);
-        used[(chain * a.n_chunks + k) * 2 + 1] = ofp_f2u(s.mx);
+        put_state(used, state_idx(chain, a.n_chunks, k), s.mn, s.mx);
         if (a.through) {
-            end0[(chain * a.n_chunks + k - 1) * 2] = ofp_f2u(s.mn);
-            end0[(chain * a.n_chunks + k - 1) * 2 + 1] = ofp_f2u(s.mx);
+            put_state(end0, (chain * a.n_chunks + k - 1) * 2, s.mn, s.mx);
         }
     }
 }
@@ -1172,53 +1196,7 @@ __global__ __launch_bounds__(64) void k_mm_chunk_il(MmArgs a, int pass, int64_t 
     if (gate && *gate == 0) return;  // (see k_ar_chunk)
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int c = (int)(id % CH);
-    const int64_t r = id / CH;
-    const int64_t k = r % a.n_chunks;
-    const int64_t clip = r / a.n_chunks;
-    const int64_t chain = clip * CH + c;
-    const int64_t did = chain * a.n_chunks + k;  // (the index the planar kernels call `id`)
-    const int64_t start = k * a.L;
-    const int64_t end = min(start + a.L, a.g.U);
-    const int64_t sidx = did * 2;
-    if (pass == 0 && a.through && chunk_walked(k, a.S, a.n_chunks)) return;  // k_mm_warm_il has been through it
-    uint32_t i0 = used[sidx], i1 = used[sidx + 1];
-    if (pass > 0) {
-        if (k == 0) {
-            end_next[sidx] = end_prev[sidx];
-            end_next[sidx + 1] = end_prev[sidx + 1];
-            return;
-        }
-        const uint32_t p0 = end_prev[sidx - 2], p1 = end_prev[sidx - 1];
-        const bool redo = a.dirty[did] != 0;  // a light pass changed this chunk's starting max
-        if (p0 == i0 && p1 == i1 && !redo) {
-            end_next[sidx] = end_prev[sidx];
-            end_next[sidx + 1] = end_prev[sidx + 1];
-            return;
-        }
-        a.dirty[did] = 0;
-        i0 = p0;
-        i1 = p1;
-        used[sidx] = i0;
-        used[sidx + 1] = i1;
-        atomicAdd(changed, 1);
-    }
-    int rem;
-    const int64_t m = start - a.g.n_wb;  // position in the main part (negative: still warm part)
-    int64_t j = 0;
-    if (m >= 0) {
-        j = m / a.g.B;
-        rem = (int)(a.g.B - 1 - (m - j * a.g.B));
-    } else {
-        rem = (int)min<int64_t>(-m + a.g.B - 1, 0x7fffffff);
-    }
-    const int64_t oi = (clip * a.nb + j) * CH + c;
-    MmStep s{ofp_u2f(i0), ofp_u2f(i1), a.minmin, v2f{a.ialpha_min, a.ialpha_max}, v2f{a.alpha_min, a.alpha_max},
-             a.thr_mn + oi, a.thr_mx + oi, CH, a.g.B, &rem};
-    const IlSrc q = mm_il_range(a, clip, c, start, end);
-    walk_il2<CH, 32, true>(q.p0, q.n0, q.p1, q.n1, rem, s);
-    end_next[sidx] = ofp_f2u(s.mn);
-    end_next[sidx + 1] = ofp_f2u(s.mx);
+    mm_chunk_body<MmIl<CH>>(a, pass, id, end_prev, end_next, used, changed);
 }
 
 template <int CH>
@@ -1229,11 +1207,10 @@ __global__ __launch_bounds__(64) void k_mm_maxpass_il(MmArgs a, int64_t n_thread
     if (gate && *gate == 0) return;
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_threads) return;
-    const int c = (int)(id % CH);
-    const int64_t r = id / CH;
-    const int64_t k = r % a.n_chunks;
-    const int64_t clip = r / a.n_chunks;
-    const int64_t did = (clip * CH + c) * a.n_chunks + k;
+    const LaneAt ln = lane_il<CH>(id, a.n_chunks);
+    const int c = ln.c;
+    const int64_t k = ln.k, clip = ln.clip;
+    const int64_t did = ln.did(a.n_chunks);
     const int64_t sidx = did * 2;
     end_next[sidx] = end_prev[sidx];  // the min is not touched here
     if (k == 0 || used[sidx + 1] == end_prev[sidx - 1]) {
@@ -1327,6 +1304,7 @@ struct HpCand {
         return (((((clip * st.n_chunks + k) * st.g.C + c) * R + r) * (S - 1)) + sb) * 4;
     }
 };
+constexpr uint32_t HP_EMPTY = 0x7fc00001u;  // start state of a slot no run filled: a NaN pattern no state can equal
 
 
 // pass A: thread = (clip, channel, chunk, candidate), candidate fastest.
@@ -1369,10 +1347,10 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_candidates(HpCand a, int
         a.guessed[ci] = 0;
         a.ran[ci] = -2;
         a.mrg[ci] = -1;
-        a.U[a.slot(clip, j, c, a.R)] = 0x7fc00001u;  // slot R empty: a NaN pattern no state can equal
+        a.U[a.slot(clip, j, c, a.R)] = HP_EMPTY;  // slot R empty
         // slots of runs that would have started before the stream: never match, never agree
         for (int rr = (int)min<int64_t>((j + 1) * Rm, a.R); rr < a.R; ++rr) {
-            a.U[a.slot(clip, j, c, rr)] = 0x7fc00001u;
+            a.U[a.slot(clip, j, c, rr)] = HP_EMPTY;
             a.E[a.slot(clip, j, c, rr)] = 0x7fc00100u + (uint32_t)rr;
         }
     }
@@ -1447,7 +1425,7 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg0(HpCand a, HpRuns ou
         a.guessed[ci] = 0;
         a.ran[ci] = -2;
         a.mrg[ci] = -1;
-        a.U[a.slot(clip, j, c, a.R)] = 0x7fc00001u;  // slot R empty: a NaN pattern no state can equal
+        a.U[a.slot(clip, j, c, a.R)] = HP_EMPTY;  // slot R empty
         off[grp] = (int32_t)(grp * a.R);
         cnt[grp] = a.R;
     }
@@ -1460,7 +1438,7 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg0(HpCand a, HpRuns ou
     hp_span<false>(st, s, chain, ws, max<int64_t>(w0 + p1, 0));
     out.grp[id] = (int32_t)grp;  // the runs of a group are neighbours in the list (k_hp_dedupe)
     out.mask[id] = 1u << r;
-    out.z[id] = make_float4(s.z[0], s.z[1], s.z[2], s.z[3]);
+    out.z[id] = s.get();
 }
 
 // between stages: 16 lanes per group, lane i holds run i of the group.  A run whose state equals (bitwise) that of
@@ -1521,11 +1499,10 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg(HpCand a, HpRuns run
     const int64_t chain = grp / st.n_chunks;
     HpStep s;
     s.coeffs(st.b, st.a);
-    const float4 v = runs.z[id];
-    s.z[0] = v.x; s.z[1] = v.y; s.z[2] = v.z; s.z[3] = v.w;
+    s.set(runs.z[id]);
     const int64_t w0 = j * st.L - st.W;
     hp_span<false>(st, s, chain, max<int64_t>(w0 + p0, 0), max<int64_t>(w0 + p1, 0));
-    runs.z[id] = make_float4(s.z[0], s.z[1], s.z[2], s.z[3]);
+    runs.z[id] = s.get();
 }
 
 // the last stage: the chunk itself, with the records of every slot the run stands for
@@ -1542,8 +1519,7 @@ __global__ __launch_bounds__(HP_CAND_THREADS) void k_hp_seg_chunk(HpCand a, HpRu
     const int c = (int)(chain % C);
     HpStep s;
     s.coeffs(st.b, st.a);
-    const float4 v = runs.z[id];
-    s.z[0] = v.x; s.z[1] = v.y; s.z[2] = v.z; s.z[3] = v.w;
+    s.set(runs.z[id]);
     const int64_t Ls = st.L / a.S;
     const int64_t start = k * st.L;
     const int64_t end = min(start + st.L, st.g.V);
@@ -1875,7 +1851,7 @@ __device__ __forceinline__ bool hp_run_item(const HpCand& a, int64_t chain, int6
         if (whole && q + 1 < q1) {
             const uint32_t z0 = ofp_f2u(s.z[0]), z1 = ofp_f2u(s.z[1]), z2 = ofp_f2u(s.z[2]), z3 = ofp_f2u(s.z[3]);
             for (int r = 0; r < a.R; ++r) {
-                if (a.U[a.slot(clip, k, c, r)] == 0x7fc00001u) continue;  // a slot no run filled: no records
+                if (a.U[a.slot(clip, k, c, r)] == HP_EMPTY) continue;  // a slot no run filled: no records
                 const uint32_t* m = a.M + a.mslot(clip, k, c, r, q);
                 if (m[0] == z0 && m[1] == z1 && m[2] == z2 && m[3] == z3) {
                     joined = r;
@@ -1997,7 +1973,7 @@ __global__ __launch_bounds__(64) void k_hp_run_lines(HpCand a, int64_t n_threads
         if (on && whole && q + 1 < q1) {
             const uint32_t z0 = ofp_f2u(s.z[0]), z1 = ofp_f2u(s.z[1]), z2 = ofp_f2u(s.z[2]), z3 = ofp_f2u(s.z[3]);
             for (int r = 0; r < a.R; ++r) {
-                if (a.U[a.slot(clip, k, c, r)] == 0x7fc00001u) continue;  // a slot no run filled: no records
+                if (a.U[a.slot(clip, k, c, r)] == HP_EMPTY) continue;  // a slot no run filled: no records
                 const uint32_t* m = a.M + a.mslot(clip, k, c, r, q);
                 if (m[0] == z0 && m[1] == z1 && m[2] == z2 && m[3] == z3) {
                     joined = r;
@@ -2488,8 +2464,8 @@ __global__ __launch_bounds__(64) void k_last_clear_scan(int32_t* __restrict__ ti
 // The state machine only has to stop at blocks where some channel crosses its on threshold
 // upwards ("visits"): everywhere else no onset can fire, the cooldown counters move in closed
 // form and a latched channel is released iff a block in between holds a row below its off
-// threshold -- which pc[] answers.  k_visits compacts, per clip and in order, the visited blocks
-// and gathers what the machine needs there: fc, lb of the block and pc of the block before.
+// threshold -- which pc[] answers.  k_visit_count / _scan / _scatter compact, per clip and in order, the visited
+// blocks and gather what the machine needs there: fc, lb of the block and pc of the block before.
 struct VisArgs {
     const uint32_t* vflag;
     const int32_t *fc, *lb, *pc;  // [clips][nb][C]
@@ -2571,7 +2547,7 @@ struct SmArgs {
     Geom g;
     int64_t nb, n_clips, cap, cooldown;
     const int32_t* vis_j;            // [clips][nb] visited blocks, in order
-    const int32_t *vfc, *vlb, *vpc;  // [clips][nb][C] their records (k_visits)
+    const int32_t *vfc, *vlb, *vpc;  // [clips][nb][C] their records (k_visit_scatter)
     const int32_t* nv;               // [clips] number of visits
     ofp_onset* records;              // [clips][cap]
     int64_t* counts;                 // [clips]
@@ -3006,6 +2982,24 @@ constexpr int OFP_N_COUNTERS = 512;  // int slots at the head of the zeroed regi
 // The stages of one call, in the order they are enqueued (see run)
 enum Stage { HEAD, CANDIDATES, ROUNDS, FOLLOWERS, TRACKER, END };
 
+// The three state arrays of a chunk-Jacobi stage, `words` each, in one work-space region: the start states used[],
+// then the two end arrays (pass 0 writes A)
+struct StateArrays {
+    uint32_t *used, *endA, *endB;
+};
+constexpr int64_t state_arrays_bytes(int64_t words) { return 3 * words * 4; }
+inline StateArrays state_arrays(uint32_t* base, int64_t words) { return StateArrays{base, base + words, base + 2 * words}; }
+// The staged candidates' two work lists of n0 runs each (HpRuns: state, group, slot set) in one region
+constexpr int64_t hp_run_lists_bytes(int64_t n0) { return 2 * n0 * (16 + 4 + 4) + 64; }
+inline void hp_run_lists(unsigned char* base, int64_t n0, HpRuns (&rl)[2]) {
+    // z (16 B) of both first, then grp, then mask
+    for (int i = 0; i < 2; ++i) {
+        rl[i].z = reinterpret_cast<float4*>(base) + i * n0;
+        rl[i].grp = reinterpret_cast<int32_t*>(base + n0 * 32) + i * n0;
+        rl[i].mask = reinterpret_cast<uint32_t*>(base + n0 * 40) + i * n0;
+    }
+}
+
 // The plan of one call: the work-space layout and every kernel-variant decision, made here from the detector's
 // parameters, its tuning and the call's sizes.  The byte offsets do not depend on `rel` (ofp_detect_workspace_bytes and
 // the planar-input queries do not know it).
@@ -3019,7 +3013,7 @@ struct Layout {
     bool hp_early;   // whole runs stop early at a sub-chunk boundary (k_hp_run)
     bool hp_staged;  // candidates in stages with duplicate runs removed between them (k_hp_seg*)
     int64_t ar_L, ar_W, ar_Wc, ar_Wf, ar_chunks, ar_S;
-    bool ar_sym;  // closed-form guess for the slow follower (k_ar_guess_sym)
+    bool ar_sym;  // closed-form guess for the slow follower (k_ar_sym_local / k_rect_db_sym, k_ar_sym_combine)
     int64_t mm_L, mm_W, mm_chunks, mm_S;
     int tu;  // time steps per transpose tile
     // kernel variants
@@ -3273,12 +3267,12 @@ Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t wa
         l.o_hp_gs = take(cc);
         l.o_hp_mrg = take(cc);
         // staged candidates: two work lists of {group, slot set, state} and the groups' ranges in the current one
-        l.o_hp_runs = take(l.hp_staged ? 2 * cc * l.hp_R * 24 + 64 : 0);
+        l.o_hp_runs = take(l.hp_staged ? hp_run_lists_bytes(cc * l.hp_R) : 0);
         l.o_hp_goff = take(l.hp_staged ? 2 * cc * 4 : 0);
     }
-    l.o_ar_state = take(3 * n_clips * l.ar_chunks * g.C * 2 * 4);
+    l.o_ar_state = take(state_arrays_bytes(n_clips * l.ar_chunks * g.C * 2));
     l.o_ar_P = take(n_clips * l.ar_chunks * g.C * 8);
-    l.o_mm_state = take(3 * n_clips * l.mm_chunks * g.C * 2 * 4);
+    l.o_mm_state = take(state_arrays_bytes(n_clips * l.mm_chunks * g.C * 2));
     l.o_thr_mn = take(n_clips * l.nb * g.C * 4);
     l.o_thr_mx = take(n_clips * l.nb * g.C * 4);
     l.o_first = take(n_clips * l.nb * g.C * 4);
@@ -3330,37 +3324,56 @@ struct Counters {
     }
 };
 
-// chunk-Jacobi driver: `chunk` kernel pass 0 (from used[]), then verification/repair passes
-// until a pass changes nothing.  used[] has been filled by the stage's warm-up kernels.
+// The launches of a chunk-Jacobi stage, for both drivers below: pass 0 (from used[], which the stage's warm-up kernels
+// have filled; it reads no end array and writes A), then passes that read the end array the pass before wrote and
+// write the other one.
+template <class K, class A>
+struct JacobiPasses {
+    using Light = void (*)(const A&, int64_t, const uint32_t*, uint32_t*, uint32_t*, int*, const int*, hipStream_t);
+    K chunk;
+    const A& args;
+    int64_t n_threads;
+    uint32_t* used;
+    Light light_pass;
+    int block;
+    hipStream_t stream;
+    uint32_t *prev, *next;
+    JacobiPasses(K chunk, const A& args, int64_t n_threads, uint32_t* used, Light light_pass, int64_t words, int block,
+                 hipStream_t stream)
+        : chunk(chunk), args(args), n_threads(n_threads), used(used), light_pass(light_pass), block(block), stream(stream) {
+        const StateArrays sa = state_arrays(used, words ? words : n_threads * 2);
+        prev = sa.endB;
+        next = sa.endA;
+    }
+    void full(int pass, int* changed, const int* gate) {
+        hipLaunchKernelGGL(chunk, dim3((unsigned)cdiv(n_threads, 64)), dim3(block), 0, stream, args, pass, n_threads,
+                           (const uint32_t*)prev, next, used, changed, gate);
+        std::swap(prev, next);
+    }
+    void light(int* changed, const int* gate) {
+        light_pass(args, n_threads, prev, next, used, changed, gate, stream);
+        std::swap(prev, next);
+    }
+};
+
+// chunk-Jacobi driver: `chunk` kernel pass 0, then verification/repair passes until a pass changes nothing.
 template <class K, class A>
 int run_jacobi(const char* name, K chunk, const A& args, int64_t n_threads, int64_t n_chunks, uint32_t* used,
                Counters& ctr, int* h_flags, int max_passes, int group, hipStream_t stream, int64_t* passes,
-               int64_t* repaired,
-               void (*light_pass)(const A&, int64_t, const uint32_t*, uint32_t*, uint32_t*, int*, const int*, hipStream_t) = nullptr,
-               int64_t words = 0, int block = 64) {
-    if (words == 0) words = n_threads * 2;  // state words per array
-    uint32_t* endA = used + words;
-    uint32_t* endB = endA + words;
-    const unsigned grid = (unsigned)cdiv(n_threads, 64);
+               int64_t* repaired, typename JacobiPasses<K, A>::Light light_pass = nullptr, int64_t words = 0, int block = 64) {
+    JacobiPasses<K, A> jp(chunk, args, n_threads, used, light_pass, words, block, stream);
     int* d_changed = ctr.base;  // pass 0 counts nothing
-    hipLaunchKernelGGL(chunk, dim3(grid), dim3(block), 0, stream, args, 0, n_threads, (const uint32_t*)endB, endA, used,
-                       d_changed, (const int*)nullptr);
+    jp.full(0, d_changed, nullptr);
     OFP_LAUNCH_CHECK(name);
     *passes = 1;
     if (n_chunks == 1) return OFP_OK;  // a single chunk starts from the true state: exact
-    uint32_t* prev = endA;
-    uint32_t* next = endB;
     // Verification passes are enqueued `group` at a time with ONE host synchronisation per group: a pass
     // that finds nothing to repair costs microseconds on the GPU (every lane compares two words and
     // copies its end state), a host round trip costs tens.  Converged = a pass of the group changed nothing.
     group = std::max(1, std::min(group, 8));
     for (int pass = 1;;) {
         if (int rc = ctr.take(group, &d_changed)) return rc;
-        for (int q = 0; q < group; ++q) {
-            hipLaunchKernelGGL(chunk, dim3(grid), dim3(block), 0, stream, args, pass + q, n_threads, (const uint32_t*)prev,
-                               next, used, d_changed + q, (const int*)nullptr);
-            std::swap(prev, next);
-        }
+        for (int q = 0; q < group; ++q) jp.full(pass + q, d_changed + q, nullptr);
         OFP_LAUNCH_CHECK(name);
         OFP_HIP(hipMemcpyAsync(h_flags, d_changed, group * sizeof(int), hipMemcpyDeviceToHost, stream));
         OFP_HIP(hipStreamSynchronize(stream));
@@ -3378,10 +3391,7 @@ int run_jacobi(const char* name, K chunk, const A& args, int64_t n_threads, int6
         if (light_pass) {  // a cascade is under way: light passes, eight per host round trip
             for (int grp = 0; grp < 4096; ++grp) {
                 if (int rc = ctr.take(1, &d_changed)) return rc;
-                for (int q = 0; q < 8; ++q) {
-                    light_pass(args, n_threads, prev, next, used, d_changed, nullptr, stream);
-                    std::swap(prev, next);
-                }
+                for (int q = 0; q < 8; ++q) jp.light(d_changed, nullptr);
                 OFP_LAUNCH_CHECK(name);
                 OFP_HIP(hipMemcpyAsync(h_flags, d_changed, sizeof(int), hipMemcpyDeviceToHost, stream));
                 OFP_HIP(hipStreamSynchronize(stream));
@@ -3401,29 +3411,15 @@ int run_jacobi(const char* name, K chunk, const A& args, int64_t n_threads, int6
 // (not converged: the call is repeated in the host-verified form above).  flags: 2 * nv zeroed ints.
 template <class K, class A>
 int run_jacobi_ahead(const char* name, K chunk, const A& args, int64_t n_threads, int64_t n_chunks, uint32_t* used,
-                     int* flags, int nv, hipStream_t stream,
-                     void (*light_pass)(const A&, int64_t, const uint32_t*, uint32_t*, uint32_t*, int*, const int*, hipStream_t) = nullptr,
+                     int* flags, int nv, hipStream_t stream, typename JacobiPasses<K, A>::Light light_pass = nullptr,
                      int64_t words = 0, int block = 64) {
-    if (words == 0) words = n_threads * 2;
-    uint32_t* endA = used + words;
-    uint32_t* endB = endA + words;
-    const unsigned grid = (unsigned)cdiv(n_threads, 64);
-    hipLaunchKernelGGL(chunk, dim3(grid), dim3(block), 0, stream, args, 0, n_threads, (const uint32_t*)endB, endA, used,
-                       flags, (const int*)nullptr);
-    uint32_t* prev = endA;
-    uint32_t* next = endB;
+    JacobiPasses<K, A> jp(chunk, args, n_threads, used, light_pass, words, block, stream);
+    jp.full(0, flags, nullptr);
     if (n_chunks > 1) {
         for (int j = 1; j <= nv; ++j) {
-            const int* gate = j > 1 ? flags + j - 2 : nullptr;
-            hipLaunchKernelGGL(chunk, dim3(grid), dim3(block), 0, stream, args, j, n_threads, (const uint32_t*)prev, next, used,
-                               flags + j - 1, gate);
-            std::swap(prev, next);
-            if (light_pass && j % 2 == 0 && j < nv) {
-                for (int q = 0; q < 8; ++q) {
-                    light_pass(args, n_threads, prev, next, used, flags + nv + j - 1, flags + j - 1, stream);
-                    std::swap(prev, next);
-                }
-            }
+            jp.full(j, flags + j - 1, j > 1 ? flags + j - 2 : nullptr);
+            if (light_pass && j % 2 == 0 && j < nv)
+                for (int q = 0; q < 8; ++q) jp.light(flags + nv + j - 1, flags + j - 1);
         }
     }
     OFP_LAUNCH_CHECK(name);
@@ -3539,14 +3535,7 @@ int iir_candidates(Call& c) {
         const int64_t n0 = nC0 * hc.R;
         OFP_REQUIRE(n0 < (1ll << 31), "ofp_detect_offline: %lld speculative runs in one call", (long long)n0);
         HpRuns rl[2];
-        // layout of the two lists: z (16 B) of both first, then grp, then mask
-        unsigned char* rb = c.ws + l.o_hp_runs;
-        rl[0].z = reinterpret_cast<float4*>(rb);
-        rl[1].z = reinterpret_cast<float4*>(rb + n0 * 16);
-        rl[0].grp = reinterpret_cast<int32_t*>(rb + n0 * 32);
-        rl[1].grp = reinterpret_cast<int32_t*>(rb + n0 * 36);
-        rl[0].mask = reinterpret_cast<uint32_t*>(rb + n0 * 40);
-        rl[1].mask = reinterpret_cast<uint32_t*>(rb + n0 * 44);
+        hp_run_lists(c.ws + l.o_hp_runs, n0, rl);
         int32_t* goff = c.at<int32_t>(l.o_hp_goff);
         int32_t* gcnt = goff + nC0;
         int* stage_n = c.at<int>(l.o_hp_stage_n);
@@ -3711,7 +3700,7 @@ int followers(Call& c, bool host_verified) {
         const int64_t ntg = chains * cdiv(l.ar_chunks, l.ar_S);  // one run per group of S chunks
         if (l.merge)
             hipLaunchKernelGGL(l.ar_lines ? k_ar_warm_both<true> : k_ar_warm_both<false>, dim3((unsigned)cdiv(ntg, 64)), dim3(64),
-                               0, c.stream, a, ntg, used, used + 2 * nt);
+                               0, c.stream, a, ntg, used, state_arrays(used, 2 * nt).endA);
         else
             hipLaunchKernelGGL(k_ar_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
         OFP_LAUNCH_CHECK("k_ar_warm2");
@@ -3770,7 +3759,7 @@ int tracker(Call& c, bool host_verified) {
     if (l.mm_il)
         with_il_channels(l.g.C, [&](auto ch) {
             hipLaunchKernelGGL(k_mm_warm_il<decltype(ch)::value>, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg,
-                               used, used + 2 * nt);
+                               used, state_arrays(used, 2 * nt).endA);
         });
     else if (l.merge)
         hipLaunchKernelGGL(k_mm_warm_both, dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
