@@ -189,8 +189,11 @@ typedef struct ofp_detect_tuning {
                                     the wave stores complete 128-byte lines (8 lanes x 16 B) instead of 64 lane-private
                                     16-byte pieces per instruction: +11 % frames/s in flight, +5 % for a lone BIG call
                                     (C3), slower for a small one.  0 auto (the throughput layout, or launches of more
-                                    than two / half a wave per SIMD), 1 whenever the sizes allow, < 0 off.  Results do
-                                    not change. */
+                                    than two / half a wave per SIMD), 1 whenever the sizes allow, < 0 off.  Where the
+                                    interleaved `rel` is what the later stages read (`interleaved`, 4 or 8 channels) and
+                                    the warm-up and main parts are multiples of 32 rows, the followers' lines go
+                                    straight into that array and the conversion back to linear runs in place there.
+                                    Results do not change. */
 } ofp_detect_tuning;
 
 typedef struct ofp_detector ofp_detector; /* opaque */

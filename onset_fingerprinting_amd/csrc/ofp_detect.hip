@@ -163,9 +163,19 @@ __device__ __forceinline__ void walk(const float* ip, float* op, int64_t n, int&
 // 8 complete lines per instruction (8 lanes x 16 B a line) 4.7-5.0 TB/s.  All 64 lanes of the wave call this together
 // (their n may differ, 0 = nothing to do; each a multiple of 32 steps; ip / op 16-byte aligned); tile: 64 x WL_PITCH
 // floats of LDS owned by the wave.
+//
+// IL = 4 or 8, the channel-fastest form: the wave's lanes were decoded with lane_il<IL>, so the IL lanes of one (clip,
+// chunk) are neighbours and their batches are the same 32 rows of the caller's interleaved [time][channel] array: 32 x IL
+// contiguous floats (1 KB, eight complete lines, at IL = 8).  The walk and the tile write are the same; the store phase
+// hands the batch of one (IL = 8) or two (IL = 4) chunk groups to each store instruction, every lane taking the four
+// channels of one row out of the tile.  The lanes of a group walk together or not at all (the same n: the caller sees to
+// it); dst_of(b) names the group's 32 rows: an element offset from `base`, or ~offset from `base_w` (the warm-up rows
+// live in an array of their own).  Both bases come straight from kernel arguments, so the selected address stays a
+// global one.
 constexpr int WL_PITCH = 36;  // 32 + 4 floats: 16-byte rows, banks spread
-template <class F, class D>
-__device__ __forceinline__ void walk_lines_to(const float* in0, const float* ip, int64_t n, F& f, float* tile, float* base, D&& dst_of) {
+template <int IL = 0, class F, class D>
+__device__ __forceinline__ void walk_lines_to(const float* in0, const float* ip, int64_t n, F& f, float* tile, float* base, D&& dst_of,
+                                              float* base_w = nullptr) {
     // dst_of(b): where the lane's batch b (32 steps) goes, as an element offset from `base`, or < 0 for a batch without
     // output.  `base` is the same for the whole wave and comes straight from a kernel argument: the row owners hand
     // OFFSETS round, so the address of a cooperative store is base + offset and stays a global one.  (A pointer rebuilt
@@ -204,6 +214,27 @@ __device__ __forceinline__ void walk_lines_to(const float* in0, const float* ip,
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if constexpr (IL != 0) {
+            constexpr int F4 = 8 * IL;  // 16-byte pieces of a group's batch; a store instruction takes 64 / F4 groups
+            constexpr int Q = IL / 4;   // pieces per row
+            const int64_t at = have ? dst_of(b) : 0;
+            const unsigned long long hv = __ballot(have);
+            const int m = lane % F4, t = m / Q, c0 = 4 * (m % Q);  // the piece: row t, channels c0 .. c0 + 3
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int g0 = (j * (64 / F4) + lane / F4) * IL;  // the group's first lane (wave-uniform at IL = 8)
+                const int lo = __shfl((int)at, g0), hi = __shfl((int)(at >> 32), g0);
+                if ((hv >> g0) & 1ull) {
+                    const int64_t enc = ((int64_t)hi << 32) | (uint32_t)lo;
+                    float* dst = (enc < 0 ? base_w + ~enc : base + enc) + 4 * m;
+                    const float* src = &tile[(g0 + c0) * WL_PITCH + t];
+                    *reinterpret_cast<float4*>(dst) = make_float4(src[0], src[WL_PITCH], src[2 * WL_PITCH], src[3 * WL_PITCH]);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();  // (the tile is free for the next batch)
+            __builtin_amdgcn_sched_barrier(0);
+            return;
+        }
         const int64_t my = have ? dst_of(b) : -1;
         const unsigned long long hv = __ballot(my >= 0);
         // store j: the lines of lanes 8 j .. 8 j + 7; this lane writes piece lane & 7 of lane 8 j + (lane >> 3)
@@ -618,6 +649,8 @@ struct ArArgs {
     Geom g;
     const float* xdb;  // planar [clip*C + c][U]
     float* dif;        // planar
+    float* rel;        // interleaved layout (Layout::ar_il): the differences go to the caller's [clip][Nm][C] array ...
+    float* rel_warm;   // ... and to the warm-up rows [clip][n_wb][C]; dif is not used then
     float fa, fr, sa, sr, floor_db;
     int64_t L, W, Wc, Wf, n_chunks;
     int64_t S;  // span of k_ar_warm2: chunks one speculative run walks through after its warm-up
@@ -629,6 +662,11 @@ struct ArArgs {
 // chunk k was walked through by its group's speculative run (ArArgs::through, MmArgs::through)
 __device__ __forceinline__ bool chunk_walked(int64_t k, int64_t S, int64_t n_chunks) {
     return k + 1 < min((k / S) * S + S, n_chunks);
+}
+// walk_lines_to<CH>'s dst_of for the 32 rows from follower-stream index u of a clip (a batch lies on one side of n_wb)
+template <int CH>
+__device__ __forceinline__ int64_t ar_il_dst(const Geom& g, int64_t clip, int64_t u) {
+    return u < g.n_wb ? ~((clip * g.n_wb + u) * CH) : (clip * g.Nm + (u - g.n_wb)) * CH;
 }
 
 // The stage is split into LEAN kernels, one walk instantiation each: measured on gfx950, the
@@ -796,19 +834,21 @@ __global__ __launch_bounds__(64) void k_ar_warm2(ArArgs a, int64_t n_threads, ui
 // length of a lane's dependent chain, and the two lanes of a chunk read the same samples at different times (the
 // slow one W ahead of the chunk, the fast one Wf), so each line of the stream came from HBM twice.  Here the
 // fast follower simply starts with the slow one (a longer warm-up than it needs).
-template <bool LINES>
+template <bool LINES, int IL = 0>
 __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads, uint32_t* __restrict__ used,
                                                      uint32_t* __restrict__ end0) {
     // a.through: the chunks the run walks through after its warm-up ARE their pass 0 -- it writes their differences and
     // their end states (end0 = the end array pass 0 writes) exactly as k_ar_chunk would from the same start state: one
     // pass over the dB stream less for those chunks.  (A wrong start guess is repaired by the verifying passes as before.)
     // LINES (with a.through): those outputs leave as complete lines (walk_lines: the whole wave stays together).
+    // IL = 4 / 8 (with LINES): channel-fastest lanes, the lines go to the interleaved a.rel / a.rel_warm (walk_lines_to<IL>).
     OFP_LATENCY_BOUND_KERNEL();
     __shared__ float tile[LINES ? 64 * WL_PITCH : 1];
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = id < n_threads;
     if (!LINES && !live) return;
-    const LaneAt ln = lane_planar(id, cdiv(a.n_chunks, a.S), a.g.C, live);  // (k: the group)
+    const LaneAt ln = IL ? lane_il<IL ? IL : 4>(live ? id : 0, cdiv(a.n_chunks, a.S))
+                         : lane_planar(id, cdiv(a.n_chunks, a.S), a.g.C, live);  // (k: the group)
     const int64_t chain = ln.chain;
     const int64_t k0 = ln.k * a.S;
     const int64_t start = k0 * a.L;
@@ -826,7 +866,14 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
         for (int64_t i = 1; i < a.S; ++i) {  // (the same trip count for the whole wave)
             const int64_t k = k0 + i;
             const bool on = live && k < a.n_chunks;
-            walk_lines(a.xdb, xs + (on ? (k - 1) * a.L : 0), a.dif, chain * a.g.U + (on ? (k - 1) * a.L : 0), on ? a.L : 0, s, tile);
+            if constexpr (IL != 0) {
+                const Geom& g = a.g;
+                const int64_t clip = ln.clip, u0 = (k - 1) * a.L;
+                walk_lines_to<IL>(a.xdb, xs + (on ? u0 : 0), on ? a.L : 0, s, tile, a.rel,
+                                  [&](int64_t b) { return ar_il_dst<IL>(g, clip, u0 + 32 * b); }, a.rel_warm);
+            } else {
+                walk_lines(a.xdb, xs + (on ? (k - 1) * a.L : 0), a.dif, chain * a.g.U + (on ? (k - 1) * a.L : 0), on ? a.L : 0, s, tile);
+            }
             if (on) {
                 put_state(used, state_idx(chain, a.n_chunks, k), s.yf, s.ys);
                 put_state(end0, (chain * a.n_chunks + k - 1) * 2, s.yf, s.ys);
@@ -842,7 +889,7 @@ __global__ __launch_bounds__(64) void k_ar_warm_both(ArArgs a, int64_t n_threads
     }
 }
 
-template <bool LINES>
+template <bool LINES, int IL = 0>
 __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_threads,
                                                  const uint32_t* __restrict__ end_prev,
                                                  uint32_t* __restrict__ end_next, uint32_t* __restrict__ used,
@@ -854,7 +901,7 @@ __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_t
     __shared__ float tile[LINES ? 64 * WL_PITCH : 1];
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool act = id < n_threads;
-    const LaneAt ln = lane_planar(id, a.n_chunks, a.g.C, act);
+    const LaneAt ln = IL ? lane_il<IL ? IL : 4>(act ? id : 0, a.n_chunks) : lane_planar(id, a.n_chunks, a.g.C, act);
     const int64_t k = ln.k, chain = ln.chain;
     const int64_t start = k * a.L;
     const int64_t end = min(start + a.L, a.g.U);
@@ -865,7 +912,19 @@ __global__ __launch_bounds__(64) void k_ar_chunk(ArArgs a, int pass, int64_t n_t
     ArStep s{ofp_u2f(st[0]), ofp_u2f(st[1]), a.fa, a.fr, a.sa, a.sr};
     if (LINES) {  // the whole wave stays together (walk_lines); lanes with nothing to do lend their stores
         if (!__any(act)) return;
-        walk_lines(a.xdb, a.xdb + chain * a.g.U + start, a.dif, chain * a.g.U + start, act ? end - start : 0, s, tile);
+        if constexpr (IL != 0) {
+            // channel-fastest lanes: the lines go to the interleaved a.rel / a.rel_warm, 32 whole rows a batch.  So when a
+            // verifying pass repairs some channels of a chunk, the other channels' lanes walk with them, from the start
+            // states they kept (st[]): they write the values that stand there again, and their end states stay kept.
+            const Geom& g = a.g;
+            const int64_t clip = ln.clip;
+            const int lane0 = (threadIdx.x & 63) & ~(IL - 1);
+            const bool with = ((__ballot(act) >> lane0) & ((1ull << IL) - 1)) != 0;
+            walk_lines_to<IL>(a.xdb, a.xdb + chain * a.g.U + start, with ? end - start : 0, s, tile, a.rel,
+                              [&](int64_t b) { return ar_il_dst<IL>(g, clip, start + 32 * b); }, a.rel_warm);
+        } else {
+            walk_lines(a.xdb, a.xdb + chain * a.g.U + start, a.dif, chain * a.g.U + start, act ? end - start : 0, s, tile);
+        }
     } else {
         if (!act) return;
         int norem = -1;
@@ -2222,6 +2281,65 @@ __global__ __launch_bounds__(256) void k_rel_out(Geom g, float* __restrict__ buf
     }
 }
 
+// Back to linear where the followers have left their differences in the interleaved arrays themselves (Layout::ar_il:
+// walk_lines_to<CH> wrote rel [clip][Nm][CH] and rel_warm [clip][n_wb][CH]): nothing is left to transpose, so the pass is
+// a stream in place, shaped like k_rect_db_sym -- 16-byte accesses, four loads in flight per lane, no LDS, no barrier.
+// One wave takes one block of B rows at a time (n_wb and Nm are whole blocks; per clip the n_wu blocks of the warm-up
+// rows, then the nb main ones), so no block is split between waves and its extremes (sum_max / sum_minv, encoding and
+// values as in rel_out_tile) leave as plain stores: no atomics here.  A 16-byte group holds four channels of one row and
+// a lane's groups are 64 apart, so a lane always holds the same four channels: it keeps their running extremes, and the
+// lanes of equal channels are reduced by shuffles once per block.
+template <int CH>
+__global__ __launch_bounds__(256) void k_rel_out_il(Geom g, float* __restrict__ rel, float* __restrict__ rel_warm, float floor_db,
+                                                    uint32_t* __restrict__ sum_max, uint32_t* __restrict__ sum_minv,
+                                                    int64_t nb, int64_t n_wu) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t clip = blockIdx.y;
+    const int n4 = g.B * (CH / 4);  // 16-byte groups of a block
+    for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < n_wu + nb; j += (int64_t)gridDim.x * 4) {
+        const bool in_main = j >= n_wu;
+        float4* const p = in_main ? reinterpret_cast<float4*>(rel + (clip * g.Nm + (j - n_wu) * g.B) * CH)
+                               : reinterpret_cast<float4*>(rel_warm + (clip * g.n_wb + j * g.B) * CH);
+        float4 hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (values are >= 0 or NaN, and fmaxf / fminf ignore NaN)
+        const float inf = __builtin_inff();
+        float4 lo = make_float4(inf, inf, inf, inf);
+        auto one = [&](int i, float4 v) {
+            v.x = ofp_rel_linear(v.x, floor_db);
+            v.y = ofp_rel_linear(v.y, floor_db);
+            v.z = ofp_rel_linear(v.z, floor_db);
+            v.w = ofp_rel_linear(v.w, floor_db);
+            p[i] = v;
+            hi.x = fmaxf(hi.x, v.x); hi.y = fmaxf(hi.y, v.y); hi.z = fmaxf(hi.z, v.z); hi.w = fmaxf(hi.w, v.w);
+            lo.x = fminf(lo.x, v.x); lo.y = fminf(lo.y, v.y); lo.z = fminf(lo.z, v.z); lo.w = fminf(lo.w, v.w);
+        };
+        int i = lane;
+        for (; i + 192 < n4; i += 256) {
+            const float4 v0 = p[i], v1 = p[i + 64], v2 = p[i + 128], v3 = p[i + 192];
+            __builtin_amdgcn_sched_barrier(0);
+            one(i, v0);
+            one(i + 64, v1);
+            one(i + 128, v2);
+            one(i + 192, v3);
+        }
+        for (; i < n4; i += 64) one(i, p[i]);
+        if (sum_max == nullptr || !in_main) continue;
+#pragma unroll
+        for (int o = 32; o >= CH / 4; o >>= 1) {  // lanes o apart hold the same channels
+            hi.x = fmaxf(hi.x, __shfl_xor(hi.x, o)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, o));
+            hi.z = fmaxf(hi.z, __shfl_xor(hi.z, o)); hi.w = fmaxf(hi.w, __shfl_xor(hi.w, o));
+            lo.x = fminf(lo.x, __shfl_xor(lo.x, o)); lo.y = fminf(lo.y, __shfl_xor(lo.y, o));
+            lo.z = fminf(lo.z, __shfl_xor(lo.z, o)); lo.w = fminf(lo.w, __shfl_xor(lo.w, o));
+        }
+        if (lane < CH / 4) {  // channels 4 lane .. 4 lane + 3
+            auto minv = [&](float v) { return 0x7f800000u - ofp_f2u(v >= 0.0f ? v : inf); };  // (none but NaN: "none yet")
+            const int64_t at = (clip * nb + (j - n_wu)) * CH + 4 * lane;
+            *reinterpret_cast<uint4*>(sum_max + at) = make_uint4(ofp_f2u(hi.x), ofp_f2u(hi.y), ofp_f2u(hi.z), ofp_f2u(hi.w));
+            *reinterpret_cast<uint4*>(sum_minv + at) = make_uint4(minv(lo.x), minv(lo.y), minv(lo.z), minv(lo.w));
+        }
+    }
+}
+
 // ---- block scan: first upward crossing and last sample below `off`, per
 // (clip, main block, channel) -- everything of detection.py:759-770,784-790 that
 // does not depend on the hysteresis state.
@@ -3026,6 +3144,8 @@ struct Layout {
     bool db_sym;        // the dB pass also forms the per-chunk sums of the closed-form guess (k_rect_db_sym)
     bool mm_il;         // tracker, crossing pass and backtracking on the caller's interleaved `rel` (k_*_il)
     bool mm_through;    // tracker: walk-through chunks as their own pass 0 (k_mm_warm_il)
+    bool ar_il;         // followers write the caller's interleaved `rel` and the warm-up rows themselves (k_ar_warm_both /
+                        // k_ar_chunk <true, C>); back to linear in place there (k_rel_out_il); the planar `dif` is not touched
     bool use_sum;       // block extremes for the crossing pass (k_rel_out -> k_block_scan)
     // verification
     bool host_verify;   // passes verified on the host (run_jacobi, one synchronisation per group), not enqueued ahead
@@ -3227,6 +3347,17 @@ Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t wa
               !p.manual &&
               (g.C == 4 || g.C == 8 || g.C == 64);
     l.mm_through = l.mm_il && d->t.walk_through >= 0;
+    // The followers' line stores go straight to the interleaved envelope its readers use (walk_lines_to<C>): every chunk
+    // is then written by a line walk (ar_through: k_ar_warm_both<true> and k_ar_chunk<true> between them), the readers
+    // are the *_il kernels, a batch of 32 rows lies on one side of the warm-up / main split, and a block is at least one
+    // 16-byte group per lane of k_rel_out_il's wave.  (open_call also wants `rel` 16-byte aligned.)
+    l.ar_il = l.ar_lines &&
+              l.ar_through &&
+              l.mm_il &&
+              (g.C == 4 || g.C == 8) &&
+              (g.n_wb & 31) == 0 &&
+              (g.Nm & 31) == 0 &&
+              (int64_t)g.B * g.C >= 256;
     // block extremes for the crossing pass: whenever the 16-byte path of k_rel_out is taken for every tile (the same
     // conditions as in the kernel) and a group of four never straddles two blocks
     l.use_sum = d->t.scan_skip >= 0 &&
@@ -3476,6 +3607,7 @@ int open_call(Call& c, ofp_detector* d, const float* d_x, int64_t n_clips, int64
     c.xt = c.at<float>(l.o_xt); c.xdb = c.at<float>(l.o_xdb); c.dif = c.at<float>(l.o_dif); c.rel_warm = c.at<float>(l.o_relw);
     c.sum_max = l.use_sum ? c.at<uint32_t>(l.o_sum) : nullptr;
     c.sum_minv = l.use_sum ? c.sum_max + n_clips * l.nb * l.g.C : nullptr;
+    if ((reinterpret_cast<uintptr_t>(d_rel) & 15u) != 0) c.l.ar_il = false;  // (16-byte stores into the caller's array)
     return OFP_OK;
 }
 
@@ -3657,7 +3789,7 @@ ArArgs ar_args(const Call& c) {
     const auto& p = c.d->p;
     ArArgs a;
     a.g = l.g;
-    a.xdb = c.xdb; a.dif = c.dif;
+    a.xdb = c.xdb; a.dif = c.dif; a.rel = c.a.rel; a.rel_warm = c.rel_warm;
     a.fa = p.fast_attack; a.fr = p.fast_release; a.sa = p.slow_attack; a.sr = p.slow_release; a.floor_db = p.floor_db;
     a.L = l.ar_L; a.W = l.ar_W; a.Wc = l.ar_Wc; a.Wf = l.ar_Wf; a.n_chunks = l.ar_chunks; a.S = l.ar_S;
     a.through = l.ar_through ? 1 : 0; a.lines = l.ar_lines ? 1 : 0;
@@ -3699,8 +3831,9 @@ int followers(Call& c, bool host_verified) {
         OFP_LAUNCH_CHECK("k_ar_sym_combine");
         const int64_t ntg = chains * cdiv(l.ar_chunks, l.ar_S);  // one run per group of S chunks
         if (l.merge)
-            hipLaunchKernelGGL(l.ar_lines ? k_ar_warm_both<true> : k_ar_warm_both<false>, dim3((unsigned)cdiv(ntg, 64)), dim3(64),
-                               0, c.stream, a, ntg, used, state_arrays(used, 2 * nt).endA);
+            hipLaunchKernelGGL(l.ar_il ? (l.g.C == 8 ? k_ar_warm_both<true, 8> : k_ar_warm_both<true, 4>)
+                                       : (l.ar_lines ? k_ar_warm_both<true> : k_ar_warm_both<false>),
+                               dim3((unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used, state_arrays(used, 2 * nt).endA);
         else
             hipLaunchKernelGGL(k_ar_warm2, dim3(2 * (unsigned)cdiv(ntg, 64)), dim3(64), 0, c.stream, a, ntg, used);
         OFP_LAUNCH_CHECK("k_ar_warm2");
@@ -3711,7 +3844,8 @@ int followers(Call& c, bool host_verified) {
         hipLaunchKernelGGL(k_ar_warm, dim3(grid), dim3(64), 0, c.stream, a, nt, used);
         OFP_LAUNCH_CHECK("k_ar_warm");
     }
-    const auto chunk = l.ar_lines ? k_ar_chunk<true> : k_ar_chunk<false>;
+    const auto chunk = l.ar_il ? (l.g.C == 8 ? k_ar_chunk<true, 8> : k_ar_chunk<true, 4>)
+                               : (l.ar_lines ? k_ar_chunk<true> : k_ar_chunk<false>);
     ofp_detect_pending& rec = *c.rec;
     if (!host_verified) {
         rec.ar_nv = l.ar_chunks > 1 ? std::max(2, std::min(AHEAD_MAX_PASSES / 2, c.d->ar_pass_hint)) : 0;
@@ -3727,6 +3861,14 @@ int rel_out(Call& c) {
     const Layout& l = c.l;
     const Geom& g = l.g;
     const int64_t n_clips = c.a.n_clips;
+    if (l.ar_il) {  // the differences are in `rel` / rel_warm already: in place there, one wave per block at a time
+        const int64_t n_wu = g.n_wb / g.B;
+        const unsigned gx = (unsigned)std::min<int64_t>(cdiv(n_wu + l.nb, 4), std::max<int64_t>(1, (int64_t)16 * c.d->n_cus / n_clips));
+        hipLaunchKernelGGL(g.C == 8 ? k_rel_out_il<8> : k_rel_out_il<4>, dim3(gx, (unsigned)n_clips), dim3(256), 0, c.stream, g,
+                           c.a.rel, c.rel_warm, c.d->p.floor_db, c.sum_max, c.sum_minv, l.nb, n_wu);
+        OFP_LAUNCH_CHECK("k_rel_out_il");
+        return OFP_OK;
+    }
     const size_t lds = c.tile_lds() + (l.use_sum ? (size_t)2 * g.C * (l.tu / g.B + 2) * 4 : 0);
     const int64_t n_tiles = cdiv(g.U, l.tu);
     const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)32 * c.d->n_cus / n_clips));
@@ -3745,7 +3887,7 @@ int tracker(Call& c, bool host_verified) {
     const int64_t chains = c.chains();
     MmArgs a;
     a.g = l.g;
-    a.rel = c.dif; a.rel_il = c.a.rel; a.rel_warm = c.rel_warm;
+    a.rel = l.mm_il ? nullptr : c.dif; a.rel_il = c.a.rel; a.rel_warm = c.rel_warm;
     a.thr_mn = c.at<float>(l.o_thr_mn); a.thr_mx = c.at<float>(l.o_thr_mx);
     a.alpha_min = p.alpha_min; a.alpha_max = p.alpha_max;
     a.ialpha_min = c.d->ialpha_min; a.ialpha_max = c.d->ialpha_max;
@@ -3815,7 +3957,7 @@ int crossings(Call& c) {
     const int64_t chains = c.chains();
     ScanArgs sa;
     sa.g = g;
-    sa.rel = c.dif; sa.thr_mn = c.at<float>(l.o_thr_mn); sa.thr_mx = c.at<float>(l.o_thr_mx);
+    sa.rel = l.mm_il ? nullptr : c.dif; sa.thr_mn = c.at<float>(l.o_thr_mn); sa.thr_mx = c.at<float>(l.o_thr_mx);
     sa.on_f = c.d->d_on_f; sa.off_f = c.d->d_off_f; sa.on_d = c.d->d_on_d; sa.manual = c.d->p.manual;
     sa.nb = l.nb; sa.n_clips = n_clips;
     sa.first_cross = c.at<int32_t>(l.o_first); sa.last_below = c.at<int32_t>(l.o_last); sa.vflag = c.at<uint32_t>(l.o_vflag);
@@ -3905,7 +4047,7 @@ int backtrack(const Call& c) {
     if (!(p.backtrack && c.a.cap > 0)) return OFP_OK;
     BtArgs bt;
     bt.g = c.l.g;
-    bt.rel = c.dif; bt.rel_il = c.l.mm_il ? c.a.rel : nullptr;
+    bt.rel = c.l.mm_il ? nullptr : c.dif; bt.rel_il = c.l.mm_il ? c.a.rel : nullptr;
     bt.records = c.a.records; bt.counts = c.a.counts; bt.cap = c.a.cap; bt.n_clips = c.a.n_clips;
     bt.N = p.backtrack_buffer_size; bt.alpha = p.backtrack_alpha; bt.tol = p.backtrack_tol;
     hipLaunchKernelGGL(k_backtrack, dim3((unsigned)cdiv(c.a.n_clips * c.a.cap, 64)), dim3(64), 0, c.stream, bt);
