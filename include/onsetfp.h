@@ -704,6 +704,15 @@ int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_grou
                       double radius, double xtol, int32_t maxfev, const ofp_mlp* mlp, double* d_xy,
                       int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream);
 int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int32_t c1, float* d_out, void* stream);
+/* ofp_locate_groups for the 2-D Multilaterate (multilateration.py:677-733; d_sensors [S][3] with z = 0, maps of the
+ * 2-D grid): the same row rule and OFP_LOCATE_* codes, but trilaterate as that class has it -- origin, a, b stay in
+ * onset order (no reordering) and delta = lag * c / sr (multiply first).  d_xy is the Cartesian root in cm; the
+ * reference's tuple is cartesian_to_polar(x, y, radius), a host formula.  No model path. */
+int ofp_locate_groups_2d(const int64_t* d_groups, int64_t n_clips, int64_t cap_groups, int32_t n_channels,
+                         const int64_t* d_n_groups, const double* d_sensors, int32_t S, const float* d_maps,
+                         const float* d_min, const float* d_max, int32_t r, double tolerance, double sr, double c,
+                         double radius, double xtol, int32_t maxfev, double* d_xy, int32_t* d_status,
+                         double* d_guess, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- Multilaterate3D.locate as device code (multilateration.py:428-575) ---------------------------------------
  * The reference's state machine with its state (`ongoing`) in device memory: one call feeds (sensor, onset, counter)
@@ -751,6 +760,16 @@ typedef struct ofp_hop_locator {
 int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset,
                       const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
                       ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream);
+/* The replay for the 2-D Multilaterate.locate (multilateration.py:677-733) on the same state: no counter and no
+ * recording (the class has no cross-correlation step), loc->use_audio and loc->max_section are ignored, loc->mlp must
+ * be NULL, S >= 3.  What differs from the 3-D routine is kept: no skip past the largest lag at the top of the loop, no
+ * swap, no break on equal first sensors, no remove_seed; a group that passes is_legal is appended twice (the second
+ * entry with alias = 1); groups grow beyond three members and only a group that has just reached three is searched and
+ * solved; a search that finds a cell ends the call with `ongoing` = the groups collected so far whether or not the
+ * solve succeeds; deltas are lag * c / sr.  d_xy is the Cartesian root in cm.  A sensor outside 0..S-1 sets
+ * OFP_LOCF_BAD_CALL. */
+int ofp_locate_stream_2d(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset, int64_t K,
+                         ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream);
 /* The stage inside the hop graph of a session (before its first hop; the graph is captured again): after the
  * detector, the hop's onsets sorted by absolute sample (ties in record order) are fed with counter =
  * (hop_index + 1) * block_size until one returns a position (detect_hits, realtime/audio.py:62-74).  Rows of the
@@ -758,6 +777,10 @@ int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const
  * UNPINNED: the reference's ring class is absent).  OFP_ERR_INVALID: S != channels, a detector that backtracks,
  * a ring shorter than max_section + block_size rows, a network that is not 2 -> 2.  ofp_hop_reset clears the state. */
 int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc);
+/* The same stage with the 2-D Multilaterate.locate (as ofp_locate_stream_2d: use_audio / max_section ignored, no
+ * network, no ring-length condition since no section is read).  h_xy of ofp_hop_collect_location is then the Cartesian
+ * root in cm; everything else -- collect_location, locator_state, reset, both graph forms, groups -- is unchanged. */
+int ofp_hop_set_locator_2d(ofp_hop_session* s, const ofp_hop_locator* loc);
 /* The location block of the last collected hop: *status 0 none / 1 located, h_xy [2], the located group as
  * trilaterate left it (*n_members, h_sensors / h_onsets [OFP_LOCS_MEMBERS]), *fed onsets given to the state machine,
  * *dropped onsets of the hop after the one that located (never fed, as in the reference), *flags. */

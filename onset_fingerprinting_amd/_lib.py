@@ -272,9 +272,13 @@ SIGNATURES = {
     "ofp_locate_groups": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
                                          _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_locate_section": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ofp_locate_groups_2d": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f64, _f64, _f64,
+                                            _f64, _f64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_locate_stream": (ctypes.c_int, [ctypes.POINTER(HopLocator), _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp,
                                          _vp]),
+    "ofp_locate_stream_2d": (ctypes.c_int, [ctypes.POINTER(HopLocator), _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ofp_hop_set_locator": (ctypes.c_int, [_vp, ctypes.POINTER(HopLocator)]),
+    "ofp_hop_set_locator_2d": (ctypes.c_int, [_vp, ctypes.POINTER(HopLocator)]),
     "ofp_hop_collect_location": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_f64), ctypes.POINTER(_i32),
                                                 ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32),
                                                 ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),

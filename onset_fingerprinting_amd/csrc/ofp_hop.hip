@@ -17,7 +17,8 @@
 // kernel node, k_hop_fused -- workgroup 0 runs the detector while workgroups 1..C run the spectral
 // branch, the hop is read from and the result block written to pinned host memory directly.
 //
-// With a locator attached (ofp_hop_set_locator) the hop also carries Multilaterate3D.locate (ofp_locate_dev.h): the
+// With a locator attached (ofp_hop_set_locator, or ofp_hop_set_locator_2d for the planar Multilaterate, which runs
+// loc_feed_2d in the same stage) the hop also carries Multilaterate3D.locate (ofp_locate_dev.h): the
 // detector's workgroup (fused form) or one more kernel node after the detector (nodes form) feeds the hop's onsets,
 // sorted by sample, to the device-resident state and writes the location block next to the records.  A hop without
 // onsets takes one uniform branch on the count and touches nothing of the stage.
@@ -479,10 +480,18 @@ __device__ __forceinline__ void hop_locate_stage(const HopArgs& a, const HopLocA
     };
     int fed = 0, status = 0;
     double xy[2] = {0.0, 0.0};
-    for (int i = 0; i < n && !status; ++i) {
-        const ofp_onset r = recs[s_order[i]];
-        status = ofp::loc_feed(T, v, r.channel, first + r.sample, counter, true, sample, xy, &s_located);
-        ++fed;
+    if (T.planar) {  // uniform: the kind is the session's
+        for (int i = 0; i < n && !status; ++i) {
+            const ofp_onset r = recs[s_order[i]];
+            status = ofp::loc_feed_2d(T, v, r.channel, first + r.sample, xy, &s_located);
+            ++fed;
+        }
+    } else {
+        for (int i = 0; i < n && !status; ++i) {
+            const ofp_onset r = recs[s_order[i]];
+            status = ofp::loc_feed(T, v, r.channel, first + r.sample, counter, true, sample, xy, &s_located);
+            ++fed;
+        }
     }
     __syncthreads();
     if (tid == 0) {
@@ -1168,20 +1177,18 @@ int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
     return OFP_OK;
 }
 
-int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
-    OFP_REQUIRE(s && loc, "ofp_hop_set_locator: NULL argument");
-    OFP_NOT_IN_GROUP(s, "ofp_hop_set_locator");
-    OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "ofp_hop_set_locator: the session has already taken a hop");
-    OFP_REQUIRE(!s->largs.enabled, "ofp_hop_set_locator: the session already has a locator");
-    ofp::LocTables T;
-    if (int rc = ofp_locate_tables(loc, "ofp_hop_set_locator", &T)) return rc;
-    OFP_REQUIRE(loc->S == s->C, "ofp_hop_set_locator: %d sensors for %d channels", loc->S, s->C);
-    OFP_REQUIRE(!s->det->p.backtrack, "ofp_hop_set_locator: a detector that backtracks moves onsets behind the hop");
-    OFP_REQUIRE(!loc->use_audio || s->R >= (int64_t)loc->max_section + s->B,
-                "ofp_hop_set_locator: the ring (%lld rows) must hold the longest section (%d) and one hop (%d)",
-                (long long)s->R, loc->max_section, s->B);
+// ofp_hop_set_locator and ofp_hop_set_locator_2d behind their own checks: T is the checked launch form of `loc`
+// (T.planar: the kind; a planar locator reads no section, so no ring-length condition applies to it)
+static int hop_attach_locator(ofp_hop_session* s, const ofp_hop_locator* loc, ofp::LocTables T, const char* who) {
+    OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
+    OFP_REQUIRE(!s->largs.enabled, "%s: the session already has a locator", who);
+    OFP_REQUIRE(loc->S == s->C, "%s: %d sensors for %d channels", who, loc->S, s->C);
+    OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
+    OFP_REQUIRE(!T.use_audio || s->R >= (int64_t)loc->max_section + s->B,
+                "%s: the ring (%lld rows) must hold the longest section (%d) and one hop (%d)", who, (long long)s->R,
+                loc->max_section, s->B);
     const size_t lds = ofp::loc_lds_bytes(s->threads, T.max_section, T.plan, (size_t)s->B * s->C * 4);  // (+ the hop rows)
-    OFP_REQUIRE(lds <= 128 * 1024, "ofp_hop_set_locator: %zu bytes of LDS needed", lds);
+    OFP_REQUIRE(lds <= 128 * 1024, "%s: %zu bytes of LDS needed", who, lds);
     const size_t lds_fused = s->lds_fused;
     auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
         if (loc->mlp) {  // the session keeps its own copy: the handle may be destroyed afterwards
@@ -1219,6 +1226,22 @@ int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
     s->lds_loc = 0;
     if (!s->exec) (void)capture_hop(s);  // (the failure came after the locator-less graph had been given up)
     return ofp::fail(rc, "%s", why.c_str());
+}
+
+int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
+    OFP_REQUIRE(s && loc, "ofp_hop_set_locator: NULL argument");
+    OFP_NOT_IN_GROUP(s, "ofp_hop_set_locator");
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables(loc, "ofp_hop_set_locator", &T)) return rc;
+    return hop_attach_locator(s, loc, T, "ofp_hop_set_locator");
+}
+
+int ofp_hop_set_locator_2d(ofp_hop_session* s, const ofp_hop_locator* loc) {
+    OFP_REQUIRE(s && loc, "ofp_hop_set_locator_2d: NULL argument");
+    OFP_NOT_IN_GROUP(s, "ofp_hop_set_locator_2d");
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables_2d(loc, "ofp_hop_set_locator_2d", &T)) return rc;
+    return hop_attach_locator(s, loc, T, "ofp_hop_set_locator_2d");
 }
 
 int ofp_hop_collect_location(ofp_hop_session* s, int32_t* status, double* h_xy, int32_t* n_members,

@@ -12,9 +12,10 @@
 // k_trilaterate: MINPACK hybrj per group (ofp_hybrj.h), one lane per group.
 // k_locate_rows: the per-row front of ofp_locate_groups: earliest three channels, is_legal on both pairs and the
 //                legality search, one workgroup per row.
-// k_locate_solve: the back: trilaterate (or the model's output * 100) per row, one lane per row.
-// k_locate_stream: Multilaterate3D.locate itself, K calls through one device-resident state (ofp_locate_dev.h),
-//                one workgroup.
+// k_locate_solve: the back: trilaterate (or the model's output * 100) per row, one lane per row.  Both serve the 2-D
+//                Multilaterate as well (LocateArgs::planar: its trilaterate keeps the sensors' order).
+// k_locate_stream: Multilaterate3D.locate itself (or the 2-D Multilaterate.locate), K calls through one
+//                device-resident state (ofp_locate_dev.h), one workgroup.
 // k_section:     Multilaterate3D.locate's cross-correlation input (multilateration.py:466-476): median filter of
 //                size 5 ('reflect') along time, first difference, non-negative values zeroed, absolute value.
 #include <cmath>
@@ -152,6 +153,7 @@ struct LocateArgs {
     int side;
     double tol, sr, c, radius, xtol;
     int maxfev;
+    int planar;  // 1: the 2-D Multilaterate's trilaterate (no reordering, delta = lag * c / sr)
     RowState* rows;
     float* lags;
 };
@@ -217,7 +219,7 @@ __global__ void k_locate_rows(LocateArgs A) {
         } else {
             s.guess[0] = (double)ix - A.radius;
             s.guess[1] = (double)iy - A.radius;
-            if (s.sens[1] == 1) {  // Multilaterate3D.trilaterate, multilateration.py:542-544
+            if (!A.planar && s.sens[1] == 1) {  // Multilaterate3D.trilaterate, multilateration.py:542-544
                 s.sens[1] = 0;
                 s.sens[2] = 1;
                 const int64_t t = s.on[1];
@@ -259,8 +261,13 @@ __global__ void k_locate_solve(LocateArgs A, int64_t n_rows, const float* __rest
         t.a[k] = A.sensors[3 * s.sens[1] + k];
         t.b[k] = A.sensors[3 * s.sens[2] + k];
     }
-    t.dda = (double)(s.on[1] - s.on[0]) / A.sr * A.c;
-    t.ddb = (double)(s.on[2] - s.on[0]) / A.sr * A.c;
+    if (A.planar) {  // Multilaterate.trilaterate, multilateration.py:724-725: multiply first
+        t.dda = (double)(s.on[1] - s.on[0]) * A.c / A.sr;
+        t.ddb = (double)(s.on[2] - s.on[0]) * A.c / A.sr;
+    } else {
+        t.dda = (double)(s.on[1] - s.on[0]) / A.sr * A.c;
+        t.ddb = (double)(s.on[2] - s.on[0]) / A.sr * A.c;
+    }
     const ofp::hybrj::Result res = ofp::hybrj::solve(t, s.guess, A.xtol, A.maxfev);
     xy[2 * row] = res.x[0];
     xy[2 * row + 1] = res.x[1];
@@ -303,7 +310,7 @@ __global__ __launch_bounds__(LOC_THREADS) void k_locate_stream(ofp::LocTables T,
     auto sample = [&](int64_t t, int col) -> float { return t >= 0 && t < n_rows ? audio[t * C + col] : 0.0f; };
     for (int64_t k = 0; k < K; ++k) {
         const int s = sensor[k];
-        const int64_t cnt = counter[k];
+        const int64_t cnt = counter ? counter[k] : 0;  // (the planar kind has no counter)
         double r[2] = {__builtin_nan(""), __builtin_nan("")};
         int f = 0;
         if (s < 0 || s >= T.S || (T.use_audio && (cnt < 0 || cnt > n_rows))) {  // uniform over the workgroup
@@ -311,7 +318,8 @@ __global__ __launch_bounds__(LOC_THREADS) void k_locate_stream(ofp::LocTables T,
             if (threadIdx.x == 0) v.L->st[v.L->cur].flags |= OFP_LOCF_BAD_CALL;
             __syncthreads();
         } else {
-            f = ofp::loc_feed(T, v, s, onset[k], cnt, false, sample, r, nullptr);
+            f = T.planar ? ofp::loc_feed_2d(T, v, s, onset[k], r, nullptr)
+                         : ofp::loc_feed(T, v, s, onset[k], cnt, false, sample, r, nullptr);
         }
         if (threadIdx.x == 0) {
             found[k] = f;
@@ -358,6 +366,17 @@ int ofp_locate_tables(const ofp_hop_locator* loc, const char* who, ofp::LocTable
     T.maxfev = loc->maxfev;
     T.use_audio = loc->use_audio ? 1 : 0;
     T.max_section = loc->use_audio ? loc->max_section : 4;
+    return OFP_OK;
+}
+
+int ofp_locate_tables_2d(const ofp_hop_locator* loc, const char* who, ofp::LocTables* out) {
+    OFP_REQUIRE(loc, "%s: NULL locator", who);
+    OFP_REQUIRE(!loc->mlp, "%s: the planar locator has no model path", who);
+    ofp_hop_locator plain = *loc;
+    plain.use_audio = 0;
+    plain.max_section = 0;
+    if (int rc = ofp_locate_tables(&plain, who, out)) return rc;
+    out->planar = 1;
     return OFP_OK;
 }
 
@@ -414,29 +433,31 @@ int64_t ofp_locate_workspace_bytes(int64_t n_rows) {
     return ofp::align_up(n_rows * (int64_t)sizeof(RowState), 256) + 2 * ofp::align_up(n_rows * 2 * 4, 256);
 }
 
-int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_groups, int32_t n_channels,
-                      const int64_t* d_n_groups, const double* d_sensors, int32_t S, const float* d_maps,
-                      const float* d_min, const float* d_max, int32_t r, double tolerance, double sr, double c,
-                      double radius, double xtol, int32_t maxfev, const ofp_mlp* mlp, double* d_xy,
-                      int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream) {
-    OFP_REQUIRE(S >= 2, "ofp_locate_groups: need at least two sensors (S = %d)", S);
+// ofp_locate_groups and ofp_locate_groups_2d: the same two kernels, the kind in LocateArgs::planar
+static int locate_groups(const char* who, int planar, const int64_t* d_groups, int64_t n_clips, int64_t cap_groups,
+                         int32_t n_channels, const int64_t* d_n_groups, const double* d_sensors, int32_t S,
+                         const float* d_maps, const float* d_min, const float* d_max, int32_t r, double tolerance,
+                         double sr, double c, double radius, double xtol, int32_t maxfev, const ofp_mlp* mlp,
+                         double* d_xy, int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes,
+                         void* stream) {
+    OFP_REQUIRE(S >= 2, "%s: need at least two sensors (S = %d)", who, S);
     OFP_REQUIRE(n_channels >= 1 && n_channels <= S,
-                "ofp_locate_groups: n_channels %d must be in 1..S (channel k is sensor k, S = %d)", n_channels, S);
-    OFP_REQUIRE(r >= 0 && r <= 4096, "ofp_locate_groups: grid radius %d outside 0..4096", r);
-    OFP_REQUIRE(n_clips >= 0 && cap_groups >= 0, "ofp_locate_groups: negative n_clips or cap_groups");
-    OFP_REQUIRE(xtol >= 0.0 && maxfev > 0, "ofp_locate_groups: xtol must be >= 0 and maxfev > 0");
-    OFP_REQUIRE(sr > 0.0 && c > 0.0, "ofp_locate_groups: speed of sound and sampling rate must be positive");
+                "%s: n_channels %d must be in 1..S (channel k is sensor k, S = %d)", who, n_channels, S);
+    OFP_REQUIRE(r >= 0 && r <= 4096, "%s: grid radius %d outside 0..4096", who, r);
+    OFP_REQUIRE(n_clips >= 0 && cap_groups >= 0, "%s: negative n_clips or cap_groups", who);
+    OFP_REQUIRE(xtol >= 0.0 && maxfev > 0, "%s: xtol must be >= 0 and maxfev > 0", who);
+    OFP_REQUIRE(sr > 0.0 && c > 0.0, "%s: speed of sound and sampling rate must be positive", who);
     const int64_t n_rows = n_clips * cap_groups;
     if (n_rows == 0) return OFP_OK;
-    OFP_REQUIRE(n_rows <= 0x7fffffff, "ofp_locate_groups: more than 2^31 - 1 rows");
+    OFP_REQUIRE(n_rows <= 0x7fffffff, "%s: more than 2^31 - 1 rows", who);
     OFP_REQUIRE(d_groups && d_sensors && d_maps && d_min && d_max && d_xy && d_status && d_ws,
-                "ofp_locate_groups: NULL argument");
-    OFP_REQUIRE(ws_bytes >= ofp_locate_workspace_bytes(n_rows), "ofp_locate_groups: work space of %lld bytes < %lld",
+                "%s: NULL argument", who);
+    OFP_REQUIRE(ws_bytes >= ofp_locate_workspace_bytes(n_rows), "%s: work space of %lld bytes < %lld", who,
                 (long long)ws_bytes, (long long)ofp_locate_workspace_bytes(n_rows));
     if (mlp) {
         const MlpPlan& P = mlp->plan;
         OFP_REQUIRE(P.dims[0] == 2 && P.dims[P.n_layers] == 2,
-                    "ofp_locate_groups: the network must map 2 lags to 2 coordinates (got %d -> %d)", P.dims[0],
+                    "%s: the network must map 2 lags to 2 coordinates (got %d -> %d)", who, P.dims[0],
                     P.dims[P.n_layers]);
     }
     char* ws = (char*)d_ws;
@@ -458,6 +479,7 @@ int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_grou
     A.radius = radius;
     A.xtol = xtol;
     A.maxfev = maxfev;
+    A.planar = planar;
     A.rows = (RowState*)ws;
     A.lags = (float*)(ws + ofp::align_up(n_rows * (int64_t)sizeof(RowState), 256));
     float* model_out = A.lags + ofp::align_up(n_rows * 2 * 4, 256) / 4;
@@ -472,6 +494,26 @@ int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_grou
                        mlp ? (const float*)model_out : nullptr, d_xy, d_status, d_guess);
     OFP_LAUNCH_CHECK("k_locate_solve");
     return OFP_OK;
+}
+
+int ofp_locate_groups(const int64_t* d_groups, int64_t n_clips, int64_t cap_groups, int32_t n_channels,
+                      const int64_t* d_n_groups, const double* d_sensors, int32_t S, const float* d_maps,
+                      const float* d_min, const float* d_max, int32_t r, double tolerance, double sr, double c,
+                      double radius, double xtol, int32_t maxfev, const ofp_mlp* mlp, double* d_xy,
+                      int32_t* d_status, double* d_guess, void* d_ws, int64_t ws_bytes, void* stream) {
+    return locate_groups("ofp_locate_groups", 0, d_groups, n_clips, cap_groups, n_channels, d_n_groups, d_sensors, S,
+                         d_maps, d_min, d_max, r, tolerance, sr, c, radius, xtol, maxfev, mlp, d_xy, d_status, d_guess,
+                         d_ws, ws_bytes, stream);
+}
+
+int ofp_locate_groups_2d(const int64_t* d_groups, int64_t n_clips, int64_t cap_groups, int32_t n_channels,
+                         const int64_t* d_n_groups, const double* d_sensors, int32_t S, const float* d_maps,
+                         const float* d_min, const float* d_max, int32_t r, double tolerance, double sr, double c,
+                         double radius, double xtol, int32_t maxfev, double* d_xy, int32_t* d_status,
+                         double* d_guess, void* d_ws, int64_t ws_bytes, void* stream) {
+    return locate_groups("ofp_locate_groups_2d", 1, d_groups, n_clips, cap_groups, n_channels, d_n_groups, d_sensors,
+                         S, d_maps, d_min, d_max, r, tolerance, sr, c, radius, xtol, maxfev, nullptr, d_xy, d_status,
+                         d_guess, d_ws, ws_bytes, stream);
 }
 
 int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int32_t c1, float* d_out, void* stream) {
@@ -504,6 +546,23 @@ int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const
     if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_stream), lds, attr, 32768)) return rc;
     hipLaunchKernelGGL(k_locate_stream, dim3(1), dim3(LOC_THREADS), lds, (hipStream_t)stream, T, d_sensor, d_onset,
                        d_counter, K, d_audio, n_rows, (int)n_channels, d_state, d_found, d_xy);
+    OFP_LAUNCH_CHECK("k_locate_stream");
+    return OFP_OK;
+}
+
+int ofp_locate_stream_2d(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset, int64_t K,
+                         ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables_2d(loc, "ofp_locate_stream_2d", &T)) return rc;
+    OFP_REQUIRE(K >= 0, "ofp_locate_stream_2d: negative call count");
+    OFP_REQUIRE(d_state, "ofp_locate_stream_2d: NULL state");
+    if (K == 0) return OFP_OK;
+    OFP_REQUIRE(d_sensor && d_onset && d_found && d_xy, "ofp_locate_stream_2d: NULL argument");
+    const size_t lds = ofp::loc_lds_bytes(LOC_THREADS, T.max_section, T.plan);
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_stream), lds, attr, 32768)) return rc;
+    hipLaunchKernelGGL(k_locate_stream, dim3(1), dim3(LOC_THREADS), lds, (hipStream_t)stream, T, d_sensor, d_onset,
+                       (const int64_t*)nullptr, K, (const float*)nullptr, (int64_t)0, 0, d_state, d_found, d_xy);
     OFP_LAUNCH_CHECK("k_locate_stream");
     return OFP_OK;
 }

@@ -77,6 +77,7 @@ struct LocTables {
     int maxfev;
     int use_audio;
     int max_section;
+    int planar;    // 1: the 2-D Multilaterate (loc_feed_2d), sensors with z = 0; never with use_audio or a network
     MlpPlan plan;  // n_layers == 0: hybrj
 };
 
@@ -443,7 +444,138 @@ __device__ inline int loc_feed(const LocTables& T, const LocView& v, int sensor,
     return found;
 }
 
+// ---- Multilaterate.locate (the planar locator) ---------------------------------------------------------------
+
+// One call of the 2-D Multilaterate.locate(sensor, onset) (reference multilateration.py:677-733) by the whole
+// workgroup, on the same state as loc_feed.  Where it differs from the 3-D routine: no skip of a group past its
+// largest lag at the top of the loop, no swap on a negative lag and no cross-correlation step (nothing is ever changed
+// in place, so an alias entry only records that two entries are one object); no break on equal first sensors and no
+// remove_seed; groups grow beyond three members and only the group that has just reached three is searched and
+// solved; a call whose search finds a cell ends with `ongoing` = new_groups whether or not the solve succeeds;
+// trilaterate keeps the sensors' order and forms its deltas as lag * c / sr.  Returns 1 when a position was returned
+// (xy: the Cartesian root in cm), else 0; `located` as in loc_feed.
+__device__ inline int loc_feed_2d(const LocTables& T, const LocView& v, int sensor, int64_t onset, double* xy,
+                                  LocGroup* located) {
+    LocLds& L = *v.L;
+    const int tid = threadIdx.x;
+    ofp_locate_state* cur = &L.st[L.cur];
+    ofp_locate_state* nxt = &L.st[L.cur ^ 1];
+    const int n_cur = cur->n_groups;
+    int flags = cur->flags;
+    int nn = 0;          // len(new_groups)
+    int prev_out = -1;   // where the previous iteration appended its (unextended) group object
+    int found = 0;
+    bool returned = false;
+    __syncthreads();
+    for (int gi = 0; gi < n_cur && !returned; ++gi) {
+        const bool alias = gi > 0 && cur->alias[gi] != 0;
+        const int src = alias ? gi - 1 : gi;
+        const int my_prev = alias ? prev_out : -1;
+        prev_out = -1;
+        const int len = cur->len[src];
+        const int s0 = cur->sensors[src][0];
+        const int64_t lag = onset - cur->onsets[src][0];
+        bool in_group = false;
+        for (int k = 0; k < len; ++k) in_group = in_group || cur->sensors[src][k] == sensor;
+        bool extended = false;
+        if (!in_group) {
+            const double dl = (double)lag;
+            const bool legal = (double)T.mn[s0 * T.S + sensor] < dl && dl < (double)T.mx[s0 * T.S + sensor];
+            if (legal && len >= OFP_LOCS_MEMBERS) {
+                flags |= OFP_LOCF_MEMBERS;
+            } else if (legal) {
+                __syncthreads();
+                if (tid == 0) {
+                    L.ext.len = len + 1;
+                    for (int k = 0; k < len; ++k) {
+                        L.ext.sens[k] = cur->sensors[src][k];
+                        L.ext.on[k] = cur->onsets[src][k];
+                    }
+                    L.ext.sens[len] = sensor;
+                    L.ext.on[len] = onset;
+                }
+                __syncthreads();
+                extended = true;
+                if (len + 1 == 3) {
+                    const int64_t da = L.ext.on[1] - L.ext.on[0], db = L.ext.on[2] - L.ext.on[0];
+                    const int64_t k = first_legal(T.maps, T.S, T.side, L.ext.sens[0], L.ext.sens[1], L.ext.sens[2],
+                                                  (double)da, (double)db, 1 * T.spc, v.smin);
+                    const int64_t ix = k < 0 ? 0 : k % T.side, iy = k < 0 ? 0 : k / T.side;
+                    if (!(ix == 0 && iy == 0)) {
+                        if (tid == 0) {  // trilaterate (:714-733)
+                            hybrj::Tdoa t;
+                            for (int q = 0; q < 3; ++q) {
+                                t.o[q] = T.sensors[3 * L.ext.sens[0] + q];
+                                t.a[q] = T.sensors[3 * L.ext.sens[1] + q];
+                                t.b[q] = T.sensors[3 * L.ext.sens[2] + q];
+                            }
+                            t.dda = (double)da * T.c / T.sr;
+                            t.ddb = (double)db * T.c / T.sr;
+                            const double guess[2] = {(double)ix - T.radius, (double)iy - T.radius};
+                            const hybrj::Result r = hybrj::solve(t, guess, T.xtol, T.maxfev);
+                            L.res[0] = r.x[0];
+                            L.res[1] = r.x[1];
+                            L.found = r.info == 1 ? 1 : 0;
+                        }
+                        __syncthreads();
+                        found = L.found;
+                        if (found) {
+                            xy[0] = L.res[0];
+                            xy[1] = L.res[1];
+                        }
+                        if (located && tid == 0) *located = L.ext;
+                        returned = true;  // self.ongoing = new_groups; return res
+                        continue;
+                    }
+                }
+                if (nn < OFP_LOCS_GROUPS) {
+                    if (tid == 0) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 0);
+                    ++nn;
+                } else {
+                    flags |= OFP_LOCF_GROUPS;
+                }
+            }
+        }
+        // the test sees the extended group: one that passed is_legal is appended a second time
+        if ((double)lag <= L.mml[s0]) {
+            if (nn < OFP_LOCS_GROUPS) {
+                if (tid == 0) {
+                    if (extended) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 1);
+                    else loc_copy_group(nxt, nn, cur->sensors[src], cur->onsets[src], len, my_prev >= 0 ? 1 : 0);
+                }
+                if (!extended) prev_out = nn;
+                ++nn;
+            } else {
+                flags |= OFP_LOCF_GROUPS;
+            }
+        }
+        __syncthreads();
+    }
+    if (!returned) {  // new_groups.append(([sensor_index], [onset_index]))
+        if (nn < OFP_LOCS_GROUPS) {
+            if (tid == 0) {
+                const int32_t s1[1] = {sensor};
+                const int64_t o1[1] = {onset};
+                loc_copy_group(nxt, nn, s1, o1, 1, 0);
+            }
+            ++nn;
+        } else {
+            flags |= OFP_LOCF_GROUPS;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        nxt->n_groups = nn;
+        nxt->flags = flags;
+        L.cur ^= 1;
+    }
+    __syncthreads();
+    return found;
+}
+
 }  // namespace ofp
 
 // the launch form of a locator's tables, checked (ofp_locate.hip); `who` names the entry point in the error text
 int ofp_locate_tables(const ofp_hop_locator* loc, const char* who, ofp::LocTables* out);
+// the same for the planar kind: use_audio and max_section are ignored, a network is refused
+int ofp_locate_tables_2d(const ofp_hop_locator* loc, const char* who, ofp::LocTables* out);

@@ -24,7 +24,8 @@ Same names, arguments and returns as the reference for:
 
 ``Multilaterate3D.locate`` also exists as device code (csrc/ofp_locate_dev.h) on a device-resident copy of ``ongoing``:
 ``Multilaterate3D.locate_stream_device`` replays a stream of calls in one launch (``ofp_locate_stream``), and
-``realtime.HopSession(locator=...)`` runs it inside the hop's graph.
+``realtime.HopSession(locator=...)`` runs it inside the hop's graph.  The 2-D ``Multilaterate`` has the same three
+device forms (``loc_feed_2d``; ``ofp_locate_stream_2d``, ``ofp_locate_groups_2d``, ``ofp_hop_set_locator_2d``).
 
 Batched, device-resident additions: ``locate_groups_device`` locates every onset group ``group_onsets_device``
 found, in one pass without host synchronisation; ``find_lags_device``, ``MultilateratePaired.locate_cc_device`` /
@@ -496,7 +497,7 @@ class Multilaterate3D:
 
 # ---- batched offline locator --------------------------------------------------------------------------------
 
-def locate_groups_device(groups, n_groups, m: Multilaterate3D, xtol=XTOL, maxfev=MAXFEV, return_guess=False):
+def locate_groups_device(groups, n_groups, m, xtol=XTOL, maxfev=MAXFEV, return_guess=False):
     """Locate every onset group of a batch on the device, without host synchronisation.
 
     groups int64 CUDA [n_clips, cap_groups, C] and n_groups int64 [n_clips] (or None: every row), as
@@ -505,6 +506,10 @@ def locate_groups_device(groups, n_groups, m: Multilaterate3D, xtol=XTOL, maxfev
     ``Multilaterate3D.locate`` applies them: the three earliest channels present, ordered by onset (ties by channel
     index), are origin, a and b; ``is_legal(origin, a)`` and ``is_legal(origin, b)``; ``is_legal_3d``;
     ``trilaterate`` from the guess (col, row) - radius, with its reordering (or ``m.model``).
+
+    `m` may also be a 2-D ``Multilaterate`` (``ofp_locate_groups_2d``): the same row rule and status codes, with that
+    class's ``trilaterate`` -- no reordering, deltas lag * c / sr, no model.  xy is then the Cartesian root in cm,
+    and ``cartesian_to_polar(x, y, m.radius)`` gives the reference's tuple.
 
     Returns xy float64 [n_clips, cap_groups, 2] (NaN where no solve ran) and status int32 [n_clips, cap_groups]:
     fsolve's ier (1 = located; the reference drops every other value), or LOCATE_UNUSED (-1, row beyond the clip's
@@ -520,7 +525,8 @@ def locate_groups_device(groups, n_groups, m: Multilaterate3D, xtol=XTOL, maxfev
         raise ValueError("locate_groups_device: n_groups must be an int64 CUDA tensor [n_clips]")
     dev = groups.device
     mlp = None
-    if m.model is not None:
+    planar = isinstance(m, Multilaterate)
+    if not planar and m.model is not None:
         if not hasattr(m.model, "device_mlp"):
             raise TypeError("locate_groups_device: the model must be a calibration.FCNN (its ofp_mlp network)")
         mlp = m.model.device_mlp(dev)
@@ -534,6 +540,14 @@ def locate_groups_device(groups, n_groups, m: Multilaterate3D, xtol=XTOL, maxfev
     status = torch.empty((n_clips, cap), dtype=torch.int32, device=dev)
     guess = torch.empty((n_clips, cap, 2), dtype=torch.float64, device=dev) if return_guess else None
     ws = torch.empty(max(int(L.ofp_locate_workspace_bytes(rows)), 16), dtype=torch.uint8, device=dev)
+    if planar:
+        check(L.ofp_locate_groups_2d(groups.data_ptr(), n_clips, cap, C, _ptr(n_groups), m.sensors_dev.data_ptr(),
+                                     m.sensors_dev.shape[0], m.maps_dev.data_ptr(), m.min_dev.data_ptr(),
+                                     m.max_dev.data_ptr(), m.grid_radius, float(m.samples_per_cm), float(m.sr),
+                                     float(speed_of_sound(100, medium=m.medium)), float(m.radius), float(xtol),
+                                     int(maxfev), xy.data_ptr(), status.data_ptr(), _ptr(guess), ws.data_ptr(),
+                                     ws.numel(), _stream(dev)), "ofp_locate_groups_2d")
+        return (xy, status, guess) if return_guess else (xy, status)
     check(L.ofp_locate_groups(groups.data_ptr(), n_clips, cap, C, _ptr(n_groups), m.sensors_dev.data_ptr(),
                               m.sensors_dev.shape[0], m.maps_dev.data_ptr(), m.min_dev.data_ptr(), m.max_dev.data_ptr(),
                               m.grid_radius, float(m.samples_per_cm), float(m.sr), float(m.c), float(m.radius),
@@ -641,9 +655,11 @@ class Multilaterate:
         _lib.require_gpu(self.device.index or 0)
         S = len(sensors)
         r, mask_r2 = _grid_2d(drum_diameter, 1, 2)
+        self.grid_radius = r
         self.maps_dev, self.min_dev, self.max_dev = lag_maps_device(
             sensors, r, speed_of_sound(100, medium=medium), sr, mask_r2, floor=-self.samples_per_cm * 1,
             device=self.device)
+        self.sensors_dev = torch.from_numpy(sensors).to(self.device)  # [S, 3] with z = 0
         maps = self.maps_dev.cpu().numpy()
         mn, mx = self.min_dev.cpu().numpy(), self.max_dev.cpu().numpy()
         self.lag_maps = [{j: maps[i, j] for j in range(S) if j != i} for i in range(S)]
@@ -700,6 +716,52 @@ class Multilaterate:
         if res is None:
             return None
         return cartesian_to_polar(*res, self.radius)
+
+    # ---- locate on the device ------------------------------------------------------------------------------
+
+    def locator_struct(self, xtol=XTOL, maxfev=MAXFEV):
+        """The ofp_hop_locator of this object's device tables (they must outlive every call that uses it), for the
+        planar entry points: no cross-correlation step (use_audio 0, max_section 0) and no network."""
+        loc = _lib.HopLocator()
+        loc.d_sensors, loc.S = self.sensors_dev.data_ptr(), self.sensors_dev.shape[0]
+        loc.d_maps, loc.d_min, loc.d_max = self.maps_dev.data_ptr(), self.min_dev.data_ptr(), self.max_dev.data_ptr()
+        loc.r = self.grid_radius
+        loc.samples_per_cm, loc.sr, loc.radius = float(self.samples_per_cm), float(self.sr), float(self.radius)
+        loc.c = float(speed_of_sound(100, medium=self.medium))
+        loc.xtol, loc.maxfev = float(xtol), int(maxfev)
+        loc.mlp = None
+        loc.use_audio, loc.max_section = 0, 0
+        return loc
+
+    def locate_stream_device(self, sensors, onsets):
+        """``locate`` for a whole stream of calls in ONE launch (``ofp_locate_stream_2d``): call k feeds
+        (sensors[k], onsets[k]).  Starts from an empty state and does not touch ``self.ongoing``.  Returns (found
+        bool [K], rphi float64 [K, 2]: (radius / drum radius, angle) as ``locate`` returns it, NaN where nothing was
+        returned, ongoing: the final state as the reference's list of ([sensors], [onsets])).  The device returns the
+        Cartesian root; ``cartesian_to_polar`` is applied here, on the host, as ``trilaterate`` applies it.  Raises
+        OnsetFPError when the state overflowed (64 groups of 8 members) or a call was refused (sensor outside
+        0..S-1)."""
+        sens = np.ascontiguousarray(sensors, dtype=np.int32).reshape(-1)
+        ons = np.ascontiguousarray(onsets, dtype=np.int64).reshape(-1)
+        K = len(sens)
+        if len(ons) != K:
+            raise ValueError(f"locate_stream_device: {K} sensors, {len(ons)} onsets")
+        dev = self.device
+        loc = self.locator_struct()
+        sd, od = torch.from_numpy(sens).to(dev), torch.from_numpy(ons).to(dev)
+        state = torch.zeros(ctypes.sizeof(_lib.LocateState), dtype=torch.uint8, device=dev)
+        found = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+        xy = torch.full((max(K, 1), 2), float("nan"), dtype=torch.float64, device=dev)
+        check(_lib.lib().ofp_locate_stream_2d(ctypes.byref(loc), sd.data_ptr(), od.data_ptr(), K, state.data_ptr(),
+                                              found.data_ptr(), xy.data_ptr(), _stream(dev)), "ofp_locate_stream_2d")
+        st = _lib.LocateState.from_buffer_copy(state.cpu().numpy().tobytes())
+        check_locate_flags(st.flags, "locate_stream_device")
+        found = found.cpu().numpy()[:K].astype(bool)
+        xy = xy.cpu().numpy()[:K]
+        rphi = np.full((K, 2), np.nan, dtype=np.float64)
+        for k in np.flatnonzero(found):
+            rphi[k] = cartesian_to_polar(np.float64(xy[k, 0]), np.float64(xy[k, 1]), self.radius)
+        return found, rphi, ongoing_list(st)
 
 
 # ---- MultilateratePaired ------------------------------------------------------------------------------------

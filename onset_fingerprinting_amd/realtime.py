@@ -57,6 +57,12 @@ class HopSession:
     ``fed`` (onsets given to the state machine) and ``dropped`` (onsets of the hop after the one that located: the
     reference returns at the first hit and never feeds them).  ``ongoing`` reads the state back.  The locator's own
     ``ongoing`` is not touched.
+
+    ``locator`` may also be the planar ``multilateration.Multilaterate`` (``ofp_hop_set_locator_2d``): the stage then
+    runs ``Multilaterate.locate``.  That class has no cross-correlation step, so ``locate_with_audio`` is ignored and
+    no ring length is required.  ``location`` is the polar tuple (radius / drum radius, angle) ``locate`` returns,
+    formed on the host from the device's Cartesian root; ``located_group``, ``fed``, ``dropped`` and ``ongoing`` are as
+    above.
     """
 
     def __init__(self, n_signals, block_size=128, sr=96000, n_fft=2048, n_mels=40, classifier=None,
@@ -73,12 +79,14 @@ class HopSession:
             if backtrack:
                 raise ValueError("HopSession: a locator needs backtrack=False (a backtracked onset may lie behind the "
                                  "current hop)")
-            self._max_section = ml.longest_section(locator.max_max_lags, block_size)
-            if locate_with_audio and (ring_rows < self._max_section + block_size
-                                      or self._max_section > ml.LOCATE_MAX_SECTION):
-                raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the longest section "
-                                 f"({self._max_section} rows, at most {ml.LOCATE_MAX_SECTION}) plus one hop")
-            ml.check_locator_model(locator.model, "HopSession")
+            self._planar = isinstance(locator, ml.Multilaterate)
+            if not self._planar:
+                self._max_section = ml.longest_section(locator.max_max_lags, block_size)
+                if locate_with_audio and (ring_rows < self._max_section + block_size
+                                          or self._max_section > ml.LOCATE_MAX_SECTION):
+                    raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the longest section "
+                                     f"({self._max_section} rows, at most {ml.LOCATE_MAX_SECTION}) plus one hop")
+                ml.check_locator_model(locator.model, "HopSession")
             want = device.index or 0 if isinstance(device, torch.device) else int(device)
             if (locator.device.index or 0) != want:
                 raise ValueError(f"HopSession: the locator lives on {locator.device}, the session on device {want}")
@@ -138,10 +146,15 @@ class HopSession:
         self.locator = locator
         if locator is not None:
             try:
-                self._loc_mlp = locator._device_model("HopSession")  # kept alive with the session
-                loc = locator.locator_struct(locate_with_audio, self._max_section, self._loc_mlp)
-                with torch.cuda.device(self.device):
-                    check(L.ofp_hop_set_locator(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator")
+                if self._planar:
+                    loc = locator.locator_struct()
+                    with torch.cuda.device(self.device):
+                        check(L.ofp_hop_set_locator_2d(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator_2d")
+                else:
+                    self._loc_mlp = locator._device_model("HopSession")  # kept alive with the session
+                    loc = locator.locator_struct(locate_with_audio, self._max_section, self._loc_mlp)
+                    with torch.cuda.device(self.device):
+                        check(L.ofp_hop_set_locator(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator")
             except Exception:
                 self.close()
                 raise
@@ -159,13 +172,15 @@ class HopSession:
         ml.check_locate_flags(flags.value, "HopSession")
         hit = status.value == 1
         out["location"] = (np.float64(self._loc_xy[0]), np.float64(self._loc_xy[1])) if hit else None
+        if hit and self._planar:  # Multilaterate.trilaterate's last step
+            out["location"] = ml.cartesian_to_polar(*out["location"], self.locator.radius)
         out["located_group"] = (list(self._loc_sens[:n.value]), list(self._loc_on[:n.value])) if hit else None
         out["fed"], out["dropped"] = fed.value, dropped.value
         return out
 
     @property
     def ongoing(self):
-        """The device state as the reference's ``Multilaterate3D.ongoing``: a list of ([sensors], [onsets])."""
+        """The device state as the reference's ``ongoing`` of the locator's class: a list of ([sensors], [onsets])."""
         from . import multilateration as ml
         if self.locator is None:
             raise ValueError("HopSession.ongoing: the session has no locator")

@@ -2,7 +2,8 @@
 """Per-hop latency of the realtime chain with hit location, at the reference's realtime setup: 3 channels x 128
 samples at 96 kHz (budget 1 333 us per hop), n_fft 2048, three drumhead sensors, the ring as rec_audio.
 
-    python tools/hop_locate_latency.py [--mode auto|graph|host] [--passes 4] [--package-root DIR] [--out FILE]
+    python tools/hop_locate_latency.py [--mode auto|graph|host] [--planar] [--passes 4] [--package-root DIR]
+                                       [--out FILE]
 
 The stream is the first case of the golden g25 (tests/golden/g25_hoplocate.npz), looped: every pass resets the
 session and plays all its hops; the first pass is warm-up.  Per hop, the host clock runs around everything a caller
@@ -16,6 +17,9 @@ needs for the hop's answer:
 older checkout (--package-root: the tree to import the package from).  Reported per class of hop: p50 / p99 / count
 for hops without onsets, hops with onsets that complete no group, and hops that complete a group (a position is
 returned).  One JSON line on stdout.
+
+``--planar`` takes the 2-D ``Multilaterate`` on the same three sensors instead (no ring: that class has no
+cross-correlation step); ``host`` is then ``Multilaterate.locate`` per onset.
 """
 import argparse
 import inspect
@@ -41,6 +45,7 @@ class SessionRing:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["auto", "graph", "host"], default="auto")
+    ap.add_argument("--planar", action="store_true", help="the 2-D Multilaterate instead of Multilaterate3D")
     ap.add_argument("--passes", type=int, default=4, help="passes over the stream, the first is warm-up")
     ap.add_argument("--package-root", default=str(REPO))
     ap.add_argument("--out", default=None)
@@ -61,7 +66,10 @@ def main():
     mode = ("graph" if has_locator else "host") if args.mode == "auto" else args.mode
     if mode == "graph" and not has_locator:
         raise SystemExit("this checkout's HopSession has no locator=")
-    m = ml.Multilaterate3D(**a["layout"])
+    if args.planar:
+        m = ml.Multilaterate(**dict(a["layout"], sensor_locations=[s[:2] for s in a["layout"]["sensor_locations"]]))
+    else:
+        m = ml.Multilaterate3D(**a["layout"])
     kw = dict(sr=96000, n_fft=2048, ring_seconds=1.0, **det)
     sess = realtime.HopSession(3, B, locator=m, **kw) if mode == "graph" else realtime.HopSession(3, B, **kw)
     hops = [np.ascontiguousarray(audio[h * B:(h + 1) * B]) for h in range(len(audio) // B)]
@@ -80,7 +88,10 @@ def main():
                 res = None
                 if n:
                     for i in np.argsort(r["onsets"], kind="stable"):
-                        res = m.locate(int(r["channels"][i]), int(r["onsets"][i]), SessionRing(sess))
+                        if args.planar:
+                            res = m.locate(int(r["channels"][i]), int(r["onsets"][i]))
+                        else:
+                            res = m.locate(int(r["channels"][i]), int(r["onsets"][i]), SessionRing(sess))
                         if res is not None:
                             break
             dt = (time.perf_counter_ns() - t0) * 1e-3
@@ -88,8 +99,9 @@ def main():
                 continue
             times["no_onsets" if n == 0 else "completes_group" if res is not None else "onsets_no_group"].append(dt)
             located += res is not None
-    want = int(g[f"{case}/audio/res"][:, 0].sum()) * (args.passes - 1)
-    out = {"mode": mode, "case": case, "device": torch.cuda.get_device_name(0), "budget_us": BUDGET_US,
+    # (the golden holds the 3-D locator's positions only)
+    want = None if args.planar else int(g[f"{case}/audio/res"][:, 0].sum()) * (args.passes - 1)
+    out = {"mode": mode, "locator": "Multilaterate" if args.planar else "Multilaterate3D", "case": case, "device": torch.cuda.get_device_name(0), "budget_us": BUDGET_US,
            "hops_timed": sum(len(v) for v in times.values()), "located": located, "located_expected": want,
            "classes": {k: {"p50_us": float(np.percentile(v, 50)), "p99_us": float(np.percentile(v, 99)),
                            "max_us": float(np.max(v)), "hops": len(v)} for k, v in times.items() if v}}

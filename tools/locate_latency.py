@@ -2,7 +2,7 @@
 """Latency and throughput of the hit locator (onset_fingerprinting_amd.multilateration), the realtime layout:
 three drumhead sensors at 96 kHz.
 
-    python tools/locate_latency.py [--out results/locate_latency.json]
+    python tools/locate_latency.py [--planar] [--out results/locate_latency.json]
 
   locate      one Multilaterate3D.locate call that completes a group (the realtime case; budget 1 333 us per
               128-sample hop at 96 kHz), without and with the ring's cross-correlation step: host clock around
@@ -11,6 +11,10 @@ three drumhead sensors at 96 kHz.
               lag maps and sensors resident on the GPU
   host scipy  the reference's per-group path on one CPU core: numpy legality search + scipy.optimize.fsolve with the
               same equations, Jacobian and arguments (xtol 0.01, maxfev 20)
+
+--planar measures the 2-D Multilaterate on the same three sensors instead: its locate (no ring: the class has no
+cross-correlation step), locate_groups_device with it, and the reference's 2-D steps on the host (no reordering, deltas
+lag * c / sr).
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
 LAYOUT = dict(sensor_locations=[(0.9, 30, 0), (0.9, 150, 0), (0.9, 270, 0)], medium="drumhead", sr=96000)
+LAYOUT_2D = dict(LAYOUT, sensor_locations=[s[:2] for s in LAYOUT["sensor_locations"]])
 
 
 def strike_rows(m, G, seed=0):
@@ -34,15 +39,23 @@ def strike_rows(m, G, seed=0):
     rng = np.random.default_rng(seed)
     ang, rad = rng.uniform(0, 2 * np.pi, G), m.radius * 0.8 * np.sqrt(rng.uniform(0, 1, G))
     p = np.stack([rad * np.cos(ang), rad * np.sin(ang)], 1)
-    s = np.array(m.sensor_locs)
+    s = np.array([list(v) + [0.0] * (3 - len(v)) for v in m.sensor_locs])
     d = np.sqrt(((p[:, None, :] - s[None, :, :2]) ** 2).sum(-1) + s[None, :, 2] ** 2)
-    return 100000 + np.round(d / m.c * m.sr).astype(np.int64)
+    return 100000 + np.round(d / speed(m) * m.sr).astype(np.int64)
 
 
-def host_scipy(m, rows):
-    """The reference's per-group steps on the host (multilateration.py:413-426, 536-565, 230-316)."""
+def speed(m):
+    """cm/s: Multilaterate3D keeps it, the 2-D class computes it where it is used."""
+    from onset_fingerprinting_amd import multilateration as ml
+    return m.c if hasattr(m, "c") else ml.speed_of_sound(100, medium=m.medium)
+
+
+def host_scipy(m, rows, planar=False):
+    """The reference's per-group steps on the host (multilateration.py:413-426, 536-565, 230-316; planar: :662-675,
+    :714-733, :170-227 -- sensors with z = 0, no reordering, deltas lag * c / sr)."""
     from scipy.optimize import fsolve
-    loc = [np.array(v, np.float64) for v in m.sensor_locs]
+    loc = [np.array(list(v) + [0.0] * (3 - len(v)), np.float64) for v in m.sensor_locs]
+    c = speed(m)
     tol = m.samples_per_cm
     maps = {(i, j): m.lag_maps[i][j] for i in range(3) for j in range(3) if i != j}
     out = []
@@ -59,10 +72,13 @@ def host_scipy(m, rows):
         if res == (0, 0):
             out.append(None)
             continue
-        if s[1] == 1:
+        if s[1] == 1 and not planar:
             s[1:], o[1:] = [0, 1], o[2:0:-1]
         a, b, c0 = loc[s[1]], loc[s[2]], loc[s[0]]
-        dda, ddb = (o[1] - o[0]) / m.sr * m.c, (o[2] - o[0]) / m.sr * m.c
+        if planar:
+            dda, ddb = (o[1] - o[0]) * c / m.sr, (o[2] - o[0]) * c / m.sr
+        else:
+            dda, ddb = (o[1] - o[0]) / m.sr * c, (o[2] - o[0]) / m.sr * c
 
         def f(p):
             da, db, d0 = (np.sqrt((p[0] - q[0]) ** 2 + (p[1] - q[1]) ** 2 + q[2] ** 2) for q in (a, b, c0))
@@ -82,13 +98,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--planar", action="store_true", help="the 2-D Multilaterate instead of Multilaterate3D")
     args = ap.parse_args()
     import torch
 
     from onset_fingerprinting_amd import multilateration as ml
     torch.set_num_threads(1)
-    m = ml.Multilaterate3D(**LAYOUT)
-    res = {"layout": LAYOUT, "device": torch.cuda.get_device_name(0)}
+    m = ml.Multilaterate(**LAYOUT_2D) if args.planar else ml.Multilaterate3D(**LAYOUT)
+    res = {"locator": type(m).__name__, "layout": LAYOUT_2D if args.planar else LAYOUT,
+           "device": torch.cuda.get_device_name(0)}
 
     # realtime: the third onset of a strike completes the group
     row = strike_rows(m, 1, seed=4)[0]  # a strike the reference locates
@@ -107,16 +125,21 @@ def main():
         def __getitem__(self, idx):
             return audio[: self.counter][idx]
 
-    for name, ring in (("locate_us", None), ("locate_with_ring_us", True)):
+    def feed(k, ring):
+        if args.planar:
+            return m.locate(int(k), int(row[k]))
+        return m.locate(int(k), int(row[k]), Ring(int(row[k]) + 256) if ring else None)
+
+    for name, ring in (("locate_us", None),) + (() if args.planar else (("locate_with_ring_us", True),)):
         times, located = [], 0
         for it in range(args.iters + 10):
             m.ongoing = []
             for k in order[:2]:
-                m.locate(int(k), int(row[k]), Ring(int(row[k]) + 256) if ring else None)
+                feed(k, ring)
             k = order[2]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            r = m.locate(int(k), int(row[k]), Ring(int(row[k]) + 256) if ring else None)
+            r = feed(k, ring)
             torch.cuda.synchronize()
             if it >= 10:
                 times.append((time.perf_counter() - t0) * 1e6)
@@ -145,7 +168,7 @@ def main():
     # the host path on one core
     rows = strike_rows(m, 300, seed=11)
     t0 = time.perf_counter()
-    host = host_scipy(m, rows)
+    host = host_scipy(m, rows, args.planar)
     dt = time.perf_counter() - t0
     res["host_scipy"] = {"us_per_group": dt / len(rows) * 1e6, "groups_per_s": len(rows) / dt,
                          "located": sum(r is not None for r in host)}

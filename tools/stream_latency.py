@@ -20,6 +20,7 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import numpy as np  # noqa: E402
+import torch  # noqa: E402, F401  (before the package, as in the other tools: both bring a HIP runtime)
 
 from onset_fingerprinting_amd import realtime, synth  # noqa: E402
 from onset_fingerprinting_amd.pipeline import seeded_fcnn  # noqa: E402
