@@ -18,8 +18,8 @@
 // branch, the hop is read from and the result block written to pinned host memory directly.
 //
 // With a locator attached (ofp_hop_set_locator, or ofp_hop_set_locator_2d for the planar Multilaterate, which runs
-// loc_feed_2d in the same stage) the hop also carries Multilaterate3D.locate (ofp_locate_dev.h): the
-// detector's workgroup (fused form) or one more kernel node after the detector (nodes form) feeds the hop's onsets,
+// loc_feed's planar instantiation in the same stage) the hop also carries Multilaterate3D.locate (ofp_locate_dev.h):
+// the detector's workgroup (fused form) or one more kernel node after the detector (nodes form) feeds the hop's onsets,
 // sorted by sample, to the device-resident state and writes the location block next to the records.  A hop without
 // onsets takes one uniform branch on the count and touches nothing of the stage.
 //
@@ -480,18 +480,10 @@ __device__ __forceinline__ void hop_locate_stage(const HopArgs& a, const HopLocA
     };
     int fed = 0, status = 0;
     double xy[2] = {0.0, 0.0};
-    if (T.planar) {  // uniform: the kind is the session's
-        for (int i = 0; i < n && !status; ++i) {
-            const ofp_onset r = recs[s_order[i]];
-            status = ofp::loc_feed_2d(T, v, r.channel, first + r.sample, xy, &s_located);
-            ++fed;
-        }
-    } else {
-        for (int i = 0; i < n && !status; ++i) {
-            const ofp_onset r = recs[s_order[i]];
-            status = ofp::loc_feed(T, v, r.channel, first + r.sample, counter, true, sample, xy, &s_located);
-            ++fed;
-        }
+    for (int i = 0; i < n && !status; ++i) {  // the locator's kind (T.planar) is the session's
+        const ofp_onset r = recs[s_order[i]];
+        status = ofp::loc_feed_kind(T, v, r.channel, first + r.sample, counter, true, sample, xy, &s_located);
+        ++fed;
     }
     __syncthreads();
     if (tid == 0) {

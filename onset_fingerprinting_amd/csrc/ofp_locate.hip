@@ -15,9 +15,11 @@
 // k_locate_solve: the back: trilaterate (or the model's output * 100) per row, one lane per row.  Both serve the 2-D
 //                Multilaterate as well (LocateArgs::planar: its trilaterate keeps the sensors' order).
 // k_locate_stream: Multilaterate3D.locate itself (or the 2-D Multilaterate.locate), K calls through one
-//                device-resident state (ofp_locate_dev.h), one workgroup.
+//                device-resident state (ofp_locate_dev.h: loc_feed_kind), one workgroup.
 // k_section:     Multilaterate3D.locate's cross-correlation input (multilateration.py:466-476): median filter of
 //                size 5 ('reflect') along time, first difference, non-negative values zeroed, absolute value.
+// The rules these kernels share with the state machine are written once in ofp_locate_dev.h: loc_cell (flat index ->
+// cell -> guess), loc_reorder_3d, loc_tdoa (the system and each kind's delta rule), section_value.
 #include <cmath>
 #include <cstring>
 
@@ -30,7 +32,6 @@ namespace {
 
 using ofp::cdiv;
 using ofp::first_legal;  // ofp_locate_dev.h
-using ofp::med5;
 
 constexpr int LOC_THREADS = 256;
 
@@ -106,8 +107,9 @@ __global__ void k_legal(const float* __restrict__ maps, int S, int side, const i
     const double lag2 = (double)(onsets[3 * g + 2] - onsets[3 * g]);
     const int64_t k = first_legal(maps, S, side, s0, s1, s2, lag1, lag2, tol, smin);
     if (threadIdx.x == 0) {
-        idx[2 * g] = k < 0 ? 0 : (int32_t)(k % side);
-        idx[2 * g + 1] = k < 0 ? 0 : (int32_t)(k / side);
+        const ofp::LocCell cell = ofp::loc_cell(k, side);
+        idx[2 * g] = (int32_t)cell.ix;
+        idx[2 * g + 1] = (int32_t)cell.iy;
     }
 }
 
@@ -211,21 +213,15 @@ __global__ void k_locate_rows(LocateArgs A) {
     __syncthreads();
     RowState s = st;
     if (s.status == 0) {
-        const int64_t k = first_legal(A.maps, A.S, A.side, s.sens[0], s.sens[1], s.sens[2],
-                                      (double)(s.on[1] - s.on[0]), (double)(s.on[2] - s.on[0]), A.tol, smin);
-        const int64_t ix = k < 0 ? 0 : k % A.side, iy = k < 0 ? 0 : k / A.side;
-        if (ix == 0 && iy == 0) {
+        const ofp::LocCell cell = ofp::loc_cell(
+            first_legal(A.maps, A.S, A.side, s.sens[0], s.sens[1], s.sens[2], (double)(s.on[1] - s.on[0]),
+                        (double)(s.on[2] - s.on[0]), A.tol, smin),
+            A.side);
+        if (cell.none()) {
             s.status = OFP_LOCATE_NO_CELL;
         } else {
-            s.guess[0] = (double)ix - A.radius;
-            s.guess[1] = (double)iy - A.radius;
-            if (!A.planar && s.sens[1] == 1) {  // Multilaterate3D.trilaterate, multilateration.py:542-544
-                s.sens[1] = 0;
-                s.sens[2] = 1;
-                const int64_t t = s.on[1];
-                s.on[1] = s.on[2];
-                s.on[2] = t;
-            }
+            cell.guess(A.radius, s.guess);
+            if (!A.planar) ofp::loc_reorder_3d(s.sens, s.on);
         }
     }
     if (threadIdx.x == 0) {
@@ -255,29 +251,11 @@ __global__ void k_locate_solve(LocateArgs A, int64_t n_rows, const float* __rest
         status[row] = 1;
         return;
     }
-    ofp::hybrj::Tdoa t;
-    for (int k = 0; k < 3; ++k) {
-        t.o[k] = A.sensors[3 * s.sens[0] + k];
-        t.a[k] = A.sensors[3 * s.sens[1] + k];
-        t.b[k] = A.sensors[3 * s.sens[2] + k];
-    }
-    if (A.planar) {  // Multilaterate.trilaterate, multilateration.py:724-725: multiply first
-        t.dda = (double)(s.on[1] - s.on[0]) * A.c / A.sr;
-        t.ddb = (double)(s.on[2] - s.on[0]) * A.c / A.sr;
-    } else {
-        t.dda = (double)(s.on[1] - s.on[0]) / A.sr * A.c;
-        t.ddb = (double)(s.on[2] - s.on[0]) / A.sr * A.c;
-    }
+    const ofp::hybrj::Tdoa t = ofp::loc_tdoa(A.sensors, s.sens, s.on, A.sr, A.c, A.planar != 0);
     const ofp::hybrj::Result res = ofp::hybrj::solve(t, s.guess, A.xtol, A.maxfev);
     xy[2 * row] = res.x[0];
     xy[2 * row + 1] = res.x[1];
     status[row] = res.info;
-}
-
-__device__ __forceinline__ float sec_at(const float* x, int64_t n, int ld, int col, int64_t t) {
-    if (t < 0) t = -t - 1;          // scipy.ndimage 'reflect': d c b a | a b c d | d c b a
-    if (t >= n) t = 2 * n - t - 1;
-    return x[t * ld + col];
 }
 
 __global__ void k_section(const float* __restrict__ x, int64_t n, int ld, int c0, int c1, float* __restrict__ out) {
@@ -285,16 +263,7 @@ __global__ void k_section(const float* __restrict__ x, int64_t n, int ld, int c0
     const int which = blockIdx.y;
     if (t >= n - 1) return;
     const int col = which == 0 ? c0 : c1;
-    float m[2];
-    for (int q = 0; q < 2; ++q) {
-        const int64_t u = t + q;
-        float w[5];
-        for (int k = 0; k < 5; ++k) w[k] = sec_at(x, n, ld, col, u + k - 2);
-        m[q] = med5(w);
-    }
-    float d = m[1] - m[0];
-    if (d >= 0.0f) d = 0.0f;
-    out[(int64_t)which * (n - 1) + t] = fabsf(d);
+    out[(int64_t)which * (n - 1) + t] = ofp::section_value([&](int64_t u) { return x[u * ld + col]; }, n, t);
 }
 
 // The replay entry: K calls of locate through one state machine, one workgroup (ofp_locate_dev.h).
@@ -318,8 +287,7 @@ __global__ __launch_bounds__(LOC_THREADS) void k_locate_stream(ofp::LocTables T,
             if (threadIdx.x == 0) v.L->st[v.L->cur].flags |= OFP_LOCF_BAD_CALL;
             __syncthreads();
         } else {
-            f = T.planar ? ofp::loc_feed_2d(T, v, s, onset[k], r, nullptr)
-                         : ofp::loc_feed(T, v, s, onset[k], cnt, false, sample, r, nullptr);
+            f = ofp::loc_feed_kind(T, v, s, onset[k], cnt, false, sample, r, nullptr);
         }
         if (threadIdx.x == 0) {
             found[k] = f;
@@ -527,21 +495,16 @@ int ofp_locate_section(const float* d_x, int64_t n, int32_t ld, int32_t c0, int3
     return OFP_OK;
 }
 
-int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset,
-                      const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
-                      ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
-    ofp::LocTables T;
-    if (int rc = ofp_locate_tables(loc, "ofp_locate_stream", &T)) return rc;
-    OFP_REQUIRE(K >= 0, "ofp_locate_stream: negative call count");
-    OFP_REQUIRE(d_state, "ofp_locate_stream: NULL state");
-    OFP_REQUIRE((d_audio != nullptr) == (loc->use_audio != 0),
-                "ofp_locate_stream: use_audio and the recording must be given together");
-    OFP_REQUIRE(!d_audio || (n_rows >= 0 && n_channels >= loc->S),
-                "ofp_locate_stream: the recording has %d channels for %d sensors", n_channels, loc->S);
+// ofp_locate_stream and ofp_locate_stream_2d: one launch of k_locate_stream on tables their caller has checked
+static int locate_stream(const char* who, const ofp::LocTables& T, const int32_t* d_sensor, const int64_t* d_onset,
+                         const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
+                         ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
+    OFP_REQUIRE(K >= 0, "%s: negative call count", who);
+    OFP_REQUIRE(d_state, "%s: NULL state", who);
     if (K == 0) return OFP_OK;
-    OFP_REQUIRE(d_sensor && d_onset && d_counter && d_found && d_xy, "ofp_locate_stream: NULL argument");
+    OFP_REQUIRE(d_sensor && d_onset && (d_counter || T.planar) && d_found && d_xy, "%s: NULL argument", who);
     const size_t lds = ofp::loc_lds_bytes(LOC_THREADS, T.max_section, T.plan);
-    OFP_REQUIRE(lds <= 150 * 1024, "ofp_locate_stream: %zu bytes of LDS needed", lds);
+    OFP_REQUIRE(lds <= 150 * 1024, "%s: %zu bytes of LDS needed", who, lds);
     static ofp::LdsAttrCache attr;
     if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_stream), lds, attr, 32768)) return rc;
     hipLaunchKernelGGL(k_locate_stream, dim3(1), dim3(LOC_THREADS), lds, (hipStream_t)stream, T, d_sensor, d_onset,
@@ -550,21 +513,25 @@ int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const
     return OFP_OK;
 }
 
+int ofp_locate_stream(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset,
+                      const int64_t* d_counter, int64_t K, const float* d_audio, int64_t n_rows, int32_t n_channels,
+                      ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
+    ofp::LocTables T;
+    if (int rc = ofp_locate_tables(loc, "ofp_locate_stream", &T)) return rc;
+    OFP_REQUIRE((d_audio != nullptr) == (loc->use_audio != 0),
+                "ofp_locate_stream: use_audio and the recording must be given together");
+    OFP_REQUIRE(!d_audio || (n_rows >= 0 && n_channels >= loc->S),
+                "ofp_locate_stream: the recording has %d channels for %d sensors", n_channels, loc->S);
+    return locate_stream("ofp_locate_stream", T, d_sensor, d_onset, d_counter, K, d_audio, n_rows, n_channels, d_state,
+                         d_found, d_xy, stream);
+}
+
 int ofp_locate_stream_2d(const ofp_hop_locator* loc, const int32_t* d_sensor, const int64_t* d_onset, int64_t K,
                          ofp_locate_state* d_state, int32_t* d_found, double* d_xy, void* stream) {
     ofp::LocTables T;
     if (int rc = ofp_locate_tables_2d(loc, "ofp_locate_stream_2d", &T)) return rc;
-    OFP_REQUIRE(K >= 0, "ofp_locate_stream_2d: negative call count");
-    OFP_REQUIRE(d_state, "ofp_locate_stream_2d: NULL state");
-    if (K == 0) return OFP_OK;
-    OFP_REQUIRE(d_sensor && d_onset && d_found && d_xy, "ofp_locate_stream_2d: NULL argument");
-    const size_t lds = ofp::loc_lds_bytes(LOC_THREADS, T.max_section, T.plan);
-    static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_stream), lds, attr, 32768)) return rc;
-    hipLaunchKernelGGL(k_locate_stream, dim3(1), dim3(LOC_THREADS), lds, (hipStream_t)stream, T, d_sensor, d_onset,
-                       (const int64_t*)nullptr, K, (const float*)nullptr, (int64_t)0, 0, d_state, d_found, d_xy);
-    OFP_LAUNCH_CHECK("k_locate_stream");
-    return OFP_OK;
+    return locate_stream("ofp_locate_stream_2d", T, d_sensor, d_onset, nullptr, K, nullptr, 0, 0, d_state, d_found,
+                         d_xy, stream);
 }
 
 }  // extern "C"

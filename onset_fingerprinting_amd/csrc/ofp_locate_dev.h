@@ -1,13 +1,15 @@
 // Device functions of the hit locator shared by ofp_locate.hip (the batched entry points), the replay kernel
-// and the per-hop graph (ofp_hop.hip): the legality search, the section filter, and Multilaterate3D.locate
-// (reference multilateration.py:428-575) as a state machine run by ONE workgroup on a state held in LDS.
+// and the per-hop graph (ofp_hop.hip): the legality search, the section filter, the rules of trilaterate, and
+// Multilaterate3D.locate (reference multilateration.py:428-575) together with the planar Multilaterate.locate
+// (:677-733) as ONE state machine run by ONE workgroup on a state held in LDS.
 //
-// loc_feed is the reference's locate, line by line (the host version in multilateration.py is its model).  The
-// bookkeeping is done by thread 0; every thread follows the same control flow on the same LDS values, so the three
-// parallel parts are reached by the whole workgroup: the lag x sample products of the correlation (one lag per
-// lane), the is_legal_3d scan (first-hit reduction) and the section filter.  hybrj runs on one lane in fp64.
-// Static bounds: groups <= OFP_LOCS_GROUPS, members <= OFP_LOCS_MEMBERS, lags <= 2 * LOC_ONSET_TOL, section rows <=
-// the caller's max_section, hybrj's maxfev.
+// loc_feed<PLANAR> is the reference's locate, line by line (the host versions in multilateration.py are its models);
+// what the planar routine leaves out stands under `if constexpr (PLANAR)`, so each kind is compiled without a test
+// of the other.  The bookkeeping is done by thread 0; every thread follows the same control flow on the same LDS
+// values, so the three parallel parts are reached by the whole workgroup: the lag x sample products of the
+// correlation (one lag per lane), the is_legal_3d scan (first-hit reduction) and the section filter.  hybrj runs on
+// one lane in fp64.  Static bounds: groups <= OFP_LOCS_GROUPS, members <= OFP_LOCS_MEMBERS, lags <= 2 *
+// LOC_ONSET_TOL, section rows <= the caller's max_section, hybrj's maxfev.
 #pragma once
 #include <cmath>
 
@@ -45,6 +47,51 @@ __device__ inline int64_t first_legal(const float* __restrict__ maps, int S, int
     return r < cells ? r : -1;
 }
 
+// first_legal's index as np.unravel_index(.., "F") returns it for a square map: (column, row), and (0, 0) for -1.
+// The reference takes (0, 0) for "no cell", so a hit in that very cell counts as none.
+struct LocCell {
+    int64_t ix, iy;
+    __device__ bool none() const { return ix == 0 && iy == 0; }
+    // trilaterate's initial guess: np.array(res) - self.radius
+    __device__ void guess(double radius, double* g) const {
+        g[0] = (double)ix - radius;
+        g[1] = (double)iy - radius;
+    }
+};
+
+__device__ __forceinline__ LocCell loc_cell(int64_t k, int side) {
+    return LocCell{k < 0 ? 0 : k % side, k < 0 ? 0 : k / side};
+}
+
+// Multilaterate3D.trilaterate's reordering (multilateration.py:542-544): a group whose second sensor is sensor 1 is
+// solved as (origin, 0, 1) with the two later onsets exchanged.  The planar class has no such step.
+__device__ __forceinline__ void loc_reorder_3d(int32_t* sens, int64_t* on) {
+    if (sens[1] == 1) {
+        sens[1] = 0;
+        sens[2] = 1;
+        const int64_t t = on[1];
+        on[1] = on[2];
+        on[2] = t;
+    }
+}
+
+// trilaterate's system for a group (origin, a, b).  The two classes form the path differences in another order of
+// operations, and they round differently: lag / sr * c (Multilaterate3D, :563-564), lag * c / sr (Multilaterate,
+// :724-725).
+__device__ __forceinline__ hybrj::Tdoa loc_tdoa(const double* __restrict__ sensors, const int32_t* sens,
+                                                const int64_t* on, double sr, double c, bool planar) {
+    hybrj::Tdoa t;
+    for (int q = 0; q < 3; ++q) {
+        t.o[q] = sensors[3 * sens[0] + q];
+        t.a[q] = sensors[3 * sens[1] + q];
+        t.b[q] = sensors[3 * sens[2] + q];
+    }
+    const double da = (double)(on[1] - on[0]), db = (double)(on[2] - on[0]);
+    t.dda = planar ? da * c / sr : da / sr * c;
+    t.ddb = planar ? db * c / sr : db / sr * c;
+    return t;
+}
+
 __device__ __forceinline__ float med5(const float* in) {
     float v[5];
     for (int i = 0; i < 5; ++i) {  // insertion sort of five finite samples
@@ -59,7 +106,28 @@ __device__ __forceinline__ float med5(const float* in) {
     return v[2];
 }
 
-// ---- Multilaterate3D.locate --------------------------------------------------------------------------------
+// Value t (0 <= t < n - 1) of locate's cross-correlation input (multilateration.py:466-476) over n rows of one
+// channel: median filter of size 5 ('reflect': d c b a | a b c d | d c b a) along time, first difference,
+// non-negative values zeroed, absolute value.  at(u): row u of the channel, 0 <= u < n.
+template <class At>
+__device__ __forceinline__ float section_value(At&& at, int64_t n, int64_t t) {
+    float md[2];
+    for (int q = 0; q < 2; ++q) {
+        float w[5];
+        for (int k = 0; k < 5; ++k) {
+            int64_t u = t + q + k - 2;
+            if (u < 0) u = -u - 1;
+            if (u >= n) u = 2 * n - u - 1;
+            w[k] = at(u);
+        }
+        md[q] = med5(w);
+    }
+    float d = md[1] - md[0];
+    if (d >= 0.0f) d = 0.0f;
+    return fabsf(d);
+}
+
+// ---- locate ------------------------------------------------------------------------------------------------
 
 constexpr int LOC_ONSET_TOL = 50;    // multilateration.py: ONSET_TOL
 constexpr int LOC_NORM_CUTOFF = 10;  // NORM_CUTOFF
@@ -77,7 +145,7 @@ struct LocTables {
     int maxfev;
     int use_audio;
     int max_section;
-    int planar;    // 1: the 2-D Multilaterate (loc_feed_2d), sensors with z = 0; never with use_audio or a network
+    int planar;    // 1: the 2-D Multilaterate (loc_feed<true>), sensors with z = 0; never with use_audio or a network
     MlpPlan plan;  // n_layers == 0: hybrj
 };
 
@@ -173,26 +241,213 @@ __device__ __forceinline__ void loc_copy_group(ofp_locate_state* dst, int di, co
     }
 }
 
-// One call of locate(sensor, onset, rec_audio) by the whole workgroup.  audio(t, col): sample t of the stream
-// (start <= t < counter); zero_pad: a section that starts before sample 0 keeps its length (rows there are what
-// audio returns) instead of being cut at row 0.  Returns 1 when a position was returned (xy), else 0; `located`
-// (LDS, may be NULL) receives the group as trilaterate left it.  Every thread returns the same values.
+// The lists of one call: `ongoing` as the call found it, and new_groups with its length and the sticky flags.  Every
+// thread holds the same values.
+struct LocCall {
+    ofp_locate_state* cur;
+    ofp_locate_state* nxt;
+    int nn;     // len(new_groups)
+    int flags;
+};
+
+// new_groups.append(group): returns the entry's index, or -1 with OFP_LOCF_GROUPS set when the list is full
+__device__ __forceinline__ int loc_append(LocCall& c, const int32_t* sens, const int64_t* on, int len, int alias) {
+    if (c.nn >= OFP_LOCS_GROUPS) {
+        c.flags |= OFP_LOCF_GROUPS;
+        return -1;
+    }
+    if (threadIdx.x == 0) loc_copy_group(c.nxt, c.nn, sens, on, len, alias);
+    return c.nn++;
+}
+
+// self.ongoing = new_groups
+__device__ __forceinline__ void loc_publish(LocLds& L, const LocCall& c) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        c.nxt->n_groups = c.nn;
+        c.nxt->flags = c.flags;
+        L.cur ^= 1;
+    }
+    __syncthreads();
+}
+
+// group = (group[0] + [sensor], group[1] + [onset]), into L.ext
+__device__ __forceinline__ void loc_extend(LocLds& L, const ofp_locate_state* cur, int src, int len, int sensor,
+                                           int64_t onset) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        L.ext.len = len + 1;
+        for (int k = 0; k < len; ++k) {
+            L.ext.sens[k] = cur->sensors[src][k];
+            L.ext.on[k] = cur->onsets[src][k];
+        }
+        L.ext.sens[len] = sensor;
+        L.ext.on[len] = onset;
+    }
+    __syncthreads();
+}
+
+// Multilaterate3D.locate's cross-correlation refinement (multilateration.py:452-497) of the lag between the group's
+// first onset o0 (sensor s0; entry src of `ongoing`) and the new one: the section rows rec_audio[-i - 1:] of the two
+// channels through section_value, cross_correlation_lag over the window around the current lag, adjust_onset.
+// Moves o0 in place -- in `ongoing`, and in the copy new_groups holds when the entry is an alias (my_prev >= 0) --
+// and `onset`, and replaces `lag`; leaves all three alone when the window is empty.  A section the LDS rows cannot
+// hold sets OFP_LOCF_SECTION.
 template <class Audio>
+__device__ __forceinline__ void loc_cc_adjust(const LocTables& T, const LocView& v, LocCall& c, Audio&& audio,
+                                              int64_t counter, bool zero_pad, int src, int my_prev, int s0, int sensor,
+                                              int64_t& o0, int64_t& onset, int64_t& lag) {
+    LocLds& L = *v.L;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int64_t want = counter - o0 + LOC_LOOKAROUND + 1;
+    int64_t start = counter - want;
+    if (!zero_pad && start < 0) start = 0;
+    const int64_t n64 = counter - start;
+    if (n64 < 3 || n64 > T.max_section) {
+        c.flags |= OFP_LOCF_SECTION;
+        return;
+    }
+    const int n = (int)n64, m = n - 1;
+    float mx = -INFINITY, my = -INFINITY;
+    for (int i = tid; i < 2 * m; i += nt) {
+        const int which = i >= m, t = which ? i - m : i;
+        const int col = which ? sensor : s0;
+        const float d = section_value([&](int64_t u) { return audio(start + u, col); }, n, t);
+        if (which) {
+            v.ys[t] = d;
+            my = fmaxf(my, d);
+        } else {
+            v.xs[t] = d;
+            mx = fmaxf(mx, d);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o));
+        my = fmaxf(my, __shfl_xor(my, o));
+    }
+    if ((tid & 63) == 0) {
+        L.red[0][tid >> 6] = mx;
+        L.red[1][tid >> 6] = my;
+    }
+    __syncthreads();
+    for (int w = 0; w < (nt + 63) / 64; ++w) {
+        mx = w ? fmaxf(mx, L.red[0][w]) : L.red[0][0];
+        my = w ? fmaxf(my, L.red[1][w]) : L.red[1][0];
+    }
+    // cross_correlation_lag(x, y, onsets=(first, new), d=0, onset_tolerance, normalization_cutoff)
+    const int current = (int)(onset - o0);
+    int lo, hi;
+    py_slice(m - current - LOC_ONSET_TOL, m - current + LOC_ONSET_TOL, 2 * m - 1, &lo, &hi);
+    if (hi > lo) {
+        for (int j = lo + tid; j < hi; j += nt) L.cc[j - lo] = cc_entry(v.xs, v.ys, m, LOC_NORM_CUTOFF, j);
+        __syncthreads();
+        int am = 0;  // np.argmax: the first maximum
+        float bv = L.cc[0];
+        for (int j = 1; j < hi - lo; ++j) {
+            if (L.cc[j] > bv) {
+                bv = L.cc[j];
+                am = j;
+            }
+        }
+        const int new_lag = -(am - (current + LOC_ONSET_TOL));
+        if (tid < XCORR_WAVE) {
+            int64_t ca = 0, cb = 0;
+            adjust_onset_wave(v.xs, v.ys, m, LOC_LOOKAROUND, current + LOC_LOOKAROUND, new_lag, mx, my, tid, &ca, &cb);
+            if (tid == 0) {
+                L.mv[0] = (int32_t)ca;
+                L.mv[1] = (int32_t)cb;
+            }
+        }
+        __syncthreads();
+        lag = new_lag;
+        o0 += L.mv[0];
+        onset += L.mv[1];
+        if (tid == 0) {
+            c.cur->onsets[src][0] = o0;
+            if (my_prev >= 0) c.nxt->onsets[my_prev][0] = o0;
+        }
+    }
+    __syncthreads();
+}
+
+// trilaterate for the three-member group in L.ext from the cell the search found: the root into L.res and the
+// return value 1 (every thread), or 0.  3-D: its reordering first (:536-575), then the network's output * 100 when
+// there is one, else hybrj on lane 0; planar (:714-733): hybrj on the group as it stands.
+template <bool PLANAR>
+__device__ __forceinline__ int loc_solve(const LocTables& T, const LocView& v, const LocCell& cell) {
+    LocLds& L = *v.L;
+    const int tid = threadIdx.x;
+    if constexpr (!PLANAR) {
+        if (tid == 0) {
+            loc_reorder_3d(L.ext.sens, L.ext.on);
+            L.found = 0;
+        }
+        __syncthreads();
+    }
+    if (!PLANAR && T.plan.n_layers > 0) {  // self.model.call_np((d_a1, d_b1)) * 100: a float32 product
+        if (tid < 64) {
+            for (int i = tid; i < 16 * T.plan.st_a; i += 64) v.ta[i] = 0.0f;
+            ofp_wave_lds_sync();
+            if (tid == 0) {
+                v.ta[0] = (float)(L.ext.on[1] - L.ext.on[0]);
+                v.ta[1] = (float)(L.ext.on[2] - L.ext.on[0]);
+            }
+            ofp_wave_lds_sync();
+            ofp_mlp_tile(T.plan, T.plan.params, v.ta, v.tb, tid, [&](int r, int col, float val) {
+                if (r == 0 && col < 2) L.res[col] = (double)(val * 100.0f);
+            });
+            if (tid == 0) L.found = 1;
+        }
+    } else if (tid == 0) {
+        const hybrj::Tdoa t = loc_tdoa(T.sensors, L.ext.sens, L.ext.on, T.sr, T.c, PLANAR);
+        double guess[2];
+        cell.guess(T.radius, guess);
+        const hybrj::Result r = hybrj::solve(t, guess, T.xtol, T.maxfev);
+        L.res[0] = r.x[0];
+        L.res[1] = r.x[1];
+        L.found = r.info == 1 ? 1 : 0;
+    }
+    __syncthreads();
+    return L.found;
+}
+
+// remove_seed(new_groups, group) for the group in L.ext (3-D only)
+__device__ __forceinline__ void loc_remove_seed(LocLds& L, LocCall& c) {
+    if (threadIdx.x == 0) {
+        ofp_locate_state* nxt = c.nxt;
+        int w = 0;
+        for (int q = 0; q < c.nn; ++q) {
+            if (nxt->sensors[q][0] == L.ext.sens[0] && nxt->onsets[q][0] == L.ext.on[0]) continue;
+            if (w != q) loc_copy_group(nxt, w, nxt->sensors[q], nxt->onsets[q], nxt->len[q], nxt->alias[q]);
+            ++w;
+        }
+        L.kept = w;
+    }
+    __syncthreads();
+    c.nn = L.kept;
+}
+
+// One call of locate by the whole workgroup: Multilaterate3D.locate(sensor, onset, rec_audio), or with PLANAR the
+// 2-D Multilaterate.locate(sensor, onset), which reads no audio (counter, zero_pad and audio are then unused).
+// audio(t, col): sample t of the stream (start <= t < counter); zero_pad: a section that starts before sample 0 keeps
+// its length (rows there are what audio returns) instead of being cut at row 0.  Returns 1 when a position was
+// returned (xy: the Cartesian root in cm), else 0; `located` (LDS, may be NULL) receives the group as trilaterate left
+// it.  Every thread returns the same values.
+template <bool PLANAR, class Audio>
 __device__ inline int loc_feed(const LocTables& T, const LocView& v, int sensor, int64_t onset, int64_t counter,
                                bool zero_pad, Audio&& audio, double* xy, LocGroup* located) {
     LocLds& L = *v.L;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    ofp_locate_state* cur = &L.st[L.cur];
-    ofp_locate_state* nxt = &L.st[L.cur ^ 1];
+    const int tid = threadIdx.x;
+    LocCall c{&L.st[L.cur], &L.st[L.cur ^ 1], 0, L.st[L.cur].flags};
+    ofp_locate_state* cur = c.cur;
     const int n_cur = cur->n_groups;
-    int flags = cur->flags;
-    int nn = 0;          // len(new_groups)
     int prev_out = -1;   // where the previous iteration appended its (unextended) group object
     int found = 0;
     bool returned = false;
     __syncthreads();
     for (int gi = 0; gi < n_cur && !returned; ++gi) {
-        // an alias entry is the same Python object as the entry before it: it shares that entry's storage
+        // an alias entry is the same Python object as the entry before it: it shares that entry's storage.  (The
+        // planar routine changes nothing in place, so there the mark only records that two entries are one object.)
         const bool alias = gi > 0 && cur->alias[gi] != 0;
         const int src = alias ? gi - 1 : gi;
         const int my_prev = alias ? prev_out : -1;
@@ -201,376 +456,97 @@ __device__ inline int loc_feed(const LocTables& T, const LocView& v, int sensor,
         int s0 = cur->sensors[src][0];
         int64_t o0 = cur->onsets[src][0];
         int64_t lag = onset - o0;
-        if ((double)lag > L.mml[s0]) continue;
-        if (lag < 0) {  // an adjustment moved an onset behind this one: swap them
-            __syncthreads();
-            if (tid == 0) {
-                cur->sensors[src][0] = sensor;
-                cur->onsets[src][0] = onset;
-                if (my_prev >= 0) {
-                    nxt->sensors[my_prev][0] = sensor;
-                    nxt->onsets[my_prev][0] = onset;
+        if constexpr (!PLANAR) {  // planar: no skip at the top of the loop: a group past its largest lag is still tried
+            if ((double)lag > L.mml[s0]) continue;
+        }
+        if constexpr (!PLANAR) {  // planar: no swap: a negative lag goes to is_legal as it is
+            if (lag < 0) {  // an adjustment moved an onset behind this one: swap them
+                __syncthreads();
+                if (tid == 0) {
+                    cur->sensors[src][0] = sensor;
+                    cur->onsets[src][0] = onset;
+                    if (my_prev >= 0) {
+                        c.nxt->sensors[my_prev][0] = sensor;
+                        c.nxt->onsets[my_prev][0] = onset;
+                    }
                 }
+                const int ts = s0;
+                const int64_t to = o0;
+                s0 = sensor;
+                o0 = onset;
+                sensor = ts;
+                onset = to;
+                lag = -lag;
+                __syncthreads();
             }
-            const int ts = s0;
-            const int64_t to = o0;
-            s0 = sensor;
-            o0 = onset;
-            sensor = ts;
-            onset = to;
-            lag = -lag;
-            __syncthreads();
         }
         bool in_group = false;
         for (int k = 0; k < len; ++k) in_group = in_group || cur->sensors[src][k] == sensor;
         bool extended = false;
         if (!in_group) {
-            if (T.use_audio) {
-                // rec_audio[-i - 1:] of the two channels -> median 5 -> diff -> negative part -> abs
-                const int64_t want = counter - o0 + LOC_LOOKAROUND + 1;
-                int64_t start = counter - want;
-                if (!zero_pad && start < 0) start = 0;
-                const int64_t n64 = counter - start;
-                if (n64 < 3 || n64 > T.max_section) {
-                    flags |= OFP_LOCF_SECTION;
-                } else {
-                    const int n = (int)n64, m = n - 1;
-                    float mx = -INFINITY, my = -INFINITY;
-                    for (int i = tid; i < 2 * m; i += nt) {
-                        const int which = i >= m, t = which ? i - m : i;
-                        const int col = which ? sensor : s0;
-                        float md[2];
-                        for (int q = 0; q < 2; ++q) {
-                            float w[5];
-                            for (int k = 0; k < 5; ++k) {
-                                int64_t u = t + q + k - 2;
-                                if (u < 0) u = -u - 1;
-                                if (u >= n) u = 2 * (int64_t)n - u - 1;
-                                w[k] = audio(start + u, col);
-                            }
-                            md[q] = med5(w);
-                        }
-                        float d = md[1] - md[0];
-                        if (d >= 0.0f) d = 0.0f;
-                        d = fabsf(d);
-                        if (which) {
-                            v.ys[t] = d;
-                            my = fmaxf(my, d);
-                        } else {
-                            v.xs[t] = d;
-                            mx = fmaxf(mx, d);
-                        }
-                    }
-                    for (int o = 32; o > 0; o >>= 1) {
-                        mx = fmaxf(mx, __shfl_xor(mx, o));
-                        my = fmaxf(my, __shfl_xor(my, o));
-                    }
-                    if ((tid & 63) == 0) {
-                        L.red[0][tid >> 6] = mx;
-                        L.red[1][tid >> 6] = my;
-                    }
-                    __syncthreads();
-                    for (int w = 0; w < (nt + 63) / 64; ++w) {
-                        mx = w ? fmaxf(mx, L.red[0][w]) : L.red[0][0];
-                        my = w ? fmaxf(my, L.red[1][w]) : L.red[1][0];
-                    }
-                    // cross_correlation_lag(x, y, onsets=(first, new), d=0, onset_tolerance, normalization_cutoff)
-                    const int current = (int)(onset - o0);
-                    int lo, hi;
-                    py_slice(m - current - LOC_ONSET_TOL, m - current + LOC_ONSET_TOL, 2 * m - 1, &lo, &hi);
-                    if (hi > lo) {
-                        for (int j = lo + tid; j < hi; j += nt) L.cc[j - lo] = cc_entry(v.xs, v.ys, m, LOC_NORM_CUTOFF, j);
-                        __syncthreads();
-                        int am = 0;  // np.argmax: the first maximum
-                        float bv = L.cc[0];
-                        for (int j = 1; j < hi - lo; ++j) {
-                            if (L.cc[j] > bv) {
-                                bv = L.cc[j];
-                                am = j;
-                            }
-                        }
-                        const int new_lag = -(am - (current + LOC_ONSET_TOL));
-                        if (tid < XCORR_WAVE) {
-                            int64_t ca = 0, cb = 0;
-                            adjust_onset_wave(v.xs, v.ys, m, LOC_LOOKAROUND, current + LOC_LOOKAROUND, new_lag, mx, my, tid,
-                                              &ca, &cb);
-                            if (tid == 0) {
-                                L.mv[0] = (int32_t)ca;
-                                L.mv[1] = (int32_t)cb;
-                            }
-                        }
-                        __syncthreads();
-                        lag = new_lag;
-                        o0 += L.mv[0];
-                        onset += L.mv[1];
-                        if (tid == 0) {
-                            cur->onsets[src][0] = o0;
-                            if (my_prev >= 0) nxt->onsets[my_prev][0] = o0;
-                        }
-                    }
-                    __syncthreads();
-                }
+            if constexpr (!PLANAR) {  // planar: no cross-correlation step: locate takes no recording
+                if (T.use_audio)
+                    loc_cc_adjust(T, v, c, audio, counter, zero_pad, src, my_prev, s0, sensor, o0, onset, lag);
             }
             const double dl = (double)lag;
             const bool legal = (double)T.mn[s0 * T.S + sensor] < dl && dl < (double)T.mx[s0 * T.S + sensor];
             if (legal && len >= OFP_LOCS_MEMBERS) {
-                flags |= OFP_LOCF_MEMBERS;
+                c.flags |= OFP_LOCF_MEMBERS;
             } else if (legal) {
-                __syncthreads();
-                if (tid == 0) {
-                    L.ext.len = len + 1;
-                    for (int k = 0; k < len; ++k) {
-                        L.ext.sens[k] = cur->sensors[src][k];
-                        L.ext.on[k] = cur->onsets[src][k];
-                    }
-                    L.ext.sens[len] = sensor;
-                    L.ext.on[len] = onset;
-                }
-                __syncthreads();
+                loc_extend(L, cur, src, len, sensor, onset);
                 extended = true;
-                if (len + 1 == 3) {
-                    if (L.ext.sens[0] == L.ext.sens[1]) break;
-                    const int64_t k = first_legal(T.maps, T.S, T.side, L.ext.sens[0], L.ext.sens[1], L.ext.sens[2],
-                                                  (double)(L.ext.on[1] - L.ext.on[0]), (double)(L.ext.on[2] - L.ext.on[0]),
-                                                  1 * T.spc, v.smin);
-                    const int64_t ix = k < 0 ? 0 : k % T.side, iy = k < 0 ? 0 : k / T.side;
-                    if (!(ix == 0 && iy == 0)) {
-                        // trilaterate (:536-575), its reordering included
-                        if (tid == 0) {
-                            if (L.ext.sens[1] == 1) {
-                                L.ext.sens[1] = 0;
-                                L.ext.sens[2] = 1;
-                                const int64_t t = L.ext.on[1];
-                                L.ext.on[1] = L.ext.on[2];
-                                L.ext.on[2] = t;
-                            }
-                            L.found = 0;
-                        }
-                        __syncthreads();
-                        const int64_t da = L.ext.on[1] - L.ext.on[0], db = L.ext.on[2] - L.ext.on[0];
-                        if (T.plan.n_layers > 0) {  // self.model.call_np((d_a1, d_b1)) * 100: a float32 product
-                            if (tid < 64) {
-                                for (int i = tid; i < 16 * T.plan.st_a; i += 64) v.ta[i] = 0.0f;
-                                ofp_wave_lds_sync();
-                                if (tid == 0) {
-                                    v.ta[0] = (float)da;
-                                    v.ta[1] = (float)db;
-                                }
-                                ofp_wave_lds_sync();
-                                ofp_mlp_tile(T.plan, T.plan.params, v.ta, v.tb, tid, [&](int r, int col, float val) {
-                                    if (r == 0 && col < 2) L.res[col] = (double)(val * 100.0f);
-                                });
-                                if (tid == 0) L.found = 1;
-                            }
-                        } else if (tid == 0) {
-                            hybrj::Tdoa t;
-                            for (int q = 0; q < 3; ++q) {
-                                t.o[q] = T.sensors[3 * L.ext.sens[0] + q];
-                                t.a[q] = T.sensors[3 * L.ext.sens[1] + q];
-                                t.b[q] = T.sensors[3 * L.ext.sens[2] + q];
-                            }
-                            t.dda = (double)da / T.sr * T.c;
-                            t.ddb = (double)db / T.sr * T.c;
-                            const double guess[2] = {(double)ix - T.radius, (double)iy - T.radius};
-                            const hybrj::Result r = hybrj::solve(t, guess, T.xtol, T.maxfev);
-                            L.res[0] = r.x[0];
-                            L.res[1] = r.x[1];
-                            L.found = r.info == 1 ? 1 : 0;
-                        }
-                        __syncthreads();
-                        found = L.found;
-                        if (found) {  // remove_seed(new_groups, group)
-                            if (tid == 0) {
-                                int w = 0;
-                                for (int q = 0; q < nn; ++q) {
-                                    if (nxt->sensors[q][0] == L.ext.sens[0] && nxt->onsets[q][0] == L.ext.on[0]) continue;
-                                    if (w != q) loc_copy_group(nxt, w, nxt->sensors[q], nxt->onsets[q], nxt->len[q], nxt->alias[q]);
-                                    ++w;
-                                }
-                                L.kept = w;
-                            }
-                            __syncthreads();
-                            nn = L.kept;
+                if (len + 1 == 3) {  // (planar groups grow beyond three members; only this one is searched)
+                    if constexpr (!PLANAR) {  // planar: no break on equal first sensors: without a swap there are none
+                        if (L.ext.sens[0] == L.ext.sens[1]) break;
+                    }
+                    const LocCell cell = loc_cell(
+                        first_legal(T.maps, T.S, T.side, L.ext.sens[0], L.ext.sens[1], L.ext.sens[2],
+                                    (double)(L.ext.on[1] - L.ext.on[0]), (double)(L.ext.on[2] - L.ext.on[0]), 1 * T.spc,
+                                    v.smin),
+                        T.side);
+                    if (!cell.none()) {
+                        // planar: no reordering, and deltas formed as lag * c / sr (loc_solve, loc_tdoa)
+                        found = loc_solve<PLANAR>(T, v, cell);
+                        if (found) {
+                            if constexpr (!PLANAR) loc_remove_seed(L, c);  // planar: no remove_seed in its locate
                             xy[0] = L.res[0];
                             xy[1] = L.res[1];
                         }
                         if (located && tid == 0) *located = L.ext;
-                        returned = true;  // self.ongoing = new_groups; return res
+                        // self.ongoing = new_groups; return res -- in both kinds a found cell ends the call whether
+                        // or not the solve succeeds
+                        returned = true;
                         continue;
                     }
                 }
-                if (nn < OFP_LOCS_GROUPS) {
-                    if (tid == 0) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 0);
-                    ++nn;
-                } else {
-                    flags |= OFP_LOCF_GROUPS;
-                }
+                loc_append(c, L.ext.sens, L.ext.on, L.ext.len, 0);
             }
         }
-        // not past the largest possible lag: keep the group (an extended one a second time)
+        // not past the largest possible lag: keep the group (the test sees the extended group, which is appended a
+        // second time)
         if ((double)lag <= L.mml[s0]) {
-            if (nn < OFP_LOCS_GROUPS) {
-                if (tid == 0) {
-                    if (extended) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 1);
-                    else loc_copy_group(nxt, nn, cur->sensors[src], cur->onsets[src], len, my_prev >= 0 ? 1 : 0);
-                }
-                if (!extended) prev_out = nn;
-                ++nn;
-            } else {
-                flags |= OFP_LOCF_GROUPS;
-            }
+            if (extended) loc_append(c, L.ext.sens, L.ext.on, L.ext.len, 1);
+            else prev_out = loc_append(c, cur->sensors[src], cur->onsets[src], len, my_prev >= 0 ? 1 : 0);
         }
         __syncthreads();
     }
     if (!returned) {  // new_groups.append(([sensor_index], [onset_index]))
-        if (nn < OFP_LOCS_GROUPS) {
-            if (tid == 0) {
-                const int32_t s1[1] = {sensor};
-                const int64_t o1[1] = {onset};
-                loc_copy_group(nxt, nn, s1, o1, 1, 0);
-            }
-            ++nn;
-        } else {
-            flags |= OFP_LOCF_GROUPS;
-        }
+        const int32_t s1[1] = {sensor};
+        const int64_t o1[1] = {onset};
+        loc_append(c, s1, o1, 1, 0);
     }
-    __syncthreads();
-    if (tid == 0) {
-        nxt->n_groups = nn;
-        nxt->flags = flags;
-        L.cur ^= 1;
-    }
-    __syncthreads();
+    loc_publish(L, c);
     return found;
 }
 
-// ---- Multilaterate.locate (the planar locator) ---------------------------------------------------------------
-
-// One call of the 2-D Multilaterate.locate(sensor, onset) (reference multilateration.py:677-733) by the whole
-// workgroup, on the same state as loc_feed.  Where it differs from the 3-D routine: no skip of a group past its
-// largest lag at the top of the loop, no swap on a negative lag and no cross-correlation step (nothing is ever changed
-// in place, so an alias entry only records that two entries are one object); no break on equal first sensors and no
-// remove_seed; groups grow beyond three members and only the group that has just reached three is searched and
-// solved; a call whose search finds a cell ends with `ongoing` = new_groups whether or not the solve succeeds;
-// trilaterate keeps the sensors' order and forms its deltas as lag * c / sr.  Returns 1 when a position was returned
-// (xy: the Cartesian root in cm), else 0; `located` as in loc_feed.
-__device__ inline int loc_feed_2d(const LocTables& T, const LocView& v, int sensor, int64_t onset, double* xy,
-                                  LocGroup* located) {
-    LocLds& L = *v.L;
-    const int tid = threadIdx.x;
-    ofp_locate_state* cur = &L.st[L.cur];
-    ofp_locate_state* nxt = &L.st[L.cur ^ 1];
-    const int n_cur = cur->n_groups;
-    int flags = cur->flags;
-    int nn = 0;          // len(new_groups)
-    int prev_out = -1;   // where the previous iteration appended its (unextended) group object
-    int found = 0;
-    bool returned = false;
-    __syncthreads();
-    for (int gi = 0; gi < n_cur && !returned; ++gi) {
-        const bool alias = gi > 0 && cur->alias[gi] != 0;
-        const int src = alias ? gi - 1 : gi;
-        const int my_prev = alias ? prev_out : -1;
-        prev_out = -1;
-        const int len = cur->len[src];
-        const int s0 = cur->sensors[src][0];
-        const int64_t lag = onset - cur->onsets[src][0];
-        bool in_group = false;
-        for (int k = 0; k < len; ++k) in_group = in_group || cur->sensors[src][k] == sensor;
-        bool extended = false;
-        if (!in_group) {
-            const double dl = (double)lag;
-            const bool legal = (double)T.mn[s0 * T.S + sensor] < dl && dl < (double)T.mx[s0 * T.S + sensor];
-            if (legal && len >= OFP_LOCS_MEMBERS) {
-                flags |= OFP_LOCF_MEMBERS;
-            } else if (legal) {
-                __syncthreads();
-                if (tid == 0) {
-                    L.ext.len = len + 1;
-                    for (int k = 0; k < len; ++k) {
-                        L.ext.sens[k] = cur->sensors[src][k];
-                        L.ext.on[k] = cur->onsets[src][k];
-                    }
-                    L.ext.sens[len] = sensor;
-                    L.ext.on[len] = onset;
-                }
-                __syncthreads();
-                extended = true;
-                if (len + 1 == 3) {
-                    const int64_t da = L.ext.on[1] - L.ext.on[0], db = L.ext.on[2] - L.ext.on[0];
-                    const int64_t k = first_legal(T.maps, T.S, T.side, L.ext.sens[0], L.ext.sens[1], L.ext.sens[2],
-                                                  (double)da, (double)db, 1 * T.spc, v.smin);
-                    const int64_t ix = k < 0 ? 0 : k % T.side, iy = k < 0 ? 0 : k / T.side;
-                    if (!(ix == 0 && iy == 0)) {
-                        if (tid == 0) {  // trilaterate (:714-733)
-                            hybrj::Tdoa t;
-                            for (int q = 0; q < 3; ++q) {
-                                t.o[q] = T.sensors[3 * L.ext.sens[0] + q];
-                                t.a[q] = T.sensors[3 * L.ext.sens[1] + q];
-                                t.b[q] = T.sensors[3 * L.ext.sens[2] + q];
-                            }
-                            t.dda = (double)da * T.c / T.sr;
-                            t.ddb = (double)db * T.c / T.sr;
-                            const double guess[2] = {(double)ix - T.radius, (double)iy - T.radius};
-                            const hybrj::Result r = hybrj::solve(t, guess, T.xtol, T.maxfev);
-                            L.res[0] = r.x[0];
-                            L.res[1] = r.x[1];
-                            L.found = r.info == 1 ? 1 : 0;
-                        }
-                        __syncthreads();
-                        found = L.found;
-                        if (found) {
-                            xy[0] = L.res[0];
-                            xy[1] = L.res[1];
-                        }
-                        if (located && tid == 0) *located = L.ext;
-                        returned = true;  // self.ongoing = new_groups; return res
-                        continue;
-                    }
-                }
-                if (nn < OFP_LOCS_GROUPS) {
-                    if (tid == 0) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 0);
-                    ++nn;
-                } else {
-                    flags |= OFP_LOCF_GROUPS;
-                }
-            }
-        }
-        // the test sees the extended group: one that passed is_legal is appended a second time
-        if ((double)lag <= L.mml[s0]) {
-            if (nn < OFP_LOCS_GROUPS) {
-                if (tid == 0) {
-                    if (extended) loc_copy_group(nxt, nn, L.ext.sens, L.ext.on, L.ext.len, 1);
-                    else loc_copy_group(nxt, nn, cur->sensors[src], cur->onsets[src], len, my_prev >= 0 ? 1 : 0);
-                }
-                if (!extended) prev_out = nn;
-                ++nn;
-            } else {
-                flags |= OFP_LOCF_GROUPS;
-            }
-        }
-        __syncthreads();
-    }
-    if (!returned) {  // new_groups.append(([sensor_index], [onset_index]))
-        if (nn < OFP_LOCS_GROUPS) {
-            if (tid == 0) {
-                const int32_t s1[1] = {sensor};
-                const int64_t o1[1] = {onset};
-                loc_copy_group(nxt, nn, s1, o1, 1, 0);
-            }
-            ++nn;
-        } else {
-            flags |= OFP_LOCF_GROUPS;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        nxt->n_groups = nn;
-        nxt->flags = flags;
-        L.cur ^= 1;
-    }
-    __syncthreads();
-    return found;
+// One call of locate of the tables' kind: the 3-D or the planar instantiation.  T.planar is the same for every thread
+// and every call of a launch.
+template <class Audio>
+__device__ __forceinline__ int loc_feed_kind(const LocTables& T, const LocView& v, int sensor, int64_t onset,
+                                             int64_t counter, bool zero_pad, Audio&& audio, double* xy,
+                                             LocGroup* located) {
+    return T.planar ? loc_feed<true>(T, v, sensor, onset, counter, zero_pad, audio, xy, located)
+                    : loc_feed<false>(T, v, sensor, onset, counter, zero_pad, audio, xy, located);
 }
 
 }  // namespace ofp

@@ -25,7 +25,8 @@ Same names, arguments and returns as the reference for:
 ``Multilaterate3D.locate`` also exists as device code (csrc/ofp_locate_dev.h) on a device-resident copy of ``ongoing``:
 ``Multilaterate3D.locate_stream_device`` replays a stream of calls in one launch (``ofp_locate_stream``), and
 ``realtime.HopSession(locator=...)`` runs it inside the hop's graph.  The 2-D ``Multilaterate`` has the same three
-device forms (``loc_feed_2d``; ``ofp_locate_stream_2d``, ``ofp_locate_groups_2d``, ``ofp_hop_set_locator_2d``).
+device forms (the planar instantiation of the same ``loc_feed``; ``ofp_locate_stream_2d``, ``ofp_locate_groups_2d``,
+``ofp_hop_set_locator_2d``).
 
 Batched, device-resident additions: ``locate_groups_device`` locates every onset group ``group_onsets_device``
 found, in one pass without host synchronisation; ``find_lags_device``, ``MultilateratePaired.locate_cc_device`` /
@@ -309,9 +310,88 @@ def check_locate_flags(flags, what):
         raise _lib.OnsetFPError(f"{what}: a call was refused (sensor index or counter out of range; flags {flags})")
 
 
+# ---- what Multilaterate3D and Multilaterate share -------------------------------------------------------------
+
+class _LagMapLocator:
+    """The lag-map tables of a locator on its device, the two legality tests on them, and the device forms of
+    ``locate``.  A subclass sets radius, sensor_locs, medium, sr and samples_per_cm, then calls ``_build_tables``."""
+
+    def _speed(self):
+        """The speed of sound in cm/s, as the class's ``trilaterate`` has it."""
+        raise NotImplementedError
+
+    def _build_tables(self, grid, drum_diameter, device):
+        """The lag maps (1 cm grid, 2 cm tolerance at the edge, values below -samples_per_cm dropped) by
+        ``ofp_lag_maps``, kept on `device`, and the reference's host views of them: ``lag_maps``, ``min_lags``,
+        ``max_lags``, ``max_max_lags``.  grid: _grid_3d or _grid_2d.  Ends with an empty ``ongoing``."""
+        sensors = _sensor_array(self.sensor_locs)  # [S, 3]; z = 0 for planar sensors
+        self.device = _dev(device)
+        _lib.require_gpu(self.device.index or 0)
+        S = len(sensors)
+        r, mask_r2 = grid(drum_diameter, 1, 2)
+        self.grid_radius = r
+        self.maps_dev, self.min_dev, self.max_dev = lag_maps_device(
+            sensors, r, self._speed(), self.sr, mask_r2, floor=-self.samples_per_cm * 1, device=self.device)
+        self.sensors_dev = torch.from_numpy(sensors).to(self.device)
+        maps = self.maps_dev.cpu().numpy()
+        mn, mx = self.min_dev.cpu().numpy(), self.max_dev.cpu().numpy()
+        self.lag_maps = [{j: maps[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.max_lags = [{j: mx[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.min_lags = [{j: mn[i, j] for j in range(S) if j != i} for i in range(S)]
+        self.max_max_lags = [np.nanmax(list(d.values())) for d in self.max_lags]
+        self.ongoing = []
+
+    def is_legal(self, first_sensor: int, later_sensor: int, lag: int) -> bool:
+        """The lag lies strictly between the extremes of the pair's lag map."""
+        return self.min_lags[first_sensor][later_sensor] < lag < self.max_lags[first_sensor][later_sensor]
+
+    def is_legal_3d(self, group, tolerance=1):
+        """multilateration.py:413-426 and :663-676: (col, row) of the first map cell consistent with both lags of the
+        group within `tolerance` cm, (0, 0) when there is none."""
+        sensors, onsets = group[0], group[1]
+        s = torch.tensor([[int(v) for v in sensors[:3]]], dtype=torch.int32, device=self.device)
+        o = torch.tensor([[int(v) for v in onsets[:3]]], dtype=torch.int64, device=self.device)
+        idx = legal_cells_device(self.maps_dev, s, o, tolerance * self.samples_per_cm).cpu().numpy()[0]
+        return int(idx[0]), int(idx[1])
+
+    def _locator_struct(self, xtol, maxfev, use_audio=0, max_section=0, mlp=None):
+        """The ofp_hop_locator of this object's device tables (they must outlive every call that uses it)."""
+        loc = _lib.HopLocator()
+        loc.d_sensors, loc.S = self.sensors_dev.data_ptr(), self.sensors_dev.shape[0]
+        loc.d_maps, loc.d_min, loc.d_max = self.maps_dev.data_ptr(), self.min_dev.data_ptr(), self.max_dev.data_ptr()
+        loc.r = self.grid_radius
+        loc.samples_per_cm, loc.sr, loc.c, loc.radius = float(self.samples_per_cm), float(self.sr), \
+            float(self._speed()), float(self.radius)
+        loc.xtol, loc.maxfev = float(xtol), int(maxfev)
+        loc.mlp = mlp.handle if mlp is not None else None
+        loc.use_audio, loc.max_section = int(bool(use_audio)), int(max_section)
+        return loc
+
+    def _replay(self, entry, loc, columns, recording=()):
+        """One launch of a stream entry point (`entry`: its name) with the ofp_hop_locator `loc`, from an empty state.
+        columns: the per-call arrays by name -- sensors first, int32; the others int64 -- in the entry point's order;
+        recording: what it takes between the call count and the state.  Returns (found bool [K], xy float64 [K, 2]
+        with NaN where nothing was returned, ongoing as ``ongoing_list`` gives it); the sticky flags raise."""
+        cols = [np.ascontiguousarray(a, dtype=np.int64 if k else np.int32).reshape(-1)
+                for k, a in enumerate(columns.values())]
+        K = len(cols[0])
+        if any(len(a) != K for a in cols):
+            raise ValueError("locate_stream_device: " + ", ".join(f"{len(a)} {n}" for a, n in zip(cols, columns)))
+        dev = self.device
+        cols = [torch.from_numpy(a).to(dev) for a in cols]
+        state = torch.zeros(ctypes.sizeof(_lib.LocateState), dtype=torch.uint8, device=dev)
+        found = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+        xy = torch.full((max(K, 1), 2), float("nan"), dtype=torch.float64, device=dev)
+        check(getattr(_lib.lib(), entry)(ctypes.byref(loc), *(a.data_ptr() for a in cols), K, *recording,
+                                         state.data_ptr(), found.data_ptr(), xy.data_ptr(), _stream(dev)), entry)
+        st = _lib.LocateState.from_buffer_copy(state.cpu().numpy().tobytes())
+        check_locate_flags(st.flags, "locate_stream_device")
+        return found.cpu().numpy()[:K].astype(bool), xy.cpu().numpy()[:K], ongoing_list(st)
+
+
 # ---- Multilaterate3D ----------------------------------------------------------------------------------------
 
-class Multilaterate3D:
+class Multilaterate3D(_LagMapLocator):
     def __init__(self, sensor_locations, drum_diameter: float = DIAMETER, medium: str = "drumhead", sr: int = 44100,
                  c: Optional[float] = None, model=None, device=0):
         """multilateration.py:320-387.  sensor_locations: (relative radius, angle, elevation) per sensor; c in m/s
@@ -327,35 +407,10 @@ class Multilaterate3D:
         self.medium = medium
         self.sr = sr
         self.samples_per_cm = sr / self.c
-        sensors = _sensor_array(self.sensor_locs)
-        self.device = _dev(device)
-        _lib.require_gpu(self.device.index or 0)
-        S = len(sensors)
-        r, mask_r2 = _grid_3d(drum_diameter, 1, 2)
-        self.grid_radius = r
-        self.maps_dev, self.min_dev, self.max_dev = lag_maps_device(
-            sensors, r, self.c, sr, mask_r2, floor=-self.samples_per_cm * 1, device=self.device)
-        self.sensors_dev = torch.from_numpy(sensors).to(self.device)
-        maps = self.maps_dev.cpu().numpy()
-        mn, mx = self.min_dev.cpu().numpy(), self.max_dev.cpu().numpy()
-        self.lag_maps = [{j: maps[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.max_lags = [{j: mx[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.min_lags = [{j: mn[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.max_max_lags = [np.nanmax(list(d.values())) for d in self.max_lags]
-        self.ongoing = []
+        self._build_tables(_grid_3d, drum_diameter, device)
 
-    def is_legal(self, first_sensor: int, later_sensor: int, lag: int) -> bool:
-        """The lag lies strictly between the extremes of the pair's lag map."""
-        return self.min_lags[first_sensor][later_sensor] < lag < self.max_lags[first_sensor][later_sensor]
-
-    def is_legal_3d(self, group, tolerance=1):
-        """multilateration.py:413-426: (col, row) of the first map cell consistent with both lags of the group
-        within `tolerance` cm, (0, 0) when there is none."""
-        sensors, onsets = group[0], group[1]
-        s = torch.tensor([[int(v) for v in sensors[:3]]], dtype=torch.int32, device=self.device)
-        o = torch.tensor([[int(v) for v in onsets[:3]]], dtype=torch.int64, device=self.device)
-        idx = legal_cells_device(self.maps_dev, s, o, tolerance * self.samples_per_cm).cpu().numpy()[0]
-        return int(idx[0]), int(idx[1])
+    def _speed(self):
+        return self.c
 
     def trilaterate(self, group, initial_guess):
         """multilateration.py:536-565 (reorders `group` in place when its second sensor is sensor 1)."""
@@ -445,16 +500,7 @@ class Multilaterate3D:
 
     def locator_struct(self, use_audio, max_section, mlp=None, xtol=XTOL, maxfev=MAXFEV):
         """The ofp_hop_locator of this object's device tables (they must outlive every call that uses it)."""
-        loc = _lib.HopLocator()
-        loc.d_sensors, loc.S = self.sensors_dev.data_ptr(), self.sensors_dev.shape[0]
-        loc.d_maps, loc.d_min, loc.d_max = self.maps_dev.data_ptr(), self.min_dev.data_ptr(), self.max_dev.data_ptr()
-        loc.r = self.grid_radius
-        loc.samples_per_cm, loc.sr, loc.c, loc.radius = float(self.samples_per_cm), float(self.sr), float(self.c), \
-            float(self.radius)
-        loc.xtol, loc.maxfev = float(xtol), int(maxfev)
-        loc.mlp = mlp.handle if mlp is not None else None
-        loc.use_audio, loc.max_section = int(bool(use_audio)), int(max_section)
-        return loc
+        return self._locator_struct(xtol, maxfev, use_audio, max_section, mlp)
 
     def locate_stream_device(self, sensors, onsets, counters, audio=None):
         """``locate`` for a whole stream of calls in ONE launch (``ofp_locate_stream``): call k feeds
@@ -464,35 +510,19 @@ class Multilaterate3D:
         the final state as the reference's list of ([sensors], [onsets])).  Raises OnsetFPError when the state
         overflowed (64 groups of 8 members), a section was longer than LOCATE_MAX_SECTION rows, or a call was refused
         (the kernel checks every call: sensor outside 0..S-1, counter outside the recording)."""
-        sens = np.ascontiguousarray(sensors, dtype=np.int32).reshape(-1)
-        ons = np.ascontiguousarray(onsets, dtype=np.int64).reshape(-1)
-        cnt = np.ascontiguousarray(counters, dtype=np.int64).reshape(-1)
-        K = len(sens)
-        if not (len(ons) == K and len(cnt) == K):
-            raise ValueError(f"locate_stream_device: {K} sensors, {len(ons)} onsets, {len(cnt)} counters")
         S = self.sensors_dev.shape[0]
         mlp = self._device_model("locate_stream_device")
-        dev = self.device
         ad, n_rows, n_ch, max_section = None, 0, 0, 0
         if audio is not None:
             ad = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
             if ad.dim() != 2 or ad.shape[1] < S:
                 raise ValueError(f"locate_stream_device: audio must be [N, C >= {S}], got {tuple(ad.shape)}")
-            ad = ad.to(dev, torch.float32).contiguous()
+            ad = ad.to(self.device, torch.float32).contiguous()
             n_rows, n_ch = ad.shape
             max_section = LOCATE_MAX_SECTION  # the counters are the caller's: any section the kernel can hold
         loc = self.locator_struct(audio is not None, max_section, mlp)
-        to = lambda a: torch.from_numpy(a).to(dev)
-        sd, od, cd = to(sens), to(ons), to(cnt)
-        state = torch.zeros(ctypes.sizeof(_lib.LocateState), dtype=torch.uint8, device=dev)
-        found = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
-        xy = torch.full((max(K, 1), 2), float("nan"), dtype=torch.float64, device=dev)
-        check(_lib.lib().ofp_locate_stream(ctypes.byref(loc), sd.data_ptr(), od.data_ptr(), cd.data_ptr(), K,
-                                           _ptr(ad), n_rows, n_ch, state.data_ptr(), found.data_ptr(), xy.data_ptr(),
-                                           _stream(dev)), "ofp_locate_stream")
-        st = _lib.LocateState.from_buffer_copy(state.cpu().numpy().tobytes())
-        check_locate_flags(st.flags, "locate_stream_device")
-        return found.cpu().numpy()[:K].astype(bool), xy.cpu().numpy()[:K], ongoing_list(st)
+        return self._replay("ofp_locate_stream", loc, dict(sensors=sensors, onsets=onsets, counters=counters),
+                            (_ptr(ad), n_rows, n_ch))
 
 
 # ---- batched offline locator --------------------------------------------------------------------------------
@@ -540,20 +570,14 @@ def locate_groups_device(groups, n_groups, m, xtol=XTOL, maxfev=MAXFEV, return_g
     status = torch.empty((n_clips, cap), dtype=torch.int32, device=dev)
     guess = torch.empty((n_clips, cap, 2), dtype=torch.float64, device=dev) if return_guess else None
     ws = torch.empty(max(int(L.ofp_locate_workspace_bytes(rows)), 16), dtype=torch.uint8, device=dev)
-    if planar:
-        check(L.ofp_locate_groups_2d(groups.data_ptr(), n_clips, cap, C, _ptr(n_groups), m.sensors_dev.data_ptr(),
-                                     m.sensors_dev.shape[0], m.maps_dev.data_ptr(), m.min_dev.data_ptr(),
-                                     m.max_dev.data_ptr(), m.grid_radius, float(m.samples_per_cm), float(m.sr),
-                                     float(speed_of_sound(100, medium=m.medium)), float(m.radius), float(xtol),
-                                     int(maxfev), xy.data_ptr(), status.data_ptr(), _ptr(guess), ws.data_ptr(),
-                                     ws.numel(), _stream(dev)), "ofp_locate_groups_2d")
-        return (xy, status, guess) if return_guess else (xy, status)
-    check(L.ofp_locate_groups(groups.data_ptr(), n_clips, cap, C, _ptr(n_groups), m.sensors_dev.data_ptr(),
-                              m.sensors_dev.shape[0], m.maps_dev.data_ptr(), m.min_dev.data_ptr(), m.max_dev.data_ptr(),
-                              m.grid_radius, float(m.samples_per_cm), float(m.sr), float(m.c), float(m.radius),
-                              float(xtol), int(maxfev), mlp.handle if mlp is not None else None, xy.data_ptr(),
-                              status.data_ptr(), _ptr(guess), ws.data_ptr(), ws.numel(), _stream(dev)),
-          "ofp_locate_groups")
+    entry, net = "ofp_locate_groups", (mlp.handle if mlp is not None else None,)
+    if planar:  # the same arguments without the network
+        entry, net = "ofp_locate_groups_2d", ()
+    check(getattr(L, entry)(groups.data_ptr(), n_clips, cap, C, _ptr(n_groups), m.sensors_dev.data_ptr(),
+                            m.sensors_dev.shape[0], m.maps_dev.data_ptr(), m.min_dev.data_ptr(), m.max_dev.data_ptr(),
+                            m.grid_radius, float(m.samples_per_cm), float(m.sr), float(m._speed()), float(m.radius),
+                            float(xtol), int(maxfev), *net, xy.data_ptr(), status.data_ptr(), _ptr(guess),
+                            ws.data_ptr(), ws.numel(), _stream(dev)), entry)
     return (xy, status, guess) if return_guess else (xy, status)
 
 
@@ -638,7 +662,7 @@ def find_lag_multi(a, b, top_n: int = 3, device=0):
 
 # ---- Multilaterate (2-D) ------------------------------------------------------------------------------------
 
-class Multilaterate:
+class Multilaterate(_LagMapLocator):
     def __init__(self, sensor_locations, drum_diameter: float = DIAMETER, medium: str = "drumhead", sr: int = 44100,
                  device=0):
         """multilateration.py:578-645.  sensor_locations: (relative radius, angle) per sensor.  The lag maps (1 cm
@@ -650,36 +674,10 @@ class Multilaterate:
         self.medium = medium
         self.sr = sr
         self.samples_per_cm = sr / speed_of_sound(100, medium=medium)
-        sensors = _sensor_array(self.sensor_locs)
-        self.device = _dev(device)
-        _lib.require_gpu(self.device.index or 0)
-        S = len(sensors)
-        r, mask_r2 = _grid_2d(drum_diameter, 1, 2)
-        self.grid_radius = r
-        self.maps_dev, self.min_dev, self.max_dev = lag_maps_device(
-            sensors, r, speed_of_sound(100, medium=medium), sr, mask_r2, floor=-self.samples_per_cm * 1,
-            device=self.device)
-        self.sensors_dev = torch.from_numpy(sensors).to(self.device)  # [S, 3] with z = 0
-        maps = self.maps_dev.cpu().numpy()
-        mn, mx = self.min_dev.cpu().numpy(), self.max_dev.cpu().numpy()
-        self.lag_maps = [{j: maps[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.max_lags = [{j: mx[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.min_lags = [{j: mn[i, j] for j in range(S) if j != i} for i in range(S)]
-        self.max_max_lags = [np.nanmax(list(d.values())) for d in self.max_lags]
-        self.ongoing = []
+        self._build_tables(_grid_2d, drum_diameter, device)
 
-    def is_legal(self, first_sensor: int, later_sensor: int, lag: int) -> bool:
-        """The lag lies strictly between the extremes of the pair's lag map."""
-        return self.min_lags[first_sensor][later_sensor] < lag < self.max_lags[first_sensor][later_sensor]
-
-    def is_legal_3d(self, group, tolerance=1):
-        """multilateration.py:663-676: (col, row) of the first map cell consistent with both lags of the group
-        within `tolerance` cm, (0, 0) when there is none."""
-        sensors, onsets = group[0], group[1]
-        s = torch.tensor([[int(v) for v in sensors[:3]]], dtype=torch.int32, device=self.device)
-        o = torch.tensor([[int(v) for v in onsets[:3]]], dtype=torch.int64, device=self.device)
-        idx = legal_cells_device(self.maps_dev, s, o, tolerance * self.samples_per_cm).cpu().numpy()[0]
-        return int(idx[0]), int(idx[1])
+    def _speed(self):
+        return speed_of_sound(100, medium=self.medium)
 
     def locate(self, sensor_index: int, onset_index: int):
         """multilateration.py:678-711: feed one onset; returns (radius / drum radius, angle) of the hit it
@@ -722,16 +720,7 @@ class Multilaterate:
     def locator_struct(self, xtol=XTOL, maxfev=MAXFEV):
         """The ofp_hop_locator of this object's device tables (they must outlive every call that uses it), for the
         planar entry points: no cross-correlation step (use_audio 0, max_section 0) and no network."""
-        loc = _lib.HopLocator()
-        loc.d_sensors, loc.S = self.sensors_dev.data_ptr(), self.sensors_dev.shape[0]
-        loc.d_maps, loc.d_min, loc.d_max = self.maps_dev.data_ptr(), self.min_dev.data_ptr(), self.max_dev.data_ptr()
-        loc.r = self.grid_radius
-        loc.samples_per_cm, loc.sr, loc.radius = float(self.samples_per_cm), float(self.sr), float(self.radius)
-        loc.c = float(speed_of_sound(100, medium=self.medium))
-        loc.xtol, loc.maxfev = float(xtol), int(maxfev)
-        loc.mlp = None
-        loc.use_audio, loc.max_section = 0, 0
-        return loc
+        return self._locator_struct(xtol, maxfev)
 
     def locate_stream_device(self, sensors, onsets):
         """``locate`` for a whole stream of calls in ONE launch (``ofp_locate_stream_2d``): call k feeds
@@ -741,27 +730,12 @@ class Multilaterate:
         Cartesian root; ``cartesian_to_polar`` is applied here, on the host, as ``trilaterate`` applies it.  Raises
         OnsetFPError when the state overflowed (64 groups of 8 members) or a call was refused (sensor outside
         0..S-1)."""
-        sens = np.ascontiguousarray(sensors, dtype=np.int32).reshape(-1)
-        ons = np.ascontiguousarray(onsets, dtype=np.int64).reshape(-1)
-        K = len(sens)
-        if len(ons) != K:
-            raise ValueError(f"locate_stream_device: {K} sensors, {len(ons)} onsets")
-        dev = self.device
-        loc = self.locator_struct()
-        sd, od = torch.from_numpy(sens).to(dev), torch.from_numpy(ons).to(dev)
-        state = torch.zeros(ctypes.sizeof(_lib.LocateState), dtype=torch.uint8, device=dev)
-        found = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
-        xy = torch.full((max(K, 1), 2), float("nan"), dtype=torch.float64, device=dev)
-        check(_lib.lib().ofp_locate_stream_2d(ctypes.byref(loc), sd.data_ptr(), od.data_ptr(), K, state.data_ptr(),
-                                              found.data_ptr(), xy.data_ptr(), _stream(dev)), "ofp_locate_stream_2d")
-        st = _lib.LocateState.from_buffer_copy(state.cpu().numpy().tobytes())
-        check_locate_flags(st.flags, "locate_stream_device")
-        found = found.cpu().numpy()[:K].astype(bool)
-        xy = xy.cpu().numpy()[:K]
-        rphi = np.full((K, 2), np.nan, dtype=np.float64)
+        found, xy, ongoing = self._replay("ofp_locate_stream_2d", self.locator_struct(),
+                                          dict(sensors=sensors, onsets=onsets))
+        rphi = np.full((len(found), 2), np.nan, dtype=np.float64)
         for k in np.flatnonzero(found):
             rphi[k] = cartesian_to_polar(np.float64(xy[k, 0]), np.float64(xy[k, 1]), self.radius)
-        return found, rphi, ongoing_list(st)
+        return found, rphi, ongoing
 
 
 # ---- MultilateratePaired ------------------------------------------------------------------------------------

@@ -147,14 +147,13 @@ class HopSession:
         if locator is not None:
             try:
                 if self._planar:
-                    loc = locator.locator_struct()
-                    with torch.cuda.device(self.device):
-                        check(L.ofp_hop_set_locator_2d(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator_2d")
+                    entry, loc = "ofp_hop_set_locator_2d", locator.locator_struct()
                 else:
                     self._loc_mlp = locator._device_model("HopSession")  # kept alive with the session
-                    loc = locator.locator_struct(locate_with_audio, self._max_section, self._loc_mlp)
-                    with torch.cuda.device(self.device):
-                        check(L.ofp_hop_set_locator(self.handle, ctypes.byref(loc)), "ofp_hop_set_locator")
+                    entry, loc = "ofp_hop_set_locator", locator.locator_struct(locate_with_audio, self._max_section,
+                                                                               self._loc_mlp)
+                with torch.cuda.device(self.device):
+                    check(getattr(L, entry)(self.handle, ctypes.byref(loc)), entry)
             except Exception:
                 self.close()
                 raise

@@ -121,6 +121,27 @@ def trace_hits(name):
     return rows
 
 
+SWAPPED_ROWS = 40
+
+
+@functools.lru_cache(maxsize=None)
+def swapped_stream(name="m3"):
+    """(sensors int32 [3 n], onsets int64 [3 n]) for the first n = SWAPPED_ROWS full rows of ``trace_hits``: each row
+    is fed with its two earliest arrivals exchanged, then the third, so a row's second call lies before the onset
+    its first call seeded a group with (or on it, where the two arrive in one sample).  The golden traces never go
+    back in time; this stream is where the planar routine has to take a negative lag as it is (the 3-D one would
+    swap)."""
+    full = [r for r in trace_hits(name) if (r >= 0).all()][:SWAPPED_ROWS]
+    assert len(full) == SWAPPED_ROWS
+    sens, ons = [], []
+    for r in full:
+        order = [int(k) for k in np.argsort(r, kind="stable")[:3]]
+        for k in (order[1], order[0], order[2]):
+            sens.append(k)
+            ons.append(int(r[k]))
+    return np.array(sens, np.int32), np.array(ons, np.int64)
+
+
 def no_cell_lags(model, o, a, b):
     """Two positive lags (so that `o` stays the earliest), each legal for its pair, that meet in no cell of the grid."""
     for la in range(int(model.mx[o, a]) - 1, 0, -7):

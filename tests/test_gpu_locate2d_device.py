@@ -1,8 +1,8 @@
-"""GPU parity of the planar locator's device forms (csrc/ofp_locate_dev.h: loc_feed_2d): the replay entry
-``Multilaterate.locate_stream_device`` against the reference's trace (golden g23, m2d/m3 and m2d/m4air) and the host
-state machine call for call, ``locate_groups_device`` with a ``Multilaterate`` against a per-row replay of the host
-functions, and ``realtime.HopSession(locator=Multilaterate)`` -- both graph forms, and in a group next to a 3-D
-member -- against detect_hits replayed on the host.
+"""GPU parity of the planar locator's device forms (csrc/ofp_locate_dev.h: the planar instantiation of loc_feed): the
+replay entry ``Multilaterate.locate_stream_device`` against the reference's trace (golden g23, m2d/m3 and m2d/m4air),
+the host state machine call for call and a stream with negative lags, ``locate_groups_device`` with a
+``Multilaterate`` against a per-row replay of the host functions, and ``realtime.HopSession(locator=Multilaterate)``
+-- both graph forms, and in a group next to a 3-D member -- against detect_hits replayed on the host.
 
 Tolerances: ROOT_TOL for roots and polar tuples against the golden or a separately launched solve, bit equality where
 both sides run the same device arithmetic, integers exact."""
@@ -72,6 +72,23 @@ def test_state_equals_the_host_state_machine_at_every_prefix(name):
         assert shared(ongoing) == host[kp][1], kp
         aliased += len(shared(ongoing))
     assert aliased >= 1
+
+
+def test_a_negative_lag_is_taken_as_it_is_never_swapped():
+    """Each row's two earliest arrivals exchanged (lc.swapped_stream): the planar routine tests the negative lag with
+    is_legal and extends the group in the order fed, where the 3-D routine would swap the two onsets first.  Expected
+    values: the host ``Multilaterate.locate``, call for call on a fresh object."""
+    sens, ons = lc.swapped_stream("m3")
+    m_dev, m = m2d("m3"), m2d("m3")
+    want = [m.locate(int(s), int(o)) for s, o in zip(sens, ons)]
+    hit = np.array([w is not None for w in want])
+    found, rphi, ongoing = m_dev.locate_stream_device(sens, ons)
+    assert np.array_equal(found, hit), np.flatnonzero(found != hit)[:10]
+    assert found.sum() >= 1
+    assert plain(ongoing) == plain(m.ongoing)  # duplicates included
+    assert shared(ongoing) == shared(m.ongoing)
+    assert np.abs(rphi[found] - np.array([w for w in want if w is not None], np.float64)).max() < ROOT_TOL
+    assert np.isnan(rphi[~found]).all()
 
 
 # ---- 3: batched rows ----------------------------------------------------------------------------------------

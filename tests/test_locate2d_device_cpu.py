@@ -115,6 +115,21 @@ def test_group_rows_hold_every_kind_of_row(name):
         assert kinds == {"few", "illegal", "no cell", "cell"} if clip == 0 else "cell" in kinds
 
 
+def test_swapped_stream_extends_groups_by_negative_lags_and_locates():
+    sens, ons = lc.swapped_stream("m3")
+    assert len(sens) == len(ons) == 3 * lc.SWAPPED_ROWS
+    model = lc.HostModel("m3")
+    negative = located = 0
+    for s, o in zip(sens, ons):
+        s, o = int(s), int(o)
+        # what locate is about to do: a group this sensor is not in, a negative lag that passes is_legal
+        negative += any(o < g[1][0] and s not in g[0] and model.is_legal(g[0][0], s, o - g[1][0])
+                        for g in model.ongoing)
+        located += model.locate(s, o) == "located"
+    assert negative >= 1  # a merged state machine that swapped here, as the 3-D routine does, would differ
+    assert located >= 1
+
+
 def test_hop_stream_locates_and_carries_onsets_that_complete_nothing():
     plan = lc.hop_plan("m3")
     assert sum(res == "located" for _, res in plan) >= 5
