@@ -1031,7 +1031,7 @@ int ofp_autocorr_softmax_backward(const float* d_f, const float* d_p, const floa
 int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const float* d_lr, int32_t first,
                  float momentum, float weight_decay, void* stream);
 
-/* ---- the trainers' random stream: dropout and per-epoch shift augmentation (csrc/ofp_train_random.h) ---------------
+/* ---- the trainers' random stream: dropout, per-epoch shift and stretch augmentation (csrc/ofp_train_random.h) ------
  * Both trainers can regularise as the reference's train.py does: a dropout in front of the Linear head, and training
  *   windows cut anew every epoch, each shifted by up to +-max_shift samples.  torch's random stream cannot be
  *   reproduced; this is a documented stream of the library's own, and the user opts in by naming a seed.
@@ -1049,11 +1049,25 @@ int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const fl
  *   to match by the caller) from the interleaved audio [audio_len][audio_channels]; d_starts [n_onsets] int64 is the
  *   hit's minimum onset less pre_samples.  The caller rules out windows that leave the audio (such rows read as 0).
  *   n_extractions = 0: no window source, d_x is used as it is.
+ * Site 2, stretches (the reference's StretchFrameExtractor, which its train.py prepares and leaves commented out as
+ *   too slow): index = item.  With the span S = int(frame_length * max_stretch) the reference draws randint(1, S) *
+ *   choice((-1, 1)), uniform on {-(S-1), ..., -1, 1, ..., S-1} and never 0; S = 1 raises inside randint.  Here v =
+ *   (word (uint32)(2 (S - 1))) >> 32, and stretch = v - (S - 1) if v < S - 1, else v - (S - 1) + 1.  stretch_span = 0
+ *   means no stretch, 1 is refused, S >= 2 stretches; the shift of site 1 is unchanged and independent.  Item j then
+ *   reads Nx_j = width + stretch_j rows of the audio from row d_starts[j % n_onsets] + shift_j, and every channel of
+ *   them is resampled to width samples by the arithmetic of ofp_resample_windows: the same bits as that function
+ *   gives for the same (start, nx, num).  A row outside the audio reads as 0; the caller rules it out.  Limits:
+ *   stretch_span <= width, width + stretch_span - 1 <= 2048, audio_len >= width + 2 max_shift + stretch_span - 1, and
+ *   16 (2 width + stretch_span - 1 + channels (width / 2 + 1)) + 4 channels (width + stretch_span - 1) bytes of LDS
+ *   <= 160 KiB; a span needs a window source.
  * ofp_*_train_random / ofp_*_loss_grads_random / ofp_*_train_random_workspace_bytes: the functions without
  *   `_random`, which they are with random = NULL, plus these options (ofp_*_loss_grads_random takes no window source).
+ * ofp_*_train_stretch / ofp_*_train_stretch_workspace_bytes: the `_random` functions, which they are with
+ *   stretch_span = 0, plus the span of site 2.
  * ofp_philox4x32: d_counters [n][4], d_keys [n][2] -> d_out [n][4].  ofp_dropout_mask: d_mask [n][F] of 0 and
  *   (float)(1 / (1 - p)).  ofp_shift_windows: d_shifts [n] (or NULL) and d_windows [n][channels][width], n =
- *   n_extractions * n_onsets.  All three run the device code of the epoch graphs. */
+ *   n_extractions * n_onsets.  ofp_stretch_windows: the same with stretch_span >= 2, and d_stretches [n] (or NULL).
+ *   All four run the device code of the epoch graphs. */
 typedef struct ofp_train_random {
     uint64_t seed;
     double dropout_p;
@@ -1091,6 +1105,24 @@ int ofp_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t F, double 
 int ofp_shift_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_t audio_len, int32_t channels,
                       const int64_t* d_starts, int64_t n_onsets, int32_t n_extractions, int32_t max_shift,
                       int32_t width, int32_t* d_shifts, float* d_windows, void* stream);
+int ofp_stretch_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_t audio_len, int32_t channels,
+                        const int64_t* d_starts, int64_t n_onsets, int32_t n_extractions, int32_t max_shift,
+                        int32_t stretch_span, int32_t width, int32_t* d_shifts, int32_t* d_stretches,
+                        float* d_windows, void* stream);
+int64_t ofp_cnn_train_stretch_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
+                                              const ofp_train_random* random, int32_t stretch_span);
+int ofp_cnn_train_stretch(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                          const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                          int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                          float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                          const ofp_train_random* random, int32_t stretch_span);
+int64_t ofp_cccnn_train_stretch_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
+                                                const ofp_train_random* random, int32_t stretch_span);
+int ofp_cccnn_train_stretch(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                            const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                            int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
+                            float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                            const ofp_train_random* random, int32_t stretch_span);
 
 #ifdef __cplusplus
 }

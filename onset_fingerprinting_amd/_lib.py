@@ -348,6 +348,18 @@ SIGNATURES = {
     "ofp_dropout_mask": (ctypes.c_int, [ctypes.c_uint64, _i32, _i64, _i32, _f64, _vp, _vp]),
     "ofp_shift_windows": (ctypes.c_int, [ctypes.c_uint64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
                                          _vp, _vp]),
+    "ofp_stretch_windows": (ctypes.c_int, [ctypes.c_uint64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32,
+                                           _vp, _vp, _vp, _vp]),
+    "ofp_cnn_train_stretch_workspace_bytes": (_i64, [ctypes.POINTER(CnnConfig), _i64, _i64,
+                                                     ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_cnn_train_stretch": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                             _i32, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                             ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_cccnn_train_stretch_workspace_bytes": (_i64, [ctypes.POINTER(CccnnConfig), _i64, _i64,
+                                                       ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_cccnn_train_stretch": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                               _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                               ctypes.POINTER(TrainRandom), _i32]),
 }
 
 _lib = None

@@ -3,8 +3,8 @@
 // optionally a validation pass with Lightning's early-stop rule.  As in csrc/ofp_cnn_train.hip one epoch is a linear
 // chain of short kernels on one stream, captured once as a hipGraph and replayed; the epoch index is a device counter
 // and once the stop word is set every kernel returns at once.  With random options (ofp_cccnn_train_random) the
-// epoch's windows come from k_shift_windows and the head's p goes through k_dropout_fwd in front of the Linear
-// (csrc/ofp_train_random.h), as in csrc/ofp_cnn_train.hip.
+// epoch's windows come from k_shift_windows (k_stretch_windows with a stretch span, ofp_cccnn_train_stretch) and the
+// head's p goes through k_dropout_fwd in front of the Linear (csrc/ofp_train_random.h), as in csrc/ofp_cnn_train.hip.
 //
 // The conv stack works on items: with group = 0 every (sample, sensor) pair is an item with 1 input channel (the
 // shared stack), with group = 1 every sample is an item with `sensors` input channels and a grouped convolution.
@@ -587,9 +587,15 @@ int64_t ofp_cccnn_train_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, 
 
 int64_t ofp_cccnn_train_random_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
                                                const ofp_train_random* random) {
+    return ofp_cccnn_train_stretch_workspace_bytes(cfg, n, n_val, random, 0);
+}
+
+int64_t ofp_cccnn_train_stretch_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
+                                                const ofp_train_random* random, int32_t stretch_span) {
     Plan p;
     Random rnd;
-    if (cfg == nullptr || make_random("cccnn training", random, n, cfg->sensors, cfg->width, true, rnd)) return -1;
+    if (cfg == nullptr || make_random("cccnn training", random, stretch_span, n, cfg->sensors, cfg->width, true, rnd))
+        return -1;
     if (make_plan(cfg, n, n_val, p, rnd)) return -1;
     return p.bytes;
 }
@@ -608,10 +614,21 @@ int ofp_cccnn_train_random(const ofp_cccnn_config* cfg, int64_t n, const float* 
                            int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
                            float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                            const ofp_train_random* random) {
+    return ofp_cccnn_train_stretch(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs,
+                                   patience, d_params, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream,
+                                   random, 0);
+}
+
+int ofp_cccnn_train_stretch(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                            const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                            int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
+                            float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                            const ofp_train_random* random, int32_t stretch_span) {
     Plan p;
     Random rnd;
     OFP_REQUIRE(cfg != nullptr, "cccnn training: config is NULL");
-    if (int rc = make_random("ofp_cccnn_train", random, n, cfg->sensors, cfg->width, true, rnd)) return rc;
+    if (int rc = make_random("ofp_cccnn_train", random, stretch_span, n, cfg->sensors, cfg->width, true, rnd))
+        return rc;
     if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
     if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
     const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
@@ -641,7 +658,7 @@ int ofp_cccnn_loss_grads_random(const ofp_cccnn_config* cfg, int64_t n, const fl
                                 void* stream, const ofp_train_random* random) {
     Plan p;
     Random rnd;
-    if (int rc = make_random("ofp_cccnn_loss_grads", random, n, 0, 0, false, rnd)) return rc;
+    if (int rc = make_random("ofp_cccnn_loss_grads", random, 0, n, 0, 0, false, rnd)) return rc;
     if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cccnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cccnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;

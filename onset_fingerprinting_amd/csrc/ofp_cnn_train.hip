@@ -4,7 +4,8 @@
 // replayed.  The epoch index (row of the rate table, slot of the loss curves) is a device counter that the chain's
 // last kernel advances, so every replay is the same graph; once the stop word is set every kernel returns at once.
 // With random options (ofp_cnn_train_random; csrc/ofp_train_random.h) the same counter drives a counter-based random
-// stream: the epoch's windows are cut from resident audio by k_shift_windows, the chain's first kernel, and the
+// stream: the epoch's windows are cut from resident audio by k_shift_windows, the chain's first kernel (with a stretch
+// span, ofp_cnn_train_stretch, by k_stretch_windows, which also resamples them), and the
 // features in front of the Linear head go through k_dropout_fwd (their gradient through k_dropout_bwd).
 //
 // Layer order as the reference builds it: conv + bias -> activation -> BatchNorm1d -> MaxPool1d(2, 2).  Only the
@@ -480,9 +481,16 @@ int64_t ofp_cnn_train_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int6
 
 int64_t ofp_cnn_train_random_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
                                              const ofp_train_random* random) {
+    return ofp_cnn_train_stretch_workspace_bytes(cfg, n, n_val, random, 0);
+}
+
+int64_t ofp_cnn_train_stretch_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
+                                              const ofp_train_random* random, int32_t stretch_span) {
     Plan p;
     Random rnd;
-    if (cfg == nullptr || make_random("cnn training", random, n, cfg->channels[0], cfg->width, true, rnd)) return -1;
+    if (cfg == nullptr ||
+        make_random("cnn training", random, stretch_span, n, cfg->channels[0], cfg->width, true, rnd))
+        return -1;
     if (make_plan(cfg, n, n_val, p, rnd)) return -1;
     return p.bytes;
 }
@@ -501,10 +509,21 @@ int ofp_cnn_train_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x,
                          int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
                          float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                          const ofp_train_random* random) {
+    return ofp_cnn_train_stretch(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs, patience,
+                                 d_params, d_stats, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream, random,
+                                 0);
+}
+
+int ofp_cnn_train_stretch(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                          const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                          int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
+                          float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                          const ofp_train_random* random, int32_t stretch_span) {
     Plan p;
     Random rnd;
     OFP_REQUIRE(cfg != nullptr, "cnn training: config is NULL");
-    if (int rc = make_random("ofp_cnn_train", random, n, cfg->channels[0], cfg->width, true, rnd)) return rc;
+    if (int rc = make_random("ofp_cnn_train", random, stretch_span, n, cfg->channels[0], cfg->width, true, rnd))
+        return rc;
     if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
     if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
     const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
@@ -536,7 +555,7 @@ int ofp_cnn_loss_grads_random(const ofp_cnn_config* cfg, int64_t n, const float*
                               void* stream, const ofp_train_random* random) {
     Plan p;
     Random rnd;
-    if (int rc = make_random("ofp_cnn_loss_grads", random, n, 0, 0, false, rnd)) return rc;
+    if (int rc = make_random("ofp_cnn_loss_grads", random, 0, n, 0, 0, false, rnd)) return rc;
     if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
     OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cnn_loss_grads: NULL argument");
     if (int rc = check_ws("ofp_cnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
@@ -635,7 +654,7 @@ int ofp_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t F, double 
     ofp_train_random o{};
     o.seed = seed, o.epoch = epoch, o.dropout_p = p;
     Random r;
-    if (int rc = make_random("ofp_dropout_mask", &o, n, 0, 0, false, r)) return rc;
+    if (int rc = make_random("ofp_dropout_mask", &o, 0, n, 0, 0, false, r)) return rc;
     return enqueue_dropout_fwd(nullptr, r, nullptr, d_mask, n * F, (hipStream_t)stream);
 }
 
@@ -651,8 +670,28 @@ int ofp_shift_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_
     o.audio_channels = channels, o.d_audio = d_audio, o.audio_len = audio_len, o.d_starts = d_starts;
     o.n_onsets = n_onsets;
     Random r;
-    if (int rc = make_random("ofp_shift_windows", &o, n_onsets * n_extractions, channels, width, true, r)) return rc;
+    if (int rc = make_random("ofp_shift_windows", &o, 0, n_onsets * n_extractions, channels, width, true, r)) return rc;
     return enqueue_shift_windows(nullptr, r, d_windows, d_shifts, (hipStream_t)stream);
+}
+
+int ofp_stretch_windows(uint64_t seed, int32_t epoch, const float* d_audio, int64_t audio_len, int32_t channels,
+                        const int64_t* d_starts, int64_t n_onsets, int32_t n_extractions, int32_t max_shift,
+                        int32_t stretch_span, int32_t width, int32_t* d_shifts, int32_t* d_stretches,
+                        float* d_windows, void* stream) {
+    OFP_REQUIRE(d_windows && channels >= 1 && width >= 1 && n_extractions >= 1 && n_onsets >= 1 &&
+                    n_onsets * n_extractions <= (1 << 20),
+                "ofp_stretch_windows: NULL windows, or %d channels, width %d, %lld onsets x %d extractions", channels,
+                width, (long long)n_onsets, n_extractions);
+    OFP_REQUIRE(stretch_span >= 2, "ofp_stretch_windows: stretch span %d (from 2; 1 leaves nothing to draw, the "
+                "reference's randint(1, 1) raises; without a stretch the call is ofp_shift_windows)", stretch_span);
+    ofp_train_random o{};
+    o.seed = seed, o.epoch = epoch, o.max_shift = max_shift, o.n_extractions = n_extractions;
+    o.audio_channels = channels, o.d_audio = d_audio, o.audio_len = audio_len, o.d_starts = d_starts;
+    o.n_onsets = n_onsets;
+    Random r;
+    if (int rc = make_random("ofp_stretch_windows", &o, stretch_span, n_onsets * n_extractions, channels, width, true, r))
+        return rc;
+    return enqueue_stretch_windows(nullptr, r, d_windows, d_shifts, d_stretches, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "ofp_common.h"
+#include "ofp_resample_dev.h"
 
 namespace {
 
@@ -94,8 +95,8 @@ __global__ __launch_bounds__(64) void k_onset_region(const float* __restrict__ a
 }
 
 // ---- scipy.signal.resample (real input, time domain, no window) of item (i, c):
-// x = audio[start_i : start_i + nx_i, c] -> y[num]; the spectrum is taken and synthesised directly (DFT with
-// tabulated fp64 twiddles: the lengths are arbitrary, a few hundred samples).  Samples outside the clip read 0.
+// x = audio[start_i : start_i + nx_i, c] -> y[num], by the arithmetic of csrc/ofp_resample_dev.h, one workgroup per
+// (item, channel).  Samples outside the clip read 0.
 struct ResampleArgs {
     const float* audio;     // [n_samples][C] (or C == 1)
     int64_t n_samples;
@@ -111,55 +112,23 @@ __global__ __launch_bounds__(256) void k_resample(ResampleArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int item = blockIdx.x / a.C, c = blockIdx.x % a.C;
     const int Nx = max(1, min(a.nx[item], a.max_nx)), num = a.num;  // (the host checks nx <= max_nx; never overrun the LDS)
-    const int N = min(num, Nx), K = N / 2;  // bins 0..K are copied
+    const int K = resample_bins(Nx, num);  // bins 0..K are copied
     double2* twx = reinterpret_cast<double2*>(smem);             // e^{-2 pi i j / Nx}, j < Nx
     double2* twy = twx + Nx;                                     // e^{+2 pi i j / num}, j < num
     double2* Y = twy + num;                                      // [K + 1]
     float* xs = reinterpret_cast<float*>(Y + K + 1);             // [Nx]
     const int64_t st = a.start[item];
     for (int j = threadIdx.x; j < Nx; j += 256) {
-        double s, co;
-        sincospi(-2.0 * (double)j / (double)Nx, &s, &co);
-        twx[j] = make_double2(co, s);
+        twx[j] = resample_twx(j, Nx);
         const int64_t t = st + j;
         xs[j] = (t >= 0 && t < a.n_samples) ? a.audio[t * a.C + c] : 0.0f;
     }
-    for (int j = threadIdx.x; j < num; j += 256) {
-        double s, co;
-        sincospi(2.0 * (double)j / (double)num, &s, &co);
-        twy[j] = make_double2(co, s);
-    }
+    for (int j = threadIdx.x; j < num; j += 256) twy[j] = resample_twy(j, num);
     __syncthreads();
-    for (int k = threadIdx.x; k <= K; k += 256) {  // rfft bins that survive
-        double re = 0.0, im = 0.0;
-        int ph = 0;  // k * n mod Nx
-        for (int n = 0; n < Nx; ++n) {
-            const double v = (double)xs[n];
-            re += v * twx[ph].x;
-            im += v * twx[ph].y;
-            ph += k;
-            if (ph >= Nx) ph -= Nx;
-        }
-        if (N % 2 == 0 && k == K) {  // the Nyquist component of the shorter length
-            if (num < Nx) { re *= 2.0; im *= 2.0; }
-            else if (Nx < num) { re *= 0.5; im *= 0.5; }
-        }
-        Y[k] = make_double2(re, im);
-    }
+    for (int k = threadIdx.x; k <= K; k += 256) Y[k] = resample_bin(xs, 1, twx, Nx, num, k);  // rfft bins that survive
     __syncthreads();
-    const double scale = ((double)num / (double)Nx) / (double)num;  // irfft's 1/num, then y *= num / Nx
     float* dst = a.out + ((int64_t)item * a.C + c) * num;
-    for (int m = threadIdx.x; m < num; m += 256) {
-        double acc = Y[0].x;
-        int ph = 0;
-        for (int k = 1; k <= K; ++k) {
-            ph += m;
-            if (ph >= num) ph -= num;
-            if (2 * k == num) acc += Y[k].x * twy[ph].x;  // irfft takes the last bin of an even length as real
-            else acc += 2.0 * (Y[k].x * twy[ph].x - Y[k].y * twy[ph].y);
-        }
-        dst[m] = (float)(acc * scale);
-    }
+    for (int m = threadIdx.x; m < num; m += 256) dst[m] = resample_sample(Y, 1, twy, Nx, num, m);
 }
 
 }  // namespace

@@ -423,7 +423,7 @@ template <class Run>
 int enqueue_epoch(const Run& r, const TrainArgs& a) {
     const auto& p = *r.p;
     if (r.rnd.windows)  // a.x is the work space's window buffer
-        if (int rc = enqueue_shift_windows(r.ctl, r.rnd, r.template at<float>(p.o_X), nullptr, r.st)) return rc;
+        if (int rc = enqueue_windows(r.ctl, r.rnd, r.template at<float>(p.o_X), r.st)) return rc;
     if (int rc = enqueue_loss_grads(r, a.x, a.y, a.n, a.train_loss)) return rc;
     if (int rc = enqueue_step(r, a.rates)) return rc;
     if (a.nv > 0) {
@@ -463,7 +463,7 @@ int run_epochs(const char* who, const char* env, hipStream_t st, Ctl* ctl, int n
     hipLaunchKernelGGL(k_init, dim3(1), dim3(kT), 0, st, ctl);
     OFP_LAUNCH_CHECK("k_init");
     // the first epoch is launched plainly: it loads every code object and sets the LDS size of kernels that need more
-    // than the default (the LCCCNN's head), neither of which may happen during capture
+    // than the default (the LCCCNN's head, k_stretch_windows at long windows), neither of which may happen during capture
     if (int rc = epoch()) return rc;
     EpochGraph g;
     if (!plain && num_epochs > 1) {

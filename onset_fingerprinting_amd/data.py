@@ -5,10 +5,10 @@ hot-path functions of the reference's ``onset_fingerprinting/data.py``
 batched forms the pipeline uses.  All arithmetic on sample data runs in the HIP
 kernels of ``csrc/ofp_spectral.hip``; there is no CPU path.
 
-Datasets (POSD/MCPOSD), stretch augmentation inside the trainers and json/wav
-parsing are out of scope; ``ShiftedWindows`` is the window
-source with per-epoch shift augmentation that ``model.fit_cnn`` /
-``model.fit_lcccnn`` take in place of ``x``.
+Datasets (POSD/MCPOSD) and json/wav parsing are out of scope (SURVEY.md section
+2); ``ShiftedWindows`` is the window source with per-epoch shift augmentation
+that ``model.fit_cnn`` / ``model.fit_lcccnn`` take in place of ``x``, and
+``StretchedWindows`` the one that stretches and resamples its windows as well.
 """
 import ctypes
 
@@ -525,3 +525,66 @@ class ShiftedWindows:
         """float32 GPU tensor [n, C, W] ([n, W] for 1-D audio): the training batch of that epoch."""
         out = self._cut(seed, epoch)[1]
         return out[:, 0, :] if self._one_d else out
+
+
+class StretchedWindows(ShiftedWindows):
+    """A ``ShiftedWindows`` whose windows are also stretched anew every epoch, as the reference's
+    ``StretchFrameExtractor(frame_length, pre_samples, max_stretch)`` would (``train.py`` prepares it and leaves it
+    commented out as too slow on the host): with the span ``stretch_span = int(frame_length * max_stretch)`` every item
+    is cut 1 .. span - 1 samples longer or shorter than ``frame_length`` -- never by 0, the reference's
+    ``randint(1, span) * choice((-1, 1))`` -- and Fourier-resampled back to ``frame_length``
+    (``scipy.signal.resample``), by the arithmetic and to the bits of ``ofp_resample_windows``.  The stretches are site
+    2 of the trainers' stream (counter (item / 4, 2, epoch, 0); include/onsetfp.h); the shifts are site 1 as before and
+    independent of them.  The epoch graph's first kernel does both.
+
+    Item order, ``resident()`` and the tiling of ``y`` are ``ShiftedWindows``'s.  ``max_stretch = 0`` (span 0) gives
+    exactly a ``ShiftedWindows``; a span of 1 raises ``ValueError``, as the reference's ``randint(1, 1)`` does.
+    ``IndexError`` at construction if any shift and stretch together could take a window out of the audio."""
+
+    def __init__(self, audio, onsets, frame_length, pre_samples=0, max_stretch=0.03, max_shift=0, n_extractions=1,
+                 device=0):
+        self.stretch_span = int(int(frame_length) * max_stretch)
+        if self.stretch_span < 0:
+            raise ValueError("max_stretch must not be negative")
+        if self.stretch_span == 1:
+            raise ValueError(f"max_stretch {max_stretch} of {int(frame_length)} samples is a span of 1, which leaves "
+                             "no stretch to draw: the reference's randint(1, 1) raises too (use 0 for no stretch, or "
+                             "a span of at least 2)")
+        if self.stretch_span > int(frame_length):
+            raise ValueError(f"a stretch span of {self.stretch_span} is more than the {int(frame_length)} samples of "
+                             "a window")
+        super().__init__(audio, onsets, frame_length, pre_samples, max_shift, n_extractions, device)
+        longest = self.frame_length + max(self.stretch_span - 1, 0)
+        if self.starts.max() + self.max_shift + longest > self._audio.shape[0]:
+            raise IndexError("stretched frame outside the audio array")
+
+    def _cut3(self, seed, epoch):
+        """(shifts, stretches, windows) of an epoch."""
+        if self.stretch_span == 0:
+            shifts, out = super()._cut(seed, epoch)
+            return shifts, torch.zeros_like(shifts), out
+        if seed is None:
+            raise ValueError("stretched windows need a seed")
+        seed = check_seed(seed)
+        if int(epoch) < 0:
+            raise ValueError("epoch must not be negative")
+        x, st = self.resident()
+        shifts = torch.empty(self.n, dtype=torch.int32, device=x.device)
+        stretches = torch.empty_like(shifts)
+        out = torch.empty((self.n, self.channels, self.frame_length), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(_lib.lib().ofp_stretch_windows(seed, int(epoch), x.data_ptr(), x.shape[0], self.channels,
+                                                 st.data_ptr(), self.n_onsets, self.n_extractions, self.max_shift,
+                                                 self.stretch_span, self.frame_length, shifts.data_ptr(),
+                                                 stretches.data_ptr(), out.data_ptr(), _stream(x.device)),
+                  "ofp_stretch_windows")
+        return shifts, stretches, out
+
+    def _cut(self, seed, epoch):
+        shifts, _stretches, out = self._cut3(seed, epoch)
+        return shifts, out
+
+    def stretches(self, seed=None, epoch=0):
+        """int32 GPU tensor [n]: what the epoch graph adds to frame_length for every item at `epoch` of a fit with
+        `seed` (all 0 without a stretch)."""
+        return self._cut3(seed, epoch)[1]

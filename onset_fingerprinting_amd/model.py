@@ -11,8 +11,9 @@ csrc/ofp_rnn.hip); torch only allocates memory and makes views.  ``rnn_forward``
 (csrc/ofp_cnn_train.hip).  ``fit_lcccnn`` trains an ``LCCCNN`` in place with the recipe of its own ``training_step`` /
 ``configure_optimizers`` (full batch, SGD with momentum 0.8 and weight decay 1e-3 at 100 x ``lr``, cosine annealing over
 100 epochs) the same way (csrc/ofp_cccnn_train.hip).  With ``seed=`` both apply the model's dropout and, given a
-``data.ShiftedWindows``, cut shifted training windows anew every epoch, from this package's own random stream
-(csrc/ofp_train_random.h).  Training the recurrent classes is out of scope.
+``data.ShiftedWindows`` or ``data.StretchedWindows``, cut shifted (and stretched) training windows anew every epoch,
+from this package's own random stream (csrc/ofp_train_random.h).  Training the recurrent classes is out of scope
+(DESIGN.md section 7).
 """
 import ctypes
 import functools
@@ -588,9 +589,14 @@ def _batch_of(x, y, what):
     return x, y, tuple(int(d) for d in x.shape)
 
 
+def _stretch_span(source):
+    """The stretch span of a window source: a data.StretchedWindows' span, else 0."""
+    return int(getattr(source, "stretch_span", 0)) if source is not None else 0
+
+
 def _check_source(x, seed):
-    if isinstance(x, ShiftedWindows) and x.max_shift > 0 and seed is None:
-        raise ValueError("a window source with max_shift > 0 needs seed=")
+    if isinstance(x, ShiftedWindows) and (x.max_shift > 0 or _stretch_span(x) > 0) and seed is None:
+        raise ValueError("a window source with max_shift > 0 or a stretch needs seed=")
 
 
 def _cnn_arch(model, width=None, seed=None):
@@ -780,7 +786,8 @@ def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed
     train_loss = torch.full((max_epochs,), float("nan"), dtype=torch.float32, device=dev)
     val_loss = torch.full_like(train_loss, float("nan")) if have_val else None
     n, nv = int(yd.shape[0]), int(xv.shape[0]) if have_val else 0
-    ws_bytes = int(getattr(L, spec.c_workspace)(ctypes.byref(cfg), n, nv, rp))
+    span = _stretch_span(source)  # 0: the entries below are the `_random` ones
+    ws_bytes = int(getattr(L, spec.c_train + "_stretch_workspace_bytes")(ctypes.byref(cfg), n, nv, rp, span))
     if ws_bytes < 0:
         raise ValueError(_lib.last_error())
     ws = _workspace(ws_bytes, dev)
@@ -792,12 +799,12 @@ def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed
     side = torch.cuda.Stream(dev)
     side.wait_stream(cur)
     with torch.cuda.device(dev):
-        check(getattr(L, spec.c_train + "_random")(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
-                                                   rates.data_ptr(), max_epochs, min_epochs,
-                                                   -1 if patience is None else int(patience), params.data_ptr(),
-                                                   *(t.data_ptr() for t in stats), train_loss.data_ptr(),
-                                                   ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(), ws_bytes,
-                                                   ctypes.c_void_p(side.cuda_stream), rp), spec.c_train)
+        check(getattr(L, spec.c_train + "_stretch")(ctypes.byref(cfg), n, ptr(xd), yd.data_ptr(), nv, ptr(xv), ptr(yv),
+                                                    rates.data_ptr(), max_epochs, min_epochs,
+                                                    -1 if patience is None else int(patience), params.data_ptr(),
+                                                    *(t.data_ptr() for t in stats), train_loss.data_ptr(),
+                                                    ptr(val_loss), ctypes.byref(epochs), ws.data_ptr(), ws_bytes,
+                                                    ctypes.c_void_p(side.cuda_stream), rp, span), spec.c_train)
     cur.wait_stream(side)
     with torch.no_grad():
         _split(params, ps, copy=True)
@@ -855,12 +862,17 @@ def fit_cnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=
     features in front of ``fc`` in the training forward, with a new mask every epoch (``dropout_mask_device`` returns
     the mask of any epoch); the validation forward is eval mode and has none.  ``x`` may be a ``data.ShiftedWindows``:
     the epoch graph then cuts the training windows from its audio as its first kernel, shifted anew every epoch, and
-    ``y`` is [n_onsets, outputs] (tiled over the extractions); with ``max_shift > 0`` that needs the seed too.
+    ``y`` is [n_onsets, outputs] (tiled over the extractions); with ``max_shift > 0`` that needs the seed too.  A
+    ``data.StretchedWindows`` is such a source whose windows that kernel also cuts a few samples longer or shorter,
+    anew every epoch, and Fourier-resamples to the window length (the reference's StretchFrameExtractor; site 2 of the
+    stream); it needs the seed, and ``x.shifts`` / ``x.stretches`` / ``x.windows(seed, epoch)`` return what any epoch
+    used.
 
     ValueError, before anything runs on the GPU: dropout_rate > 0 without a seed, dropout_rate >= 1, a seed out of
-    range, a window source as x_val or with other rows in y than onsets, a loss other than F.l1_loss / F.mse_loss, an
-    activation without HIP implementation, BatchNorm1d(momentum=None), shapes beyond the limits (3 conv layers, 128
-    channels, kernel 8, window 512, batch 1024, 16 outputs)."""
+    range, a window source as x_val or with other rows in y than onsets, a shifting or stretching source without a
+    seed, a loss other than F.l1_loss / F.mse_loss, an activation without HIP implementation,
+    BatchNorm1d(momentum=None), shapes beyond the limits (3 conv layers, 128 channels, kernel 8, window 512, batch 1024,
+    16 outputs)."""
     return _fit(_CNN, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed)
 
 
@@ -1130,10 +1142,11 @@ def fit_lcccnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epoc
     record with ``train_loss`` and ``val_loss`` (or None): float32 GPU tensors [max_epochs], NaN beyond the epochs
     run; ``epochs``: epochs run; ``lrs``: float64 [epochs]; ``seed``.
 
-    ``seed`` and a ``data.ShiftedWindows`` as ``x`` work as in ``fit_cnn``: the seed opts into this package's own
-    random stream, with which the net's dropout is applied to the head's softmax values in front of ``fc`` in the
-    training forward (a new mask every epoch, none in the validation forward), and the window source makes the epoch
-    graph cut its training windows from the resident audio, shifted anew every epoch.
+    ``seed`` and a ``data.ShiftedWindows`` or ``data.StretchedWindows`` as ``x`` work as in ``fit_cnn``: the seed opts
+    into this package's own random stream, with which the net's dropout is applied to the head's softmax values in
+    front of ``fc`` in the training forward (a new mask every epoch, none in the validation forward), and the window
+    source makes the epoch graph cut its training windows from the resident audio, shifted -- and, by a
+    ``StretchedWindows``, stretched and resampled -- anew every epoch.
 
     ValueError, before anything runs on the GPU: dropout_rate > 0 without a seed, dropout_rate >= 1, a seed out of
     range, a window source as x_val or with other rows in y than onsets, a loss other than F.l1_loss / F.mse_loss, an

@@ -10,14 +10,15 @@ that end in a device synchronise, divided by the epochs; fit_cnn's figure theref
 (packing the parameters, the rate table, capturing the graph, copying the result back).  Each round reports the p50
 of `reps` such measurements per side, after one untimed warm-up call of each.  One JSON line per shape.
 
-    python tools/cnn_train_latency.py --random [--modes p0 p0.5 p0.5_shift] [--repo OTHER_TREE]
+    python tools/cnn_train_latency.py --random [--modes p0 p0.5 p0.5_shift p0.5_shift_stretch] [--repo OTHER_TREE]
 
 measures what the trainer's own random stream costs at the default architecture (default_bn_B620): fit_cnn with
 dropout_rate 0 (the chain without any of the new kernels), with dropout_rate 0.5 and a seed (k_dropout_fwd and
 k_dropout_bwd per epoch), and with that plus a data.ShiftedWindows source of 155 onsets x 4 extractions shifted by up
-to 16 samples (k_shift_windows as well), alternating over `rounds` rounds in this one process.  `--repo` imports the
-package from another built tree (a checkout of the parent commit, which has only the p0 mode), so that both can be
-measured in one visit to the GPU."""
+to 16 samples (k_shift_windows as well), and with a data.StretchedWindows source of the same hits that also stretches
+by max_stretch 0.03 (a span of 7: k_stretch_windows in place of k_shift_windows), alternating over `rounds` rounds in
+this one process.  `--repo` imports the package from another built tree (a checkout of the parent commit, which lacks
+the newest mode: name the others with --modes), so that both can be measured in one visit to the GPU."""
 import argparse
 import json
 import statistics
@@ -38,8 +39,9 @@ SHAPES = {
 WIDTH, CHANNELS = 264, 4
 
 
-RANDOM_SHAPE, RANDOM_MODES = "default_bn_B620", ("p0", "p0.5", "p0.5_shift")
+RANDOM_SHAPE, RANDOM_MODES = "default_bn_B620", ("p0", "p0.5", "p0.5_shift", "p0.5_shift_stretch")
 MAX_SHIFT, EXTRACTIONS, SEED = 16, 4, 1  # train.py: MCPOSD.from_file(..., w, pre_samp, 16, 4)
+MAX_STRETCH = 0.03                       # train.py: data.StretchFrameExtractor(w, 0, 0.03), commented out there
 
 
 def make(cfg, dropout_rate=0.0):
@@ -55,8 +57,9 @@ def make(cfg, dropout_rate=0.0):
     return m, x, y
 
 
-def window_source(n, channels, width):
-    """(data.ShiftedWindows of n / EXTRACTIONS onsets in seeded noise, y [onsets, 2])."""
+def window_source(n, channels, width, stretch=False):
+    """(data.ShiftedWindows -- with `stretch` data.StretchedWindows -- of n / EXTRACTIONS onsets in seeded noise,
+    y [onsets, 2])."""
     import numpy as np
     import torch
 
@@ -67,7 +70,11 @@ def window_source(n, channels, width):
     rng = np.random.default_rng(1)
     audio = rng.standard_normal((gap * (onsets_n + 1), channels)).astype(np.float32)
     onsets = gap * (1 + np.arange(onsets_n))
-    src = data.ShiftedWindows(audio, onsets, width, pre_samples=8, max_shift=MAX_SHIFT, n_extractions=EXTRACTIONS)
+    if stretch:  # (the gap's 8 spare samples hold the longest window's span - 1 more)
+        src = data.StretchedWindows(audio, onsets, width, pre_samples=8, max_stretch=MAX_STRETCH, max_shift=MAX_SHIFT,
+                                    n_extractions=EXTRACTIONS)
+    else:
+        src = data.ShiftedWindows(audio, onsets, width, pre_samples=8, max_shift=MAX_SHIFT, n_extractions=EXTRACTIONS)
     return src, torch.from_numpy((rng.random((onsets_n, 2)) - 0.5).astype(np.float32)).cuda()
 
 
@@ -112,8 +119,8 @@ def random_modes(args):
     for mode in args.modes:
         start, x, y = make(cfg, 0.0 if mode == "p0" else 0.5)
         kw = {} if mode == "p0" else dict(seed=SEED)
-        if mode.endswith("_shift"):
-            x, y = window_source(cfg["n"], CHANNELS, WIDTH)
+        if "_shift" in mode:
+            x, y = window_source(cfg["n"], CHANNELS, WIDTH, stretch=mode.endswith("_stretch"))
         run[mode] = lambda start=start, x=x, y=y, kw=kw: ours(copy.deepcopy(start), x, y, E, **kw)
     for fn in run.values():
         fn()
@@ -126,7 +133,8 @@ def random_modes(args):
         rounds.append({mode: round(statistics.median(v) * 1e6, 2) for mode, v in samples.items()})
     rec = dict(tool="cnn_train_latency --random", tree=str(REPO.name), shape=RANDOM_SHAPE, n=cfg["n"],
                layer_sizes=cfg["layer_sizes"], width=WIDTH, channels=CHANNELS, batch_norm=True, max_shift=MAX_SHIFT,
-               n_extractions=EXTRACTIONS, epochs_per_measurement=E, reps=args.reps, p50_us_per_epoch=rounds,
+               n_extractions=EXTRACTIONS, max_stretch=MAX_STRETCH, epochs_per_measurement=E, reps=args.reps,
+               p50_us_per_epoch=rounds,
                device=torch.cuda.get_device_name(0))
     print(json.dumps(rec), flush=True)
     if args.out:
