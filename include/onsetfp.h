@@ -789,6 +789,69 @@ int ofp_hop_collect_location(ofp_hop_session* s, int32_t* status, double* h_xy, 
 /* copies `ongoing` out (no hop may be in flight) */
 int ofp_hop_locator_state(ofp_hop_session* s, ofp_locate_state* h_state);
 
+/* ---- the window regressor of a stream ("The window regressor in the hop") ------------------------
+ * detection.find_onset_groups (detection.py:131-189) as an online state machine, fed the stream's onsets hop by hop,
+ * each hop's sorted by sample (stable): a group is anchored at its first onset and takes every following onset with
+ * sample - anchor <= max_distance; the first onset outside closes it, and so does the end of hop h (hops from 1) as
+ * soon as h * block > anchor + max_distance.  A closed group with at least min_channels channels waits in a FIFO of
+ * OFP_REG_QUEUE groups with start = min(row entries >= 0) - pre_samples; at the end of a hop the head is evaluated
+ * when h * block >= start + frame_length: the window [channels][frame_length] from `start` (rows before sample 0
+ * are zeros) goes through the model.  At most one group per hop.  The flags are sticky and never silent. */
+#define OFP_REG_MAX_LAYERS 8
+#define OFP_REG_MAX_SIGNALS 8
+#define OFP_REG_MAX_OUT 64
+#define OFP_REG_MAX_FRAME 4096
+#define OFP_REG_QUEUE 8
+#define OFP_REGF_QUEUE 1      /* a kept group was lost: more than OFP_REG_QUEUE groups pending */
+#define OFP_REGF_BAD_ONSET 2  /* an onset was ignored: channel outside 0..channels-1 or a negative sample */
+typedef struct ofp_regress_state {
+    int32_t open, head, len, flags;   /* a group is open; the FIFO's head slot and length; OFP_REGF_* seen so far */
+    int64_t anchor;
+    int64_t wake;                      /* the first hop end at which the open group times out or the head is due */
+    int64_t row[OFP_REG_MAX_SIGNALS];  /* the open group's row */
+    int64_t q_start[OFP_REG_QUEUE];
+    int64_t q_row[OFP_REG_QUEUE][OFP_REG_MAX_SIGNALS];
+} ofp_regress_state;
+/* A model.CNN (kind 0), the shared-stack model.CCCNN (kind 1) or the grouped one (kind 2) in eval semantics, and the
+ * stage's four parameters.  cout / kernels / strides [n_conv] and groups are the Conv1d modules' own (kind 1: groups
+ * 1 and one input channel, every sensor channel an item; kind 2: groups = channels).  norm 0: none; 1: an eval-mode
+ * BatchNorm1d folded into (scale, shift) by the caller (kind 0 only); 2: GroupNorm(1, cout) with gn_eps (kinds 1, 2).
+ * d_params, device memory, n_params floats: per conv layer weight [cout][cin / groups][k], bias [cout], then with a
+ * norm (scale, shift) or (gamma, beta) [cout] each; then fc weight [n_out][fc_in], fc bias [n_out].  A session and
+ * the replay copy nothing but read it while they run; a session keeps its own copy.
+ * Envelope: channels 1..OFP_REG_MAX_SIGNALS, n_conv 1..OFP_REG_MAX_LAYERS, n_out 1..OFP_REG_MAX_OUT, width ==
+ * frame_length <= OFP_REG_MAX_FRAME, every tensor between two layers at most 2^20 floats. */
+typedef struct ofp_hop_regressor {
+    int32_t kind, channels, width, n_out, n_conv;
+    int32_t cout[OFP_REG_MAX_LAYERS], kernels[OFP_REG_MAX_LAYERS], strides[OFP_REG_MAX_LAYERS];
+    int32_t padding, dilation, groups, act, norm, pool;
+    float gn_eps;
+    const float* d_params;
+    int64_t n_params;
+    int32_t frame_length, pre_samples, max_distance, min_channels;
+} ofp_hop_regressor;
+/* Replay: the state machine and the model over a resident recording d_audio [n_rows][channels] and a given onset
+ * list (d_channel / d_onset [K], already in feed order: sorted by sample, stable), hop by hop (n_rows / block_size
+ * hops; onset k belongs to hop d_onset[k] / block_size + 1) in ONE launch of one workgroup, from an empty state.
+ * Per hop h - 1: d_status 1 when a hit was evaluated, then d_start, d_row [channels] and d_y [n_out] (untouched
+ * otherwise); d_pending the FIFO's length before the hop's evaluation (its highest value during the hop);
+ * *d_flags the final OFP_REGF_*.  d_ws: 2 * ofp_regress_workspace_floats floats, or NULL when that is 0. */
+int64_t ofp_regress_workspace_floats(const ofp_hop_regressor* r);
+int ofp_regress_stream(const ofp_hop_regressor* r, const float* d_audio, int64_t n_rows, int32_t block_size,
+                       const int32_t* d_channel, const int64_t* d_onset, int64_t K, int32_t* d_status, int64_t* d_start,
+                       int64_t* d_row, float* d_y, int32_t* d_pending, int32_t* d_flags, float* d_ws, void* stream);
+/* The stage inside the hop graph of a session (before its first hop; the graph is captured again; on failure the
+ * session is the one it was).  It runs after the detector and the locator stage, in the detector's workgroup (one
+ * kernel form) or as one more node before the spectral node.  OFP_ERR_INVALID: channels != the session's, a detector
+ * that backtracks, max_distance < block_size, min_channels outside 1..channels, more groups pending than
+ * OFP_REG_QUEUE or a ring shorter than max_distance + pre_samples + (K + 1) * block_size rows, K = max(0,
+ * ceil((max_distance + frame_length - pre_samples) / block_size) - 1) (INTEGRATION.md derives both).
+ * ofp_hop_reset clears the state. */
+int ofp_hop_set_regressor(ofp_hop_session* s, const ofp_hop_regressor* r);
+/* The hit block of the last collected hop: *status 0 none / 1 evaluated, then *start, h_row [channels] and h_y
+ * [n_out]; *flags always. */
+int ofp_hop_collect_hit(ofp_hop_session* s, int32_t* status, int64_t* start, int64_t* h_row, float* h_y, int32_t* flags);
+
 /* ---- 2-D hit location: find_lag, MultilateratePaired, lag_intensity_map (multilateration.py) -------------------
  * ofp_find_lags: find_lag / find_lag_multi (:878-899) for n_rows row pairs.  Row r of a starts at
  *   d_a + (d_a_off ? d_a_off[r] : r * a_stride) and steps elem_stride floats (b likewise, same element stride), so

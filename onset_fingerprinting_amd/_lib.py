@@ -127,6 +127,29 @@ class HopLocator(ctypes.Structure):
     ]
 
 
+REG_MAX_LAYERS, REG_MAX_SIGNALS, REG_MAX_OUT, REG_MAX_FRAME, REG_QUEUE = 8, 8, 64, 4096, 8  # OFP_REG_*
+REGF_QUEUE, REGF_BAD_ONSET = 1, 2
+REG_KIND_CNN, REG_KIND_CCCNN, REG_KIND_CCCNN_GROUPED = 0, 1, 2
+REG_NORM_NONE, REG_NORM_BATCH, REG_NORM_GROUP = 0, 1, 2
+
+
+class HopRegressor(ctypes.Structure):
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("channels", ctypes.c_int32), ("width", ctypes.c_int32), ("n_out", ctypes.c_int32),
+        ("n_conv", ctypes.c_int32),
+        ("cout", ctypes.c_int32 * REG_MAX_LAYERS),
+        ("kernels", ctypes.c_int32 * REG_MAX_LAYERS),
+        ("strides", ctypes.c_int32 * REG_MAX_LAYERS),
+        ("padding", ctypes.c_int32), ("dilation", ctypes.c_int32), ("groups", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("norm", ctypes.c_int32), ("pool", ctypes.c_int32),
+        ("gn_eps", ctypes.c_float),
+        ("d_params", ctypes.c_void_p),
+        ("n_params", ctypes.c_int64),
+        ("frame_length", ctypes.c_int32), ("pre_samples", ctypes.c_int32), ("max_distance", ctypes.c_int32),
+        ("min_channels", ctypes.c_int32),
+    ]
+
+
 class CnnConfig(ctypes.Structure):
     _fields_ = [
         ("n_conv", ctypes.c_int32),
@@ -283,6 +306,12 @@ SIGNATURES = {
                                                 ctypes.POINTER(_i32), ctypes.POINTER(_i64), ctypes.POINTER(_i32),
                                                 ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "ofp_hop_locator_state": (ctypes.c_int, [_vp, ctypes.POINTER(LocateState)]),
+    "ofp_regress_workspace_floats": (_i64, [ctypes.POINTER(HopRegressor)]),
+    "ofp_regress_stream": (ctypes.c_int, [ctypes.POINTER(HopRegressor), _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp]),
+    "ofp_hop_set_regressor": (ctypes.c_int, [_vp, ctypes.POINTER(HopRegressor)]),
+    "ofp_hop_collect_hit": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i64), _vp, _vp,
+                                           ctypes.POINTER(_i32)]),
     "ofp_find_lags": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp,
                                      _vp, _vp, _vp, _vp]),
     "ofp_vote_index": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

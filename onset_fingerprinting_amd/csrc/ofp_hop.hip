@@ -23,6 +23,10 @@
 // sorted by sample, to the device-resident state and writes the location block next to the records.  A hop without
 // onsets takes one uniform branch on the count and touches nothing of the stage.
 //
+// With a regressor attached (ofp_hop_set_regressor) the same workgroup / one more node then runs the window regressor's
+// step (ofp_regress_dev.h): the hop's onsets go through the grouping state machine, and the group whose window the hop
+// completes goes through the model; a hop with nothing to feed, close or evaluate takes uniform branches only.
+//
 // A replay needs no argument update: the write cursor is a counter in device memory.  The frame the
 // spectral kernel computes for the hop that ends at sample e is bit-identical to frame (e - n_fft)/B
 // of the dense kernel (k_stft_power, hop = B) on the same stream: same tables, same FFT, same mel
@@ -38,6 +42,7 @@
 #include "ofp_fft.h"
 #include "ofp_locate_dev.h"
 #include "ofp_mlp.h"
+#include "ofp_regress_dev.h"
 #include "ofp_stream_dev.h"
 
 using namespace ofpfft;
@@ -511,6 +516,63 @@ __global__ __launch_bounds__(256) void k_hop_locate(HopArgs a, HopLocArgs la, co
     hop_locate_stage(a, la, a.ctl[0], (int)(n < a.C ? n : a.C), recs, smem);
 }
 
+// The hit block of a hop in the result block (ofp_hop_collect_hit); `hop` names the hop (counted from 1) that wrote
+// start, row and y, so a hop that evaluates nothing writes nothing
+struct HopRegBlock {
+    int64_t hop;
+    int32_t flags, pad;
+    int64_t start;
+    int64_t row[OFP_REG_MAX_SIGNALS];
+    float y[OFP_REG_MAX_OUT];
+};
+
+struct HopRegArgs {
+    int enabled;
+    ofpreg::Cfg g;
+    HopRegBlock* out;
+};
+
+// The window regressor's step for one hop, by one workgroup of 256 threads, after the detector and the locator stage:
+// the hop's n records in the locator stage's order (sorted by sample, ties in record order), rows by the same rule
+// (current hop from the hop buffer -- each needed sample is fetched once --, older rows from the ring, rows before
+// sample 0 zero).  h = hops pushed including this one; wake: the state's word of that name, loaded by the caller
+// before the detector ran, so that a hop with nothing to feed, close or evaluate leaves on one uniform comparison.
+__device__ __forceinline__ void hop_regress_stage(const HopArgs& a, const HopRegArgs& ra, int64_t h, int n, int64_t wake,
+                                                  const ofp_onset* recs, unsigned char* smem) {
+    const int C = a.C, B = a.B;
+    n = n < C ? n : C;
+    if (ofpreg::idle(ra.g, h, n, wake)) return;
+    __syncthreads();  // the detector and the locator stage are done with this LDS
+    const int64_t first = (h - 1) * B;
+    auto rec = [&](int i, int& ch, int64_t& s) {  // the i-th record of the stable argsort (n <= 8: by rank)
+        for (int j = 0; j < n; ++j) {
+            int rank = 0;
+            for (int k = 0; k < n; ++k)
+                rank += recs[k].sample < recs[j].sample || (recs[k].sample == recs[j].sample && k < j);
+            if (rank == i) {
+                ch = recs[j].channel;
+                s = first + recs[j].sample;
+                return;
+            }
+        }
+    };
+    auto sample = [&](int64_t t, int col) -> float {
+        if (t < 0) return 0.0f;
+        if (t >= first) return a.hop[(t - first) * C + col];
+        return a.ring[(t % a.R) * C + col];
+    };
+    HopRegBlock* o = ra.out;
+    const int ev = ofpreg::step(ra.g, h, n, rec, sample, smem, &o->start, o->row, o->y, &o->flags);
+    if (ev && threadIdx.x == 0) o->hop = h;
+}
+
+// Nodes form: the stage as a kernel of its own after the detector and the locate node.
+__global__ __launch_bounds__(256) void k_hop_regress(HopArgs a, HopRegArgs ra, const ofp_onset* recs) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t n = *a.count;
+    hop_regress_stage(a, ra, a.ctl[0], (int)(n < a.C ? n : a.C), ra.g.state->wake, recs, smem);
+}
+
 // The whole hop in ONE launch: workgroup 0 is the detector (the phase-split block step of
 // ofp_stream_dev.h), workgroups 1..C the spectral branch of one channel each -- the two do not depend
 // on each other, so the hop takes max(detector, spectral) instead of their sum plus three launch gaps.
@@ -524,15 +586,23 @@ struct FusedCfg {
 // Everything a workgroup of the fused hop does, from the read of the hop counter to the completion word; the
 // arguments are the caller's (kernel arguments or a group's device arrays), never copies.
 // LOC: the instantiation of a session with a locator; without one the kernel is the one it always was.
-template <int F, bool LOC>
+// REG: the instantiation of a session with a regressor (ra is read only then); the same holds.
+template <int F, bool LOC, bool REG>
 __device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream::StreamArgs& sa, const HopLocArgs& la,
-                                               unsigned char* smem) {
+                                               const HopRegArgs* ra, unsigned char* smem) {
     const int64_t done = a.ctl[0];  // hops completed before this one
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) *a.hop_index = done;
-        if constexpr (LOC) {
+        if constexpr (LOC || REG) {
+            int64_t wake = 0;
+            if constexpr (REG) wake = ra->g.state->wake;  // (in flight while the detector runs)
             const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
-            if (n_on > 0) hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
+            if constexpr (LOC)
+                if (n_on > 0) hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
+            if constexpr (REG) {
+                static_assert(FusedCfg<F>::WGS == ofpnn::WG, "the per-item forward passes are written for 256 threads");
+                hop_regress_stage(a, *ra, done + 1, (int)(n_on < a.C ? n_on : a.C), wake, sa.mirror, smem);
+            }
         } else {
             ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
         }
@@ -561,7 +631,15 @@ __device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream
 template <int F, bool LOC>
 __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la) {
     extern __shared__ __align__(16) unsigned char smem[];
-    hop_fused_body<F, LOC>(a, sa, la, smem);
+    hop_fused_body<F, LOC, false>(a, sa, la, nullptr, smem);
+}
+
+// The fused hop of a session with a regressor: a kernel of its own, so that k_hop_fused keeps its arguments and code.
+template <int F, bool LOC>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_reg(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la,
+                                                                    HopRegArgs ra) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    hop_fused_body<F, LOC, true>(a, sa, la, &ra, smem);
 }
 
 // S sessions' hops in ONE launch: grid (C + 1 + strength, S), row blockIdx.y is member blockIdx.y of an
@@ -577,7 +655,18 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group(const HopA
                                                                       const HopLocArgs* __restrict__ largs, int dry) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (dry) return;
-    hop_fused_body<F, LOC>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], smem);
+    hop_fused_body<F, LOC, false>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], nullptr, smem);
+}
+
+// The group launch of members with a regressor each (rargs: the members' stage arguments, architectures may differ).
+template <int F, bool LOC>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group_reg(const HopArgs* __restrict__ args,
+                                                                          const ofpstream::StreamArgs* __restrict__ sargs,
+                                                                          const HopLocArgs* __restrict__ largs,
+                                                                          const HopRegArgs* __restrict__ rargs, int dry) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (dry) return;
+    hop_fused_body<F, LOC, true>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], rargs + blockIdx.y, smem);
 }
 
 }  // namespace
@@ -627,6 +716,13 @@ struct ofp_hop_session {
     ofp_onset* d_mirror = nullptr;  // fused form: the records in device memory
     int64_t o_loc = 0;
     size_t lds_loc = 0;
+    // the regressor (ofp_hop_set_regressor)
+    HopRegArgs rargs;
+    ofp_regress_state* d_reg_state = nullptr;
+    float* d_reg_prm = nullptr;  // own copy of the model's parameters
+    float* d_reg_ws = nullptr;   // activations of a model too large for the LDS
+    int64_t o_reg = 0;
+    size_t lds_reg = 0;
     int device = 0;
     ofp_hop_group* owner = nullptr;  // the group whose launches carry this session's hops (ofp_hop_group_create)
 };
@@ -636,7 +732,7 @@ struct ofp_hop_session {
 struct ofp_hop_group {
     std::vector<ofp_hop_session*> members;
     int device = 0, n_fft = 0, grid_x = 0;
-    bool loc = false;
+    bool loc = false, reg = false;
     size_t lds = 0;
     hipStream_t stream = nullptr;
     hipGraph_t graph = nullptr;
@@ -644,6 +740,7 @@ struct ofp_hop_group {
     HopArgs* d_args = nullptr;
     ofpstream::StreamArgs* d_sargs = nullptr;
     HopLocArgs* d_largs = nullptr;
+    HopRegArgs* d_rargs = nullptr;
 };
 
 namespace {
@@ -687,11 +784,22 @@ int hop_fused(ofp_hop_session* s) {
     return OFP_OK;
 }
 
+template <int F, bool LOC>
+int hop_fused_reg(ofp_hop_session* s) {
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_reg<F, LOC>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_reg<F, LOC>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
+                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->largs, s->rargs);
+    OFP_LAUNCH_CHECK("k_hop_fused_reg");
+    return OFP_OK;
+}
+
 // the per-hop sequence, enqueued on the session's stream (captured once, then replayed)
 int enqueue_hop(ofp_hop_session* s) {
     if (s->fused)  // one kernel: no copy nodes, no begin kernel
         return with_n_fft(s->n_fft, [&](auto f) {
             constexpr int F = decltype(f)::value;
+            if (s->rargs.enabled) return s->largs.enabled ? hop_fused_reg<F, true>(s) : hop_fused_reg<F, false>(s);
             return s->largs.enabled ? hop_fused<F, true>(s) : hop_fused<F, false>(s);
         });
     OFP_HIP(hipMemcpyAsync(s->d_hop, s->h_hop, (size_t)s->B * s->C * sizeof(float), hipMemcpyHostToDevice, s->stream));
@@ -709,6 +817,13 @@ int enqueue_hop(ofp_hop_session* s) {
                            reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
         OFP_LAUNCH_CHECK("k_hop_locate");
     }
+    if (s->rargs.enabled) {  // (after the locate node, before the spectral node: the ring holds the older hops only)
+        static ofp::LdsAttrCache attr;
+        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_regress), s->lds_reg, attr)) != OFP_OK) return rc;
+        hipLaunchKernelGGL(k_hop_regress, dim3(1), dim3(256), s->lds_reg, s->stream, s->args, s->rargs,
+                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
+        OFP_LAUNCH_CHECK("k_hop_regress");
+    }
     if (s->args.sg.enabled) {  // (before the spectral node: it reads ring rows the spectral node is about to overwrite
                                //  only for hops older than the ring, never the current one)
         rc = with_n_fft(s->n_fft, [&](auto f) { return hop_strength<decltype(f)::value>(s); });
@@ -716,7 +831,9 @@ int enqueue_hop(ofp_hop_session* s) {
     }
     rc = with_n_fft(s->n_fft, [&](auto f) { return hop_spectral<decltype(f)::value>(s); });
     if (rc != OFP_OK) return rc;
-    OFP_HIP(hipMemcpyAsync(s->h_res, s->d_res, (size_t)s->res_bytes, hipMemcpyDeviceToHost, s->stream));
+    // (the hit block is the result block's tail: a session without a regressor copies the bytes it always copied)
+    OFP_HIP(hipMemcpyAsync(s->h_res, s->d_res, (size_t)(s->rargs.enabled ? s->res_bytes : s->o_reg), hipMemcpyDeviceToHost,
+                           s->stream));
     return OFP_OK;
 }
 
@@ -727,6 +844,7 @@ int reset_state(ofp_hop_session* s) {
     OFP_HIP(hipMemsetAsync(s->d_ctl, 0, 2 * sizeof(int64_t), s->stream));
     OFP_HIP(hipMemsetAsync(s->d_res, 0, (size_t)s->res_bytes, s->stream));
     if (s->d_loc_state) OFP_HIP(hipMemsetAsync(s->d_loc_state, 0, sizeof(ofp_locate_state), s->stream));
+    if (s->d_reg_state) OFP_HIP(hipMemsetAsync(s->d_reg_state, 0, sizeof(ofp_regress_state), s->stream));
     if (s->d_sg) {
         OFP_HIP(hipMemsetAsync(s->d_sg, 0, s->sg_floats * 4, s->stream));
         OFP_HIP(hipMemcpyAsync(s->args.sg.st, s->sg_init, 16, hipMemcpyHostToDevice, s->stream));
@@ -822,6 +940,16 @@ int hop_group_launch(ofp_hop_group* g, int dry) {
     return OFP_OK;
 }
 
+template <int F, bool LOC>
+int hop_group_launch_reg(ofp_hop_group* g, int dry) {
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group_reg<F, LOC>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_group_reg<F, LOC>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
+                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_largs, g->d_rargs, dry);
+    OFP_LAUNCH_CHECK("k_hop_fused_group_reg");
+    return OFP_OK;
+}
+
 void group_free(ofp_hop_group* g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
@@ -829,6 +957,7 @@ void group_free(ofp_hop_group* g) {
     if (g->d_args) (void)hipFree(g->d_args);
     if (g->d_sargs) (void)hipFree(g->d_sargs);
     if (g->d_largs) (void)hipFree(g->d_largs);
+    if (g->d_rargs) (void)hipFree(g->d_rargs);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -839,10 +968,12 @@ int group_build(ofp_hop_group* g) {
     std::vector<HopArgs> a(n);
     std::vector<ofpstream::StreamArgs> q(n);
     std::vector<HopLocArgs> l(n);
+    std::vector<HopRegArgs> r(n);
     for (size_t i = 0; i < n; ++i) {
         a[i] = g->members[i]->args;
         q[i] = g->members[i]->sargs;
         l[i] = g->members[i]->largs;
+        r[i] = g->members[i]->rargs;
     }
     OFP_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     OFP_HIP(hipMalloc(&g->d_args, n * sizeof(HopArgs)));
@@ -851,6 +982,10 @@ int group_build(ofp_hop_group* g) {
     OFP_HIP(hipMemcpy(g->d_args, a.data(), n * sizeof(HopArgs), hipMemcpyHostToDevice));
     OFP_HIP(hipMemcpy(g->d_sargs, q.data(), n * sizeof(ofpstream::StreamArgs), hipMemcpyHostToDevice));
     OFP_HIP(hipMemcpy(g->d_largs, l.data(), n * sizeof(HopLocArgs), hipMemcpyHostToDevice));
+    if (g->reg) {
+        OFP_HIP(hipMalloc(&g->d_rargs, n * sizeof(HopRegArgs)));
+        OFP_HIP(hipMemcpy(g->d_rargs, r.data(), n * sizeof(HopRegArgs), hipMemcpyHostToDevice));
+    }
     // a member that joins mid-stream: its last stand-alone hop must have left its own stream
     for (ofp_hop_session* s : g->members)
         if (int rc = retire_last_hop(s)) return rc;
@@ -858,6 +993,7 @@ int group_build(ofp_hop_group* g) {
     auto launch = [&](int dry) {
         return with_n_fft(g->n_fft, [&](auto f) {
             constexpr int F = decltype(f)::value;
+            if (g->reg) return g->loc ? hop_group_launch_reg<F, true>(g, dry) : hop_group_launch_reg<F, false>(g, dry);
             return g->loc ? hop_group_launch<F, true>(g, dry) : hop_group_launch<F, false>(g, dry);
         });
     };
@@ -877,7 +1013,7 @@ int ofp_hop_destroy(ofp_hop_session* s) {
     if (s->exec) (void)hipGraphExecDestroy(s->exec);
     if (s->graph) (void)hipGraphDestroy(s->graph);
     void* dev[] = {s->d_state, s->d_hop, s->d_ring, s->d_ctl, s->d_twM, s->d_twF, s->d_win, s->d_wsym, s->d_tgw, s->d_sg, s->d_fb_i, s->d_fb_w,
-                   s->d_prm, s->d_res, s->d_loc_state, s->d_loc_prm, s->d_mirror};
+                   s->d_prm, s->d_res, s->d_loc_state, s->d_loc_prm, s->d_mirror, s->d_reg_state, s->d_reg_prm, s->d_reg_ws};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (s->h_hop) (void)hipHostFree(s->h_hop);
@@ -945,7 +1081,8 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     s->o_rel = up8(s->o_mel + (int64_t)C * s->n_mels * 4);
     s->o_sg = up8(s->o_rel + (s->want_rel ? (int64_t)B * C * 4 : 0));
     s->o_loc = up8(s->o_sg + 16 + (cfg->strength ? 4 * (int64_t)cfg->tg_win_length : 0));
-    s->res_bytes = up8(s->o_loc + (int64_t)sizeof(HopLocBlock));
+    s->o_reg = up8(s->o_loc + (int64_t)sizeof(HopLocBlock));
+    s->res_bytes = up8(s->o_reg + (int64_t)sizeof(HopRegBlock));
     const int M = s->n_fft / 2;
     s->lds = lds;
     s->lds_strength = lds_strength;
@@ -992,6 +1129,7 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     HopArgs& a = s->args;
     std::memset(&a, 0, sizeof(a));
     std::memset(&s->largs, 0, sizeof(s->largs));
+    std::memset(&s->rargs, 0, sizeof(s->rargs));
     a.C = C;
     a.B = B;
     a.n_mels = s->n_mels;
@@ -1174,6 +1312,7 @@ int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
 static int hop_attach_locator(ofp_hop_session* s, const ofp_hop_locator* loc, ofp::LocTables T, const char* who) {
     OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
     OFP_REQUIRE(!s->largs.enabled, "%s: the session already has a locator", who);
+    OFP_REQUIRE(!s->rargs.enabled, "%s: the session already has a regressor (attach the locator first)", who);
     OFP_REQUIRE(loc->S == s->C, "%s: %d sensors for %d channels", who, loc->S, s->C);
     OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
     OFP_REQUIRE(!T.use_audio || s->R >= (int64_t)loc->max_section + s->B,
@@ -1269,6 +1408,94 @@ int ofp_hop_locator_state(ofp_hop_session* s, ofp_locate_state* h_state) {
     return OFP_OK;
 }
 
+int ofp_hop_set_regressor(ofp_hop_session* s, const ofp_hop_regressor* r) {
+    const char* who = "ofp_hop_set_regressor";
+    OFP_REQUIRE(s && r, "%s: NULL argument", who);
+    OFP_NOT_IN_GROUP(s, "ofp_hop_set_regressor");
+    OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
+    OFP_REQUIRE(!s->rargs.enabled, "%s: the session already has a regressor", who);
+    ofpreg::Plan plan;
+    if (int rc = ofp_regress_plan(r, who, &plan)) return rc;
+    OFP_REQUIRE(r->channels == s->C, "%s: the model takes %d channels, the session has %d", who, r->channels, s->C);
+    OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
+    OFP_REQUIRE(r->max_distance >= s->B, "%s: max_distance %d is shorter than one hop (%d): two groups could close in one hop",
+                who, r->max_distance, s->B);
+    // a group is evaluated at most K hops after the hop that closes it; that bounds the groups
+    // pending at once and the oldest row a window still needs
+    const int64_t B = s->B, D = r->max_distance, span = D + (int64_t)r->frame_length - r->pre_samples;
+    const int64_t K = std::max<int64_t>(0, (span + B - 1) / B - 1);
+    const int64_t pending = std::min<int64_t>(K + 1, (K * B + D - 1) / (D + 1) + 1);
+    OFP_REQUIRE(pending <= OFP_REG_QUEUE, "%s: up to %lld groups can be pending, the queue holds %d", who, (long long)pending,
+                OFP_REG_QUEUE);
+    const int64_t rows = D + r->pre_samples + (K + 1) * B;
+    OFP_REQUIRE(s->R >= rows, "%s: the ring (%lld rows) must hold the oldest row a pending window can need plus one hop (%lld)",
+                who, (long long)s->R, (long long)rows);
+    const size_t lds = ofpreg::lds_bytes(plan);
+    OFP_REQUIRE(lds <= 128 * 1024, "%s: %zu bytes of LDS needed", who, lds);
+    const size_t lds_fused = s->lds_fused;
+    const bool own_mirror = s->fused && !s->d_mirror;
+    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+        OFP_HIP(hipMalloc(&s->d_reg_prm, (size_t)plan.n_params * 4));
+        OFP_HIP(hipMemcpy(s->d_reg_prm, r->d_params, (size_t)plan.n_params * 4, hipMemcpyDeviceToDevice));
+        plan.params = s->d_reg_prm;
+        OFP_HIP(hipMalloc(&s->d_reg_state, sizeof(ofp_regress_state)));
+        OFP_HIP(hipMemset(s->d_reg_state, 0, sizeof(ofp_regress_state)));
+        if (!plan.use_lds) OFP_HIP(hipMalloc(&s->d_reg_ws, (size_t)2 * plan.act_floats * 4));
+        ofpreg::Cfg& g = s->rargs.g;
+        g.plan = plan;
+        g.B = s->B;
+        g.F = r->frame_length;
+        g.pre = r->pre_samples;
+        g.D = r->max_distance;
+        g.min_channels = r->min_channels;
+        g.state = s->d_reg_state;
+        g.ws = s->d_reg_ws;
+        s->rargs.out = reinterpret_cast<HopRegBlock*>(s->res_dev + s->o_reg);
+        s->lds_reg = lds;
+        if (s->fused) {
+            if (own_mirror) {
+                OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
+                OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
+                s->sargs.mirror = s->d_mirror;
+            }
+            s->lds_fused = std::max(s->lds_fused, lds);
+        }
+        s->rargs.enabled = 1;
+        return capture_hop(s);
+    };
+    const int rc = attach();
+    if (rc == OFP_OK) return OFP_OK;
+    // the session is again exactly the one it was, and a later call is accepted
+    const std::string why = ofp::err_buf();
+    void** dev[] = {(void**)&s->d_reg_prm, (void**)&s->d_reg_state, (void**)&s->d_reg_ws, own_mirror ? (void**)&s->d_mirror : nullptr};
+    for (void** p : dev) {
+        if (p && *p) (void)hipFree(*p);
+        if (p) *p = nullptr;
+    }
+    std::memset(&s->rargs, 0, sizeof(s->rargs));
+    if (own_mirror) s->sargs.mirror = nullptr;
+    s->lds_fused = lds_fused;
+    s->lds_reg = 0;
+    if (!s->exec) (void)capture_hop(s);  // (the failure came after the earlier graph had been given up)
+    return ofp::fail(rc, "%s", why.c_str());
+}
+
+int ofp_hop_collect_hit(ofp_hop_session* s, int32_t* status, int64_t* start, int64_t* h_row, float* h_y, int32_t* flags) {
+    OFP_REQUIRE(s, "ofp_hop_collect_hit: NULL session");
+    OFP_REQUIRE(s->rargs.enabled, "ofp_hop_collect_hit: the session has no regressor");
+    OFP_REQUIRE(!s->in_flight && s->pushed > 0, "ofp_hop_collect_hit: no collected hop");
+    HopRegBlock b;
+    std::memcpy(&b, s->h_res + s->o_reg, sizeof(b));
+    const bool hit = b.hop == s->pushed;  // (a hop that evaluates nothing leaves the block of an earlier one)
+    if (status) *status = hit ? 1 : 0;
+    if (flags) *flags = b.flags;
+    if (!hit) return OFP_OK;
+    if (start) *start = b.start;
+    if (h_row) std::memcpy(h_row, b.row, (size_t)s->C * sizeof(int64_t));
+    if (h_y) std::memcpy(h_y, b.y, (size_t)s->rargs.g.plan.n_out * sizeof(float));
+    return OFP_OK;
+}
+
 int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group** out) {
     OFP_REQUIRE(sessions && out, "ofp_hop_group_create: NULL argument");
     OFP_REQUIRE(n >= 1 && n <= 1024, "ofp_hop_group_create: 1..1024 members (got %d)", n);
@@ -1292,6 +1519,8 @@ int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group*
                     "ofp_hop_group_create: members 0 and %d differ in having the onset strength enabled", i);
         OFP_REQUIRE(!s->largs.enabled == !f->largs.enabled, "ofp_hop_group_create: members 0 and %d differ in having a locator",
                     i);
+        OFP_REQUIRE(!s->rargs.enabled == !f->rargs.enabled, "ofp_hop_group_create: members 0 and %d differ in having a regressor",
+                    i);
         lds = std::max(lds, s->lds_fused);
     }
     ofp_hop_group* g = new (std::nothrow) ofp_hop_group();
@@ -1301,6 +1530,7 @@ int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group*
     g->n_fft = f->n_fft;
     g->grid_x = f->C + 1 + (f->args.sg.enabled ? 1 : 0);
     g->loc = f->largs.enabled != 0;
+    g->reg = f->rargs.enabled != 0;
     g->lds = lds;
     int prev = 0;
     hipError_t e = hipGetDevice(&prev);

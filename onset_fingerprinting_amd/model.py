@@ -34,6 +34,17 @@ def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def fold_batchnorm(bn, device):
+    """An eval-mode BatchNorm1d as float32 (scale, shift) on `device`: y = (v - mean) / sqrt(var + eps) * gamma + beta,
+    folded in double."""
+    inv = (bn.running_var.double() + bn.eps).rsqrt()
+    g = bn.weight.double() if bn.weight is not None else torch.ones_like(inv)
+    b = bn.bias.double() if bn.bias is not None else torch.zeros_like(inv)
+    scale = (g * inv).to(device, torch.float32).contiguous()
+    shift = (b - bn.running_mean.double() * g * inv).to(device, torch.float32).contiguous()
+    return scale, shift
+
+
 def conv1d_forward(x, weight, bias, padding, dilation, act_code, groups=1, bn=None, pool=False, stride=1):
     """Conv1d + bias + activation (+ eval-mode BatchNorm1d `bn` + MaxPool1d(2, 2)): the layer of
     model.py:91-107 in one kernel."""
@@ -44,12 +55,8 @@ def conv1d_forward(x, weight, bias, padding, dilation, act_code, groups=1, bn=No
     if pool:
         wout //= 2
     scale = shift = None
-    if bn is not None:  # y = (v - mean) / sqrt(var + eps) * gamma + beta, folded in double
-        inv = (bn.running_var.double() + bn.eps).rsqrt()
-        g = bn.weight.double() if bn.weight is not None else torch.ones_like(inv)
-        b = bn.bias.double() if bn.bias is not None else torch.zeros_like(inv)
-        scale = (g * inv).to(x.device, torch.float32).contiguous()
-        shift = (b - bn.running_mean.double() * g * inv).to(x.device, torch.float32).contiguous()
+    if bn is not None:
+        scale, shift = fold_batchnorm(bn, x.device)
     out = torch.empty((n, cout, wout), dtype=torch.float32, device=x.device)
     check(L.ofp_conv1d(x.data_ptr(), n, cin, w, weight.data_ptr(), bias.data_ptr() if bias is not None else None,
                        cout, k, padding, dilation, groups, stride, act_code,
@@ -126,6 +133,7 @@ class CNN(nn.Module):
         self.fc = nn.Linear(cur * width, output_size)
         self.loss = loss
         self.lr = lr
+        self.input_size, self.channels = input_size, channels
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x [batch, channels, input_size] -> [batch, output_size] (eval-mode semantics)."""
@@ -208,6 +216,7 @@ class CCCNN(nn.Module):
             cur = size * g
         self.dropout = nn.Dropout(dropout_rate)
         self.fc = nn.Linear(channels * (2 * width - 1), output_size)
+        self.input_size = input_size
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x [batch, channels, input_size] -> [batch, output_size] (eval-mode semantics)."""
@@ -255,6 +264,81 @@ class LCCCNN(nn.Module):
 
 
 LCCCNN_MOMENTUM, LCCCNN_WEIGHT_DECAY = 0.8, 1e-3  # model.py:608-614
+
+
+# ---- the window regressor of a realtime session (realtime.HopSession(regressor=...)) ---------------------------------
+def _conv_blocks(layers):
+    """[(Conv1d, BatchNorm1d or None, GroupNorm or None, pooled)] of a conv stack, as _run_conv_stack walks it."""
+    blocks = []
+    for m in layers:
+        if isinstance(m, nn.Conv1d):
+            blocks.append([m, None, None, False])
+        elif isinstance(m, nn.BatchNorm1d):
+            blocks[-1][1] = m
+        elif isinstance(m, nn.GroupNorm):
+            blocks[-1][2] = m
+        elif isinstance(m, nn.MaxPool1d):
+            blocks[-1][3] = True
+    return blocks
+
+
+def hop_regressor_arch(model, what):
+    """What the hop's regress stage needs to know of a ``CNN`` / ``CCCNN`` / ``LCCCNN``, read without a GPU call:
+    a namespace with net (the module that owns conv_layers and fc), kind, channels, input_size, n_out, blocks, norm,
+    pool.  ValueError for every other class (``RNN`` / ``CNNRNN`` by name: their forward exceeds a hop's budget) and
+    for a model outside the stage's envelope."""
+    if isinstance(model, (RNN, CNNRNN)):
+        raise ValueError(f"{what}: model.{type(model).__name__} is refused as a regressor: the measured forward of "
+                         f"RNN / CNNRNN exceeds the hop budget (README.md)")
+    net = model.model if isinstance(model, LCCCNN) else model
+    if not isinstance(net, (CNN, CCCNN)):
+        raise ValueError(f"{what}: the regressor must be a model.CNN, CCCNN or LCCCNN, got {type(model).__name__}")
+    blocks = _conv_blocks(net.conv_layers)
+    if isinstance(net, CNN):
+        kind = _lib.REG_KIND_CNN
+        norm = _lib.REG_NORM_BATCH if blocks[0][1] is not None else _lib.REG_NORM_NONE
+    else:
+        kind = _lib.REG_KIND_CCCNN_GROUPED if net.group else _lib.REG_KIND_CCCNN
+        norm = _lib.REG_NORM_GROUP if blocks[0][2] is not None else _lib.REG_NORM_NONE
+    a = SimpleNamespace(net=net, kind=kind, channels=net.channels, input_size=net.input_size,
+                        n_out=net.fc.out_features, blocks=blocks, norm=norm, pool=blocks[0][3])
+    if not 1 <= a.channels <= _lib.REG_MAX_SIGNALS:
+        raise ValueError(f"{what}: the regressor takes {a.channels} channels, 1..{_lib.REG_MAX_SIGNALS} supported")
+    if not 1 <= len(blocks) <= _lib.REG_MAX_LAYERS:
+        raise ValueError(f"{what}: the regressor has {len(blocks)} conv layers, 1..{_lib.REG_MAX_LAYERS} supported")
+    if not 1 <= a.n_out <= _lib.REG_MAX_OUT:
+        raise ValueError(f"{what}: the regressor has {a.n_out} outputs, 1..{_lib.REG_MAX_OUT} supported")
+    if not 1 <= a.input_size <= _lib.REG_MAX_FRAME:
+        raise ValueError(f"{what}: the regressor's input_size {a.input_size} is outside 1..{_lib.REG_MAX_FRAME}")
+    return a
+
+
+def hop_regressor_struct(model, device, frame_length, pre_samples, max_distance, min_channels, what="hop_regressor"):
+    """(_lib.HopRegressor, the flat parameter tensor it points to) of a ``CNN`` / ``CCCNN`` / ``LCCCNN`` on `device`:
+    weights as ``forward`` hands them to the kernels, BatchNorm folded by ``fold_batchnorm``."""
+    a = hop_regressor_arch(model, what)
+    net, dev = a.net, torch.device("cuda", device) if not isinstance(device, torch.device) else device
+    to = lambda t: t.detach().to(dev, torch.float32).contiguous().reshape(-1)
+    parts = []
+    r = _lib.HopRegressor()
+    r.kind, r.channels, r.width, r.n_out, r.n_conv = a.kind, a.channels, a.input_size, a.n_out, len(a.blocks)
+    for i, (conv, bn, gn, _) in enumerate(a.blocks):
+        r.cout[i], r.kernels[i], r.strides[i] = conv.out_channels, conv.kernel_size[0], conv.stride[0]
+        parts.append(to(conv.weight))
+        parts.append(to(conv.bias) if conv.bias is not None else torch.zeros(conv.out_channels, device=dev))
+        if bn is not None:
+            parts += list(fold_batchnorm(bn, dev))
+        elif gn is not None:
+            parts.append(to(gn.weight) if gn.weight is not None else torch.ones(conv.out_channels, device=dev))
+            parts.append(to(gn.bias) if gn.bias is not None else torch.zeros(conv.out_channels, device=dev))
+            r.gn_eps = float(gn.eps)
+    parts += [to(net.fc.weight), to(net.fc.bias)]
+    flat = torch.cat([p.reshape(-1).to(torch.float32) for p in parts]).contiguous()
+    r.padding, r.dilation, r.act, r.norm, r.pool = net._padding, net._dilation, net._act_code, a.norm, int(a.pool)
+    r.groups = a.blocks[0][0].groups
+    r.d_params, r.n_params = flat.data_ptr(), flat.numel()
+    r.frame_length, r.pre_samples, r.max_distance, r.min_channels = frame_length, pre_samples, max_distance, min_channels
+    return r, flat
 
 
 # ---- recurrent models (model.py:168-440) ---------------------------------------------------------------------------

@@ -41,6 +41,109 @@ def _band_csr(dense):
             np.asarray(w if w else [0.0], np.float32))
 
 
+def regress_hold_hops(block_size, frame_length, pre_samples, max_distance):
+    """K: a kept group is evaluated at most K hops after the hop that closes it ("The window
+    regressor in the hop").  The group anchored at sample a closes at a hop c with c * B > a + B, and its window
+    (start <= a + max_distance - pre_samples) is complete at the hop d with d * B < start + frame_length + B, so
+    d - c < (max_distance + frame_length - pre_samples) / B; one group closes per hop at most (max_distance >= B) and
+    one is evaluated per hop, so a backlog never adds to that."""
+    return max(0, -(-(max_distance + frame_length - pre_samples) // block_size) - 1)
+
+
+def regress_pending_bound(block_size, frame_length, pre_samples, max_distance):
+    """Most groups in the stage's FIFO at once: the groups closed in the K + 1 hops up to h.  At most one closes per
+    hop, and their anchors lie in [(h - K - 1) * B - max_distance, (h - 1) * B), more than max_distance apart."""
+    K = regress_hold_hops(block_size, frame_length, pre_samples, max_distance)
+    return min(K + 1, (K * block_size + max_distance - 1) // (max_distance + 1) + 1)
+
+
+def regress_ring_rows(block_size, frame_length, pre_samples, max_distance):
+    """Rows the ring must hold: from the earliest start (anchor - pre_samples) to the end of the latest hop that can
+    evaluate the group (anchor + max_distance + (K + 1) * B), the hop being written included."""
+    K = regress_hold_hops(block_size, frame_length, pre_samples, max_distance)
+    return max_distance + pre_samples + (K + 1) * block_size
+
+
+def _check_regressor(what, model, n_signals, block_size, frame_length, pre_samples, max_distance, min_channels):
+    """The argument errors of a regress stage that need no GPU -> (the model's arch, frame_length)."""
+    from . import model as mdl
+    arch = mdl.hop_regressor_arch(model, what)
+    if arch.channels != n_signals:
+        raise ValueError(f"{what}: the regressor takes {arch.channels} channels, the stream has {n_signals} signals")
+    if frame_length is None:
+        frame_length = arch.input_size
+    if int(frame_length) != arch.input_size:
+        raise ValueError(f"{what}: frame_length {frame_length}, the regressor's input_size is {arch.input_size}")
+    if pre_samples < 0:
+        raise ValueError(f"{what}: pre_samples {pre_samples} is negative")
+    if max_distance < 0:
+        raise ValueError(f"{what}: max_distance {max_distance} is negative")
+    if not 1 <= min_channels <= n_signals:
+        raise ValueError(f"{what}: min_channels {min_channels} outside 1..{n_signals}")
+    return arch, int(frame_length)
+
+
+def check_regress_flags(flags, what):
+    """The regress stage's sticky flags are never silent."""
+    if flags & _lib.REGF_QUEUE:
+        raise _lib.OnsetFPError(f"{what}: the regress queue overflowed (more than {_lib.REG_QUEUE} groups pending; "
+                                f"flags {flags})")
+    if flags & _lib.REGF_BAD_ONSET:
+        raise _lib.OnsetFPError(f"{what}: an onset was refused (channel out of range or negative sample; flags {flags})")
+
+
+def regress_stream_device(model, audio, channels, onsets, block_size, frame_length=None, pre_samples=0,
+                          max_distance=1000, min_channels=3, device=0):
+    """What a ``HopSession(regressor=model)`` would have answered on a finished recording, in ONE launch
+    (``ofp_regress_stream``): the stage's grouping state machine and model over ``audio`` [N, C] float32 (numpy or a
+    CUDA tensor) and the onset list (``channels`` / ``onsets`` [K], absolute samples; fed sorted by sample, stable),
+    hop by hop (N // block_size hops).  Returns a dict of per-hop arrays: ``hit`` bool [H], ``start`` int64 [H],
+    ``group`` int64 [H, C], ``position`` float32 [H, n_out] (zeros where ``hit`` is False) and ``pending`` int32 [H],
+    the FIFO's length before the hop's evaluation.  The ring and queue conditions of a session do not apply (the
+    recording is resident); a queue overflow raises OnsetFPError."""
+    what = "regress_stream_device"
+    ad = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    if ad.dim() != 2:
+        raise ValueError(f"{what}: audio must be [N, C], got {tuple(ad.shape)}")
+    C = int(ad.shape[1])
+    arch, frame_length = _check_regressor(what, model, C, block_size, frame_length, pre_samples, max_distance,
+                                          min_channels)
+    onsets = np.asarray(onsets, dtype=np.int64).reshape(-1)
+    channels = np.asarray(channels, dtype=np.int32).reshape(-1)
+    if len(onsets) != len(channels):
+        raise ValueError(f"{what}: {len(channels)} channels for {len(onsets)} onsets")
+    order = np.argsort(onsets, kind="stable")
+    onsets, channels = onsets[order], channels[order]
+    from . import model as mdl
+    dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
+    _lib.require_gpu(dev.index or 0)
+    L = _lib.lib()
+    ad = ad.to(dev, torch.float32).contiguous()
+    H = int(ad.shape[0]) // block_size
+    with torch.cuda.device(dev):
+        r, keep = mdl.hop_regressor_struct(model, dev, frame_length, pre_samples, max_distance, min_channels, what)
+        ws_floats = int(L.ofp_regress_workspace_floats(ctypes.byref(r)))
+        if ws_floats < 0:
+            raise ValueError(_lib.last_error())
+        ws = torch.empty(2 * ws_floats, dtype=torch.float32, device=dev) if ws_floats else None
+        ch_d, on_d = torch.from_numpy(channels).to(dev), torch.from_numpy(onsets).to(dev)
+        status = torch.zeros(H, dtype=torch.int32, device=dev)
+        start = torch.zeros(H, dtype=torch.int64, device=dev)
+        rows = torch.zeros((H, C), dtype=torch.int64, device=dev)
+        y = torch.zeros((H, arch.n_out), dtype=torch.float32, device=dev)
+        pending = torch.zeros(H, dtype=torch.int32, device=dev)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(L.ofp_regress_stream(ctypes.byref(r), ad.data_ptr(), ad.shape[0], block_size, ch_d.data_ptr(),
+                                   on_d.data_ptr(), len(onsets), status.data_ptr(), start.data_ptr(), rows.data_ptr(),
+                                   y.data_ptr(), pending.data_ptr(), flags.data_ptr(),
+                                   ws.data_ptr() if ws is not None else None, stream), "ofp_regress_stream")
+        del keep
+    check_regress_flags(int(flags.item()), what)
+    return dict(hit=status.cpu().numpy().astype(bool), start=start.cpu().numpy(), group=rows.cpu().numpy(),
+                position=y.cpu().numpy(), pending=pending.cpu().numpy())
+
+
 class HopSession:
     """One stream: ring buffer + detector + per-hop spectral fingerprint + classifier.
 
@@ -63,14 +166,40 @@ class HopSession:
     no ring length is required.  ``location`` is the polar tuple (radius / drum radius, angle) ``locate`` returns,
     formed on the host from the device's Cartesian root; ``located_group``, ``fed``, ``dropped`` and ``ongoing`` are as
     above.
+
+    ``regressor``: a ``model.CNN``, ``CCCNN`` or ``LCCCNN`` (eval semantics) on ``frame_length`` (default and only
+    value: its ``input_size``) samples of every channel.  The hop's graph then also groups the stream's onsets as
+    ``detection.find_onset_groups(max_distance, min_channels)`` would on the whole list, and runs the model on the
+    window of the group whose last row the hop delivers (``data.FrameExtractor``, ``use_min_onset``, ``pre_samples``,
+    no shift; at most one group per hop, after the locator stage).  The result dict gains ``hit``: None, or a dict
+    with ``position`` float32 [n_out], ``group`` int64 [n_signals] (the group's row, -1 where a channel is missing)
+    and ``start`` (the window's first sample).  INTEGRATION.md, "The window regressor in the hop", has the details.
     """
 
     def __init__(self, n_signals, block_size=128, sr=96000, n_fft=2048, n_mels=40, classifier=None,
                  ring_seconds=60.0, want_rel=False, device=0, floor=-70.0, hipass_freq=2000.0,
                  fast_ar=(3.0, 383.0), slow_ar=(2205.0, 2205.0), on_threshold=0.5, off_threshold=0.1,
                  cooldown=1323, backtrack=False, backtrack_buffer_size=None, backtrack_smooth_size=5,
-                 onset_strength=None, locator=None, locate_with_audio=True):
+                 onset_strength=None, locator=None, locate_with_audio=True, regressor=None, frame_length=None,
+                 pre_samples=0, max_distance=1000, min_channels=3):
         ring_rows = max(int(round(ring_seconds * sr)), n_fft, block_size)  # realtime/config.py:45,59
+        if regressor is not None:  # argument errors before any GPU call
+            what = "HopSession"
+            if backtrack:
+                raise ValueError("HopSession: a regressor needs backtrack=False (a backtracked onset may lie behind the "
+                                 "current hop)")
+            _, frame_length = _check_regressor(what, regressor, n_signals, block_size, frame_length, pre_samples,
+                                               max_distance, min_channels)
+            if max_distance < block_size:  # (the bounds below rest on it; the replay has no such condition)
+                raise ValueError(f"HopSession: max_distance {max_distance} is shorter than one hop ({block_size} "
+                                 "samples): two groups could close in one hop")
+            bounds = (block_size, frame_length, pre_samples, max_distance)
+            if regress_pending_bound(*bounds) > _lib.REG_QUEUE:
+                raise ValueError(f"HopSession: up to {regress_pending_bound(*bounds)} groups can be pending with these "
+                                 f"parameters, the device queue holds {_lib.REG_QUEUE}")
+            if ring_rows < regress_ring_rows(*bounds):
+                raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the oldest row a pending "
+                                 f"window can still need plus one hop ({regress_ring_rows(*bounds)} rows)")
         if locator is not None:  # argument errors before any GPU call
             from . import multilateration as ml
             if len(locator.sensor_locs) != n_signals:
@@ -161,6 +290,33 @@ class HopSession:
             self._loc_xy = (ctypes.c_double * 2)()
             self._loc_sens = (ctypes.c_int32 * _lib.LOCS_MEMBERS)()
             self._loc_on = (ctypes.c_int64 * _lib.LOCS_MEMBERS)()
+        self.regressor = regressor
+        if regressor is not None:  # (after the locator: its stage runs first)
+            from . import model as mdl
+            try:
+                with torch.cuda.device(self.device):
+                    r, keep = mdl.hop_regressor_struct(regressor, self.device, frame_length, pre_samples, max_distance,
+                                                       min_channels, "HopSession")
+                    check(L.ofp_hop_set_regressor(self.handle, ctypes.byref(r)), "ofp_hop_set_regressor")
+                    del keep  # (the session has copied the parameters)
+            except Exception:
+                self.close()
+                raise
+            self.frame_length, self.pre_samples = frame_length, pre_samples
+            self.max_distance, self.min_channels = max_distance, min_channels
+            self._hit_i = [ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32()]  # status, start, flags
+            self._hit_row = np.zeros(n_signals, dtype=np.int64)
+            self._hit_y = np.zeros(r.n_out, dtype=np.float32)
+
+    def _hit(self, out):
+        status, start, flags = self._hit_i
+        check(self._L.ofp_hop_collect_hit(self.handle, ctypes.byref(status), ctypes.byref(start),
+                                          self._hit_row.ctypes.data, self._hit_y.ctypes.data, ctypes.byref(flags)),
+              "ofp_hop_collect_hit")
+        check_regress_flags(flags.value, "HopSession")
+        out["hit"] = (dict(position=self._hit_y.copy(), group=self._hit_row.copy(), start=int(start.value))
+                      if status.value == 1 else None)
+        return out
 
     def _location(self, out):
         from . import multilateration as ml
@@ -238,6 +394,8 @@ class HopSession:
                     strength=self._sg[:4].copy() if self.onset_strength else None,
                     # recording.py:313-327 (None unless onset_strength has tg_win_length)
                     tempogram=self._sg[4:].copy() if self.onset_strength and len(self._sg) > 4 else None)
+        if self.regressor is not None:
+            self._hit(out)
         if self.locator is None:
             return out
         if k == 0:  # the stage did not run: nothing to read
@@ -271,7 +429,7 @@ class HopSessionGroup:
     hops arrive on the same clock.
 
     ``sessions``: ``HopSession`` objects on one device with the same ``n_fft`` and channel count that agree on
-    having a locator and on having the onset strength; everything else (block size, ``sr``, detector arguments, ring
+    having a locator, on having a regressor (its architecture may differ) and on having the onset strength; everything else (block size, ``sr``, detector arguments, ring
     length, ``want_rel``, ``n_mels``, classifier, the locator's geometry and model) may differ.  They may be warmed
     up or mid-stream.  Each member keeps its own state and runs the device code it runs alone, so every output is
     bit for bit the stand-alone session's.  While grouped a member still takes ``reset()``,
