@@ -940,7 +940,10 @@ int ofp_intensity_maps(const double* d_mics, int32_t r, double reflectivity, flo
  *   d_sensors0 [M][4][3], d_sounds0 [M][n][2], d_c0 [M]; d_rates [U][num_epochs][4] = the step sizes of sensors,
  *   sounds and C, then sqrt(1 - 0.999^t).  The early-stop test comes before the loss is counted: d_epochs [M] is
  *   the number of updates, and d_loss [m][d_epochs[m]] holds the stopping epoch's loss when the run stopped.  d_sounds
- *   [M][n][3] are the positions the last forward pass used (z = 0), as the reference returns them.  n 1..4096. */
+ *   [M][n][3] are the positions the last forward pass used (z = 0), as the reference returns them.  n 1..4096.
+ * ofp_tdoa_loss_grads: the same kernel, leaving after the first epoch's sums: d_loss [M], d_g_sensors [M][4][3],
+ *   d_g_sounds [M][n][2] and d_g_c [M], the unclipped gradients at d_sensors / d_sounds [M][n][2] / d_c.  No rate
+ *   tables; the limits of ofp_tdoa_fit. */
 int64_t ofp_fcnn_train_lds_bytes(int32_t n_layers, const int32_t* dims, int32_t batch_norm, int32_t bias, int64_t n);
 int64_t ofp_fcnn_train_workspace_bytes(int32_t n_layers, const int32_t* dims, int32_t batch_norm, int32_t bias,
                                        int64_t n, int64_t M);
@@ -957,6 +960,9 @@ int ofp_tdoa_fit(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, c
                  const float* d_sounds0, const float* d_c0, int32_t loss, const float* d_rates,
                  const int32_t* d_rate_idx, int32_t num_epochs, float eps, int32_t patience, float* d_sensors,
                  float* d_sounds, float* d_c, float* d_loss, int32_t* d_epochs, void* stream);
+int ofp_tdoa_loss_grads(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, const float* d_sensors,
+                        const float* d_sounds, const float* d_c, int32_t loss, float* d_loss, float* d_g_sensors,
+                        float* d_g_sounds, float* d_g_c, void* stream);
 
 /* ---- training model.CNN (model.py:52-162, the loop of train.py) -----------------------------------------------
  * Network: n_conv layers of Conv1d (stride 1, bias) -> activation -> BatchNorm1d (when batch_norm) -> MaxPool1d(2, 2)

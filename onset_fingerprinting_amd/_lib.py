@@ -330,6 +330,7 @@ SIGNATURES = {
                                            _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_tdoa_fit": (ctypes.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
+    "ofp_tdoa_loss_grads": (ctypes.c_int, [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ofp_cnn_train_slab": (_i32, []),
     "ofp_cnn_train_workspace_bytes": (_i64, [ctypes.POINTER(CnnConfig), _i64, _i64]),
     "ofp_cnn_train": (ctypes.c_int, [ctypes.POINTER(CnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32,

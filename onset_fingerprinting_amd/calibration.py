@@ -598,15 +598,13 @@ class PositionFits:
         return [np.asarray(v) for v in self.losses[i, :int(self.epochs[i])].cpu().numpy()]
 
 
-def optimize_positions_device(observed_lags, initial_sensor_positions, initial_sound_positions, lr=0.01,
-                              lossfun=F.mse_loss, num_epochs=1000, C=342.29, sr=96000, eps=1e-12, patience=10):
-    """M independent optimize_positions fits in one launch.  observed_lags [M, N, 2] (or [N, 2]) in samples,
-    initial_sensor_positions [M, 4, 3] (or [4, 3]), initial_sound_positions [M, N, >= 2] (or [N, >= 2]); lr and C
-    numbers or M of them.  Returns PositionFits."""
-    loss = _loss_code(lossfun)
+def _position_inputs(observed_lags, sensor_positions, sound_positions, per_problem, sr):
+    """Shapes, broadcasting and refusals shared by optimize_positions_device and tdoa_loss_and_grads_device:
+    (M, N, device, obs [N, 2] or [M, N, 2] in seconds, sensors [M, 4, 3], sounds [M, N, 2], the per-problem value
+    lists); nothing touches the GPU before every ValueError had its chance."""
     lags = torch.as_tensor(observed_lags)
-    sens = torch.as_tensor(initial_sensor_positions)
-    snd = torch.as_tensor(initial_sound_positions)
+    sens = torch.as_tensor(sensor_positions)
+    snd = torch.as_tensor(sound_positions)
     if sens.dim() not in (2, 3) or tuple(sens.shape[-2:]) != (4, 3):
         raise ValueError(f"initial_sensor_positions {tuple(sens.shape)}: exactly 4 sensors [4, 3] are needed (the "
                          "lags pair sensor 0 with 2 and 1 with 3)")
@@ -618,21 +616,32 @@ def optimize_positions_device(observed_lags, initial_sensor_positions, initial_s
     if N < 1 or N > TDOA_MAX_SOUNDS:
         raise ValueError(f"{N} sounds: the limit is 1..{TDOA_MAX_SOUNDS}")
     sizes = [t.shape[0] for t in (lags, sens, snd) if t.dim() == 3]
-    sizes += [int(np.size(v)) for v in (lr, C) if np.size(v) > 1]
+    sizes += [int(np.size(v)) for _w, v in per_problem if np.size(v) > 1]
     M = max(sizes) if sizes else 1
     if any(s != M for s in sizes):
         raise ValueError(f"inputs disagree on the number of problems: {sizes}")
-    lrs, cs = _per_problem(lr, M, "lr"), _per_problem(C, M, "C")
+    values = [_per_problem(v, M, what) for what, v in per_problem]
+    dev = _device_of(lags)
+    _lib.require_gpu(dev.index or 0)
+    obs = (lags.detach().to(dev) / sr).to(torch.float32).contiguous()
+    sens0 = sens.detach().to(dev, torch.float32).expand(M, 4, 3).contiguous()
+    snd0 = snd.detach()[..., :2].to(dev, torch.float32).expand(M, N, 2).contiguous()
+    return M, N, dev, obs, sens0, snd0, values
+
+
+def optimize_positions_device(observed_lags, initial_sensor_positions, initial_sound_positions, lr=0.01,
+                              lossfun=F.mse_loss, num_epochs=1000, C=342.29, sr=96000, eps=1e-12, patience=10):
+    """M independent optimize_positions fits in one launch.  observed_lags [M, N, 2] (or [N, 2]) in samples,
+    initial_sensor_positions [M, 4, 3] (or [4, 3]), initial_sound_positions [M, N, >= 2] (or [N, >= 2]); lr and C
+    numbers or M of them.  Returns PositionFits."""
+    loss = _loss_code(lossfun)
     num_epochs, patience = int(num_epochs), int(math.ceil(patience))
     if num_epochs < 1:
         raise ValueError("num_epochs must be at least 1")
 
-    dev = _device_of(lags)
-    _lib.require_gpu(dev.index or 0)
+    M, N, dev, obs, sens0, snd0, (lrs, cs) = _position_inputs(observed_lags, initial_sensor_positions,
+                                                             initial_sound_positions, (("lr", lr), ("C", C)), sr)
     L = _lib.lib()
-    obs = (lags.detach().to(dev) / sr).to(torch.float32).contiguous()
-    sens0 = sens.detach().to(dev, torch.float32).expand(M, 4, 3).contiguous()
-    snd0 = snd.detach()[..., :2].to(dev, torch.float32).expand(M, N, 2).contiguous()
     c0 = torch.tensor(cs, dtype=torch.float32, device=dev)
     table, rows = _rate_rows(lrs, lambda v: _position_tables(v, num_epochs)[1])
     table, rows = table.to(dev), rows.to(dev)
@@ -647,6 +656,26 @@ def optimize_positions_device(observed_lags, initial_sensor_positions, initial_s
                              sensors.data_ptr(), sounds.data_ptr(), c_out.data_ptr(), losses.data_ptr(),
                              epochs.data_ptr(), _stream(dev)), "ofp_tdoa_fit")
     return PositionFits(sensors, sounds, c_out, losses, epochs)
+
+
+def tdoa_loss_and_grads_device(observed_lags, sensor_positions, sound_positions, C=342.29, lossfun=F.mse_loss,
+                               sr=96000):
+    """Loss and unclipped gradients of optimize_positions' objective at the given point, by the fit's own forward
+    and reduction (k_tdoa_fit leaving after its first epoch's sums, csrc/ofp_train.hip).  Inputs broadcast as in
+    optimize_positions_device.  Returns (loss [M], {"sensors": [M, 4, 3], "sounds": [M, N, 2], "C": [M]}) on the
+    GPU."""
+    loss = _loss_code(lossfun)
+    M, N, dev, obs, sens0, snd0, (cs,) = _position_inputs(observed_lags, sensor_positions, sound_positions,
+                                                          (("C", C),), sr)
+    L = _lib.lib()
+    c0 = torch.tensor(cs, dtype=torch.float32, device=dev)
+    out_loss = torch.empty(M, dtype=torch.float32, device=dev)
+    g_sens, g_snd, g_c = torch.empty_like(sens0), torch.empty_like(snd0), torch.empty_like(c0)
+    with torch.cuda.device(dev):
+        check(L.ofp_tdoa_loss_grads(M, N, obs.data_ptr(), N * 2 if obs.dim() == 3 else 0, sens0.data_ptr(),
+                                    snd0.data_ptr(), c0.data_ptr(), loss, out_loss.data_ptr(), g_sens.data_ptr(),
+                                    g_snd.data_ptr(), g_c.data_ptr(), _stream(dev)), "ofp_tdoa_loss_grads")
+    return out_loss, {"sensors": g_sens, "sounds": g_snd, "C": g_c}
 
 
 def optimize_positions(observed_lags, initial_sensor_positions, initial_sound_positions, lr=0.01,

@@ -414,6 +414,10 @@ struct TdoaArgs {
     float* c;
     float* lossc;
     int32_t* epochs;
+    int grads_only;  // leave after the first epoch's sums: loss [M], g_sensors [M][12], g_sounds [M][N][2], g_c [M]
+    float* g_sensors;
+    float* g_sounds;
+    float* g_c;
 };
 
 __device__ __forceinline__ void adam1(float& p, float& mo, float& vo, float gr, float nstep, float bc2) {
@@ -443,7 +447,7 @@ __global__ __launch_bounds__(kT) void k_tdoa_fit(const TdoaArgs a) {
         SP[n] = a.sounds0[(m * N + n) * 2], SP[N + n] = a.sounds0[(m * N + n) * 2 + 1];
         SM[n] = SM[N + n] = SV[n] = SV[N + n] = 0.0f;
     }
-    const float* rates = a.rates + (int64_t)a.rate_idx[m] * E * 4;
+    const float* rates = a.grads_only ? nullptr : a.rates + (int64_t)a.rate_idx[m] * E * 4;
     const float inv_numel = 1.0f / (float)(2 * N);
     const float mse_scale = 2.0f / (float)(2 * N);
     float last = INFINITY;
@@ -494,6 +498,18 @@ __global__ __launch_bounds__(kT) void k_tdoa_fit(const TdoaArgs a) {
         for (int i = 0; i < 15; ++i)
             acc[i] = ((s_part[e & 1][0][i] + s_part[e & 1][1][i]) + s_part[e & 1][2][i]) + s_part[e & 1][3][i];
         const float loss = acc[13] * inv_numel;
+        if (a.grads_only) {  // the fit's own sums, unclipped; every thread wrote its own SG entries
+            for (int n = tid; n < N; n += kT) {
+                float* o = a.g_sounds + (m * N + n) * 2;
+                o[0] = SG[n], o[1] = SG[N + n];
+            }
+            if (tid == 0) {
+                a.lossc[m] = loss;
+                for (int i = 0; i < 12; ++i) a.g_sensors[m * 12 + i] = acc[i];
+                a.g_c[m] = acc[12];
+            }
+            return;
+        }
         bool stop = false;
         if (loss < last - a.eps) {
             last = loss;
@@ -533,6 +549,14 @@ __global__ __launch_bounds__(kT) void k_tdoa_fit(const TdoaArgs a) {
 }
 
 ofp::LdsAttrCache g_train_lds, g_tdoa_lds;
+
+int tdoa_launch(const TdoaArgs& a, int64_t M, hipStream_t st) {
+    const size_t bytes = (size_t)a.N * 8 * sizeof(float);
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_tdoa_fit, bytes, g_tdoa_lds)) return rc;
+    hipLaunchKernelGGL(k_tdoa_fit, dim3((unsigned)M), dim3(kT), bytes, st, a);
+    OFP_LAUNCH_CHECK("k_tdoa_fit");
+    return OFP_OK;
+}
 
 int fcnn_launch(const FcnnDesc& d, const FcnnArgs& a, int64_t M, int64_t ws_bytes, hipStream_t st) {
     const int64_t bytes = (int64_t)d.arena_floats * 4;
@@ -610,13 +634,26 @@ int ofp_tdoa_fit(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, c
     OFP_REQUIRE(d_obs && d_sensors0 && d_sounds0 && d_c0 && d_rates && d_rate_idx && d_sensors && d_sounds && d_c &&
                     d_loss && d_epochs,
                 "ofp_tdoa_fit: NULL argument");
-    TdoaArgs a{d_obs,    obs_stride, d_sensors0, d_sounds0, d_c0,     d_rates, d_rate_idx, (int)n,
-               num_epochs, loss,     eps,        patience,  d_sensors, d_sounds, d_c,      d_loss, d_epochs};
-    const size_t bytes = (size_t)n * 8 * sizeof(float);
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_tdoa_fit, bytes, g_tdoa_lds)) return rc;
-    hipLaunchKernelGGL(k_tdoa_fit, dim3((unsigned)M), dim3(kT), bytes, (hipStream_t)stream, a);
-    OFP_LAUNCH_CHECK("k_tdoa_fit");
-    return OFP_OK;
+    TdoaArgs a{d_obs,      obs_stride, d_sensors0, d_sounds0, d_c0,      d_rates,  d_rate_idx, (int)n,
+               num_epochs, loss,       eps,        patience,  d_sensors, d_sounds, d_c,        d_loss,
+               d_epochs,   0,          nullptr,    nullptr,   nullptr};
+    return tdoa_launch(a, M, (hipStream_t)stream);
+}
+
+int ofp_tdoa_loss_grads(int64_t M, int64_t n, const float* d_obs, int64_t obs_stride, const float* d_sensors,
+                        const float* d_sounds, const float* d_c, int32_t loss, float* d_loss, float* d_g_sensors,
+                        float* d_g_sounds, float* d_g_c, void* stream) {
+    OFP_REQUIRE(M >= 1 && M <= 1 << 20, "ofp_tdoa_loss_grads: %lld problems (limit: 1..2^20)", (long long)M);
+    OFP_REQUIRE(n >= 1 && n <= kMaxSounds, "ofp_tdoa_loss_grads: %lld sounds (limit: 1..%d)", (long long)n,
+                kMaxSounds);
+    OFP_REQUIRE(loss == 0 || loss == 1, "ofp_tdoa_loss_grads: loss %d (0 = L1, 1 = MSE)", loss);
+    OFP_REQUIRE(d_obs && d_sensors && d_sounds && d_c && d_loss && d_g_sensors && d_g_sounds && d_g_c,
+                "ofp_tdoa_loss_grads: NULL argument");
+    // the fit itself, leaving after the first epoch's reduction; no rate tables are read, no state is written
+    TdoaArgs a{d_obs,   obs_stride, d_sensors, d_sounds, d_c,     nullptr, nullptr, (int)n,
+               1,       loss,       0.0f,      0,        nullptr, nullptr, nullptr, d_loss,
+               nullptr, 1,          d_g_sensors, d_g_sounds, d_g_c};
+    return tdoa_launch(a, M, (hipStream_t)stream);
 }
 
 }  // extern "C"
