@@ -209,6 +209,49 @@ int ofp_detector_set_tuning(ofp_detector* det, const ofp_detect_tuning* t);
 int64_t ofp_detect_workspace_bytes(const ofp_detector* det, int64_t n_clips, int64_t n_samples,
                                    int64_t warm_samples);
 
+/* The plan of a call: which of the detector's kernel variants a call of these sizes runs, and the geometry that decides
+ * it.  Host arithmetic only: the queries launch nothing and allocate nothing on the device. */
+typedef struct ofp_detect_plan {
+    int64_t n_w;        /* warm samples through the high-pass: min(warm, n_samples), at least 0 */
+    int64_t n_wb;       /* warm samples through followers and tracker: whole blocks of n_w */
+    int64_t Nm;         /* floor(n_samples / B) * B: rows of `rel` */
+    int64_t U;          /* follower stream length n_wb + Nm */
+    int64_t V;          /* high-pass stream length n_w + Nm */
+    int64_t Nv;         /* floats per series of the planar input copy: n_w + n_samples rounded up to 4 */
+    int64_t hp_L;       /* IIR stage: samples per chunk */
+    int64_t hp_S;       /* sub-chunks per chunk */
+    int64_t hp_R;       /* speculative candidates per chunk */
+    int64_t hp_span;    /* chunks one speculative run walks through */
+    int64_t ar_L;       /* follower stage: samples per chunk */
+    int64_t ar_S;       /* chunks one speculative warm-up run walks through */
+    int64_t mm_L;       /* tracker stage: samples per chunk */
+    int64_t mm_S;       /* chunks one speculative warm-up run walks through */
+    int64_t tu;         /* time steps per tile of the entry and exit transposes */
+    int32_t sm_seg;     /* hysteresis machine time-parallel over the visit list */
+    int32_t merge;      /* followers / tracker: the two recurrences of a chunk in one lane */
+    int32_t hp_early;   /* whole IIR re-runs stop early at a sub-chunk boundary */
+    int32_t hp_staged;  /* IIR candidates in stages with duplicate runs removed between them */
+    int32_t hp_spread;  /* the candidates launch has no more workgroups than the device has CUs */
+    int32_t hp_lines;   /* IIR output walk stores complete 128-byte lines */
+    int32_t ar_sym;     /* closed-form guess for a symmetric slow follower */
+    int32_t ar_through; /* followers: walk-through chunks are their own pass 0 */
+    int32_t ar_lines;   /* followers: output walks store complete 128-byte lines */
+    int32_t db_sym;     /* the dB pass also forms the per-chunk sums of the closed-form guess */
+    int32_t mm_il;      /* tracker, crossing pass and backtracking read the caller's interleaved `rel` */
+    int32_t mm_through; /* tracker: walk-through chunks are their own pass 0 */
+    int32_t ar_il;      /* followers write the caller's interleaved `rel` themselves; back to linear in place */
+    int32_t use_sum;    /* the back-to-linear pass leaves block extremes for the crossing pass */
+} ofp_detect_plan;
+/* What ofp_detect_offline (and every other entry point) decides for a call of `det` with these sizes.  want_rel: the
+ * call passes a d_rel; d_rel: its address (only its low four bits are used: the followers write `rel` themselves only
+ * into a 16-byte-aligned array), or NULL to leave the alignment out. */
+int ofp_detect_plan_query(const ofp_detector* det, int64_t n_clips, int64_t n_samples, int64_t warm, int want_rel,
+                          const void* d_rel, ofp_detect_plan* out);
+/* The same for a detector that is never created: its parameters, a tuning (NULL: defaults) and the device's CU count.
+ * Makes no HIP call, so it also runs on a machine without a GPU. */
+int ofp_detect_plan_for(const ofp_detector_params* p, const ofp_detect_tuning* t, int n_cus, int64_t n_clips,
+                        int64_t n_samples, int64_t warm, int want_rel, const void* d_rel, ofp_detect_plan* out);
+
 /* detect_onsets_amplitude (detection.py:19-86) for a batch of independent clips.
  *   d_x        [n_clips][n_samples][C] float32, interleaved as the reference expects
  *   warm       number of leading samples double-processed by init_minmax_tracker

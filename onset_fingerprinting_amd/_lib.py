@@ -72,6 +72,18 @@ class DetectTuning(ctypes.Structure):
     ]
 
 
+class DetectPlan(ctypes.Structure):
+    """ofp_detect_plan: the geometry of a call and the kernel variants it runs (include/onsetfp.h)."""
+    _fields_ = ([(n, ctypes.c_int64) for n in ("n_w", "n_wb", "Nm", "U", "V", "Nv", "hp_L", "hp_S", "hp_R", "hp_span",
+                                               "ar_L", "ar_S", "mm_L", "mm_S", "tu")] +
+                [(n, ctypes.c_int32) for n in ("sm_seg", "merge", "hp_early", "hp_staged", "hp_spread", "hp_lines",
+                                               "ar_sym", "ar_through", "ar_lines", "db_sym", "mm_il", "mm_through",
+                                               "ar_il", "use_sum")])
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class HopConfig(ctypes.Structure):
     _fields_ = [
         ("n_fft", ctypes.c_int32),
@@ -214,6 +226,9 @@ SIGNATURES = {
     "ofp_detector_set_tuning": (ctypes.c_int, [_vp, ctypes.POINTER(DetectTuning)]),
     "ofp_pack_records": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, ctypes.c_int32, _vp, _vp]),
     "ofp_detect_workspace_bytes": (_i64, [_vp, _i64, _i64, _i64]),
+    "ofp_detect_plan_query": (ctypes.c_int, [_vp, _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.POINTER(DetectPlan)]),
+    "ofp_detect_plan_for": (ctypes.c_int, [ctypes.POINTER(DetectorParams), ctypes.POINTER(DetectTuning), ctypes.c_int,
+                                           _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.POINTER(DetectPlan)]),
     "ofp_detect_offline": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
                                           ctypes.POINTER(_i64), _vp]),
     "ofp_detect_offline_enqueue": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),

@@ -3437,6 +3437,26 @@ Layout make_layout(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t wa
     return l;
 }
 
+// The plan of a call as its kernels are chosen: make_layout, and the one decision that depends on an address -- the
+// followers store 16-byte groups into the caller's `rel`, so an array that is not 16-byte aligned takes the planar form.
+// (open_call and the plan queries share this body.)
+Layout plan_call(const ofp_detector* d, int64_t n_clips, int64_t N, int64_t warm, bool rel, uintptr_t rel_addr) {
+    Layout l = make_layout(d, n_clips, N, warm, rel);
+    if ((rel_addr & 15u) != 0) l.ar_il = false;  // (16-byte stores into the caller's array)
+    return l;
+}
+
+void report_plan(const Layout& l, ofp_detect_plan* out) {
+    const Geom& g = l.g;
+    out->n_w = g.n_w; out->n_wb = g.n_wb; out->Nm = g.Nm; out->U = g.U; out->V = g.V; out->Nv = g.Nv;
+    out->hp_L = l.hp_L; out->hp_S = l.hp_S; out->hp_R = l.hp_R; out->hp_span = l.hp_span;
+    out->ar_L = l.ar_L; out->ar_S = l.ar_S; out->mm_L = l.mm_L; out->mm_S = l.mm_S; out->tu = l.tu;
+    out->sm_seg = l.sm_seg; out->merge = l.merge; out->hp_early = l.hp_early; out->hp_staged = l.hp_staged;
+    out->hp_spread = l.hp_spread; out->hp_lines = l.hp_lines; out->ar_sym = l.ar_sym; out->ar_through = l.ar_through;
+    out->ar_lines = l.ar_lines; out->db_sym = l.db_sym; out->mm_il = l.mm_il; out->mm_through = l.mm_through;
+    out->ar_il = l.ar_il; out->use_sum = l.use_sum;
+}
+
 // Zeroed int counters for the verification passes: the region is cleared once per call and every
 // use takes a fresh slot (the last slot is recycled with a fill when a call needs more).
 struct Counters {
@@ -3593,7 +3613,7 @@ int open_call(Call& c, ofp_detector* d, const float* d_x, int64_t n_clips, int64
     OFP_REQUIRE(d_x || N == 0, "ofp_detect_offline: d_x is NULL");
     OFP_REQUIRE(d_records || cap == 0, "ofp_detect_offline: d_records is NULL");
     OFP_REQUIRE(n_clips <= 65535, "ofp_detect_offline: at most 65535 clips per call");
-    c.l = make_layout(d, n_clips, N, warm, d_rel != nullptr);
+    c.l = plan_call(d, n_clips, N, warm, d_rel != nullptr, reinterpret_cast<uintptr_t>(d_rel));
     const Layout& l = c.l;
     if (ws_bytes < l.total)
         return ofp::fail(OFP_ERR_WORKSPACE, "work space %lld < required %lld bytes", (long long)ws_bytes, (long long)l.total);
@@ -3607,7 +3627,6 @@ int open_call(Call& c, ofp_detector* d, const float* d_x, int64_t n_clips, int64
     c.xt = c.at<float>(l.o_xt); c.xdb = c.at<float>(l.o_xdb); c.dif = c.at<float>(l.o_dif); c.rel_warm = c.at<float>(l.o_relw);
     c.sum_max = l.use_sum ? c.at<uint32_t>(l.o_sum) : nullptr;
     c.sum_minv = l.use_sum ? c.sum_max + n_clips * l.nb * l.g.C : nullptr;
-    if ((reinterpret_cast<uintptr_t>(d_rel) & 15u) != 0) c.l.ar_il = false;  // (16-byte stores into the caller's array)
     return OFP_OK;
 }
 
@@ -4350,6 +4369,29 @@ int64_t ofp_detect_workspace_bytes(const ofp_detector* d, int64_t n_clips, int64
                                    int64_t warm) {
     if (!d || n_clips < 0 || n_samples < 0) return -1;
     return make_layout(d, n_clips, n_samples, warm).total;
+}
+
+int ofp_detect_plan_query(const ofp_detector* d, int64_t n_clips, int64_t n_samples, int64_t warm, int want_rel,
+                          const void* d_rel, ofp_detect_plan* out) {
+    OFP_REQUIRE(d && out, "ofp_detect_plan_query: NULL argument");
+    OFP_REQUIRE(n_clips >= 1 && n_samples >= 0, "ofp_detect_plan_query: bad sizes");
+    report_plan(plan_call(d, n_clips, n_samples, warm, want_rel != 0, reinterpret_cast<uintptr_t>(d_rel)), out);
+    return OFP_OK;
+}
+
+int ofp_detect_plan_for(const ofp_detector_params* p, const ofp_detect_tuning* t, int n_cus, int64_t n_clips,
+                        int64_t n_samples, int64_t warm, int want_rel, const void* d_rel, ofp_detect_plan* out) {
+    OFP_REQUIRE(p && out, "ofp_detect_plan_for: NULL argument");
+    OFP_REQUIRE(p->n_channels >= 1 && p->n_channels <= 4096 && p->block_size >= 1 && p->block_size <= (1 << 20),
+                "ofp_detect_plan_for: n_channels or block_size out of range");
+    OFP_REQUIRE(n_cus >= 1, "ofp_detect_plan_for: n_cus must be positive");
+    // a host-side detector: the parameters, the tuning and the CU count are all that make_layout reads; no HIP call
+    ofp_detector d;
+    d.p = *p;
+    if (t) d.t = *t;
+    else std::memset(&d.t, 0, sizeof(d.t));
+    d.n_cus = n_cus;
+    return ofp_detect_plan_query(&d, n_clips, n_samples, warm, want_rel, d_rel, out);
 }
 
 int ofp_detect_offline(ofp_detector* d, const float* d_x, int64_t n_clips, int64_t N, int64_t warm, float* d_rel,

@@ -32,6 +32,47 @@ def _dev(device):
     return torch.device("cuda", int(device))
 
 
+def _detector_params(n_signals, block_size, floor, hipass_freq, fast_ar, slow_ar, on_threshold, off_threshold,
+                     cooldown, backtrack, backtrack_buffer_size, backtrack_smooth_size, sr):
+    """The reference's kwargs as (ofp_detector_params, on [C] float64, off [C] float64).  Host arithmetic only."""
+    p = DetectorParams()
+    p.n_channels = int(n_signals)
+    p.block_size = int(block_size)
+    p.floor_db = floor
+    p.hp_enabled = int(hipass_freq != 0)
+    if p.hp_enabled:
+        # detection.py:492-496: scipy design in double, coefficients cast to float32
+        b, a = sig.butter(4, hipass_freq, btype="high", analog=False, output="ba", fs=sr)
+        p.hp_b[:] = [float(v) for v in np.float32(b)]
+        p.hp_a[:] = [float(v) for v in np.float32(a)]
+    # detection.py:514-515: the follower coefficients are np.float32(1 / x)
+    p.fast_attack, p.fast_release = np.float32(1 / fast_ar[0]), np.float32(1 / fast_ar[1])
+    p.slow_attack, p.slow_release = np.float32(1 / slow_ar[0]), np.float32(1 / slow_ar[1])
+    # detection.py:703-708
+    p.alpha_min, p.alpha_max, p.minmin = 1e-4, 1e-5, 2.0
+    p.min0, p.max0 = 0.0, 10.0
+    on = np.ascontiguousarray(np.broadcast_to(np.asarray(on_threshold, dtype=np.float64), (n_signals,)))
+    off = np.ascontiguousarray(np.broadcast_to(np.asarray(off_threshold, dtype=np.float64), (n_signals,)))
+    p.manual = int(bool(np.all(np.asarray(on_threshold) > 1)))  # detection.py:687
+    p.cooldown = int(cooldown)
+    p.backtrack = int(bool(backtrack))
+    p.backtrack_buffer_size = int(backtrack_buffer_size)
+    if backtrack:
+        assert block_size <= backtrack_buffer_size, \
+            "backtrack_buffer_size should be at least block_size!"  # detection.py:716-718
+        b_alpha = np.float32(2 / (backtrack_smooth_size + 1))
+        p.backtrack_alpha = b_alpha
+        p.backtrack_tol = np.float32((1 - b_alpha) ** backtrack_buffer_size)
+    return p, on, off
+
+
+def _tuning(kw):
+    t = DetectTuning()
+    for k, v in kw.items():
+        setattr(t, k, int(v))
+    return t
+
+
 class _DeviceDetector:
     """Owns the opaque ofp_detector handle built from the reference's kwargs."""
 
@@ -42,34 +83,8 @@ class _DeviceDetector:
         _lib.require_gpu(_dev(device).index or 0)
         self.device = _dev(device)
         torch.cuda.set_device(self.device)
-        p = DetectorParams()
-        p.n_channels = int(n_signals)
-        p.block_size = int(block_size)
-        p.floor_db = floor
-        p.hp_enabled = int(hipass_freq != 0)
-        if p.hp_enabled:
-            # detection.py:492-496: scipy design in double, coefficients cast to float32
-            b, a = sig.butter(4, hipass_freq, btype="high", analog=False, output="ba", fs=sr)
-            p.hp_b[:] = [float(v) for v in np.float32(b)]
-            p.hp_a[:] = [float(v) for v in np.float32(a)]
-        # detection.py:514-515: the follower coefficients are np.float32(1 / x)
-        p.fast_attack, p.fast_release = np.float32(1 / fast_ar[0]), np.float32(1 / fast_ar[1])
-        p.slow_attack, p.slow_release = np.float32(1 / slow_ar[0]), np.float32(1 / slow_ar[1])
-        # detection.py:703-708
-        p.alpha_min, p.alpha_max, p.minmin = 1e-4, 1e-5, 2.0
-        p.min0, p.max0 = 0.0, 10.0
-        on = np.ascontiguousarray(np.broadcast_to(np.asarray(on_threshold, dtype=np.float64), (n_signals,)))
-        off = np.ascontiguousarray(np.broadcast_to(np.asarray(off_threshold, dtype=np.float64), (n_signals,)))
-        p.manual = int(bool(np.all(np.asarray(on_threshold) > 1)))  # detection.py:687
-        p.cooldown = int(cooldown)
-        p.backtrack = int(bool(backtrack))
-        p.backtrack_buffer_size = int(backtrack_buffer_size)
-        if backtrack:
-            assert block_size <= backtrack_buffer_size, \
-                "backtrack_buffer_size should be at least block_size!"  # detection.py:716-718
-            b_alpha = np.float32(2 / (backtrack_smooth_size + 1))
-            p.backtrack_alpha = b_alpha
-            p.backtrack_tol = np.float32((1 - b_alpha) ** backtrack_buffer_size)
+        p, on, off = _detector_params(n_signals, block_size, floor, hipass_freq, fast_ar, slow_ar, on_threshold,
+                                      off_threshold, cooldown, backtrack, backtrack_buffer_size, backtrack_smooth_size, sr)
         self.params = p
         self._on, self._off = on, off
         h = ctypes.c_void_p()
@@ -90,9 +105,7 @@ class _DeviceDetector:
             pass
 
     def set_tuning(self, **kw):
-        t = DetectTuning()
-        for k, v in kw.items():
-            setattr(t, k, int(v))
+        t = _tuning(kw)
         check(self.lib.ofp_detector_set_tuning(self.handle, ctypes.byref(t)), "ofp_detector_set_tuning")
 
 
@@ -120,6 +133,17 @@ class BatchDetector:
 
     def workspace_bytes(self, n_clips, n_samples, warm):
         return int(self.d.lib.ofp_detect_workspace_bytes(self.d.handle, n_clips, n_samples, warm))
+
+    def plan(self, n_clips, n_samples, warm=None, want_rel=True, rel=None):
+        """What a call of these sizes decides (ofp_detect_plan_query): a dict of the geometry and one 0 / 1 per kernel
+        variant.  `rel`: the tensor (or device address) the call will write `rel` into -- `detect` allocates an aligned
+        one; an array that is not 16-byte aligned switches `ar_il` off.  Nothing is launched."""
+        warm = int(0.5 * self.sr) if warm is None else int(warm)
+        addr = rel.data_ptr() if torch.is_tensor(rel) else rel
+        plan = _lib.DetectPlan()
+        check(self.d.lib.ofp_detect_plan_query(self.d.handle, n_clips, n_samples, warm, int(bool(want_rel)),
+                                               addr if want_rel else None, ctypes.byref(plan)), "ofp_detect_plan_query")
+        return plan.as_dict()
 
     def reserve(self, n_clips, n_samples, warm):
         need = self.workspace_bytes(n_clips, n_samples, warm)
@@ -259,6 +283,24 @@ def detect_batch(x, block_size=128, sr=96000, device=0, warm=None, want_rel=True
     recs = BatchDetector.records_to_numpy(out)
     rel = out["rel"].cpu().numpy() if want_rel else None
     return recs, rel, bd.last_info
+
+
+def detect_plan(n_signals, n_clips, n_samples, block_size=128, sr=96000, warm=None, want_rel=True, rel_aligned=True,
+                tuning=None, n_cus=256, floor=-70.0, hipass_freq=2000.0, fast_ar=(3.0, 383.0), slow_ar=(2205.0, 2205.0),
+                on_threshold=0.5, off_threshold=0.1, cooldown=1323, backtrack=False, backtrack_buffer_size=128,
+                backtrack_smooth_size=5):
+    """`BatchDetector(...).plan(...)` without a detector or a GPU (ofp_detect_plan_for): the plan a device of `n_cus`
+    compute units would make for `BatchDetector`'s arguments, a tuning dict and the call's sizes.  rel_aligned=False: a
+    `rel` array 4 bytes off a 16-byte boundary."""
+    p, _, _ = _detector_params(n_signals, block_size, floor, hipass_freq, fast_ar, slow_ar, on_threshold, off_threshold,
+                               cooldown, backtrack, backtrack_buffer_size, backtrack_smooth_size, sr)
+    t = _tuning(tuning or {})
+    warm = int(0.5 * sr) if warm is None else int(warm)
+    plan = _lib.DetectPlan()
+    check(_lib.lib().ofp_detect_plan_for(ctypes.byref(p), ctypes.byref(t), int(n_cus), n_clips, n_samples, warm,
+                                         int(bool(want_rel)), None if rel_aligned or not want_rel else 4,
+                                         ctypes.byref(plan)), "ofp_detect_plan_for")
+    return plan.as_dict()
 
 
 def group_onsets_device(out, n_channels, max_distance=1000, min_channels=3, close_channel=None, cap_groups=None):

@@ -78,3 +78,4 @@ def test_struct_mirrors_follow_the_header_field_for_field():
     assert fields("ofp_detect_tuning") == [f[0] for f in _lib.DetectTuning._fields_]
     assert fields("ofp_hop_config") == [f[0] for f in _lib.HopConfig._fields_]
     assert fields("ofp_detector_params") == [f[0] for f in _lib.DetectorParams._fields_]
+    assert fields("ofp_detect_plan") == [f[0] for f in _lib.DetectPlan._fields_]

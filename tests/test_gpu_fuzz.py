@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 import pytest
+import torch  # noqa: F401  (loaded before the library: this file then also runs on its own)
 
 import oracle
 from onset_fingerprinting_amd import synth
@@ -97,6 +98,39 @@ def test_random_configurations_match_the_oracle(capsys):
         assert np.array_equal(bits(rel[0]), bits(orel)), msg
         n_onsets += len(c)
     assert n_onsets > 8 * n_cases
+
+
+def test_random_geometries_match_the_oracle():
+    """Random GEOMETRIES (tests/detect_geometry_cases.random_geometry_case): any block size from 8 to 300, warm-ups at the
+    edges (none, one sample, a block less or more one, the whole clip and past it), clips cut to a random length, `x` and
+    `rel` off their 16-byte boundaries, chunk lengths that are no multiples of 32 or of 4 -- the layout guards of
+    make_layout from both sides.  Records and every bit of `rel` against the oracle with the same warm-up, and the plan the
+    detector reports against its restatement."""
+    import torch
+
+    from onset_fingerprinting_amd.detection import BatchDetector
+    from tests import detect_geometry_cases as cases
+    n_cases = int(os.environ.get("OFP_FUZZ_CASES", str(cases.FUZZ_CASES)))
+    rng = np.random.default_rng(int(os.environ.get("OFP_FUZZ_SEED", str(cases.FUZZ_SEED))))
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_onsets = 0
+    for i in range(n_cases):
+        case = cases.random_geometry_case(rng)
+        msg = (i, case)
+        warm = cases.fuzz_warm(case)
+        x = cases.make_input(case)
+        bd = BatchDetector(case["C"], case["B"], sr=SR, device=0)
+        bd.set_tuning(**case["tuning"])
+        recs, rel, plan, _ = cases.gpu_detect(bd, x, warm, case["x_off"], case["rel_off"])
+        want = cases.restate_plan(dict(n_signals=case["C"], block_size=case["B"], sr=SR), case["tuning"], n_cus, 1,
+                                  case["N"], warm, True, case["rel_off"] == 0)[0]
+        assert plan == want, (msg, {k: (plan[k], want[k]) for k in plan if plan[k] != want[k]})
+        c, o, orel = oracle.OracleDetector(case["C"], case["B"], sr=SR).detect(x[0], warm)
+        assert np.array_equal(recs[0]["channel"], np.array(c, np.int64)), msg
+        assert np.array_equal(recs[0]["sample"], np.array(o, np.int64)), msg
+        assert rel[0].shape == orel.shape and np.array_equal(bits(rel[0]), bits(orel)), msg
+        n_onsets += len(c)
+    assert n_onsets > 3 * n_cases
 
 
 def test_random_batches_of_clips():

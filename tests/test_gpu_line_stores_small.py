@@ -3,8 +3,8 @@ smallest shapes at which they can go wrong.  The row owners hand element offsets
 the wave; lanes whose batches have run out load a shared line instead of skipping their loads.  Every case must give the
 oracle's records and `rel` bit for bit, and the bits of the same call with lane-private stores (line_stores=-1).
 
-The plan does not report which form it took, so each case checks make_layout's conditions for the line forms by arithmetic
-(`takes_lines`): with lane_merge=1 they are geometric only.
+Each case checks make_layout's conditions for the line forms by arithmetic (`takes_lines`: with lane_merge=1 they are
+geometric only) and asks the detector's plan (BatchDetector.plan) which form the call takes.
 
 Offsets past 2^32 bytes have no case here: 24 clips x 8 channels x 60 s is a 2.2 GB stream (offsets below 2^32 bytes), and a
 call whose stream passes 4.3 GB needs as much again for its input and for each of the two `rel` outputs compared.  The
@@ -52,6 +52,11 @@ def check(key, make, tuning, **kw):
     x, c, o, orel = reference(key, make, **kw)
     got = {}
     for ls in (0, -1):
+        # (every case here asserts `takes_lines`: the plan must say the same, and say no for the lane-private twin)
+        bd = detection.BatchDetector(x.shape[1], device=0, **kw)
+        bd.set_tuning(**dict(tuning, lane_merge=1, line_stores=ls))
+        plan = bd.plan(1, len(x))
+        assert plan["hp_lines"] == plan["ar_lines"] == int(ls == 0), (ls, plan)
         recs, rel, _ = detection.detect_batch(x[None], tuning=dict(tuning, lane_merge=1, line_stores=ls), **kw)
         assert np.array_equal(recs[0]["channel"], c) and np.array_equal(recs[0]["sample"], o), f"records, line_stores={ls}"
         assert rel[0].shape == orel.shape

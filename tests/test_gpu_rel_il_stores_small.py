@@ -9,7 +9,7 @@ with tuning interleaved=-1, the planar path.  The block extremes (sum_max / sum_
 the crossing pass, so the records stand for them.
 
 Which form a call took: `takes_il` restates make_layout's conditions by arithmetic (with lane_merge=1 and line_stores=1
-they are geometric only), and `untouched_run` observes it -- the work space is filled with a byte pattern before the call,
+they are geometric only), the detector's plan reports it (BatchDetector.plan), and `untouched_run` observes it -- the work space is filled with a byte pattern before the call,
 and only the new form leaves a stretch as long as the planar `dif` array (C x U floats per clip) as it was.
 
 A value that is NaN compares as NaN on both sides instead of bit for bit against the ORACLE only: the sign and payload of
@@ -83,6 +83,9 @@ def check(key, make, B, warm, tuning, expect_il, **kw):
     for il in (0, -1):
         bd = BatchDetector(C, B, device=0, **kw)
         bd.set_tuning(**dict(tuning, lane_merge=1, line_stores=1, interleaved=il))
+        plan = bd.plan(n_clips, N, warm)
+        assert plan["ar_il"] == int(expect_il and il == 0) and plan["mm_il"] == int(il == 0 and C in (4, 8, 64)), (il, plan)
+        assert {k: plan[k] for k in g} == g
         ws = bd.reserve(n_clips, N, warm)
         ws.fill_(FILL)
         out = bd.detect(xt, warm=warm)
