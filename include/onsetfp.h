@@ -1035,7 +1035,13 @@ int ofp_tdoa_loss_grads(int64_t M, int64_t n, const float* d_obs, int64_t obs_st
  * ofp_conv1d_backward: d_dz [n][cout][wc] (wc = w + 2 padding - dilation (k - 1)) -> d_dw [cout][cin/groups][k],
  *   d_db [cout] and, unless NULL, d_dx [n][cin][w].  ofp_batchnorm_train_forward / _backward: BatchNorm1d in training
  *   mode on d_x [n][C][w]: d_y, the saved d_mean / d_rstd [C], running statistics updated in place; and d_dx,
- *   d_dgamma, d_dbeta from d_dy.  ofp_nadam_step: one NAdam step of n elements with one row of the rate table. */
+ *   d_dgamma, d_dbeta from d_dy.  ofp_nadam_step: one NAdam step of n elements with one row of the rate table.
+ * ofp_linear_head_train: the Linear head both trainers end in, by the launches of their epochs: d_h [n][F], d_w [O][F],
+ *   d_b [O], targets d_y [n][O], loss 0 = L1, 1 = MSE -> d_out [n][O] = h W^T + b, d_dy [n][O] = d loss / d out of
+ *   the mean loss, d_loss [1] the mean loss, d_dw [O][F], d_db [O], d_dh [n][F].  Sums over features and over samples
+ *   are fp64 rounded once (samples in chunks of 64, the chunks added in order); d_dh is an fp32 fmaf chain over the
+ *   outputs.  Limits: n 1..1024, O 1..16, F >= 1; beyond them OFP_ERR_INVALID before any launch (-1 from the size
+ *   function). */
 typedef struct ofp_cnn_config {
     int32_t n_conv;
     int32_t channels[4];
@@ -1059,6 +1065,10 @@ int64_t ofp_conv1d_backward_workspace_bytes(int64_t n, int32_t cin, int32_t w, i
 int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, const float* d_w, int32_t cout,
                         int32_t k, int32_t padding, int32_t dilation, int32_t groups, const float* d_dz, float* d_dx,
                         float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
+int64_t ofp_linear_head_train_workspace_bytes(int64_t n, int32_t F, int32_t O);
+int ofp_linear_head_train(const float* d_h, int64_t n, int32_t F, const float* d_w, int32_t O, const float* d_b,
+                          const float* d_y, int32_t loss, float* d_out, float* d_dy, float* d_loss, float* d_dw,
+                          float* d_db, float* d_dh, void* d_ws, int64_t ws_bytes, void* stream);
 int64_t ofp_batchnorm_train_workspace_bytes(int64_t n, int32_t C, int32_t w);
 int ofp_batchnorm_train_forward(const float* d_x, int64_t n, int32_t C, int32_t w, const float* d_gamma,
                                 const float* d_beta, double eps, float momentum, float* d_running_mean,

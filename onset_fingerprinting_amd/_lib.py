@@ -354,6 +354,9 @@ SIGNATURES = {
     "ofp_conv1d_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "ofp_conv1d_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                            _vp, _vp, _i64, _vp]),
+    "ofp_linear_head_train_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ofp_linear_head_train": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _i64, _vp]),
     "ofp_batchnorm_train_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "ofp_batchnorm_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _f64, _f32, _vp, _vp, _vp, _vp,
                                                    _vp, _vp, _i64, _vp]),

@@ -403,7 +403,7 @@ int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, cons
     OFP_REQUIRE(head_lds(p.K, p.V) <= kMaxLds, "%s: the head's %d maps of %d columns do not fit the LDS (%d bytes)", who,
                 p.K, p.V, (int)kMaxLds);
     p.F = p.C * (2 * p.V - 1);
-    max_part = std::max<int64_t>(max_part, ofp::cdiv(n, kFcChunk) * p.O * p.F);
+    max_part = std::max<int64_t>(max_part, (int64_t)fc_chunks(n) * p.O * p.F);
     max_h = std::max<int64_t>(max_h, nmax * p.F);
     p.fcw_off = np, np += p.O * p.F;
     p.fcb_off = np, np += p.O;
@@ -504,8 +504,14 @@ int enqueue_head_bwd(const Ctl* ctl, const float* f, const float* prob, const fl
     return OFP_OK;
 }
 
-// conv stack, correlation head and Linear of a batch; train: model.loss and d loss / d out kept; else L1
-int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train) {
+Fc fc_of(const Run& r, const float* h, int64_t n, const float* y) {
+    const Plan& p = *r.p;
+    return Fc{h, n, p.F, p.O, r.P + p.fcw_off, r.P + p.fcb_off, y};
+}
+
+// conv stack, correlation head and Linear of a batch, its mean loss into `curve`; train: model.loss, d loss / d out
+// kept and the Linear's bias gradient; else L1 and the early-stop rule
+int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
     const Plan& p = *r.p;
     const int64_t items = p.items(n);
     const float* in = x;
@@ -525,12 +531,9 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
         if (int rc = enqueue_dropout_fwd(r.ctl, r.rnd, prob, r.at<float>(p.o_HD), n * p.F, r.st)) return rc;
         feat = r.at<float>(p.o_HD);
     }
-    const float inv_numel = 1.0f / (float)(n * p.O);
-    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, feat, p.F, p.O, r.P + p.fcw_off,
-                       r.P + p.fcb_off, y, train ? p.loss : 0, inv_numel, r.at<float>(p.o_out),
-                       train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart));
-    OFP_LAUNCH_CHECK("k_fc_fwd");
-    return OFP_OK;
+    return enqueue_fc_forward(r.ctl, fc_of(r, feat, n, y), p.loss, r.at<float>(p.o_out),
+                              train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart), curve, patience,
+                              r.G + p.fcb_off, r.st);
 }
 
 int enqueue_backward(const Run& r, const float* x, int64_t n) {
@@ -539,17 +542,12 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     float* GH = r.at<float>(p.o_gh);
     float* GZ = r.at<float>(p.o_gz);
     double* part = r.at<double>(p.o_part);
-    const int nchunk = (int)ofp::cdiv(n, kFcChunk);
     // the Linear head's weight gradient; the d p it also writes is not used (k_head_bwd forms its own, per item)
     // unless there is a dropout: then it is masked in place and k_head_bwd takes it
     float* DP = r.rnd.drop ? r.at<float>(p.o_DP) : nullptr;
-    hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(p.F, kT), nchunk), dim3(kT), 0, r.st, r.ctl,
-                       r.at<float>(r.rnd.drop ? p.o_HD : p.o_P), r.at<float>(p.o_dy), n, p.F, p.O, r.P + p.fcw_off,
-                       part, DP ? DP : GH);
-    OFP_LAUNCH_CHECK("k_fc_bwd");
-    hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)p.O * p.F, kT)), dim3(kT), 0, r.st, r.ctl, part,
-                       nchunk, (int64_t)p.O * p.F, r.G + p.fcw_off);
-    OFP_LAUNCH_CHECK("k_fc_wfinal");
+    if (int rc = enqueue_fc_backward(r.ctl, fc_of(r, r.at<float>(r.rnd.drop ? p.o_HD : p.o_P), n, nullptr),
+                                     r.at<float>(p.o_dy), part, r.G + p.fcw_off, DP ? DP : GH, r.st))
+        return rc;
     if (DP)
         if (int rc = enqueue_dropout_bwd(r.ctl, r.rnd, DP, n * p.F, r.st)) return rc;
     if (int rc = enqueue_head_bwd(r.ctl, r.at<float>(p.o_H[p.L - 1]), r.at<float>(p.o_P), r.at<float>(p.o_dy),

@@ -316,7 +316,7 @@ int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const 
         width = p.wo[l];
     }
     p.F = c->channels[p.L] * width;
-    max_part = std::max<int64_t>(max_part, ofp::cdiv(n, kFcChunk) * p.O * p.F);
+    max_part = std::max<int64_t>(max_part, (int64_t)fc_chunks(n) * p.O * p.F);
     p.fcw_off = np, np += p.O * p.F;
     p.fcb_off = np, np += p.O;
     p.np = np, p.ns = ns;
@@ -397,8 +397,14 @@ int enqueue_post_bwd(const Ctl* ctl, const Post& t, int64_t n, const float* z, c
 }
 
 
-// conv stack and head of a batch; train: batch statistics, d loss / d out kept; else running statistics, L1
-int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train) {
+Fc fc_of(const Run& r, const float* h, int64_t n, const float* y) {
+    const Plan& p = *r.p;
+    return Fc{h, n, p.F, p.O, r.P + p.fcw_off, r.P + p.fcb_off, y};
+}
+
+// conv stack and head of a batch, its mean loss into `curve`; train: batch statistics, d loss / d out kept and the
+// head's bias gradient; else running statistics, L1 and the early-stop rule
+int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
     const Plan& p = *r.p;
     const float* in = x;
     for (int l = 0; l < p.L; ++l) {
@@ -424,12 +430,9 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
         if (int rc = enqueue_dropout_fwd(r.ctl, r.rnd, in, HD, n * p.F, r.st)) return rc;
         in = HD;
     }
-    const float inv_numel = 1.0f / (float)(n * p.O);
-    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)n), dim3(kT), 0, r.st, r.ctl, in, p.F, p.O, r.P + p.fcw_off,
-                       r.P + p.fcb_off, y, train ? p.loss : 0, inv_numel, r.at<float>(p.o_out),
-                       train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart));
-    OFP_LAUNCH_CHECK("k_fc_fwd");
-    return OFP_OK;
+    return enqueue_fc_forward(r.ctl, fc_of(r, in, n, y), p.loss, r.at<float>(p.o_out),
+                              train ? r.at<float>(p.o_dy) : nullptr, r.at<double>(p.o_lpart), curve, patience,
+                              r.G + p.fcb_off, r.st);
 }
 
 int enqueue_backward(const Run& r, const float* x, int64_t n) {
@@ -437,14 +440,9 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     float* GH = r.at<float>(p.o_gh);
     float* GZ = r.at<float>(p.o_gz);
     double* part = r.at<double>(p.o_part);
-    const int nchunk = (int)ofp::cdiv(n, kFcChunk);
-    hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(p.F, kT), nchunk), dim3(kT), 0, r.st, r.ctl,
-                       r.at<float>(r.rnd.drop ? p.o_HD : p.o_H[p.L - 1]), r.at<float>(p.o_dy), n, p.F, p.O,
-                       r.P + p.fcw_off, part, GH);
-    OFP_LAUNCH_CHECK("k_fc_bwd");
-    hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)p.O * p.F, kT)), dim3(kT), 0, r.st, r.ctl, part,
-                       nchunk, (int64_t)p.O * p.F, r.G + p.fcw_off);
-    OFP_LAUNCH_CHECK("k_fc_wfinal");
+    if (int rc = enqueue_fc_backward(r.ctl, fc_of(r, r.at<float>(r.rnd.drop ? p.o_HD : p.o_H[p.L - 1]), n, nullptr),
+                                     r.at<float>(p.o_dy), part, r.G + p.fcw_off, GH, r.st))
+        return rc;
     if (r.rnd.drop)
         if (int rc = enqueue_dropout_bwd(r.ctl, r.rnd, GH, n * p.F, r.st)) return rc;
     for (int l = p.L - 1; l >= 0; --l) {
@@ -579,6 +577,30 @@ int ofp_conv1d_backward(const float* d_x, int64_t n, int32_t cin, int32_t w, con
                           ofp_conv1d_backward_workspace_bytes(n, cin, w, cout, k, padding, dilation, groups), d_x, n,
                           cin, w, d_w, cout, k, padding, dilation, groups, 1, d_dz, d_dx, d_dw, d_db, d_ws, ws_bytes,
                           stream);
+}
+
+// work space of the head alone: the samples' loss shares, then the chunks of the weight gradient
+int64_t ofp_linear_head_train_workspace_bytes(int64_t n, int32_t F, int32_t O) {
+    if (n < 1 || n > kMaxBatch || O < 1 || O > kMaxOut || F < 1) return -1;
+    return ofp::align_up(n * 8, 256) + (int64_t)fc_chunks(n) * O * F * 8;
+}
+
+int ofp_linear_head_train(const float* d_h, int64_t n, int32_t F, const float* d_w, int32_t O, const float* d_b,
+                          const float* d_y, int32_t loss, float* d_out, float* d_dy, float* d_loss, float* d_dw,
+                          float* d_db, float* d_dh, void* d_ws, int64_t ws_bytes, void* stream) {
+    const int64_t need = ofp_linear_head_train_workspace_bytes(n, F, O);
+    OFP_REQUIRE(need >= 0, "ofp_linear_head_train: n %lld, %d features, %d outputs (limits: 1..%d, >= 1, 1..%d)",
+                (long long)n, F, O, kMaxBatch, kMaxOut);
+    OFP_REQUIRE(loss == 0 || loss == 1, "ofp_linear_head_train: loss %d (0 = L1, 1 = MSE)", loss);
+    OFP_REQUIRE(d_h && d_w && d_b && d_y && d_out && d_dy && d_loss && d_dw && d_db && d_dh,
+                "ofp_linear_head_train: NULL argument");
+    if (int rc = check_ws("ofp_linear_head_train", d_ws, ws_bytes, need)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Fc f{d_h, n, F, O, d_w, d_b, d_y};
+    double* lpart = (double*)d_ws;
+    double* part = reinterpret_cast<double*>((char*)d_ws + ofp::align_up(n * 8, 256));
+    if (int rc = enqueue_fc_forward(nullptr, f, loss, d_out, d_dy, lpart, d_loss, -1, d_db, st)) return rc;
+    return enqueue_fc_backward(nullptr, f, d_dy, part, d_dw, d_dh, st);
 }
 
 int64_t ofp_batchnorm_train_workspace_bytes(int64_t n, int32_t C, int32_t w) {

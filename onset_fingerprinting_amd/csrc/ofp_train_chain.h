@@ -334,6 +334,46 @@ int enqueue_conv_bwd(const Ctl* ctl, const Conv& c, int64_t n, const float* x, c
     return OFP_OK;
 }
 
+// The Linear head of a batch: h [n][F], w [O][F], b [O], targets y [n][O]; `lpart` takes n doubles, `part` (backward)
+// fc_chunks(n) * O * F doubles.
+struct Fc {
+    const float* h;
+    int64_t n;
+    int F, O;
+    const float* w;
+    const float* b;
+    const float* y;
+};
+
+int fc_chunks(int64_t n) { return (int)ofp::cdiv(n, kFcChunk); }
+
+// out = W h + b and the batch's mean loss into `curve` (slot `epoch` of it inside a run).  With dy (training):
+// d loss / d out and the bias gradient db; without (validation, L1): the early-stop rule with `patience`.
+int enqueue_fc_forward(Ctl* ctl, const Fc& f, int loss, float* out, float* dy, double* lpart, float* curve,
+                       int patience, float* db, hipStream_t st) {
+    const float inv_numel = 1.0f / (float)(f.n * f.O);
+    hipLaunchKernelGGL(k_fc_fwd, dim3((unsigned)f.n), dim3(kT), 0, st, ctl, f.h, f.F, f.O, f.w, f.b, f.y,
+                       dy ? loss : 0, inv_numel, out, dy, lpart);
+    OFP_LAUNCH_CHECK("k_fc_fwd");
+    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, st, ctl, lpart, f.n, f.O, curve, dy ? 0 : 1,
+                       dy ? -1 : patience, (const float*)dy, dy ? db : (float*)nullptr);
+    OFP_LAUNCH_CHECK("k_loss_final");
+    return OFP_OK;
+}
+
+// dw = dy^T h (chunks of kFcChunk samples through `part`, added in chunk order) and dh = dy W
+int enqueue_fc_backward(const Ctl* ctl, const Fc& f, const float* dy, double* part, float* dw, float* dh,
+                        hipStream_t st) {
+    const int nchunk = fc_chunks(f.n);
+    hipLaunchKernelGGL(k_fc_bwd, dim3((unsigned)ofp::cdiv(f.F, kT), nchunk), dim3(kT), 0, st, ctl, f.h, dy, f.n, f.F,
+                       f.O, f.w, part, dh);
+    OFP_LAUNCH_CHECK("k_fc_bwd");
+    hipLaunchKernelGGL(k_fc_wfinal, dim3((unsigned)ofp::cdiv((int64_t)f.O * f.F, kT)), dim3(kT), 0, st, ctl, part,
+                       nchunk, (int64_t)f.O * f.F, dw);
+    OFP_LAUNCH_CHECK("k_fc_wfinal");
+    return OFP_OK;
+}
+
 int check_ws(const char* who, const void* ws, int64_t given, int64_t need) {
     if (ws == nullptr || given < need)
         return ofp::fail(OFP_ERR_WORKSPACE, "%s: work space of %lld bytes needed, %lld given", who, (long long)need,
@@ -362,10 +402,10 @@ int conv_bwd_alone(const char* who, int64_t need, const float* d_x, int64_t n, i
 }
 
 // ---- one epoch and its driver ---------------------------------------------------------------------------------------
-// A trainer derives its Plan from WsPlan and its Run from WsRun and defines enqueue_forward(r, x, y, n, train),
-// enqueue_backward(r, x, n) and enqueue_step(r, rates), its optimiser, for its own Run; the templates below find them
-// by the Run they are called with.  Of the Run they read p, G, ctl, st and rnd (csrc/ofp_train_random.h), of the
-// Plan O, fcb_off, o_lpart, o_dy and o_X.
+// A trainer derives its Plan from WsPlan and its Run from WsRun and defines enqueue_forward(r, x, y, n, train, curve,
+// patience), which ends in enqueue_fc_forward, enqueue_backward(r, x, n) and enqueue_step(r, rates), its optimiser, for
+// its own Run; the templates below find them by the Run they are called with.  Of the Run they read p, ctl, st and rnd
+// (csrc/ofp_train_random.h), of the Plan o_X.
 
 // base of a Plan: the byte offsets of the work space's blocks come from a bump allocator
 struct WsPlan {
@@ -411,11 +451,7 @@ int check_train(const char* who, const TrainArgs& a, int num_epochs, const float
 // training forward, the batch's mean loss into `loss` (slot `epoch` of it inside a run) and backward
 template <class Run>
 int enqueue_loss_grads(const Run& r, const float* x, const float* y, int64_t n, float* loss) {
-    const auto& p = *r.p;
-    if (int rc = enqueue_forward(r, x, y, n, true)) return rc;
-    hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.template at<double>(p.o_lpart), n, p.O, loss,
-                       0, -1, r.template at<float>(p.o_dy), r.G + p.fcb_off);
-    OFP_LAUNCH_CHECK("k_loss_final");
+    if (int rc = enqueue_forward(r, x, y, n, true, loss, -1)) return rc;
     return enqueue_backward(r, x, n);
 }
 
@@ -426,12 +462,8 @@ int enqueue_epoch(const Run& r, const TrainArgs& a) {
         if (int rc = enqueue_windows(r.ctl, r.rnd, r.template at<float>(p.o_X), r.st)) return rc;
     if (int rc = enqueue_loss_grads(r, a.x, a.y, a.n, a.train_loss)) return rc;
     if (int rc = enqueue_step(r, a.rates)) return rc;
-    if (a.nv > 0) {
-        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false)) return rc;
-        hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kT), 0, r.st, r.ctl, r.template at<double>(p.o_lpart), a.nv,
-                           p.O, a.val_loss, 1, a.patience, (const float*)nullptr, (float*)nullptr);
-        OFP_LAUNCH_CHECK("k_loss_final");
-    }
+    if (a.nv > 0)
+        if (int rc = enqueue_forward(r, a.xv, a.yv, a.nv, false, a.val_loss, a.patience)) return rc;
     hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(kT), 0, r.st, r.ctl, a.min_epochs);
     OFP_LAUNCH_CHECK("k_epoch_end");
     return OFP_OK;

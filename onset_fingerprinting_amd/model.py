@@ -1004,6 +1004,38 @@ def conv1d_backward(x, weight, dz, padding, dilation, groups=1, *, dx=None, dw=N
     return (dx if need_dx else None), dw, db
 
 
+def linear_head_train(h, weight, bias, y, loss=0, *, out=None, dy=None, loss_out=None, dw=None, db=None, dh=None):
+    """The Linear head of both trainers with its loss, forward and backward (ofp_linear_head_train), on float32 CUDA
+    tensors: h [n, F], weight [O, F], bias [O], targets y [n, O], loss 0 = L1 / 1 = MSE -> (out [n, O], dy [n, O] =
+    d loss / d out, the mean loss [1], dw [O, F], db [O], dh [n, F]); preallocated outputs may be passed."""
+    L = _lib.lib()
+    n, F_ = h.shape
+    O = weight.shape[0]
+    dev = h.device
+    if weight.shape != (O, F_) or bias.shape != (O,) or y.shape != (n, O):
+        raise ValueError(f"h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias {tuple(bias.shape)}, y "
+                         f"{tuple(y.shape)} do not fit together")
+    ws_bytes = int(L.ofp_linear_head_train_workspace_bytes(n, F_, O))
+    if ws_bytes < 0:
+        raise ValueError(f"n {n}, {F_} features, {O} outputs: beyond the Linear head's limits (1..{CNN_TRAIN_MAX_BATCH},"
+                         f" >= 1, 1..{CNN_TRAIN_MAX_OUT})")
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    out = new(n, O) if out is None else out
+    dy = new(n, O) if dy is None else dy
+    loss_out = new(1) if loss_out is None else loss_out
+    dw = new(O, F_) if dw is None else dw
+    db = new(O) if db is None else db
+    dh = new(n, F_) if dh is None else dh
+    ws = _workspace(ws_bytes, dev)
+    check(L.ofp_linear_head_train(h.data_ptr(), n, F_, weight.data_ptr(), O, bias.data_ptr(), y.data_ptr(), int(loss),
+                                  out.data_ptr(), dy.data_ptr(), loss_out.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                  dh.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev)), "ofp_linear_head_train")
+    return out, dy, loss_out, dw, db, dh
+
+
 def batchnorm_train_forward(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, *, out=None):
     """BatchNorm1d in training mode on float32 CUDA x [n, C, w]: -> (y, mean, rstd); running_mean / running_var are
     updated in place (the variance written is the unbiased one)."""

@@ -48,6 +48,24 @@ def conv1d_backward_strided_ref(x, w, dz, padding, dilation, groups, stride):
             "db": (db, (n * wc + 4) * U * db_abs)}
 
 
+# The weight-gradient kernel gives the T = cin / groups * k + 1 outputs of a channel (its weights and its bias) g lanes
+# each: g = 64 for T <= 4, halved at every doubling of T down to 1 above 128, and a second pass over the outputs above
+# 256.  These cases sit on both sides of every change; 128 itself cannot be had (127 is prime and above the limits
+# of k and of the channels), 127 stands in for it.  cout = 2, n * wc is no multiple of 64 and lies inside one slab of
+# 2048 pairs, except in the last two, which span two slabs with g = 4 and g = 2.
+# (k, stride, dilation, padding, groups, cin, cout, width, n)
+WGRAD_LANE_CASES = [
+    (3, 1, 1, 1, 1, 1, 2, 37, 5), (4, 2, 1, 1, 1, 1, 2, 41, 5),      # T = 4, 5
+    (7, 1, 1, 3, 1, 1, 2, 33, 7), (4, 1, 1, 0, 2, 4, 2, 30, 5),      # T = 8, 9
+    (5, 1, 1, 2, 1, 3, 2, 29, 5), (8, 1, 1, 0, 1, 2, 2, 40, 3),      # T = 16, 17
+    (31, 1, 1, 15, 1, 1, 2, 35, 3), (16, 1, 1, 0, 2, 4, 2, 50, 3),   # T = 32, 33
+    (21, 1, 1, 10, 1, 3, 2, 45, 3), (64, 1, 1, 0, 1, 1, 2, 100, 3),  # T = 64, 65
+    (63, 1, 1, 31, 1, 2, 2, 50, 3), (64, 1, 1, 0, 1, 2, 2, 90, 3),   # T = 127, 129
+    (51, 1, 1, 25, 1, 5, 2, 30, 3), (64, 2, 1, 0, 1, 4, 2, 101, 3),  # T = 256, 257
+    (21, 1, 1, 10, 1, 3, 2, 45, 47), (63, 1, 1, 31, 2, 4, 2, 50, 43),  # T = 64, 127 over two slabs
+]
+
+
 def _gn_stats(x, eps):
     """Per item: element count, mean, biased variance, rstd and the relative error of an rstd formed from float64 sums
     of x and x^2 as E[x^2] - mean^2 (a few 2^-53 E[x^2] in the variance; 2^-48 leaves room for the sums' own

@@ -1,5 +1,6 @@
-"""float64 references of the two directly tested training kernels (csrc/ofp_cnn_train.hip): the three gradients of a
-stride-1 Conv1d and BatchNorm1d in training mode, forward and backward.  Written from the formulas; every result
+"""float64 references of the directly tested training kernels (csrc/ofp_cnn_train.hip): the three gradients of a
+stride-1 Conv1d, BatchNorm1d in training mode, forward and backward, and the Linear head with its loss, forward and
+backward (with the shapes and inputs of its tests).  Written from the formulas; every result
 comes with an element-wise bound on what a float32 kernel may lose, derived from the roundings it has to make, not
 from what the kernels give.  u = 2^-24 is the unit roundoff of float32.
 
@@ -97,6 +98,89 @@ def batchnorm_train_backward_ref(x, gamma, dy, eps):
              + 2 * U * (np.abs(dy) + np.abs(t2) + np.abs(t3)))
     b_dx = r * np.abs(ga) * inner + (3 * U + rel[None, :, None]) * np.abs(dx)
     return {"dx": (dx, b_dx), "dgamma": (s2, b_dgamma), "dbeta": (s1, b_dbeta)}
+
+
+U53 = 2.0 ** -53
+
+
+def _sum64(n_terms, abs_sum):
+    """What an fp64 sum of n_terms exact terms may lose, in any order of summation."""
+    return (n_terms + 4) * U53 * abs_sum
+
+
+def _rounded(value, before):
+    """Bound of a value computed to within `before` and then rounded to float32 once."""
+    return before + U * (np.abs(value) + before)
+
+
+def linear_head_ref(h, w, b, y, loss):
+    """The Linear head with its loss: h [n, F], w [O, F], b [O], y [n, O], loss 0 = L1 / 1 = MSE ->
+    {"out", "dy", "loss", "dw", "db", "dh"}: (value, bound).
+        out[s][j] = b[j] + sum_f h[s][f] w[j][f]          fp64 sum of F + 1 exact terms, rounded once
+        r         = out - y                               the rounded out, rounded once more
+        dy        = sign(r) inv  |  (2 inv) r             inv the float32 1 / (float)(n O); 2 inv is exact
+        loss      = mean |r|  |  mean r^2                 fp64 sum of n O terms, rounded once
+        db[j]     = sum_s dy[s][j]                        fp64 sum of the float32 dy, rounded once
+        dw[j][f]  = sum_s dy[s][j] h[s][f]                fp64 sum of exact products, rounded once
+        dh[s][f]  = sum_j dy[s][j] w[j][f]                float32 fmaf chain of O terms: (O + 4) u sum |terms|
+    Everything after `out` is computed from rounded values, so its bound also carries what those may be off by.  For
+    L1 the sign is taken as exact: the caller keeps |out - y| clear of out's bound (l1_margin)."""
+    h, w, b, y = (a.astype(f64) for a in (h, w, b, y))
+    n, F = h.shape
+    O = w.shape[0]
+    inv = float(np.float32(1.0) / np.float32(n * O))
+    out = h @ w.T + b
+    out_abs = np.abs(h) @ np.abs(w).T + np.abs(b)
+    b_out = _rounded(out, _sum64(F + 1, out_abs))
+    r = out - y
+    b_r = _rounded(r, b_out)
+    if loss == 0:
+        dy, b_dy = np.sign(r) * inv, np.zeros_like(r)
+        terms, b_terms = np.abs(r), b_r
+    else:
+        dy = (2.0 * inv) * r
+        b_dy = _rounded(dy, (2.0 * inv) * b_r)
+        terms, b_terms = r * r, b_r * (2.0 * np.abs(r) + b_r)
+    total = terms.sum()
+    mean = np.array([total / (n * O)])
+    b_mean = _rounded(mean, (b_terms.sum() + _sum64(n * O, total)) / (n * O) + 2 * U53 * mean)
+    db = dy.sum(0)
+    b_db = _rounded(db, b_dy.sum(0) + _sum64(n, np.abs(dy).sum(0)))
+    dw = dy.T @ h
+    b_dw = _rounded(dw, b_dy.T @ np.abs(h) + _sum64(n, np.abs(dy).T @ np.abs(h)))
+    dh = dy @ w
+    b_dh = b_dy @ np.abs(w) + (O + 4) * U * ((np.abs(dy) + b_dy) @ np.abs(w))
+    return {"out": (out, b_out), "dy": (dy, b_dy), "loss": (mean, b_mean), "dw": (dw, b_dw), "db": (db, b_db),
+            "dh": (dh, b_dh)}
+
+
+def l1_margin(ref, y):
+    """Smallest |out - y| / bound of out over the batch: the sign L1 takes is the exact one while this is far above 1."""
+    out, b_out = ref["out"]
+    return float(np.min(np.abs(out - y.astype(f64)) / b_out))
+
+
+# (n, F, O) of the Linear head's direct tests: each axis in full with the others at a mid value, and four corners.
+#   n  one chunk of 64 samples or two, a last chunk of one sample, the 256-thread stride of the loss kernel, the limit
+#   F  the forward's stride of 256 features, the backward's grid over F
+#   O  the odd tail of the loops that take two outputs at a time, the limit of 16
+HEAD_N, HEAD_F, HEAD_O = (1, 63, 64, 65, 128, 129, 256, 257, 1024), (1, 255, 256, 257, 600), (1, 2, 3, 15, 16)
+HEAD_MID = (65, 257, 3)
+HEAD_SHAPES = sorted({(n, HEAD_MID[1], HEAD_MID[2]) for n in HEAD_N} | {(HEAD_MID[0], F, HEAD_MID[2]) for F in HEAD_F}
+                     | {(HEAD_MID[0], HEAD_MID[1], O) for O in HEAD_O}
+                     | {(1, 1, 1), (1024, 600, 16), (129, 257, 15), (257, 255, 1)})
+
+
+def linear_head_inputs(n, F, O):
+    """float32 h, w, b, y of one shape.  The weights are scaled so that out is of order 1; the targets lie 0.25 to 2
+    away from the float64 out, on either side, so that no residual is near the kink of L1."""
+    rng = np.random.default_rng([n, F, O])
+    h = rng.standard_normal((n, F)).astype(np.float32)
+    w = (rng.standard_normal((O, F)) / np.sqrt(F)).astype(np.float32)
+    b = rng.standard_normal(O).astype(np.float32)
+    out = h.astype(f64) @ w.astype(f64).T + b.astype(f64)
+    y = (out + rng.choice([-1.0, 1.0], (n, O)) * rng.uniform(0.25, 2.0, (n, O))).astype(np.float32)
+    return h, w, b, y
 
 
 def nadam_step_ref(p, g, m, v, factors):

@@ -147,6 +147,40 @@ def test_sgd_reference_against_torch():
     assert (model.LCCCNN_MOMENTUM, model.LCCCNN_WEIGHT_DECAY) == (0.8, 1e-3)
 
 
+def lanes_per_output(outputs):
+    """csrc/ofp_train_chain.h: the largest power of two <= 64 with outputs * g <= 256 threads."""
+    g = 64
+    while g > 1 and outputs * g > 256:
+        g >>= 1
+    return g
+
+
+def test_lane_cases_sit_on_both_sides_of_every_change_of_g():
+    """R.WGRAD_LANE_CASES, which the GPU test of the strided convolution's gradients runs: every lane count, both
+    neighbours of every change (127 for the unreachable 128), the second pass above 256 outputs, one slab except for
+    one case each with g = 4 and g = 2, and limits that the strided entry accepts."""
+    per_g, slabs_of_g = {}, {}
+    for k, stride, dil, pad, groups, cin, cout, w, n in R.WGRAD_LANE_CASES:
+        assert 1 <= k <= 64 and 1 <= stride <= 4 and cin % groups == 0 and cout % groups == 0 and cout == 2
+        assert 1 <= cin <= 64 and 1 <= w <= 1024 and 1 <= n <= 4096
+        T = cin // groups * k + 1
+        pairs = n * R.conv_width(w, k, pad, dil, stride)
+        assert pairs % 64 and pairs >= 1
+        g = lanes_per_output(T)
+        per_g.setdefault(g, set()).add(T)
+        slabs_of_g.setdefault(g, set()).add(-(-pairs // 2048))
+    assert sorted(per_g) == [1, 2, 4, 8, 16, 32, 64]
+    Ts = set().union(*per_g.values())
+    assert Ts == {4, 5, 8, 9, 16, 17, 32, 33, 64, 65, 127, 129, 256, 257}
+    for lo in (4, 8, 16, 32, 64):
+        assert lanes_per_output(lo) == 2 * lanes_per_output(lo + 1)
+    assert lanes_per_output(127) == lanes_per_output(128) == 2 and lanes_per_output(129) == 1
+    assert all(127 % d for d in range(2, 127))  # T = 128 would need cin / groups * k = 127 with both factors <= 64
+    assert {g: s for g, s in slabs_of_g.items()} == {64: {1}, 32: {1}, 16: {1}, 8: {1}, 4: {1, 2}, 2: {1, 2}, 1: {1}}
+    # the references of the new shapes against autograd, at the cheapest of them
+    test_conv_reference_against_autograd(R.WGRAD_LANE_CASES[3])
+
+
 # ---- float32 emulations of the kernels, and planted faults -----------------------------------------------------------
 def emul_conv(x, w, dz, pad, dil, groups, stride, drop_last_tap=False, ignore_stride=False):
     n, cin, win = x.shape

@@ -200,3 +200,46 @@ def test_batchnorm_reference_against_autograd(n, C, w):
     for d in (fwd, bwd):
         for val, bound in d.values():
             assert bound.shape == val.shape and np.all(bound >= 0)
+
+
+@pytest.mark.parametrize("loss", [0, 1], ids=["l1", "mse"])
+@pytest.mark.parametrize("n,Fe,O", [(1, 1, 1), (5, 7, 3), (65, 257, 3), (129, 40, 16)])
+def test_linear_head_reference_against_autograd(n, Fe, O, loss):
+    """nn.Linear + F.l1_loss / F.mse_loss in float64.  The reference scales d loss / d out by the float32 1 / (n O) the
+    kernel receives, autograd by the exact quotient: the ratio of the two is taken out before comparing."""
+    h, w, b, y = R.linear_head_inputs(n, Fe, O)
+    ref = R.linear_head_ref(h, w, b, y, loss)
+    lin = nn.Linear(Fe, O).double()
+    with torch.no_grad():
+        lin.weight.copy_(torch.tensor(w)), lin.bias.copy_(torch.tensor(b))
+    ht = torch.tensor(h, dtype=torch.float64, requires_grad=True)
+    out = lin(ht)
+    out.retain_grad()
+    v = (F.mse_loss if loss else F.l1_loss)(out, torch.tensor(y, dtype=torch.float64))
+    v.backward()
+    scale = float(np.float32(1.0) / np.float32(n * O)) * (n * O)
+    assert abs(scale - 1) <= 2.0 ** -24
+    close = lambda a, t, s=1.0: np.max(np.abs(a - s * t.detach().numpy())) <= 1e-12 * max(1.0, np.max(np.abs(a)))
+    assert close(ref["out"][0], out) and close(ref["loss"][0], v.reshape(1))
+    assert close(ref["dy"][0], out.grad, scale) and close(ref["dh"][0], ht.grad, scale)
+    assert close(ref["dw"][0], lin.weight.grad, scale) and close(ref["db"][0], lin.bias.grad, scale)
+    shapes = {"out": (n, O), "dy": (n, O), "loss": (1,), "dw": (O, Fe), "db": (O,), "dh": (n, Fe)}
+    for name, (val, bound) in ref.items():
+        assert val.shape == bound.shape == shapes[name] and np.all(bound >= 0) and np.all(np.isfinite(bound))
+    # the bounds are roundings, not slack: a few units of float32 on values of order 1
+    assert np.all(ref["out"][1] <= 4 * R.U * (1 + np.abs(ref["out"][0])))
+
+
+def test_linear_head_shapes_and_the_margin_of_l1():
+    """The table of the GPU test: every axis in full, the corners, and for every shape a residual |out - y| at least
+    2^16 bounds of out away from the kink of L1 (a condition on the inputs, asserted here without a GPU)."""
+    S = set(R.HEAD_SHAPES)
+    assert len(S) == len(R.HEAD_SHAPES) == 9 + 5 + 5 - 2 + 4
+    assert {s[0] for s in S} == set(R.HEAD_N) and {s[1] for s in S} == set(R.HEAD_F)
+    assert {s[2] for s in S} == set(R.HEAD_O)
+    assert {(1, 1, 1), (1024, 600, 16), (129, 257, 15), (257, 255, 1)} <= S
+    for n, Fe, O in R.HEAD_SHAPES:
+        h, w, b, y = R.linear_head_inputs(n, Fe, O)
+        margin = R.l1_margin(R.linear_head_ref(h, w, b, y, 0), y)
+        print(f"n {n} F {Fe} O {O}: smallest |out - y| / bound of out {margin:.3g}")
+        assert margin >= 2.0 ** 16

@@ -5,7 +5,10 @@ reference's recorded runs (tests/golden/g27_cccnn_train.npz, made by make_golden
               backward and the SGD step, called directly, element-wise against float64 with the derived bounds of
               tests/cccnn_train_ref.py; outputs go into NaN-filled buffers with a guard tail
   gradients   per tensor, max |ours - g64| <= 4 x max |g32 - g64|, floored at 2^-23 x max |g64|; the inputs or
-              GroupNorm's weights are scaled so that the softmax of the head is not saturated (asserted)
+              GroupNorm's weights are scaled so that the softmax of the head is not saturated (asserted); up to the
+              limit of 4 096 (window, sensor) pairs, so that whole chains cross slabs and chunks
+  epoch       with more validation than training windows: the first losses against the start and against torch in
+              float64, graph and plain launches bit for bit
   trajectory  over the comparable prefix (the epochs before the 8 disturbed reference curves first stray more than
               1e-5 relative): |ours_e - ref_e| <= 4 x the largest, up to e, of the disturbed runs' spread and of
               |ref32 - ref64|, floored at 2^-22 x loss_e
@@ -77,7 +80,7 @@ CONV_CASES = [
     (5, 2, 1, 1, 4, 4, 8, 33, 3), (3, 3, 2, 2, 1, 2, 3, 34, 2),  # the stride does not divide
     (4, 4, 1, 0, 2, 4, 4, 19, 3),
     (3, 2, 1, 1, 1, 1, 2, 257, 40),  # n * wc = 5160 spans three slabs
-]
+] + R.WGRAD_LANE_CASES  # both sides of every change of the lanes per output (tests/test_cccnn_train_cpu.py)
 
 
 def check_conv_backward(k, stride, dil, pad, groups, cin, cout, w, n, need_dx=True):
@@ -268,10 +271,12 @@ def check_grads(ours, loss_ours, g32, g64, loss64, n, label):
         err32 = np.max(np.abs(g32[k].astype(f64) - ref64))
         bound = max(4 * err32, U23 * np.max(np.abs(ref64)))
         print(f"{label} {k}: |ours - g64| {err:.3e}  |g32 - g64| {err32:.3e}  bound {bound:.3e}  max |g64| "
-              f"{np.max(np.abs(ref64)):.3e} ({np.max(np.abs(ref64)) / top:.2g} of the largest)")
+              f"{np.max(np.abs(ref64)):.3e} ({np.max(np.abs(ref64)) / top:.2g} of the largest)  error / bound "
+              f"{err / bound:.3g}")
         assert err <= bound, (label, k, err, bound)
     rel = abs(float(loss_ours) - loss64) / loss64
-    print(f"{label} loss: ours {float(loss_ours):.9g} ref64 {loss64:.9g} rel {rel:.3e} bound {n * U24:.3e}")
+    print(f"{label} loss: ours {float(loss_ours):.9g} ref64 {loss64:.9g} rel {rel:.3e} bound {n * U24:.3e}  error / "
+          f"bound {rel / (n * U24):.3g}")
     assert rel <= n * U24
 
 
@@ -318,6 +323,52 @@ def test_gradients_of_the_architecture_matrix(arch):
     assert pmax < 0.9, "the softmax of the head is saturated: the float32 gradients would be noise"
     loss, grads = model.cccnn_loss_and_grads_device(m, x.cuda(), y.cuda())
     check_grads(grads, loss, ref[torch.float32][0], ref[torch.float64][0], ref[torch.float64][1], 2 * len(x),
+                arch_id(arch))
+
+
+# Whole networks at the batch sizes of the workload.  Width 30, 3 sensors: n = 65 windows are 195 items when the stack
+# is shared (5850 pairs, three slabs of the reducer) and two chunks of the Linear's weight gradient; n = 257 lies past
+# the 256-thread stride of the loss kernel; n = 1024 with 4 sensors is the limit of both, 4096 items.  Smooth
+# activations (SiLU by default, Tanh), so that the float32 reference is not itself at a kink.
+BIG = [dict(n=n, batch_norm=bn, group=gr, activation=nn.Tanh if gr else nn.SiLU) for n in (65, 257)
+       for bn in (False, True) for gr in (False, True)] + [
+    dict(n=65, output_size=1, batch_norm=True), dict(n=65, output_size=3), dict(n=65, output_size=16, batch_norm=True),
+    dict(n=65, strides=[2, 1], pool=True, batch_norm=True),
+    dict(n=1024, channels=4, batch_norm=True),
+]
+
+
+def big_model(arch):
+    """arch_model at a batch size and output count of its own: the same scaling of GroupNorm's weights and inputs."""
+    from onset_fingerprinting_amd import model
+    kw = dict(arch)
+    n, channels, out = kw.pop("n"), kw.pop("channels", 3), kw.pop("output_size", 2)
+    torch.manual_seed(len(arch_id(arch)))
+    m = model.LCCCNN(30, out, channels=channels, dropout_rate=0.0, **{"layer_sizes": [3, 2], **kw})
+    with torch.no_grad():
+        for mod in m.model.conv_layers:
+            if isinstance(mod, nn.GroupNorm):
+                mod.weight.mul_(0.2)
+    x, y = torch.randn(n, channels, 30) * (1.0 if kw.get("batch_norm") else 0.5), torch.randn(n, out)
+    return m, x, y
+
+
+@pytest.mark.parametrize("arch", BIG, ids=arch_id)
+def test_gradients_past_one_slab_and_one_chunk(arch):
+    from onset_fingerprinting_amd import _lib, model
+    m, x, y = big_model(arch)
+    n, C = x.shape[:2]
+    items = n if arch.get("group") else n * C
+    wc = R.conv_width(30, 3, 1, 1, arch.get("strides", [1])[0])  # of the first layer
+    # two chunks at least; several slabs too, unless the windows themselves are the items (65 x 30 pairs are one slab)
+    assert n > 64 and (items * wc > int(_lib.lib().ofp_cnn_train_slab()) or (arch.get("group") and n == 65))
+    assert n * C <= model.CCCNN_TRAIN_MAX_ITEMS and n <= model.CCCNN_TRAIN_MAX_BATCH
+    ref = autograd_reference(m, x, y)
+    pmax = ref[torch.float64][2]
+    print(f"{arch_id(arch)}: largest p of the head {pmax:.4f}")
+    assert pmax < 0.9, "the softmax of the head is saturated: the float32 gradients would be noise"
+    loss, grads = model.cccnn_loss_and_grads_device(m, x.cuda(), y.cuda())
+    check_grads(grads, loss, ref[torch.float32][0], ref[torch.float64][0], ref[torch.float64][1], y.numel(),
                 arch_id(arch))
 
 
@@ -553,3 +604,59 @@ def test_in_place_semantics(g):
     # NaN beyond the epochs run
     short = model.fit_lcccnn(load_case(g, case)[1], x, y, max_epochs=12, min_epochs=3)
     assert short.epochs == 12 and bool(torch.isfinite(short.train_loss).all())
+
+
+# ---- the epoch past one slab, one chunk and 256 validation windows --------------------------------------------------
+def epoch_start():
+    """Width 30 with GroupNorm, 3 sensors, n = 130 (390 items, six slabs; three chunks), n_val = 300 > n and > the
+    loss kernel's 256 threads: the work space is sized by the validation batch."""
+    from onset_fingerprinting_amd import model
+    torch.manual_seed(130)
+    m = model.LCCCNN(30, 2, channels=3, dropout_rate=0.0, layer_sizes=[3, 2], batch_norm=True)
+    with torch.no_grad():
+        for mod in m.model.conv_layers:
+            if isinstance(mod, nn.GroupNorm):
+                mod.weight.mul_(0.2)
+    return m, torch.randn(130, 3, 30), torch.randn(130, 2), torch.randn(300, 3, 30), torch.randn(300, 2)
+
+
+def test_one_epoch_with_a_validation_batch_larger_than_the_training_batch():
+    from onset_fingerprinting_amd import model
+    m, x, y, xv, yv = epoch_start()
+    m = m.cuda()
+    loss0, _g = model.cccnn_loss_and_grads_device(m, x.cuda(), y.cuda())
+    fit = model.fit_lcccnn(m, x.cuda(), y.cuda(), x_val=xv.cuda(), y_val=yv.cuda(), max_epochs=1)
+    assert fit.epochs == 1
+    assert float(fit.train_loss[0]) == float(loss0)
+    ref = {}
+    for dtype in (torch.float32, torch.float64):
+        net = copy.deepcopy(m).cpu().to(dtype).eval()
+        with torch.no_grad():
+            out, probs = torch_forward(net.model, xv.to(dtype))
+            ref[dtype] = float(F.l1_loss(out, yv.to(dtype)))
+        assert float(probs.max()) < 0.9
+    ours, l32, l64 = float(fit.val_loss[0]), ref[torch.float32], ref[torch.float64]
+    bound = max(4 * abs(l32 - l64), U22 * l64)
+    print(f"validation loss after one epoch: ours {ours:.9g} torch float32 {l32:.9g} float64 {l64:.9g}; |ours - l64| "
+          f"{abs(ours - l64):.3e} bound {bound:.3e}  error / bound {abs(ours - l64) / bound:.3g}")
+    assert abs(ours - l64) <= bound
+
+
+def test_determinism_past_one_slab_and_one_chunk(monkeypatch):
+    """Five epochs twice as a graph and once as plain launches: the same bits in both curves and in the final state."""
+    from onset_fingerprinting_amd import model
+    start, x, y, xv, yv = epoch_start()
+    results = []
+    for mode in (None, None, "nodes"):
+        if mode:
+            monkeypatch.setenv("OFP_CCCNN_GRAPH", mode)
+        m = copy.deepcopy(start).cuda()
+        fit = model.fit_lcccnn(m, x.cuda(), y.cuda(), x_val=xv.cuda(), y_val=yv.cuda(), max_epochs=5)
+        results.append((fit, torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values()])))
+    monkeypatch.delenv("OFP_CCCNN_GRAPH", raising=False)
+    (a, pa) = results[0]
+    assert a.epochs == 5 and bool(torch.isfinite(a.train_loss).all()) and bool(torch.isfinite(a.val_loss).all())
+    for b, pb in results[1:]:
+        assert b.epochs == 5 and torch.equal(pa, pb)
+        assert torch.equal(a.train_loss.view(torch.int32), b.train_loss.view(torch.int32))
+        assert torch.equal(a.val_loss.view(torch.int32), b.val_loss.view(torch.int32))

@@ -1,10 +1,14 @@
 """GPU: training model.CNN (csrc/ofp_cnn_train.hip, model.fit_cnn) against float64 references and the reference's
 recorded runs (tests/golden/g26_cnn_train.npz, made by make_golden_cnn_train.py).
 
-  kernels     the convolution's three gradients, BatchNorm in training mode and the NAdam step, called directly,
-              element-wise against float64 with the derived bounds of tests/cnn_train_ref.py; outputs go into
-              NaN-filled buffers with a guard tail
-  gradients   per tensor, max |ours - g64| <= 4 x max |g32 - g64|, floored at 2^-23 x max |g64|
+  kernels     the convolution's three gradients, BatchNorm in training mode, the Linear head with its loss (forward
+              and backward, on both sides of its chunk of 64 samples and its 256-thread strides) and the NAdam step,
+              called directly, element-wise against float64 with the derived bounds of tests/cnn_train_ref.py;
+              outputs go into NaN-filled buffers with a guard tail
+  gradients   per tensor, max |ours - g64| <= 4 x max |g32 - g64|, floored at 2^-23 x max |g64|; up to the limit of
+              1 024 windows, so that whole chains cross slabs and chunks
+  epoch       with more validation than training windows: the first losses against the start and against torch in
+              float64, graph and plain launches bit for bit
   trajectory  over the comparable prefix (the epochs before the 8 disturbed reference curves first stray more than
               1e-5 relative): |ours_e - ref_e| <= 4 x the largest, up to e, of the disturbed runs' spread and of
               |ref32 - ref64|, floored at 2^-22 x loss_e
@@ -209,6 +213,68 @@ def test_nadam_step(step):
     within("exp_avg_sq", vd, v1, 4 * U24 * np.abs(v1), ctx)
 
 
+# ---- the Linear head with its loss ----------------------------------------------------------------------------------
+_head = {}
+
+
+def head_case(shape, loss):
+    """Inputs and float64 reference of one shape and loss; computed once."""
+    if (shape, loss) not in _head:
+        inputs = R.linear_head_inputs(*shape)
+        _head[shape, loss] = (inputs, R.linear_head_ref(*inputs, loss))
+    return _head[shape, loss]
+
+
+def check_head(shape, loss, label=""):
+    from onset_fingerprinting_amd import model
+    (h, w, b, y), ref = head_case(shape, loss)
+    n, Fe, O = shape
+    sizes = {"out": (n, O), "dy": (n, O), "loss": (1,), "dw": (O, Fe), "db": (O,), "dh": (n, Fe)}
+    bufs = {k: guarded(*s) for k, s in sizes.items()}
+    model.linear_head_train(dev(h), dev(w), dev(b), dev(y), loss, out=bufs["out"][0], dy=bufs["dy"][0],
+                            loss_out=bufs["loss"][0], dw=bufs["dw"][0], db=bufs["db"][0], dh=bufs["dh"][0])
+    torch.cuda.synchronize()
+    ctx = f"head{label} n{n} F{Fe} O{O} {'mse' if loss else 'l1'}"
+    for k in sizes:
+        within(k, bufs[k][0], *ref[k], ctx, bufs[k][1])
+
+
+@pytest.mark.parametrize("loss", [0, 1], ids=["l1", "mse"])
+@pytest.mark.parametrize("shape", R.HEAD_SHAPES, ids=lambda s: "n{}_F{}_O{}".format(*s))
+def test_linear_head(shape, loss):
+    """ofp_linear_head_train, the launches both trainers' epochs make, element-wise against float64 on either side of
+    the chunk of 64 samples, the 256-thread strides over samples and features and the odd output tail."""
+    check_head(shape, loss)
+
+
+def test_linear_head_refusals():
+    """n = 0, n = 1025, O = 17, F = 0 and a NULL pointer: OFP_ERR_INVALID, nothing written, the device usable."""
+    from onset_fingerprinting_amd import _lib, model
+    L, INVALID = _lib.lib(), 1  # OFP_ERR_INVALID of include/onsetfp.h
+    n, Fe, O = 4, 5, 3
+    src = torch.ones(1025 * 17, dtype=torch.float32, device="cuda")
+    outs = [torch.full((1025 * 17,), float("nan"), dtype=torch.float32, device="cuda") for _ in range(6)]
+    ws = torch.full((1 << 16,), float("nan"), dtype=torch.float32, device="cuda")
+    p, o = src.data_ptr(), [t.data_ptr() for t in outs]
+
+    def call(n, Fe, O, h=p, dw=o[3]):
+        return L.ofp_linear_head_train(h, n, Fe, p, O, p, p, 0, o[0], o[1], o[2], dw, o[4], o[5], ws.data_ptr(),
+                                       ws.numel() * 4, None)
+
+    for args in ((0, Fe, O), (1025, Fe, O), (n, Fe, 17), (n, 0, O)):
+        assert L.ofp_linear_head_train_workspace_bytes(*args) == -1
+        assert call(*args) == INVALID, args
+        assert b"ofp_linear_head_train" in L.ofp_last_error()
+    assert call(n, Fe, O, h=None) == INVALID and call(n, Fe, O, dw=None) == INVALID
+    assert L.ofp_linear_head_train(p, n, Fe, p, O, p, p, 2, *o, ws.data_ptr(), ws.numel() * 4, None) == INVALID
+    assert L.ofp_linear_head_train(p, n, Fe, p, O, p, p, 0, *o, ws.data_ptr(), 8, None) != 0  # work space too small
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(t).all()) for t in outs + [ws]), "a refused call wrote something"
+    with pytest.raises(ValueError, match="limits"):
+        model.linear_head_train(src[:1025 * 2].view(1025, 2), src[:4].view(2, 2), src[:2], src[:2050].view(1025, 2))
+    check_head((65, 257, 3), 1, " after the refusals")
+
+
 # ---- gradients at the start -----------------------------------------------------------------------------------------
 def autograd_reference(model, x, y):
     """Loss and gradients of torch autograd on the CPU over the model's own torch layers, in float32 and float64."""
@@ -229,10 +295,12 @@ def check_grads(ours, loss_ours, g32, g64, loss64, n, label):
         err = np.max(np.abs(mine - ref64))
         err32 = np.max(np.abs(g32[k].astype(f64) - ref64))
         bound = max(4 * err32, U23 * np.max(np.abs(ref64)))
-        print(f"{label} {k}: |ours - g64| {err:.3e}  |g32 - g64| {err32:.3e}  bound {bound:.3e}")
+        print(f"{label} {k}: |ours - g64| {err:.3e}  |g32 - g64| {err32:.3e}  bound {bound:.3e}  error / bound "
+              f"{err / bound:.3g}")
         assert err <= bound, (label, k, err, bound)
     rel = abs(float(loss_ours) - loss64) / loss64
-    print(f"{label} loss: ours {float(loss_ours):.9g} ref64 {loss64:.9g} rel {rel:.3e} bound {n * U24:.3e}")
+    print(f"{label} loss: ours {float(loss_ours):.9g} ref64 {loss64:.9g} rel {rel:.3e} bound {n * U24:.3e}  error / "
+          f"bound {rel / (n * U24):.3g}")
     assert rel <= n * U24
 
 
@@ -263,6 +331,42 @@ def test_gradients_of_the_architecture_matrix(arch):
     loss, grads = model.cnn_loss_and_grads_device(m, x.cuda(), y.cuda())
     ref = autograd_reference(m, x, y)
     check_grads(grads, loss, ref[torch.float32][0], ref[torch.float64][0], ref[torch.float64][1], 2 * n, arch_id(arch))
+
+
+# Whole networks at the batch sizes of the workload.  Width 32, kernel 3, padding 1: 32 (sample, position) pairs per
+# sample, so n = 64 is exactly one slab of the reducer and one chunk of the Linear head's weight gradient, n = 65 adds
+# a slab of 32 pairs and a chunk of one sample, n = 1024 (the limit) has 16 of each; 129 and 257 lie past two chunks
+# and past the 256-thread stride of the loss kernel.  Smooth activations, so that the float32 reference is not itself
+# at a kink; one ReLU case with a pool.
+BIG = [dict(n=n, batch_norm=bn, activation=nn.Tanh if bn else nn.SiLU) for n in (64, 65, 129, 257, 1024)
+       for bn in (False, True)] + [
+    dict(n=65, output_size=1), dict(n=65, output_size=3, batch_norm=True), dict(n=65, output_size=16),
+    dict(n=65, pool=True, width=33, batch_norm=True, activation=nn.ReLU),
+    dict(n=65, groups=2, channels=4, layer_sizes=[6, 4], batch_norm=True), dict(n=65, loss=F.mse_loss, activation=nn.Tanh),
+]
+
+
+def big_model(arch):
+    from onset_fingerprinting_amd import model
+    kw = dict(arch)
+    n, width, channels, out = kw.pop("n"), kw.pop("width", 32), kw.pop("channels", 3), kw.pop("output_size", 2)
+    torch.manual_seed(len(arch_id(arch)))
+    m = model.CNN(width, out, channels=channels, dropout_rate=0.0, **{"layer_sizes": [5, 6], **kw})
+    return m, torch.randn(n, channels, width), torch.randn(n, out)
+
+
+@pytest.mark.parametrize("arch", BIG, ids=arch_id)
+def test_gradients_past_one_slab_and_one_chunk(arch):
+    from onset_fingerprinting_amd import _lib, model
+    m, x, y = big_model(arch)
+    n, wc = len(x), x.shape[2]
+    if "width" not in arch:
+        slab = int(_lib.lib().ofp_cnn_train_slab())
+        assert wc * 64 == slab and (n == 64 or n * wc > slab)
+    loss, grads = model.cnn_loss_and_grads_device(m, x.cuda(), y.cuda())
+    ref = autograd_reference(m, x, y)
+    check_grads(grads, loss, ref[torch.float32][0], ref[torch.float64][0], ref[torch.float64][1], y.numel(),
+                arch_id(arch))
 
 
 @pytest.mark.parametrize("case", CASES + [STOP])
@@ -436,3 +540,54 @@ def test_in_place_semantics(g):
     assert float(again.train_loss[0]) == float(loss_now)
     assert float(again.train_loss[0]) < float(fit.train_loss[0])
     assert int(m.conv_layers.bn1.num_batches_tracked) == 45
+
+
+# ---- the epoch past one slab, one chunk and 256 validation windows --------------------------------------------------
+def epoch_start():
+    """Width 32 with BatchNorm, n = 130 (three slabs, three chunks), n_val = 300 > n and > the loss kernel's 256
+    threads: the work space is sized by the validation batch."""
+    from onset_fingerprinting_amd import model
+    torch.manual_seed(130)
+    m = model.CNN(32, 2, channels=3, dropout_rate=0.0, layer_sizes=[5, 6], batch_norm=True)
+    return m, torch.randn(130, 3, 32), torch.randn(130, 2), torch.randn(300, 3, 32), torch.randn(300, 2)
+
+
+def test_one_epoch_with_a_validation_batch_larger_than_the_training_batch():
+    from onset_fingerprinting_amd import model
+    m, x, y, xv, yv = epoch_start()
+    m = m.cuda()
+    loss0, _g = model.cnn_loss_and_grads_device(m, x.cuda(), y.cuda())
+    fit = model.fit_cnn(m, x.cuda(), y.cuda(), x_val=xv.cuda(), y_val=yv.cuda(), max_epochs=1)
+    assert fit.epochs == 1
+    assert float(fit.train_loss[0]) == float(loss0)
+    ref = {}
+    for dtype in (torch.float32, torch.float64):
+        net = copy.deepcopy(m).cpu().to(dtype).eval()
+        with torch.no_grad():
+            ref[dtype] = float(F.l1_loss(net.fc(torch.flatten(net.conv_layers(xv.to(dtype)), start_dim=1)),
+                                         yv.to(dtype)))
+    ours, l32, l64 = float(fit.val_loss[0]), ref[torch.float32], ref[torch.float64]
+    bound = max(4 * abs(l32 - l64), U22 * l64)
+    print(f"validation loss after one epoch: ours {ours:.9g} torch float32 {l32:.9g} float64 {l64:.9g}; |ours - l64| "
+          f"{abs(ours - l64):.3e} bound {bound:.3e}  error / bound {abs(ours - l64) / bound:.3g}")
+    assert abs(ours - l64) <= bound
+
+
+def test_determinism_past_one_slab_and_one_chunk(monkeypatch):
+    """Five epochs twice as a graph and once as plain launches: the same bits in both curves and in the final state."""
+    from onset_fingerprinting_amd import model
+    start, x, y, xv, yv = epoch_start()
+    results = []
+    for mode in (None, None, "nodes"):
+        if mode:
+            monkeypatch.setenv("OFP_CNN_GRAPH", mode)
+        m = copy.deepcopy(start).cuda()
+        fit = model.fit_cnn(m, x.cuda(), y.cuda(), x_val=xv.cuda(), y_val=yv.cuda(), max_epochs=5)
+        results.append((fit, torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values()])))
+    monkeypatch.delenv("OFP_CNN_GRAPH", raising=False)
+    (a, pa) = results[0]
+    assert a.epochs == 5 and bool(torch.isfinite(a.train_loss).all()) and bool(torch.isfinite(a.val_loss).all())
+    for b, pb in results[1:]:
+        assert b.epochs == 5 and torch.equal(pa, pb)
+        assert torch.equal(a.train_loss.view(torch.int32), b.train_loss.view(torch.int32))
+        assert torch.equal(a.val_loss.view(torch.int32), b.val_loss.view(torch.int32))
