@@ -85,7 +85,7 @@ int ofp_lfilter(const float* x, float* y, const float* b, const float* a, int or
 typedef struct ofp_detector_params {
     int32_t n_channels;   /* C: signals per detector instance (detection.py:633) */
     int32_t block_size;   /* B (detection.py:634) */
-    float floor_db;       /* floor (detection.py:635) */
+    float floor_db;       /* floor (detection.py:635); zero or negative (-inf allowed): a positive or NaN floor is refused */
     int32_t hp_enabled;   /* hipass_freq != 0 (detection.py:692-696) */
     float hp_b[5];        /* np.float32(butter(4, f, "high", fs=sr)) (detection.py:492-496) */
     float hp_a[5];
@@ -251,6 +251,28 @@ int ofp_detect_plan_query(const ofp_detector* det, int64_t n_clips, int64_t n_sa
  * Makes no HIP call, so it also runs on a machine without a GPU. */
 int ofp_detect_plan_for(const ofp_detector_params* p, const ofp_detect_tuning* t, int n_cus, int64_t n_clips,
                         int64_t n_samples, int64_t warm, int want_rel, const void* d_rel, ofp_detect_plan* out);
+
+/* The arithmetic canon of include/ofp_math.h on the device, one value at a time (tests): d_out[i] = op(d_x[i], d_y[i]) for
+ * i < n, each op calling the header's function and nothing else.  d_x, d_y, d_out: device arrays of n floats, any 4-byte
+ * alignment; d_y may be NULL for the one-operand ops.  Parameters per op:
+ *   LOG10(x), EXP10(x)                 none
+ *   RECT_DB(x), REL_LINEAR(x)          p0 = floor_db
+ *   AR_STEP(x, y)                      p0 = attack, p1 = release (the coefficients)
+ *   MIN_STEP(x, y = mn)                p0 = alpha, p1 = minmin; ialpha = ofp_ialpha(alpha) is formed on the host, as
+ *   MAX_STEP(x, y = mx)                p0 = alpha                ofp_detector_create forms it
+ * p2 is not used by any op yet.  An unknown op, a negative n or a missing array is refused and nothing is launched;
+ * n = 0 launches nothing. */
+enum {
+    OFP_CANON_LOG10 = 0,
+    OFP_CANON_EXP10 = 1,
+    OFP_CANON_RECT_DB = 2,
+    OFP_CANON_REL_LINEAR = 3,
+    OFP_CANON_AR_STEP = 4,
+    OFP_CANON_MIN_STEP = 5,
+    OFP_CANON_MAX_STEP = 6
+};
+int ofp_canon_eval(int32_t op, const float* d_x, const float* d_y, int64_t n, float p0, float p1, float p2, float* d_out,
+                   void* stream);
 
 /* detect_onsets_amplitude (detection.py:19-86) for a batch of independent clips.
  *   d_x        [n_clips][n_samples][C] float32, interleaved as the reference expects

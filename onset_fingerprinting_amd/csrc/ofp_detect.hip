@@ -4278,6 +4278,11 @@ int ofp_detector_create(const ofp_detector_params* p, const double* on_threshold
     OFP_REQUIRE(!p->backtrack || p->backtrack_buffer_size >= p->block_size,
                 "backtrack_buffer_size should be at least block_size!");
     OFP_REQUIRE(!p->hp_enabled || p->hp_a[0] != 0.0f, "hp_a[0] must be non-zero");
+    // rel = rel.clip(0, -floor) (detection.py:754): with floor > 0 the bounds cross and every value of the relative
+    // envelope becomes the negative constant -floor, with a NaN floor every value becomes NaN -- no onset can follow from
+    // either, and the block extremes of the back-to-linear pass (rel_out_tile) rely on clipped, non-negative values
+    OFP_REQUIRE(p->floor_db <= 0.0f, "floor_db %g must be zero or negative (NaN is refused too): rel.clip(0, -floor) "
+                "leaves no envelope otherwise", (double)p->floor_db);
     ofp_detector* d = new (std::nothrow) ofp_detector();
     if (!d) return ofp::fail(OFP_ERR_INVALID, "out of host memory");
     d->p = *p;

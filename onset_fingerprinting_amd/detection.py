@@ -303,6 +303,24 @@ def detect_plan(n_signals, n_clips, n_samples, block_size=128, sr=96000, warm=No
     return plan.as_dict()
 
 
+CANON_OPS = {"log10": 0, "exp10": 1, "rect_db": 2, "rel_linear": 3, "ar_step": 4, "min_step": 5, "max_step": 6}  # OFP_CANON_*
+
+
+def canon_eval(op, x, y=None, p0=0.0, p1=0.0, out=None):
+    """The canon of include/ofp_math.h on the device, elementwise (ofp_canon_eval): x, y float32 CUDA tensors of one
+    size (y for "ar_step", "min_step", "max_step" only); p0, p1 as the header lists them per op (floor; attack, release;
+    alpha, minmin; alpha).  Writes `out` (default: a new tensor like x) and returns it."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    if y is not None:
+        assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.numel() == x.numel()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.numel()
+    check(_lib.lib().ofp_canon_eval(CANON_OPS[op], x.data_ptr(), y.data_ptr() if y is not None else None, x.numel(),
+                                    p0, p1, 0.0, out.data_ptr(), _stream_ptr(x.device)), "ofp_canon_eval")
+    return out
+
+
 def group_onsets_device(out, n_channels, max_distance=1000, min_channels=3, close_channel=None, cap_groups=None):
     """find_onset_groups (detection.py:131-189) for every clip of a `BatchDetector.detect`
     result, on the device.  Returns ``groups`` int64 [n_clips, cap_groups, n_channels] and

@@ -12,6 +12,9 @@ from .detector import (  # noqa: F401
     OracleDetector,
     init_ranges,
     ar_envelope,
+    ar_step,
+    max_step,
+    min_step,
     backtrack_onsets,
     butter_hp_f32,
     detect_onsets_amplitude,

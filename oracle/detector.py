@@ -59,6 +59,9 @@ for _n in ("oracle_rect_db", "oracle_rel_linear"):
     getattr(lib, _n).argtypes = [_f32p, _f32p, ctypes.c_long, ctypes.c_float]
 for _n in ("oracle_log10f", "oracle_exp10f"):
     getattr(lib, _n).argtypes = [_f32p, _f32p, ctypes.c_long]
+lib.oracle_ar_step.argtypes = [_f32p, _f32p, _f32p, ctypes.c_long, ctypes.c_float, ctypes.c_float]
+lib.oracle_min_step.argtypes = [_f32p, _f32p, _f32p, ctypes.c_long, ctypes.c_float, ctypes.c_float]
+lib.oracle_max_step.argtypes = [_f32p, _f32p, _f32p, ctypes.c_long, ctypes.c_float]
 lib.oracle_detector_create.restype = ctypes.c_void_p
 lib.oracle_detector_create.argtypes = [ctypes.POINTER(_Params), _f64p, _f64p]
 lib.oracle_detector_destroy.argtypes = [ctypes.c_void_p]
@@ -163,6 +166,30 @@ def rect_db(x, floor):
 def rel_linear(d, floor):
     """detection.py:753-754."""
     return _ew(lib.oracle_rel_linear, d, floor)
+
+
+def _ew2(fn, x, y, *extra):
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    assert x.size == y.size
+    out = np.empty_like(x)
+    fn(x, y, out, x.size, *extra)
+    return out
+
+
+def ar_step(x, y, attack, release):
+    """One follower step per element (envelope_follower.c:15-22): state y, input x -> the new state."""
+    return _ew2(lib.oracle_ar_step, x, y, attack, release)
+
+
+def min_step(x, mn, alpha, minmin):
+    """One EMA-min step per element (envelope_follower.c:39-45)."""
+    return _ew2(lib.oracle_min_step, x, mn, alpha, minmin)
+
+
+def max_step(x, mx, alpha):
+    """One EMA-max step per element (envelope_follower.c:47-51)."""
+    return _ew2(lib.oracle_max_step, x, mx, alpha)
 
 
 def init_ranges(n, block_size, sr):

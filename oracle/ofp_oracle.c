@@ -146,6 +146,20 @@ void oracle_exp10f(const float* x, float* y, long n) {
     for (long i = 0; i < n; ++i) y[i] = ofp_exp10f(x[i]);
 }
 
+/* ---- one follower / tracker step per element (envelope_follower.c:15-22, :39-51): y[i] is the state before the
+ * step, out[i] the state after it; ialpha is formed as oracle_minmax_envelope forms it */
+void oracle_ar_step(const float* x, const float* y, float* out, long n, float attack, float release) {
+    for (long i = 0; i < n; ++i) out[i] = ofp_ar_step(x[i], y[i], attack, release);
+}
+void oracle_min_step(const float* x, const float* mn, float* out, long n, float alpha, float minmin) {
+    float ialpha = ofp_ialpha(alpha);
+    for (long i = 0; i < n; ++i) out[i] = ofp_min_step(x[i], mn[i], ialpha, alpha, minmin);
+}
+void oracle_max_step(const float* x, const float* mx, float* out, long n, float alpha) {
+    float ialpha = ofp_ialpha(alpha);
+    for (long i = 0; i < n; ++i) out[i] = ofp_max_step(x[i], mx[i], ialpha, alpha);
+}
+
 /* ---- AmplitudeOnsetDetector: detection.py:595-888 ------------------------- */
 typedef struct {
     int C, B;
