@@ -1204,6 +1204,9 @@ int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const fl
  *   stretch_span <= width, width + stretch_span - 1 <= 2048, audio_len >= width + 2 max_shift + stretch_span - 1, and
  *   16 (2 width + stretch_span - 1 + channels (width / 2 + 1)) + 4 channels (width + stretch_span - 1) bytes of LDS
  *   <= 160 KiB; a span needs a window source.
+ * Site 3, attention dropout (ofp_cnnrnn_train_stretch only): index = ((s heads + h) T + i) T + j over the softmax
+ *   probabilities [n][heads][T][T]; the rule and the scale of site 0, with the same dropout_p.  In that trainer site 0
+ *   indexes the conv features [n][C W] in front of the GRU.
  * ofp_*_train_random / ofp_*_loss_grads_random / ofp_*_train_random_workspace_bytes: the functions without
  *   `_random`, which they are with random = NULL, plus these options (ofp_*_loss_grads_random takes no window source).
  * ofp_*_train_stretch / ofp_*_train_stretch_workspace_bytes: the `_random` functions, which they are with
@@ -1267,6 +1270,82 @@ int ofp_cccnn_train_stretch(const ofp_cccnn_config* cfg, int64_t n, const float*
                             int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
                             float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                             const ofp_train_random* random, int32_t stretch_span);
+
+/* ---- training model.CNNRNN (model.py:310-440; csrc/ofp_cnnrnn_train.hip) -------------------------------------------
+ * Network: the conv stack of ofp_cnn_config (`cnn`; its n_out and loss are the head's), the model's dropout on the
+ *   conv features, a one-layer GRU (batch_first, biases, gate order r, z, n, h_0 = 0) that takes the last conv layer's
+ *   C channels as T time steps and its W columns as features, self-attention of `heads` heads over the `hidden` wide
+ *   output sequence with dropout on the softmax probabilities, the mean over time, out_proj, and a Linear to n_out
+ *   values.  The recipe is ofp_cnn_train's (NAdam rows in d_rates [num_epochs][4], the validation loss always L1, the
+ *   stop rule, one captured graph per epoch with the first epoch launched plainly, a created stream);
+ *   OFP_CNNRNN_GRAPH=nodes launches the same chain without a graph.
+ * Parameters are packed in state_dict order: the conv stack as for ofp_cnn_train, then rnn.weight_ih_l0 [3 hidden][W],
+ *   weight_hh_l0 [3 hidden][hidden], bias_ih_l0, bias_hh_l0 [3 hidden], attention.in_proj_weight [3 hidden][hidden],
+ *   in_proj_bias [3 hidden], out_proj.weight [hidden][hidden], out_proj.bias [hidden], fc.weight [n_out][hidden],
+ *   fc.bias [n_out].  The running statistics as for ofp_cnn_train.
+ * Limits (beyond them OFP_ERR_INVALID, or -1 from the size functions): those of ofp_cnn_train, hidden 1..128, heads
+ *   1..8 dividing hidden, C <= 128 time steps.
+ * Random stream (ofp_train_random): site 0 is the dropout on the conv features [n][C W], element s C W + f; site 3 the
+ *   dropout on the attention's probabilities [n][heads][T][T], element ((s heads + h) T + i) T + j; both with dropout_p,
+ *   word < (uint32)(dropout_p 2^32) drops, kept values are multiplied by (float)(1 / (1 - dropout_p)).  Neither is
+ *   applied in the validation forward.  The window source (sites 1 and 2) is ofp_cnn_train_stretch's.
+ * Sums: no atomics; every dot product and every sum over rows is fp64 in ascending order, rounded to fp32 once; the
+ *   weight and bias gradients of a dense layer are summed over slabs of ofp_linear_backward_slab() rows and the slabs
+ *   added in order.
+ * ofp_cnnrnn_loss_grads_random: one training-mode forward and backward (no window source): d_loss [1], d_grads packed
+ *   like the parameters; d_ws of ofp_cnnrnn_loss_grads_random_workspace_bytes (n_val = 0).
+ * ofp_linear_backward: y = x w^T + b with d_x [rows][n_in], d_w [n_out][n_in], d_dy [rows][n_out] -> d_dx [rows][n_in]
+ *   (unless NULL), d_dw [n_out][n_in], d_db [n_out].  rows 1..2^20, n_in and n_out 1..4096.
+ * ofp_gru_train_forward: d_x [n][T][F] -> d_out [n][T][H] and d_gates [n][T][4 H] = r, z, n and W_hn h + b_hn of every
+ *   step.  ofp_gru_train_backward: with those and d_dout [n][T][H] -> d_dx [n][T][F], d_dw_ih [3H][F], d_dw_hh [3H][H],
+ *   d_db_ih, d_db_hh [3H].  n 1..1024, T 1..128, F 1..1024, H 1..128.
+ * ofp_attention_mean_train_forward: d_h [n][T][E] -> d_qkv [n][T][3E] (the in-projection), d_probs [n][heads][T][T]
+ *   (softmax, before dropout) and d_ctx [n][E] = attention(h, h, h) before out_proj, averaged over time; `random`
+ *   (NULL: none) gives seed, epoch and dropout_p of site 3.  _backward: with those and d_dctx [n][E] -> d_dh [n][T][E],
+ *   d_dw [3E][E], d_db [3E] of the in-projection.  n 1..1024, T 1..128, E 1..128, heads 1..8 dividing E.
+ * ofp_attention_dropout_mask: d_mask [n][heads][T][T] of 0 and (float)(1 / (1 - p)), site 3. */
+typedef struct ofp_cnnrnn_config {
+    ofp_cnn_config cnn;
+    int32_t hidden, heads;
+} ofp_cnnrnn_config;
+int32_t ofp_linear_backward_slab(void);
+int64_t ofp_cnnrnn_train_stretch_workspace_bytes(const ofp_cnnrnn_config* cfg, int64_t n, int64_t n_val,
+                                                 const ofp_train_random* random, int32_t stretch_span);
+int ofp_cnnrnn_train_stretch(const ofp_cnnrnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                             int64_t n_val, const float* d_x_val, const float* d_y_val, const float* d_rates,
+                             int32_t num_epochs, int32_t min_epochs, int32_t patience, float* d_params, float* d_stats,
+                             float* d_train_loss, float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes,
+                             void* stream, const ofp_train_random* random, int32_t stretch_span);
+int64_t ofp_cnnrnn_loss_grads_random_workspace_bytes(const ofp_cnnrnn_config* cfg, int64_t n, int64_t n_val,
+                                                     const ofp_train_random* random);
+int ofp_cnnrnn_loss_grads_random(const ofp_cnnrnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                                 const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                                 void* stream, const ofp_train_random* random);
+int64_t ofp_linear_backward_workspace_bytes(int64_t rows, int32_t n_in, int32_t n_out);
+int ofp_linear_backward(const float* d_x, int64_t rows, int32_t n_in, const float* d_w, int32_t n_out,
+                        const float* d_dy, float* d_dx, float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes,
+                        void* stream);
+int64_t ofp_gru_train_forward_workspace_bytes(int64_t n, int32_t T, int32_t F, int32_t H);
+int ofp_gru_train_forward(const float* d_x, int64_t n, int32_t T, int32_t F, int32_t H, const float* d_w_ih,
+                          const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, float* d_out, float* d_gates,
+                          void* d_ws, int64_t ws_bytes, void* stream);
+int64_t ofp_gru_train_backward_workspace_bytes(int64_t n, int32_t T, int32_t F, int32_t H);
+int ofp_gru_train_backward(const float* d_x, int64_t n, int32_t T, int32_t F, int32_t H, const float* d_w_ih,
+                           const float* d_w_hh, const float* d_out, const float* d_gates, const float* d_dout,
+                           float* d_dx, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, void* d_ws,
+                           int64_t ws_bytes, void* stream);
+int64_t ofp_attention_mean_train_forward_workspace_bytes(int64_t n, int32_t T, int32_t E, int32_t heads);
+int ofp_attention_mean_train_forward(const float* d_h, int64_t n, int32_t T, int32_t E, int32_t heads,
+                                     const float* d_in_w, const float* d_in_b, const ofp_train_random* random,
+                                     float* d_qkv, float* d_probs, float* d_ctx, void* d_ws, int64_t ws_bytes,
+                                     void* stream);
+int64_t ofp_attention_mean_train_backward_workspace_bytes(int64_t n, int32_t T, int32_t E, int32_t heads);
+int ofp_attention_mean_train_backward(const float* d_h, int64_t n, int32_t T, int32_t E, int32_t heads,
+                                      const float* d_in_w, const float* d_qkv, const float* d_probs,
+                                      const float* d_dctx, const ofp_train_random* random, float* d_dh, float* d_dw,
+                                      float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_attention_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t heads, int32_t T, double p,
+                               float* d_mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,11 @@ class CnnConfig(ctypes.Structure):
     ]
 
 
+class CnnrnnConfig(ctypes.Structure):
+    _fields_ = [("cnn", CnnConfig), ("hidden", ctypes.c_int32), ("heads", ctypes.c_int32)]
+    width = property(lambda self: self.cnn.width)  # what model._fit compares between x and x_val
+
+
 class CccnnConfig(ctypes.Structure):
     _fields_ = [
         ("n_conv", ctypes.c_int32),
@@ -409,6 +414,31 @@ SIGNATURES = {
     "ofp_cccnn_train_stretch": (ctypes.c_int, [ctypes.POINTER(CccnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
                                                _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
                                                ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_linear_backward_slab": (_i32, []),
+    "ofp_cnnrnn_train_stretch_workspace_bytes": (_i64, [ctypes.POINTER(CnnrnnConfig), _i64, _i64,
+                                                        ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_cnnrnn_train_stretch": (ctypes.c_int, [ctypes.POINTER(CnnrnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                                _i32, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                                ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_cnnrnn_loss_grads_random_workspace_bytes": (_i64, [ctypes.POINTER(CnnrnnConfig), _i64, _i64,
+                                                            ctypes.POINTER(TrainRandom)]),
+    "ofp_cnnrnn_loss_grads_random": (ctypes.c_int, [ctypes.POINTER(CnnrnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _i64, _vp, ctypes.POINTER(TrainRandom)]),
+    "ofp_linear_backward_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ofp_linear_backward": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_gru_train_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_gru_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                             _vp]),
+    "ofp_gru_train_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_gru_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _i64, _vp]),
+    "ofp_attention_mean_train_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_attention_mean_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp,
+                                                        ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_attention_mean_train_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_attention_mean_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                         ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_attention_dropout_mask": (ctypes.c_int, [ctypes.c_uint64, _i32, _i64, _i32, _i32, _f64, _vp, _vp]),
 }
 
 _lib = None

@@ -3,8 +3,9 @@
 // so a replayed graph draws a new mask and new shifts at every launch without any argument changing; without a
 // control block (the stand-alone forms and the loss-and-gradients functions) it is an argument.  Nothing is stored: any
 // mask, shift or stretch can be recomputed from (seed, epoch, index).  Site 0 is the dropout in front of the Linear
-// head, site 1 the shift of the training windows, site 2 their stretch.  File-local like ofp_train_chain.h, which it
-// builds on.
+// head, site 1 the shift of the training windows, site 2 their stretch.  Site 3 is the dropout on the attention's softmax
+// probabilities in csrc/ofp_cnnrnn_train.hip, where site 0 is the dropout on the conv features in front of the GRU.
+// File-local like ofp_train_chain.h, which it builds on.
 #pragma once
 #include "ofp_resample_dev.h"
 #include "ofp_train_chain.h"

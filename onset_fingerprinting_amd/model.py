@@ -12,7 +12,9 @@ csrc/ofp_rnn.hip); torch only allocates memory and makes views.  ``rnn_forward``
 ``configure_optimizers`` (full batch, SGD with momentum 0.8 and weight decay 1e-3 at 100 x ``lr``, cosine annealing over
 100 epochs) the same way (csrc/ofp_cccnn_train.hip).  With ``seed=`` both apply the model's dropout and, given a
 ``data.ShiftedWindows`` or ``data.StretchedWindows``, cut shifted (and stretched) training windows anew every epoch,
-from this package's own random stream (csrc/ofp_train_random.h).  Training the recurrent classes is out of scope
+from this package's own random stream (csrc/ofp_train_random.h).  ``fit_cnnrnn`` trains a ``CNNRNN`` in place with the
+recipe of its ``training_step`` / ``configure_optimizers`` (full batch, NAdam, cosine annealing over 100 epochs) the same
+way, back-propagating through the GRU and the attention (csrc/ofp_cnnrnn_train.hip).  Training ``RNN`` is out of scope
 (DESIGN.md section 7).
 """
 import ctypes
@@ -683,8 +685,9 @@ def _check_source(x, seed):
         raise ValueError("a window source with max_shift > 0 or a stretch needs seed=")
 
 
-def _cnn_arch(model, width=None, seed=None):
-    """(CnnConfig, convs, batch norms) of a CNN for the trainer; ValueError for what it cannot run."""
+def _cnn_arch(model, width=None, seed=None, flat_head=True):
+    """(CnnConfig, convs, batch norms) of a CNN for the trainer; ValueError for what it cannot run.  flat_head=False:
+    ``fc`` does not read the flattened conv features (a CNNRNN; _cnnrnn_arch checks what does)."""
     _check_dropout(model.dropout.p, seed)
     loss = _loss_code(model.loss)
     mods = list(model.conv_layers)
@@ -742,7 +745,7 @@ def _cnn_arch(model, width=None, seed=None):
             w = w // 2 if pools else w
             if w < 1:
                 raise ValueError(f"a window of {width} samples leaves no column after the conv layers")
-        if channels[-1] * w != model.fc.in_features:
+        if flat_head and channels[-1] * w != model.fc.in_features:
             raise ValueError(f"a window of {width} samples gives {channels[-1] * w} features; the model's Linear "
                              f"expects {model.fc.in_features}")
     return cfg, convs, bns
@@ -810,7 +813,7 @@ def _split(flat, tensors, copy=False):
 
 
 def _loss_and_grads(spec, model, x, y, seed, epoch):
-    """cnn_loss_and_grads_device / cccnn_loss_and_grads_device; `spec` is _CNN or _LCCCNN."""
+    """cnn_ / cccnn_ / cnnrnn_loss_and_grads_device; `spec` is _CNN, _LCCCNN or _CNNRNN."""
     x, y, cfg = spec.batch(model, x, y, seed=seed)
     net = spec.net(model)
     rnd, _keep = _train_random(net.dropout.p, seed, epoch)
@@ -836,7 +839,7 @@ def _loss_and_grads(spec, model, x, y, seed, epoch):
 
 
 def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed):
-    """fit_cnn / fit_lcccnn; `spec` is _CNN or _LCCCNN."""
+    """fit_cnn / fit_lcccnn / fit_cnnrnn; `spec` is _CNN, _LCCCNN or _CNNRNN."""
     x, y, cfg = spec.batch(model, x, y, seed=seed)
     _check_source(x, seed)
     source = x if isinstance(x, ShiftedWindows) else None
@@ -906,7 +909,7 @@ def _cnn_count_batches(model, epochs):
             m.num_batches_tracked += epochs
 
 
-# What differs between the two trainable models, for _fit and _loss_and_grads: the batch checker, the (name, tensor)
+# What differs between the trainable models (_CNN, _LCCCNN, _CNNRNN), for _fit and _loss_and_grads: the batch checker, the (name, tensor)
 # lists (parameters, running statistics), the module that carries `dropout` and `fc`, the rate table sent to the device
 # and the rates returned, the C entries, whether the train entry takes d_stats, and what is left to do after a fit.
 _CNN = SimpleNamespace(
@@ -1350,3 +1353,275 @@ def sgd_step(p, g, buf, lr, first, momentum=LCCCNN_MOMENTUM, weight_decay=LCCCNN
                                   int(bool(first)), float(momentum), float(weight_decay), _stream(p.device)),
           "ofp_sgd_step")
     return p
+
+
+# ---- training model.CNNRNN (model.py:310-440) ----------------------------------------------------------------------
+CNNRNN_TRAIN_MAX_HIDDEN, CNNRNN_TRAIN_MAX_STEPS, CNNRNN_TRAIN_HEADS = 128, 128, 2  # csrc/ofp_cnnrnn_train.hip
+SITE_ATTENTION = 3  # the random stream's site of the attention dropout (include/onsetfp.h)
+
+
+@functools.lru_cache(maxsize=256)
+def cnnrnn_rates(lr, num_epochs):
+    """The learning rate of every epoch of CNNRNN.configure_optimizers(): torch's own NAdam at ``lr`` and
+    CosineAnnealingLR(T_max = 100) stepped once per epoch on a dummy parameter (the rate reaches 0 at epoch 100 and
+    rises again after it).  float64 [num_epochs]."""
+    p = nn.Parameter(torch.zeros(1))
+    opt = torch.optim.NAdam([p], lr=lr)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, 100)
+    opt.step()
+    rates = np.empty(num_epochs, np.float64)
+    for e in range(num_epochs):
+        rates[e] = float(opt.param_groups[0]["lr"])
+        sched.step()
+    rates.setflags(write=False)
+    return rates
+
+
+def _cnnrnn_device_rows(lr, num_epochs):
+    """float32 [num_epochs][4] for ofp_cnnrnn_train_stretch: cnn_step_factors of NAdam at cnnrnn_rates, rounded once."""
+    table = np.array(cnn_rate_table(lr, num_epochs))  # NAdam's own factors do not depend on the schedule
+    table[:, 0] = cnnrnn_rates(float(lr), int(num_epochs))
+    rows = np.zeros((num_epochs, 4), np.float32)
+    rows[:, :3] = cnn_step_factors(table)
+    return rows
+
+
+def _cnnrnn_arch(model, width=None, seed=None):
+    """(CnnrnnConfig, convs, batch norms) of a CNNRNN for the trainer; ValueError for what it cannot run."""
+    if not isinstance(model, CNNRNN):
+        raise ValueError(f"{type(model).__name__} is not a CNNRNN")
+    cnn, convs, bns = _cnn_arch(model, width, seed, flat_head=False)
+    rnn, att = model.rnn, model.attention
+    if not isinstance(rnn, nn.GRU) or rnn.num_layers != 1 or not rnn.batch_first or rnn.bidirectional or not rnn.bias:
+        raise ValueError("the trainer runs one unidirectional nn.GRU layer with batch_first and biases "
+                         f"(n_rnn_layers={getattr(rnn, 'num_layers', '?')} is not trained on the GPU)")
+    H = rnn.hidden_size
+    if H % 2 or not 2 <= H <= CNNRNN_TRAIN_MAX_HIDDEN:
+        raise ValueError(f"n_hidden {H}: the trainer needs an even hidden size of at most {CNNRNN_TRAIN_MAX_HIDDEN}")
+    if convs[-1].out_channels > CNNRNN_TRAIN_MAX_STEPS:
+        raise ValueError(f"{convs[-1].out_channels} channels in the last conv layer are the GRU's time steps: the "
+                         f"trainer's limit is {CNNRNN_TRAIN_MAX_STEPS}")
+    if att.num_heads != CNNRNN_TRAIN_HEADS or not att.batch_first or att.in_proj_bias is None \
+            or att.in_proj_weight is None or att.embed_dim != H or att.bias_k is not None or att.add_zero_attn \
+            or att.out_proj.bias is None:
+        raise ValueError(f"the attention must have {CNNRNN_TRAIN_HEADS} heads, batch_first, biases and one embed dim "
+                         f"of n_hidden for q, k and v")
+    if att.dropout != model.dropout.p:
+        raise ValueError(f"the attention's dropout {att.dropout} differs from the model's {model.dropout.p}")
+    if model.fc.in_features != H:
+        raise ValueError(f"fc reads {model.fc.in_features} features, the attention gives {H}")
+    cfg = _lib.CnnrnnConfig()
+    cfg.cnn, cfg.hidden, cfg.heads = cnn, H, att.num_heads
+    if width is not None:
+        w = width
+        for _ in convs:
+            w = w + 2 * cnn.padding - cnn.dilation * (cnn.kernel - 1)
+            w = w // 2 if cnn.pool else w
+        if w != rnn.input_size:
+            raise ValueError(f"a window of {width} samples gives conv features {w} wide; the model's GRU expects "
+                             f"{rnn.input_size}")
+    return cfg, convs, bns
+
+
+def _cnnrnn_tensors(model, seed=None):
+    """[(state_dict name, tensor)] of a CNNRNN's parameters in packing order, and the running statistics likewise."""
+    _cnnrnn_arch(model, seed=seed)
+    ps, st = _cnn_tensors(model, seed)
+    rnn, att = model.rnn, model.attention
+    ps = ps[:-2] + [("rnn.weight_ih_l0", rnn.weight_ih_l0), ("rnn.weight_hh_l0", rnn.weight_hh_l0),
+                    ("rnn.bias_ih_l0", rnn.bias_ih_l0), ("rnn.bias_hh_l0", rnn.bias_hh_l0),
+                    ("attention.in_proj_weight", att.in_proj_weight), ("attention.in_proj_bias", att.in_proj_bias),
+                    ("attention.out_proj.weight", att.out_proj.weight), ("attention.out_proj.bias", att.out_proj.bias)
+                    ] + ps[-2:]
+    return ps, st
+
+
+def _cnnrnn_batch(model, x, y, what="x", seed=None):
+    x, y, shape = _batch_of(x, y, what)
+    if not 1 <= shape[0] <= CNN_TRAIN_MAX_BATCH:
+        raise ValueError(f"{shape[0]} windows: the trainer's limit is 1..{CNN_TRAIN_MAX_BATCH} (one full batch)")
+    cfg, _c, bns = _cnnrnn_arch(model, shape[2], seed)
+    c = cfg.cnn
+    if shape[1] != c.channels[0] or y.shape[1] != c.n_out:
+        raise ValueError(f"{what} {shape} / y {tuple(y.shape)} do not fit a model of {c.channels[0]} "
+                         f"channels and {c.n_out} outputs")
+    if bns and shape[0] * (shape[2] + 2 * c.padding - c.dilation * (c.kernel - 1)) < 2:
+        raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d)")
+    return x, y, cfg
+
+
+_CNNRNN = SimpleNamespace(
+    batch=_cnnrnn_batch, tensors=_cnnrnn_tensors, net=lambda model: model, device_rates=_cnnrnn_device_rows,
+    rates=cnnrnn_rates, c_workspace="ofp_cnnrnn_loss_grads_random_workspace_bytes", c_train="ofp_cnnrnn_train",
+    c_grads="ofp_cnnrnn_loss_grads", stats=True, after_fit=_cnn_count_batches)
+
+
+def cnnrnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
+    """Loss (``model.loss``) and the gradient of every parameter of a CNNRNN for the full batch x [n, channels, width],
+    y [n, outputs], in training mode (BatchNorm on batch statistics; the module's running statistics are not
+    touched), by the trainer's own forward and backward kernels.  With a seed both dropouts are applied as epoch
+    `epoch` of ``fit_cnnrnn(..., seed=seed)`` applies them (``dropout_mask_device`` on the conv features [n, C * W],
+    ``attention_dropout_mask_device`` on the probabilities).  Returns (loss, {state_dict name: gradient}) on the GPU."""
+    return _loss_and_grads(_CNNRNN, model, x, y, seed, epoch)
+
+
+def fit_cnnrnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
+    """Train a ``CNNRNN`` in place with the reference's recipe (model.py:400-440): the whole of x [n, channels, width] /
+    y [n, outputs] is one batch; every epoch is one training-mode forward, ``model.loss`` (F.l1_loss or F.mse_loss),
+    backward and one NAdam step (no weight decay) at the learning rate of CosineAnnealingLR(100) starting from
+    ``model.lr`` (``cnnrnn_rates``); then, with a validation set, an eval-mode forward of x_val and its L1 loss.  The
+    contract, the stop rule and the returned record are ``fit_cnn``'s: trained in place, left in eval mode, BatchNorm
+    running statistics and num_batches_tracked updated; one epoch is one launch of a captured graph of HIP kernels
+    (csrc/ofp_cnnrnn_train.hip).
+
+    ``seed`` opts into this package's own random stream as in ``fit_cnn``: ``model.dropout`` is then applied to the
+    conv features [n, C * W] in front of the GRU (site 0; ``dropout_mask_device(seed, epoch, n, C * W, p)`` is the
+    mask) and the attention's dropout to its softmax probabilities [n, 2, T, T] (site 3;
+    ``attention_dropout_mask_device``), both scaled by 1 / (1 - p), neither in the validation forward.  ``x`` may be a
+    ``data.ShiftedWindows`` / ``StretchedWindows`` as for ``fit_cnn``.
+
+    ValueError, before anything runs on the GPU: everything ``fit_cnn`` refuses about the conv stack, the batch, the
+    loss, the dropout and the window source; an ``rnn`` that is not one unidirectional batch_first nn.GRU layer with
+    biases whose input size is the conv output width; an odd n_hidden or one above 128; more than 128 channels in the
+    last conv layer (they are the GRU's time steps); an attention without 2 heads, batch_first, biases and a single
+    embed dim, or whose dropout differs from the model's; ``fc`` without a bias."""
+    return _fit(_CNNRNN, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed)
+
+
+def _f32_cuda(name, t, shape):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous float32 GPU tensor {list(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _outs(dev, given, shapes):
+    """The output tensors of a stand-alone kernel call: those given (checked), the others new."""
+    return [torch.empty(s, dtype=torch.float32, device=dev) if g is None else _f32_cuda("an out= tensor", g, s)
+            for g, s in zip(given, shapes)]
+
+
+def linear_backward(x, w, dy, *, out=None, need_dx=True):
+    """The three gradients of y = x w^T + b (ofp_linear_backward) on float32 CUDA tensors: x [rows, in], w [out, in],
+    dy [rows, out] -> (dx [rows, in] or None, dw [out, in], db [out]); ``out=(dx, dw, db)`` are preallocated outputs."""
+    L = _lib.lib()
+    R, I = x.shape
+    O = w.shape[0]
+    _f32_cuda("x", x, (R, I)), _f32_cuda("w", w, (O, I)), _f32_cuda("dy", dy, (R, O))
+    ws_bytes = int(L.ofp_linear_backward_workspace_bytes(R, I, O))
+    if ws_bytes < 0:
+        raise ValueError(f"{R} rows, {I} inputs, {O} outputs: beyond the Linear backward's limits (2^20, 4096, 4096)")
+    dx, dw, db = _outs(x.device, out or (None,) * 3, [(R, I), (O, I), (O,)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_linear_backward(x.data_ptr(), R, I, w.data_ptr(), O, dy.data_ptr(), dx.data_ptr() if need_dx else None,
+                                dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws_bytes, _stream(x.device)),
+          "ofp_linear_backward")
+    return (dx if need_dx else None), dw, db
+
+
+def gru_train_forward(x, w_ih, w_hh, b_ih, b_hh, *, out=None):
+    """A one-layer batch_first GRU with zero initial state in training form (ofp_gru_train_forward) on float32 CUDA
+    tensors: x [n, T, F], w_ih [3H, F], w_hh [3H, H], b_ih, b_hh [3H] (gate order r, z, n) -> (the output sequence
+    [n, T, H], gates [n, T, 4H] = r, z, n and W_hn h + b_hn of every step, for gru_train_backward);
+    ``out=(sequence, gates)`` are preallocated outputs."""
+    L = _lib.lib()
+    n, T, F_ = x.shape
+    H = w_hh.shape[1]
+    _f32_cuda("x", x, (n, T, F_)), _f32_cuda("w_ih", w_ih, (3 * H, F_)), _f32_cuda("w_hh", w_hh, (3 * H, H))
+    _f32_cuda("b_ih", b_ih, (3 * H,)), _f32_cuda("b_hh", b_hh, (3 * H,))
+    ws_bytes = int(L.ofp_gru_train_forward_workspace_bytes(n, T, F_, H))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    seq, gates = _outs(x.device, out or (None,) * 2, [(n, T, H), (n, T, 4 * H)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_gru_train_forward(x.data_ptr(), n, T, F_, H, w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(),
+                                  b_hh.data_ptr(), seq.data_ptr(), gates.data_ptr(), ws.data_ptr(), ws_bytes,
+                                  _stream(x.device)), "ofp_gru_train_forward")
+    return seq, gates
+
+
+def gru_train_backward(x, w_ih, w_hh, seq, gates, dseq, *, out=None):
+    """Back-propagation through time of gru_train_forward (ofp_gru_train_backward): dseq [n, T, H] = the gradient at the
+    output sequence -> (dx [n, T, F], dw_ih, dw_hh, db_ih, db_hh); ``out=`` are those five, preallocated."""
+    L = _lib.lib()
+    n, T, F_ = x.shape
+    H = w_hh.shape[1]
+    _f32_cuda("x", x, (n, T, F_)), _f32_cuda("w_ih", w_ih, (3 * H, F_)), _f32_cuda("w_hh", w_hh, (3 * H, H))
+    _f32_cuda("seq", seq, (n, T, H)), _f32_cuda("gates", gates, (n, T, 4 * H)), _f32_cuda("dseq", dseq, (n, T, H))
+    ws_bytes = int(L.ofp_gru_train_backward_workspace_bytes(n, T, F_, H))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    outs = _outs(x.device, out or (None,) * 5, [(n, T, F_), (3 * H, F_), (3 * H, H), (3 * H,), (3 * H,)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_gru_train_backward(x.data_ptr(), n, T, F_, H, w_ih.data_ptr(), w_hh.data_ptr(), seq.data_ptr(),
+                                   gates.data_ptr(), dseq.data_ptr(), *(t.data_ptr() for t in outs), ws.data_ptr(),
+                                   ws_bytes, _stream(x.device)), "ofp_gru_train_backward")
+    return tuple(outs)
+
+
+def _attention_random(p, seed, epoch):
+    if p and seed is None:
+        raise ValueError("attention dropout needs seed=")
+    rnd, _k = _train_random(float(p), seed, epoch)
+    return rnd
+
+
+def attention_mean_train_forward(h, in_proj_w, in_proj_b, num_heads, p=0.0, seed=None, epoch=0, *, out=None):
+    """``attention(h, h, h)[0].mean(1)`` without out_proj, in training form (ofp_attention_mean_train_forward), on
+    float32 CUDA tensors: h [n, T, E], in_proj_w [3E, E], in_proj_b [3E] -> (ctx [n, E], qkv [n, T, 3E], probs [n,
+    heads, T, T] = the softmax before dropout).  With p > 0 and a seed the probabilities are dropped by site 3 of the
+    random stream (``attention_dropout_mask_device``).  ``out=(ctx, qkv, probs)`` are preallocated outputs."""
+    L = _lib.lib()
+    n, T, E = h.shape
+    _f32_cuda("h", h, (n, T, E)), _f32_cuda("in_proj_w", in_proj_w, (3 * E, E)), _f32_cuda("in_proj_b", in_proj_b, (3 * E,))
+    rnd = _attention_random(p, seed, epoch)
+    ws_bytes = int(L.ofp_attention_mean_train_forward_workspace_bytes(n, T, E, num_heads))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ctx, qkv, probs = _outs(h.device, out or (None,) * 3, [(n, E), (n, T, 3 * E), (n, num_heads, T, T)])
+    ws = _workspace(ws_bytes, h.device)
+    check(L.ofp_attention_mean_train_forward(h.data_ptr(), n, T, E, num_heads, in_proj_w.data_ptr(),
+                                             in_proj_b.data_ptr(), ctypes.byref(rnd) if rnd is not None else None,
+                                             qkv.data_ptr(), probs.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws_bytes,
+                                             _stream(h.device)), "ofp_attention_mean_train_forward")
+    return ctx, qkv, probs
+
+
+def attention_mean_train_backward(h, in_proj_w, num_heads, qkv, probs, dctx, p=0.0, seed=None, epoch=0, *, out=None):
+    """Backward of attention_mean_train_forward with the same p, seed and epoch: dctx [n, E] -> (dh [n, T, E],
+    d in_proj_w [3E, E], d in_proj_b [3E]); ``out=`` are those three, preallocated."""
+    L = _lib.lib()
+    n, T, E = h.shape
+    _f32_cuda("h", h, (n, T, E)), _f32_cuda("in_proj_w", in_proj_w, (3 * E, E)), _f32_cuda("qkv", qkv, (n, T, 3 * E))
+    _f32_cuda("probs", probs, (n, num_heads, T, T)), _f32_cuda("dctx", dctx, (n, E))
+    rnd = _attention_random(p, seed, epoch)
+    ws_bytes = int(L.ofp_attention_mean_train_backward_workspace_bytes(n, T, E, num_heads))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    outs = _outs(h.device, out or (None,) * 3, [(n, T, E), (3 * E, E), (3 * E,)])
+    ws = _workspace(ws_bytes, h.device)
+    check(L.ofp_attention_mean_train_backward(h.data_ptr(), n, T, E, num_heads, in_proj_w.data_ptr(), qkv.data_ptr(),
+                                              probs.data_ptr(), dctx.data_ptr(),
+                                              ctypes.byref(rnd) if rnd is not None else None,
+                                              *(t.data_ptr() for t in outs), ws.data_ptr(), ws_bytes,
+                                              _stream(h.device)), "ofp_attention_mean_train_backward")
+    return tuple(outs)
+
+
+def attention_dropout_mask_device(seed, epoch, n, heads, T, p, device=0, *, out=None):
+    """The attention dropout mask of epoch `epoch` of ``fit_cnnrnn(..., seed=seed)``: float32 GPU tensor [n, heads, T,
+    T] of 0 (dropped) and float32(1 / (1 - p)) (kept), site 3 of the random stream (``ofp_attention_dropout_mask``)."""
+    seed = check_seed(seed)
+    n, heads, T = int(n), int(heads), int(T)
+    if not 0 <= p < 1 or n < 1 or heads < 1 or T < 1 or int(epoch) < 0:
+        raise ValueError("attention_dropout_mask_device needs 0 <= p < 1, n, heads, T >= 1 and epoch >= 0")
+    if out is not None:
+        dev = _f32_cuda("out", out, (n, heads, T, T)).device
+    else:
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    _lib.require_gpu(dev.index or 0)
+    if out is None:
+        out = torch.empty((n, heads, T, T), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().ofp_attention_dropout_mask(seed, int(epoch), n, heads, T, float(p), out.data_ptr(),
+                                                    _stream(dev)), "ofp_attention_dropout_mask")
+    return out
