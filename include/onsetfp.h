@@ -1206,7 +1206,10 @@ int ofp_sgd_step(float* d_p, const float* d_g, float* d_buf, int64_t n, const fl
  *   <= 160 KiB; a span needs a window source.
  * Site 3, attention dropout (ofp_cnnrnn_train_stretch only): index = ((s heads + h) T + i) T + j over the softmax
  *   probabilities [n][heads][T][T]; the rule and the scale of site 0, with the same dropout_p.  In that trainer site 0
- *   indexes the conv features [n][C W] in front of the GRU.
+ *   indexes the conv features [n][C W] in front of the GRU.  ofp_rnn_train_stretch has it too.
+ * Site 4, dropout between recurrent layers (ofp_rnn_train_stretch only): index = ((l n + s) T + t) H + j over the
+ *   output [n][T][H] of layer l, for every layer but the last; the rule and the scale of site 0, with the same
+ *   dropout_p; in the training forward and the backward, not in the validation forward.
  * ofp_*_train_random / ofp_*_loss_grads_random / ofp_*_train_random_workspace_bytes: the functions without
  *   `_random`, which they are with random = NULL, plus these options (ofp_*_loss_grads_random takes no window source).
  * ofp_*_train_stretch / ofp_*_train_stretch_workspace_bytes: the `_random` functions, which they are with
@@ -1346,6 +1349,91 @@ int ofp_attention_mean_train_backward(const float* d_h, int64_t n, int32_t T, in
                                       float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
 int ofp_attention_dropout_mask(uint64_t seed, int32_t epoch, int64_t n, int32_t heads, int32_t T, double p,
                                float* d_mask, void* stream);
+
+/* ---- training model.RNN (model.py:168-307; csrc/ofp_rnn_train.hip) ------------------------------------------------
+ * Network: `layers` unidirectional GRU layers (batch_first, biases, gate order r, z, n, h_0 = 0) over the window
+ *   itself -- `width` time steps of `channels` features, read in place from d_x [n][channels][width] (permute_input
+ *   != 0) or [n][width][channels] (permute_input == 0) --, nn.GRU's dropout on the output of every layer but the last,
+ *   LayerNorm(hidden, eps = ln_eps), self-attention of `heads` heads with dropout on the softmax probabilities, the mean
+ *   over time, out_proj, and a Linear to n_out values.  The recipe is ofp_cnn_train's (rows in d_rates
+ *   [num_epochs][4], the validation loss always L1, the stop rule, one captured graph per epoch with the first epoch
+ *   launched plainly, a created stream) with one difference: NAdam has torch's coupled weight decay, the gradient that
+ *   enters the moments and the step is g + weight_decay p.  OFP_RNN_GRAPH=nodes launches the same chain without a
+ *   graph.  There are no running statistics, so no d_stats.
+ * Parameters are packed in state_dict order: per layer l rnn.weight_ih_l [3 hidden][channels, or hidden for l > 0],
+ *   weight_hh_l [3 hidden][hidden], bias_ih_l, bias_hh_l [3 hidden]; layer_norm.weight, layer_norm.bias [hidden];
+ *   attention.in_proj_weight [3 hidden][hidden], in_proj_bias [3 hidden], out_proj.weight [hidden][hidden],
+ *   out_proj.bias [hidden]; fc.weight [n_out][hidden], fc.bias [n_out].
+ * Limits (beyond them OFP_ERR_INVALID, or -1 from the size functions): n and n_val 1..1024 (n_val from 0), channels
+ *   1..8, width 1..512, hidden 1..128, layers 1..4, heads 1..8 dividing hidden, n_out 1..16; n heads width^2 and
+ *   (layers - 1) n width hidden below 2^32, because the random stream indexes elements with 32 bits; a window source
+ *   needs permute_input.
+ * Random stream (ofp_train_random), both sites with dropout_p, the rule and the scale of site 0: site 3 is the dropout
+ *   on the attention's probabilities [n][heads][T][T], element ((s heads + h) T + i) T + j.
+ * Site 4, the dropout between recurrent layers (ofp_rnn_train_stretch only): index = ((l n + s) T + t) hidden + j over
+ *   the output of layer l < layers - 1, [layers - 1][n][T][hidden]; applied in the training forward and in the
+ *   backward, absent from the validation forward.  The window source (sites 1 and 2) is ofp_cnn_train_stretch's.
+ * Sums: as for ofp_cnnrnn_train_stretch; the sums over a LayerNorm row are a butterfly over the 64 lanes of a wave,
+ *   d gamma / d beta and the input projection's weight gradient go through fp64 slabs added in slab order.
+ * ofp_rnn_loss_grads_random: one training-mode forward and backward (no window source): d_loss [1], d_grads packed
+ *   like the parameters; d_ws of ofp_rnn_loss_grads_random_workspace_bytes (n_val = 0).
+ * ofp_layernorm_train_forward: d_x [rows][E] -> d_y, and d_mean, d_rstd [rows] (1 / sqrt(biased variance + eps)).
+ *   _backward: with those and d_dy [rows][E] -> d_dx [rows][E], d_dgamma, d_dbeta [E].  rows 1..2^20, E 1..128.
+ * ofp_rnn_gru_train_forward: the GRU stack alone.  d_x [n][T][F] (permuted == 0) or [n][F][T] (permuted != 0), d_params
+ *   the stack's parameters packed as above, `random` (NULL: none) seed, epoch and dropout_p of site 4 -> d_seqs
+ *   [L][n][T][H], every layer's output before its dropout, and d_gates [L][n][T][4 H] as ofp_gru_train_forward keeps
+ *   them.  _backward: with those and d_dseq [n][T][H], the gradient at the last layer's output -> d_grads packed like
+ *   d_params (the window gets no gradient).  n 1..1024, T 1..512, F 1..8, H 1..128, L 1..4.
+ * ofp_rnn_attention_train_forward / _backward: ofp_attention_mean_train_forward / _backward with T 1..512.
+ * ofp_rnn_layer_dropout_mask: d_mask [layers][n][T][H] of 0 and (float)(1 / (1 - p)), site 4; `layers` counts the
+ *   layers that have a dropout, the network's less one.
+ * ofp_nadam_decay_step: ofp_nadam_step with the gradient g + weight_decay p. */
+typedef struct ofp_rnn_config {
+    int32_t channels, width, hidden, layers, heads, n_out, loss, permute_input;
+    float weight_decay;
+    double ln_eps;
+} ofp_rnn_config;
+int64_t ofp_rnn_train_stretch_workspace_bytes(const ofp_rnn_config* cfg, int64_t n, int64_t n_val,
+                                              const ofp_train_random* random, int32_t stretch_span);
+int ofp_rnn_train_stretch(const ofp_rnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                          const float* d_x_val, const float* d_y_val, const float* d_rates, int32_t num_epochs,
+                          int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
+                          float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
+                          const ofp_train_random* random, int32_t stretch_span);
+int64_t ofp_rnn_loss_grads_random_workspace_bytes(const ofp_rnn_config* cfg, int64_t n, int64_t n_val,
+                                                  const ofp_train_random* random);
+int ofp_rnn_loss_grads_random(const ofp_rnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
+                              const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
+                              void* stream, const ofp_train_random* random);
+int ofp_layernorm_train_forward(const float* d_x, int64_t rows, int32_t E, const float* d_gamma, const float* d_beta,
+                                double eps, float* d_y, float* d_mean, float* d_rstd, void* stream);
+int64_t ofp_layernorm_train_backward_workspace_bytes(int64_t rows, int32_t E);
+int ofp_layernorm_train_backward(const float* d_x, int64_t rows, int32_t E, const float* d_gamma, const float* d_mean,
+                                 const float* d_rstd, const float* d_dy, float* d_dx, float* d_dgamma, float* d_dbeta,
+                                 void* d_ws, int64_t ws_bytes, void* stream);
+int64_t ofp_rnn_gru_train_forward_workspace_bytes(int64_t n, int32_t T, int32_t F, int32_t H, int32_t L);
+int ofp_rnn_gru_train_forward(const float* d_x, int32_t permuted, int64_t n, int32_t T, int32_t F, int32_t H, int32_t L,
+                              const float* d_params, const ofp_train_random* random, float* d_seqs, float* d_gates,
+                              void* d_ws, int64_t ws_bytes, void* stream);
+int64_t ofp_rnn_gru_train_backward_workspace_bytes(int64_t n, int32_t T, int32_t F, int32_t H, int32_t L);
+int ofp_rnn_gru_train_backward(const float* d_x, int32_t permuted, int64_t n, int32_t T, int32_t F, int32_t H, int32_t L,
+                               const float* d_params, const ofp_train_random* random, const float* d_seqs,
+                               const float* d_gates, const float* d_dseq, float* d_grads, void* d_ws, int64_t ws_bytes,
+                               void* stream);
+int64_t ofp_rnn_attention_train_forward_workspace_bytes(int64_t n, int32_t T, int32_t E, int32_t heads);
+int ofp_rnn_attention_train_forward(const float* d_h, int64_t n, int32_t T, int32_t E, int32_t heads,
+                                    const float* d_in_w, const float* d_in_b, const ofp_train_random* random,
+                                    float* d_qkv, float* d_probs, float* d_ctx, void* d_ws, int64_t ws_bytes,
+                                    void* stream);
+int64_t ofp_rnn_attention_train_backward_workspace_bytes(int64_t n, int32_t T, int32_t E, int32_t heads);
+int ofp_rnn_attention_train_backward(const float* d_h, int64_t n, int32_t T, int32_t E, int32_t heads,
+                                     const float* d_in_w, const float* d_qkv, const float* d_probs,
+                                     const float* d_dctx, const ofp_train_random* random, float* d_dh, float* d_dw,
+                                     float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
+int ofp_rnn_layer_dropout_mask(uint64_t seed, int32_t epoch, int32_t layers, int64_t n, int32_t T, int32_t H, double p,
+                               float* d_mask, void* stream);
+int ofp_nadam_decay_step(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, const float* d_row,
+                         float weight_decay, void* stream);
 
 #ifdef __cplusplus
 }

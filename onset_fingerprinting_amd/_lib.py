@@ -180,6 +180,16 @@ class CnnrnnConfig(ctypes.Structure):
     width = property(lambda self: self.cnn.width)  # what model._fit compares between x and x_val
 
 
+class RnnConfig(ctypes.Structure):
+    _fields_ = [
+        ("channels", ctypes.c_int32), ("width", ctypes.c_int32), ("hidden", ctypes.c_int32),
+        ("layers", ctypes.c_int32), ("heads", ctypes.c_int32), ("n_out", ctypes.c_int32), ("loss", ctypes.c_int32),
+        ("permute_input", ctypes.c_int32),
+        ("weight_decay", ctypes.c_float),
+        ("ln_eps", ctypes.c_double),
+    ]
+
+
 class CccnnConfig(ctypes.Structure):
     _fields_ = [
         ("n_conv", ctypes.c_int32),
@@ -439,6 +449,33 @@ SIGNATURES = {
     "ofp_attention_mean_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                                          ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _i64, _vp]),
     "ofp_attention_dropout_mask": (ctypes.c_int, [ctypes.c_uint64, _i32, _i64, _i32, _i32, _f64, _vp, _vp]),
+    "ofp_rnn_train_stretch_workspace_bytes": (_i64, [ctypes.POINTER(RnnConfig), _i64, _i64,
+                                                     ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_rnn_train_stretch": (ctypes.c_int, [ctypes.POINTER(RnnConfig), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32,
+                                             _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_i32), _vp, _i64, _vp,
+                                             ctypes.POINTER(TrainRandom), _i32]),
+    "ofp_rnn_loss_grads_random_workspace_bytes": (_i64, [ctypes.POINTER(RnnConfig), _i64, _i64,
+                                                         ctypes.POINTER(TrainRandom)]),
+    "ofp_rnn_loss_grads_random": (ctypes.c_int, [ctypes.POINTER(RnnConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                 _vp, ctypes.POINTER(TrainRandom)]),
+    "ofp_layernorm_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp]),
+    "ofp_layernorm_train_backward_workspace_bytes": (_i64, [_i64, _i32]),
+    "ofp_layernorm_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                    _vp]),
+    "ofp_rnn_gru_train_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "ofp_rnn_gru_train_forward": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp,
+                                                 ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _i64, _vp]),
+    "ofp_rnn_gru_train_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "ofp_rnn_gru_train_backward": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp,
+                                                  ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_rnn_attention_train_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_rnn_attention_train_forward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp,
+                                                       ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_rnn_attention_train_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ofp_rnn_attention_train_backward": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                        ctypes.POINTER(TrainRandom), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ofp_rnn_layer_dropout_mask": (ctypes.c_int, [ctypes.c_uint64, _i32, _i32, _i64, _i32, _i32, _f64, _vp, _vp]),
+    "ofp_nadam_decay_step": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _vp]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 // mask, shift or stretch can be recomputed from (seed, epoch, index).  Site 0 is the dropout in front of the Linear
 // head, site 1 the shift of the training windows, site 2 their stretch.  Site 3 is the dropout on the attention's softmax
 // probabilities in csrc/ofp_cnnrnn_train.hip, where site 0 is the dropout on the conv features in front of the GRU.
+// Site 4 is nn.GRU's dropout between the recurrent layers in csrc/ofp_rnn_train.hip, which has site 3 too.
 // File-local like ofp_train_chain.h, which it builds on.
 #pragma once
 #include "ofp_resample_dev.h"

@@ -470,7 +470,14 @@ class RNN(nn.Module):
     pair with shared weights), LayerNorm, multi-head self-attention, the mean over time and a Linear.  Same
     constructor arguments, defaults and parameter names (``rnn``, ``layer_norm``, ``attention``, ``fc``) as the
     reference; ``forward`` is inference-only and runs as HIP kernels.  ``activation`` is accepted and unused, as in
-    the reference."""
+    the reference.
+
+    Training: ``fit_rnn(model, x, y, ...)`` trains the module in place by the reference's recipe (NAdam with weight
+    decay 1e-4, CosineAnnealingLR(3000), one full batch per epoch) as one captured graph of HIP kernels per epoch;
+    ``rnn_loss_and_grads_device`` returns the loss and every gradient of one batch.  Trained are GRU stacks of 1 to 4
+    unidirectional layers with batch_first, biases and their own input weights, hidden_size up to 128, up to 8 channels
+    and windows of up to 512 samples; LSTM, the plain RNN cell, bidirectional stacks, share_input_weights=True and
+    batch_first=False run here (inference) but are not trained."""
 
     def __init__(self, input_size: int, output_size: int, channels: int = 3, hidden_size: int = 64,
                  num_layers: int = 2, dropout_rate: float = 0.5, loss=F.l1_loss, rnn_type: str = "GRU",
@@ -813,10 +820,10 @@ def _split(flat, tensors, copy=False):
 
 
 def _loss_and_grads(spec, model, x, y, seed, epoch):
-    """cnn_ / cccnn_ / cnnrnn_loss_and_grads_device; `spec` is _CNN, _LCCCNN or _CNNRNN."""
+    """cnn_ / cccnn_ / cnnrnn_ / rnn_loss_and_grads_device; `spec` is _CNN, _LCCCNN, _CNNRNN or _RNN."""
     x, y, cfg = spec.batch(model, x, y, seed=seed)
     net = spec.net(model)
-    rnd, _keep = _train_random(net.dropout.p, seed, epoch)
+    rnd, _keep = _train_random(spec.dropout(net), seed, epoch)
     dev = _train_device(net, x)
     _lib.require_gpu(dev.index or 0)
     L = _lib.lib()
@@ -839,7 +846,7 @@ def _loss_and_grads(spec, model, x, y, seed, epoch):
 
 
 def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed):
-    """fit_cnn / fit_lcccnn / fit_cnnrnn; `spec` is _CNN, _LCCCNN or _CNNRNN."""
+    """fit_cnn / fit_lcccnn / fit_cnnrnn / fit_rnn; `spec` is _CNN, _LCCCNN, _CNNRNN or _RNN."""
     x, y, cfg = spec.batch(model, x, y, seed=seed)
     _check_source(x, seed)
     source = x if isinstance(x, ShiftedWindows) else None
@@ -866,7 +873,7 @@ def _fit(spec, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed
     stats = (_flat(st, dev),) if spec.stats else ()
     to = lambda t: t.detach().to(dev, torch.float32).contiguous()
     xd, yd = (None if source else to(x)), to(y)
-    rnd, _keep = _train_random(net.dropout.p, seed, 0, source)
+    rnd, _keep = _train_random(spec.dropout(net), seed, 0, source)
     rp = ctypes.byref(rnd) if rnd is not None else None
     xv, yv = (to(x_val), to(y_val)) if have_val else (None, None)
     rates = torch.from_numpy(spec.device_rates(lr, max_epochs)).to(dev)
@@ -909,13 +916,14 @@ def _cnn_count_batches(model, epochs):
             m.num_batches_tracked += epochs
 
 
-# What differs between the trainable models (_CNN, _LCCCNN, _CNNRNN), for _fit and _loss_and_grads: the batch checker, the (name, tensor)
-# lists (parameters, running statistics), the module that carries `dropout` and `fc`, the rate table sent to the device
-# and the rates returned, the C entries, whether the train entry takes d_stats, and what is left to do after a fit.
+# What differs between the trainable models (_CNN, _LCCCNN, _CNNRNN, _RNN), for _fit and _loss_and_grads: the batch
+# checker, the (name, tensor) lists (parameters, running statistics), the module that carries `fc`, its dropout rate,
+# the rate table sent to the device and the rates returned, the C entries, whether the train entry takes d_stats, and
+# what is left to do after a fit.
 _CNN = SimpleNamespace(
     batch=_cnn_batch, tensors=_cnn_tensors, net=lambda model: model, device_rates=_cnn_device_rows, rates=cnn_rates,
     c_workspace="ofp_cnn_train_random_workspace_bytes", c_train="ofp_cnn_train", c_grads="ofp_cnn_loss_grads",
-    stats=True, after_fit=_cnn_count_batches)
+    stats=True, after_fit=_cnn_count_batches, dropout=lambda net: net.dropout.p)
 
 
 def cnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
@@ -1077,11 +1085,19 @@ def batchnorm_train_backward(x, gamma, mean, rstd, dy, *, out=None):
     return dx, dgamma, dbeta
 
 
-def nadam_step(p, g, m, v, row):
+def nadam_step(p, g, m, v, row, weight_decay=0.0):
     """One NAdam step in place on float32 CUDA tensors p, m, v with gradient g; row: float32 CUDA [>= 3] =
-    cnn_step_factors of the step, rounded."""
-    check(_lib.lib().ofp_nadam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
-                                    row.data_ptr(), _stream(p.device)), "ofp_nadam_step")
+    cnn_step_factors of the step, rounded.  With weight_decay > 0 the gradient is g + weight_decay p, torch's coupled
+    form (ofp_nadam_decay_step, the RNN trainer's step); without it the call is ofp_nadam_step."""
+    if weight_decay < 0:
+        raise ValueError("weight_decay must not be negative")
+    if weight_decay == 0:
+        check(_lib.lib().ofp_nadam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
+                                        row.data_ptr(), _stream(p.device)), "ofp_nadam_step")
+    else:
+        check(_lib.lib().ofp_nadam_decay_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
+                                              row.data_ptr(), float(weight_decay), _stream(p.device)),
+              "ofp_nadam_decay_step")
     return p
 
 
@@ -1231,7 +1247,7 @@ _LCCCNN = SimpleNamespace(
     batch=_cccnn_batch, tensors=lambda model, seed: (_cccnn_tensors(model, seed), []), net=lambda model: model.model,
     device_rates=lambda lr, num_epochs: np.asarray(lcccnn_rates(lr, num_epochs), np.float32), rates=lcccnn_rates,
     c_workspace="ofp_cccnn_train_random_workspace_bytes", c_train="ofp_cccnn_train", c_grads="ofp_cccnn_loss_grads",
-    stats=False, after_fit=lambda model, epochs: None)
+    stats=False, after_fit=lambda model, epochs: None, dropout=lambda net: net.dropout.p)
 
 
 def cccnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
@@ -1453,7 +1469,7 @@ def _cnnrnn_batch(model, x, y, what="x", seed=None):
 _CNNRNN = SimpleNamespace(
     batch=_cnnrnn_batch, tensors=_cnnrnn_tensors, net=lambda model: model, device_rates=_cnnrnn_device_rows,
     rates=cnnrnn_rates, c_workspace="ofp_cnnrnn_loss_grads_random_workspace_bytes", c_train="ofp_cnnrnn_train",
-    c_grads="ofp_cnnrnn_loss_grads", stats=True, after_fit=_cnn_count_batches)
+    c_grads="ofp_cnnrnn_loss_grads", stats=True, after_fit=_cnn_count_batches, dropout=lambda net: net.dropout.p)
 
 
 def cnnrnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
@@ -1624,4 +1640,345 @@ def attention_dropout_mask_device(seed, epoch, n, heads, T, p, device=0, *, out=
     with torch.cuda.device(dev):
         check(_lib.lib().ofp_attention_dropout_mask(seed, int(epoch), n, heads, T, float(p), out.data_ptr(),
                                                     _stream(dev)), "ofp_attention_dropout_mask")
+    return out
+
+
+# ---- training model.RNN (model.py:168-307) ---------------------------------------------------------------------------
+RNN_TRAIN_MAX_LAYERS, RNN_TRAIN_MAX_HIDDEN, RNN_TRAIN_MAX_HEADS = 4, 128, 8  # csrc/ofp_rnn_train.hip
+RNN_TRAIN_MAX_CHANNELS, RNN_TRAIN_MAX_STEPS, RNN_TRAIN_MAX_ROWS = 8, 512, 1 << 20
+RNN_WEIGHT_DECAY, RNN_T_MAX = 1e-4, 3000  # RNN.configure_optimizers
+SITE_LAYER = 4  # the random stream's site of the dropout between recurrent layers (include/onsetfp.h)
+
+
+@functools.lru_cache(maxsize=256)
+def rnn_rates(lr, num_epochs):
+    """The learning rate of every epoch of RNN.configure_optimizers(): torch's own NAdam at ``lr`` (weight decay 1e-4)
+    and CosineAnnealingLR(T_max = 3000) stepped once per epoch on a dummy parameter.  float64 [num_epochs]."""
+    p = nn.Parameter(torch.zeros(1))
+    opt = torch.optim.NAdam([p], lr=lr, weight_decay=RNN_WEIGHT_DECAY)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, RNN_T_MAX)
+    opt.step()
+    rates = np.empty(num_epochs, np.float64)
+    for e in range(num_epochs):
+        rates[e] = float(opt.param_groups[0]["lr"])
+        sched.step()
+    rates.setflags(write=False)
+    return rates
+
+
+def _rnn_device_rows(lr, num_epochs):
+    """float32 [num_epochs][4] for ofp_rnn_train_stretch: cnn_step_factors of NAdam at rnn_rates, rounded once (the
+    weight decay is part of the config, not of the rows)."""
+    table = np.array(cnn_rate_table(lr, num_epochs))
+    table[:, 0] = rnn_rates(float(lr), int(num_epochs))
+    rows = np.zeros((num_epochs, 4), np.float32)
+    rows[:, :3] = cnn_step_factors(table)
+    return rows
+
+
+def _rnn_arch(model, seed=None):
+    """The RnnConfig of an RNN for the trainer, without the window length; ValueError for what it cannot run."""
+    if not isinstance(model, RNN):
+        raise ValueError(f"{type(model).__name__} is not an RNN")
+    rnn, att, ln = model.rnn, model.attention, model.layer_norm
+    if isinstance(rnn, nn.LSTM):
+        raise ValueError("rnn_type 'LSTM' is not trained on the GPU (only 'GRU' is)")
+    if not isinstance(rnn, nn.GRU):
+        raise ValueError("rnn_type 'RNN', the plain recurrent cell, is not trained on the GPU (only 'GRU' is)")
+    if rnn.bidirectional:
+        raise ValueError("a bidirectional stack is not trained on the GPU")
+    if model.share_input_weights:
+        raise ValueError("share_input_weights=True is not trained on the GPU")
+    if not rnn.batch_first:
+        raise ValueError("batch_first=False is not trained on the GPU")
+    if not rnn.bias:
+        raise ValueError("a recurrent stack without biases (bias=False) is not trained on the GPU")
+    L_, H, C = rnn.num_layers, rnn.hidden_size, rnn.input_size
+    if not 1 <= L_ <= RNN_TRAIN_MAX_LAYERS:
+        raise ValueError(f"num_layers {L_}: the trainer's limit is 1..{RNN_TRAIN_MAX_LAYERS}")
+    if not 1 <= H <= RNN_TRAIN_MAX_HIDDEN:
+        raise ValueError(f"hidden_size {H}: the trainer's limit is 1..{RNN_TRAIN_MAX_HIDDEN}")
+    if not 1 <= att.num_heads <= RNN_TRAIN_MAX_HEADS or H % att.num_heads:
+        raise ValueError(f"num_heads {att.num_heads}: the trainer needs 1..{RNN_TRAIN_MAX_HEADS} heads that divide "
+                         f"hidden_size {H}")
+    if not 1 <= C <= RNN_TRAIN_MAX_CHANNELS:
+        raise ValueError(f"{C} channels: the trainer's limit is 1..{RNN_TRAIN_MAX_CHANNELS}")
+    if not att.batch_first or att.in_proj_bias is None or att.in_proj_weight is None or att.embed_dim != H \
+            or att.bias_k is not None or att.add_zero_attn or att.out_proj.bias is None:
+        raise ValueError("the attention must have batch_first, biases and one embed dim of hidden_size for q, k and v")
+    p = float(att.dropout)
+    _check_dropout(p, seed)
+    if L_ > 1 and float(rnn.dropout) != p:
+        raise ValueError(f"the stack's dropout {rnn.dropout} differs from the attention's {att.dropout}")
+    if tuple(ln.normalized_shape) != (H,) or not ln.elementwise_affine or ln.bias is None:
+        raise ValueError(f"layer_norm must be an affine LayerNorm({H}) with a bias")
+    if model.fc.in_features != H or model.fc.bias is None or not 1 <= model.fc.out_features <= CNN_TRAIN_MAX_OUT:
+        raise ValueError(f"the Linear head needs {H} inputs, a bias and at most {CNN_TRAIN_MAX_OUT} outputs")
+    cfg = _lib.RnnConfig()
+    cfg.channels, cfg.hidden, cfg.layers, cfg.heads, cfg.n_out = C, H, L_, att.num_heads, model.fc.out_features
+    cfg.loss, cfg.permute_input = _loss_code(model.loss), int(bool(model.permute_input))
+    cfg.weight_decay, cfg.ln_eps = RNN_WEIGHT_DECAY, float(ln.eps)
+    return cfg
+
+
+def _rnn_tensors(model, seed=None):
+    """[(state_dict name, tensor)] of an RNN's parameters in packing order, which is named_parameters()'; no running
+    statistics."""
+    _rnn_arch(model, seed)
+    rnn, att = model.rnn, model.attention
+    ps = []
+    for l in range(rnn.num_layers):
+        ps += [(f"rnn.{k}_l{l}", getattr(rnn, f"{k}_l{l}")) for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    ps += [("layer_norm.weight", model.layer_norm.weight), ("layer_norm.bias", model.layer_norm.bias),
+           ("attention.in_proj_weight", att.in_proj_weight), ("attention.in_proj_bias", att.in_proj_bias),
+           ("attention.out_proj.weight", att.out_proj.weight), ("attention.out_proj.bias", att.out_proj.bias),
+           ("fc.weight", model.fc.weight), ("fc.bias", model.fc.bias)]
+    return ps, []
+
+
+def _rnn_check_stream(n, heads, T, layers, hidden):
+    """The random stream indexes the elements of a site with 32 bits.  Inside the other limits (batch 1024, 8 heads,
+    512 steps, 4 layers, hidden 128) neither count reaches 2^32; the C entries check the same."""
+    if n * heads * T * T >= 1 << 32:
+        raise ValueError(f"{n} windows x {heads} heads x {T}^2 attention probabilities: the random stream indexes "
+                         "2^32 elements")
+    if (layers - 1) * n * T * hidden >= 1 << 32:
+        raise ValueError(f"{layers - 1} x {n} x {T} x {hidden} outputs between the layers: the random stream "
+                         "indexes 2^32 elements")
+
+
+def _rnn_batch(model, x, y, what="x", seed=None):
+    cfg = _rnn_arch(model, seed)
+    x, y, shape = _batch_of(x, y, what)
+    if isinstance(x, ShiftedWindows) and not model.permute_input:
+        raise ValueError("a window source gives [n, channels, width]: it needs permute_input=True")
+    n, (C, T) = shape[0], (shape[1:] if model.permute_input else shape[:0:-1])
+    if not 1 <= n <= CNN_TRAIN_MAX_BATCH:
+        raise ValueError(f"{n} windows: the trainer's limit is 1..{CNN_TRAIN_MAX_BATCH} (one full batch)")
+    if not 1 <= T <= RNN_TRAIN_MAX_STEPS:
+        raise ValueError(f"input_size {T}: the trainer's limit is 1..{RNN_TRAIN_MAX_STEPS} (the window is the "
+                         "sequence)")
+    if C != cfg.channels or y.shape[1] != cfg.n_out:
+        raise ValueError(f"{what} {shape} / y {tuple(y.shape)} do not fit a model of {cfg.channels} channels and "
+                         f"{cfg.n_out} outputs")
+    _rnn_check_stream(n, cfg.heads, T, cfg.layers, cfg.hidden)
+    cfg.width = T
+    return x, y, cfg
+
+
+_RNN = SimpleNamespace(
+    batch=_rnn_batch, tensors=_rnn_tensors, net=lambda model: model, device_rates=_rnn_device_rows, rates=rnn_rates,
+    c_workspace="ofp_rnn_loss_grads_random_workspace_bytes", c_train="ofp_rnn_train", c_grads="ofp_rnn_loss_grads",
+    stats=False, after_fit=lambda model, epochs: None, dropout=lambda net: float(net.attention.dropout))
+
+
+def rnn_train_workspace_bytes(model, n, n_val=0, input_size=256, seed=None):
+    """Bytes of GPU work space ``fit_rnn`` asks for at n training and n_val validation windows of `input_size` samples
+    (the plan of ofp_rnn_train_stretch; nothing runs on the GPU)."""
+    cfg = _rnn_arch(model, seed)
+    cfg.width = int(input_size)
+    rnd, _k = _train_random(float(model.attention.dropout), seed)
+    nbytes = int(_lib.lib().ofp_rnn_train_stretch_workspace_bytes(
+        ctypes.byref(cfg), int(n), int(n_val), ctypes.byref(rnd) if rnd is not None else None, 0))
+    if nbytes < 0:
+        raise ValueError(_lib.last_error())
+    return nbytes
+
+
+def rnn_loss_and_grads_device(model, x, y, seed=None, epoch=0):
+    """Loss (``model.loss``) and the gradient of every parameter of an RNN for the full batch x [n, channels,
+    input_size] ([n, input_size, channels] with permute_input=False), y [n, outputs], in training mode, by the trainer's
+    own forward and backward kernels.  With a seed both dropouts are applied as epoch `epoch` of ``fit_rnn(...,
+    seed=seed)`` applies them (``rnn_layer_dropout_mask_device`` between the layers, ``attention_dropout_mask_device``
+    on the probabilities).  Returns (loss, {state_dict name: gradient}) on the GPU."""
+    return _loss_and_grads(_RNN, model, x, y, seed, epoch)
+
+
+def fit_rnn(model, x, y, *, x_val=None, y_val=None, max_epochs=1000, min_epochs=0, patience=None, seed=None):
+    """Train an ``RNN`` in place with the reference's recipe (model.py:265-307): the whole of x [n, channels,
+    input_size] ([n, input_size, channels] with permute_input=False) / y [n, outputs] is one batch; every epoch is one
+    training-mode forward, ``model.loss`` (F.l1_loss or F.mse_loss), backward and one NAdam step with weight decay 1e-4
+    in torch's coupled form (g + 1e-4 p enters the moments) at the learning rate of CosineAnnealingLR(3000) starting
+    from ``model.lr`` (``rnn_rates``); then, with a validation set, an eval-mode forward of x_val and its L1 loss.  The
+    contract, the stop rule and the returned record are ``fit_cnn``'s: trained in place, left in eval mode, a fresh
+    optimiser state per call; one epoch is one launch of a captured graph of HIP kernels (csrc/ofp_rnn_train.hip;
+    OFP_RNN_GRAPH=nodes in the environment launches the kernels one by one).
+
+    The window is the sequence: ``input_size`` time steps of ``channels`` features, read in place with the strides
+    ``permute_input`` asks for.  ``seed`` opts into this package's own random stream as in ``fit_cnn``: nn.GRU's dropout
+    on the output of every layer but the last (site 4; ``rnn_layer_dropout_mask_device``) and the attention's dropout on
+    its softmax probabilities [n, heads, T, T] (site 3; ``attention_dropout_mask_device``), both at ``dropout_rate``
+    and scaled by 1 / (1 - p), neither in the validation forward.  ``x`` may be a ``data.ShiftedWindows`` /
+    ``StretchedWindows`` as for ``fit_cnn`` (with permute_input=True, the layout those give).
+
+    ValueError, before anything runs on the GPU: rnn_type 'LSTM' or 'RNN', a bidirectional stack,
+    share_input_weights=True, batch_first=False, bias=False; num_layers outside 1..4, hidden_size outside 1..128 or not
+    divisible by num_heads (1..8), more than 8 channels, input_size above 512, a batch above 1024, more than 16
+    outputs; dropout_rate > 0 without a seed, dropout_rate >= 1; a window source with permute_input=False, as x_val, or
+    shifting or stretching without a seed; n * heads * input_size^2 or (num_layers - 1) * n * input_size * hidden_size
+    of 2^32 or more (the random stream indexes elements with 32 bits); a loss other than F.l1_loss / F.mse_loss."""
+    return _fit(_RNN, model, x, y, x_val, y_val, max_epochs, min_epochs, patience, seed)
+
+
+def layernorm_train_forward(x, gamma, beta, eps=1e-5, *, out=None):
+    """nn.LayerNorm over the last axis in training form (ofp_layernorm_train_forward) on float32 CUDA tensors: x [rows,
+    E] (E <= 128), gamma, beta [E] -> (y [rows, E], mean [rows], rstd [rows] = 1 / sqrt(biased variance + eps));
+    ``out=(y, mean, rstd)`` are preallocated outputs."""
+    R_, E = x.shape
+    _f32_cuda("x", x, (R_, E)), _f32_cuda("gamma", gamma, (E,)), _f32_cuda("beta", beta, (E,))
+    if not (1 <= R_ <= RNN_TRAIN_MAX_ROWS and 1 <= E <= RNN_TRAIN_MAX_HIDDEN and eps > 0):
+        raise ValueError(f"{R_} rows of {E}, eps {eps}: beyond the LayerNorm kernels' limits (2^20 rows, width "
+                         f"{RNN_TRAIN_MAX_HIDDEN}, eps > 0)")
+    y, mean, rstd = _outs(x.device, out or (None,) * 3, [(R_, E), (R_,), (R_,)])
+    check(_lib.lib().ofp_layernorm_train_forward(x.data_ptr(), R_, E, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                                 y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _stream(x.device)),
+          "ofp_layernorm_train_forward")
+    return y, mean, rstd
+
+
+def layernorm_train_backward(x, gamma, mean, rstd, dy, *, out=None):
+    """Backward of layernorm_train_forward (ofp_layernorm_train_backward): dy [rows, E] -> (dx [rows, E], dgamma [E],
+    dbeta [E]); ``out=`` are those three, preallocated."""
+    R_, E = x.shape
+    _f32_cuda("x", x, (R_, E)), _f32_cuda("gamma", gamma, (E,)), _f32_cuda("dy", dy, (R_, E))
+    _f32_cuda("mean", mean, (R_,)), _f32_cuda("rstd", rstd, (R_,))
+    L = _lib.lib()
+    ws_bytes = int(L.ofp_layernorm_train_backward_workspace_bytes(R_, E))
+    if ws_bytes < 0:
+        raise ValueError(f"{R_} rows of {E}: beyond the LayerNorm kernels' limits (2^20 rows, width "
+                         f"{RNN_TRAIN_MAX_HIDDEN})")
+    dx, dgamma, dbeta = _outs(x.device, out or (None,) * 3, [(R_, E), (E,), (E,)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_layernorm_train_backward(x.data_ptr(), R_, E, gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                         dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                         ws.data_ptr(), ws_bytes, _stream(x.device)), "ofp_layernorm_train_backward")
+    return dx, dgamma, dbeta
+
+
+def _stack_args(x, params_per_layer, permuted):
+    """(n, T, F, H, L, the stack's parameters packed) of a stand-alone GRU stack call; x is [n, T, F], or [n, F, T]
+    with permuted=True."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3):
+        raise ValueError("x must be a contiguous float32 GPU tensor [n, T, F] ([n, F, T] with permuted=True)")
+    n, T, F_ = (x.shape[0], x.shape[2], x.shape[1]) if permuted else x.shape
+    L_ = len(params_per_layer)
+    if L_ < 1:
+        raise ValueError("params_per_layer is empty")
+    H = params_per_layer[0][1].shape[1]
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(params_per_layer):
+        _f32_cuda(f"w_ih of layer {l}", w_ih, (3 * H, H if l else F_)), _f32_cuda(f"w_hh of layer {l}", w_hh, (3 * H, H))
+        _f32_cuda(f"b_ih of layer {l}", b_ih, (3 * H,)), _f32_cuda(f"b_hh of layer {l}", b_hh, (3 * H,))
+    flat = torch.cat([t.reshape(-1) for layer in params_per_layer for t in layer])
+    return int(n), int(T), int(F_), int(H), L_, flat
+
+
+def rnn_gru_train_forward(x, params_per_layer, p=0.0, seed=None, epoch=0, *, permuted=False, out=None):
+    """An L-layer batch_first GRU stack with zero initial states in training form (ofp_rnn_gru_train_forward) on
+    float32 CUDA tensors: x [n, T, F] (or the window as stored, [n, F, T], with permuted=True; F <= 8, T <= 512),
+    params_per_layer = [(w_ih, w_hh, b_ih, b_hh)] per layer -> (seqs [L, n, T, H], every layer's output before its
+    dropout, seqs[-1] being the stack's; gates [L, n, T, 4H]).  With p > 0 and a seed the output of every layer but the
+    last is dropped by site 4 of the random stream (``rnn_layer_dropout_mask_device``) before the next layer reads it.
+    ``out=(seqs, gates)`` are preallocated outputs."""
+    n, T, F_, H, L_, flat = _stack_args(x, params_per_layer, permuted)
+    rnd = _attention_random(p, seed, epoch)
+    L = _lib.lib()
+    ws_bytes = int(L.ofp_rnn_gru_train_forward_workspace_bytes(n, T, F_, H, L_))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    seqs, gates = _outs(x.device, out or (None,) * 2, [(L_, n, T, H), (L_, n, T, 4 * H)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_rnn_gru_train_forward(x.data_ptr(), int(bool(permuted)), n, T, F_, H, L_, flat.data_ptr(),
+                                      ctypes.byref(rnd) if rnd is not None else None, seqs.data_ptr(),
+                                      gates.data_ptr(), ws.data_ptr(), ws_bytes, _stream(x.device)),
+          "ofp_rnn_gru_train_forward")
+    return seqs, gates
+
+
+def rnn_gru_train_backward(x, params_per_layer, seqs, gates, dseq, p=0.0, seed=None, epoch=0, *, permuted=False,
+                           out=None):
+    """Back-propagation through time and through the layers of rnn_gru_train_forward with the same p, seed and epoch
+    (ofp_rnn_gru_train_backward): dseq [n, T, H] = the gradient at the last layer's output -> [(dw_ih, dw_hh, db_ih,
+    db_hh)] per layer, views of one tensor packed like the parameters (``out=``: that tensor, preallocated, of as many
+    elements as the parameters have).  The input x gets no gradient: it is the window."""
+    n, T, F_, H, L_, flat = _stack_args(x, params_per_layer, permuted)
+    _f32_cuda("seqs", seqs, (L_, n, T, H)), _f32_cuda("gates", gates, (L_, n, T, 4 * H))
+    _f32_cuda("dseq", dseq, (n, T, H))
+    rnd = _attention_random(p, seed, epoch)
+    L = _lib.lib()
+    ws_bytes = int(L.ofp_rnn_gru_train_backward_workspace_bytes(n, T, F_, H, L_))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    (grads,) = _outs(x.device, (out,), [(flat.numel(),)])
+    ws = _workspace(ws_bytes, x.device)
+    check(L.ofp_rnn_gru_train_backward(x.data_ptr(), int(bool(permuted)), n, T, F_, H, L_, flat.data_ptr(),
+                                       ctypes.byref(rnd) if rnd is not None else None, seqs.data_ptr(),
+                                       gates.data_ptr(), dseq.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws_bytes,
+                                       _stream(x.device)), "ofp_rnn_gru_train_backward")
+    per_layer, o = [], 0
+    for layer in params_per_layer:
+        pieces = []
+        for t in layer:
+            pieces.append(grads[o:o + t.numel()].reshape(t.shape))
+            o += t.numel()
+        per_layer.append(tuple(pieces))
+    return per_layer
+
+
+def rnn_attention_train_forward(h, in_proj_w, in_proj_b, num_heads, p=0.0, seed=None, epoch=0, *, out=None):
+    """``attention_mean_train_forward`` at the RNN trainer's capacity, T <= 512 (ofp_rnn_attention_train_forward)."""
+    n, T, E = h.shape
+    _f32_cuda("h", h, (n, T, E)), _f32_cuda("in_proj_w", in_proj_w, (3 * E, E)), _f32_cuda("in_proj_b", in_proj_b, (3 * E,))
+    rnd = _attention_random(p, seed, epoch)
+    L = _lib.lib()
+    ws_bytes = int(L.ofp_rnn_attention_train_forward_workspace_bytes(n, T, E, num_heads))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    ctx, qkv, probs = _outs(h.device, out or (None,) * 3, [(n, E), (n, T, 3 * E), (n, num_heads, T, T)])
+    ws = _workspace(ws_bytes, h.device)
+    check(L.ofp_rnn_attention_train_forward(h.data_ptr(), n, T, E, num_heads, in_proj_w.data_ptr(),
+                                            in_proj_b.data_ptr(), ctypes.byref(rnd) if rnd is not None else None,
+                                            qkv.data_ptr(), probs.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws_bytes,
+                                            _stream(h.device)), "ofp_rnn_attention_train_forward")
+    return ctx, qkv, probs
+
+
+def rnn_attention_train_backward(h, in_proj_w, num_heads, qkv, probs, dctx, p=0.0, seed=None, epoch=0, *, out=None):
+    """``attention_mean_train_backward`` at the RNN trainer's capacity, T <= 512 (ofp_rnn_attention_train_backward)."""
+    n, T, E = h.shape
+    _f32_cuda("h", h, (n, T, E)), _f32_cuda("in_proj_w", in_proj_w, (3 * E, E)), _f32_cuda("qkv", qkv, (n, T, 3 * E))
+    _f32_cuda("probs", probs, (n, num_heads, T, T)), _f32_cuda("dctx", dctx, (n, E))
+    rnd = _attention_random(p, seed, epoch)
+    L = _lib.lib()
+    ws_bytes = int(L.ofp_rnn_attention_train_backward_workspace_bytes(n, T, E, num_heads))
+    if ws_bytes < 0:
+        raise ValueError(_lib.last_error())
+    outs = _outs(h.device, out or (None,) * 3, [(n, T, E), (3 * E, E), (3 * E,)])
+    ws = _workspace(ws_bytes, h.device)
+    check(L.ofp_rnn_attention_train_backward(h.data_ptr(), n, T, E, num_heads, in_proj_w.data_ptr(), qkv.data_ptr(),
+                                             probs.data_ptr(), dctx.data_ptr(),
+                                             ctypes.byref(rnd) if rnd is not None else None,
+                                             *(t.data_ptr() for t in outs), ws.data_ptr(), ws_bytes,
+                                             _stream(h.device)), "ofp_rnn_attention_train_backward")
+    return tuple(outs)
+
+
+def rnn_layer_dropout_mask_device(seed, epoch, layers, n, T, H, p, device=0, *, out=None):
+    """The dropout masks between the recurrent layers of epoch `epoch` of ``fit_rnn(..., seed=seed)``: float32 GPU
+    tensor [layers, n, T, H] of 0 (dropped) and float32(1 / (1 - p)) (kept), site 4 of the random stream
+    (``ofp_rnn_layer_dropout_mask``); `layers` counts the layers whose output is dropped, num_layers - 1."""
+    seed = check_seed(seed)
+    layers, n, T, H = int(layers), int(n), int(T), int(H)
+    if not 0 <= p < 1 or min(layers, n, T, H) < 1 or int(epoch) < 0 or layers * n * T * H > 1 << 32:
+        raise ValueError("rnn_layer_dropout_mask_device needs 0 <= p < 1, layers, n, T, H >= 1 with at most 2^32 "
+                         "elements, and epoch >= 0")
+    if out is not None:
+        dev = _f32_cuda("out", out, (layers, n, T, H)).device
+    else:
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    _lib.require_gpu(dev.index or 0)
+    if out is None:
+        out = torch.empty((layers, n, T, H), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().ofp_rnn_layer_dropout_mask(seed, int(epoch), layers, n, T, H, float(p), out.data_ptr(),
+                                                    _stream(dev)), "ofp_rnn_layer_dropout_mask")
     return out
