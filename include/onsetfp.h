@@ -273,6 +273,9 @@ enum {
 };
 int ofp_canon_eval(int32_t op, const float* d_x, const float* d_y, int64_t n, float p0, float p1, float p2, float* d_out,
                    void* stream);
+/* RECT_DB and REL_LINEAR (no other op) with the canon's tables read from a copy in LDS that each workgroup fills: the form
+ * the detector's elementwise passes run (csrc/ofp_canon_dev.h).  Same arrays and refusals as ofp_canon_eval. */
+int ofp_canon_eval_lds(int32_t op, const float* d_x, int64_t n, float floor_db, float* d_out, void* stream);
 
 /* detect_onsets_amplitude (detection.py:19-86) for a batch of independent clips.
  *   d_x        [n_clips][n_samples][C] float32, interleaved as the reference expects

@@ -245,6 +245,7 @@ SIGNATURES = {
     "ofp_detect_plan_for": (ctypes.c_int, [ctypes.POINTER(DetectorParams), ctypes.POINTER(DetectTuning), ctypes.c_int,
                                            _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.POINTER(DetectPlan)]),
     "ofp_canon_eval": (ctypes.c_int, [_i32, _vp, _vp, _i64, _f32, _f32, _f32, _vp, _vp]),
+    "ofp_canon_eval_lds": (ctypes.c_int, [_i32, _vp, _i64, _f32, _vp, _vp]),
     "ofp_detect_offline": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
                                           ctypes.POINTER(_i64), _vp]),
     "ofp_detect_offline_enqueue": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),

@@ -5,8 +5,13 @@
 // binades (tests/test_gpu_canon.py).  The file is built with the library's flags like every other translation unit: what
 // it computes is what the same functions compute inside the detector.  Each op calls the header's function and nothing
 // else.
+//
+// The detector's dB and back-to-linear passes evaluate the canon with its tables held in LDS (ofp_canon_dev.h).
+// ofp_canon_eval_lds runs exactly that form of RECT_DB and REL_LINEAR, tables filled per workgroup as the passes fill them,
+// so that a test can hold it against the header's form over every float32 bit pattern (tests/test_gpu_canon_tables.py).
 #include "ofp_common.h"
 #include "../../include/ofp_math.h"
+#include "ofp_canon_dev.h"
 
 namespace {
 
@@ -36,6 +41,19 @@ __global__ __launch_bounds__(256) void k_canon_eval(CanonArgs a, const float* __
     }
 }
 
+__global__ __launch_bounds__(256) void k_canon_eval_lds(CanonArgs a, const float* __restrict__ x, int64_t n,
+                                                        float* __restrict__ out) {
+    __shared__ ofp_canon::LogTables lg;
+    __shared__ ofp_canon::ExpTable ex;
+    ofp_canon::fill(lg);
+    ofp_canon::fill(ex);
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const float xi = x[i];
+        out[i] = a.op == OFP_CANON_RECT_DB ? ofp_canon::rect_db(xi, a.p0, lg.r, lg.t) : ofp_canon::rel_linear(xi, a.p0, ex.t);
+    }
+}
+
 }  // namespace
 
 extern "C" int ofp_canon_eval(int32_t op, const float* d_x, const float* d_y, int64_t n, float p0, float p1, float p2,
@@ -51,5 +69,17 @@ extern "C" int ofp_canon_eval(int32_t op, const float* d_x, const float* d_y, in
     const unsigned blocks = (unsigned)(cdiv(n, 256) < 8192 ? cdiv(n, 256) : 8192);
     hipLaunchKernelGGL(k_canon_eval, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, d_x, d_y, n, d_out);
     OFP_LAUNCH_CHECK("k_canon_eval");
+    return OFP_OK;
+}
+
+extern "C" int ofp_canon_eval_lds(int32_t op, const float* d_x, int64_t n, float floor_db, float* d_out, void* stream) {
+    OFP_REQUIRE(op == OFP_CANON_RECT_DB || op == OFP_CANON_REL_LINEAR, "ofp_canon_eval_lds: unknown op %d", (int)op);
+    OFP_REQUIRE(n >= 0, "ofp_canon_eval_lds: negative n");
+    if (n == 0) return OFP_OK;
+    OFP_REQUIRE(d_x && d_out, "ofp_canon_eval_lds: NULL argument");
+    CanonArgs a{op, floor_db, 0.0f, 0.0f};
+    const unsigned blocks = (unsigned)(cdiv(n, 256) < 8192 ? cdiv(n, 256) : 8192);
+    hipLaunchKernelGGL(k_canon_eval_lds, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, d_x, n, d_out);
+    OFP_LAUNCH_CHECK("k_canon_eval_lds");
     return OFP_OK;
 }

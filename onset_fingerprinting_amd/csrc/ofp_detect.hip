@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/ofp_math.h"
+#include "ofp_canon_dev.h"
 #include "ofp_common.h"
 
 #include "ofp_detector.h"
@@ -2068,29 +2069,71 @@ __global__ __launch_bounds__(64) void k_hp_run_lines(HpCand a, int64_t n_threads
 // ---- elementwise stages (planar, in place) -------------------------------------------
 // rectified dB (detection.py:747-748).  from_x: no high-pass, read the audio through the
 // stream mapping; else in place on the filtered buffer.
+// The canon's tables are read from a copy in LDS (ofp_canon_dev.h) here and in the three kernels below: a lookup then
+// waits on lgkmcnt and no longer drains the lane's streaming loads and stores once per sample.
+//
+// With no vector-memory wait left in the arithmetic, a lane's trips are software-pipelined (stream_trips, two register
+// sets as in walk<>): the loads of trip k + 1 are issued before the arithmetic of trip k, so the only vmcnt waits of a
+// loop are counted ones that leave the newer trip's loads and the older trip's stores in flight.  `load(i)` returns what
+// trip i reads (a value, or a Quad of four 16-byte groups), `work(i, v)` does the arithmetic and the stores of trip i;
+// trips are at i, i + step, ... below n.  A trip never reads what an earlier trip of the same lane wrote.
+struct Quad {
+    float4 v0, v1, v2, v3;
+};
+// The loop body holds no branch around its loads (the last trip is written out after it): where a path without them
+// joined one with them, the compiler's wait for `cur` had to assume the fewest younger accesses of any path and became
+// a wait for the new loads as well.
+template <class I, class Load, class Work>
+__device__ __forceinline__ void stream_trips(I i, I n, I step, Load load, Work work) {
+    if (i >= n) return;
+    auto cur = load(i);
+    for (I ni = i + step; ni < n; ni += step) {
+        const auto nxt = load(ni);
+        __builtin_amdgcn_sched_barrier(0);
+        work(i, cur);
+        cur = nxt;
+        i = ni;
+    }
+    work(i, cur);
+}
+
+__device__ __forceinline__ float4 rect_db4(float4 v, float floor_db, const ofp_canon::LogTables& tb) {
+    v.x = ofp_canon::rect_db(v.x, floor_db, tb.r, tb.t);
+    v.y = ofp_canon::rect_db(v.y, floor_db, tb.r, tb.t);
+    v.z = ofp_canon::rect_db(v.z, floor_db, tb.r, tb.t);
+    v.w = ofp_canon::rect_db(v.w, floor_db, tb.r, tb.t);
+    return v;
+}
+__device__ __forceinline__ float4 rel_linear4(float4 v, float floor_db, const ofp_canon::ExpTable& tb) {
+    v.x = ofp_canon::rel_linear(v.x, floor_db, tb.t);
+    v.y = ofp_canon::rel_linear(v.y, floor_db, tb.t);
+    v.z = ofp_canon::rel_linear(v.z, floor_db, tb.t);
+    v.w = ofp_canon::rel_linear(v.w, floor_db, tb.t);
+    return v;
+}
+
 __global__ __launch_bounds__(256) void k_rect_db(Geom g, const float* __restrict__ xt, float* __restrict__ buf,
                                                  int64_t n_chains, int from_x, float floor_db) {
+    __shared__ ofp_canon::LogTables tb;
+    ofp_canon::fill(tb);
     const int64_t total = n_chains * g.U;
     const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     if (!from_x) {
         // in place on the filtered stream: 16 bytes per lane and access (the work space is 256-byte aligned)
         float4* b4 = reinterpret_cast<float4*>(buf);
         const int64_t n4 = total >> 2;
-        for (int64_t i = tid0; i < n4; i += nthr) {
-            float4 v = b4[i];
-            v.x = ofp_rect_db(v.x, floor_db);
-            v.y = ofp_rect_db(v.y, floor_db);
-            v.z = ofp_rect_db(v.z, floor_db);
-            v.w = ofp_rect_db(v.w, floor_db);
-            b4[i] = v;
-        }
-        for (int64_t i = (n4 << 2) + tid0; i < total; i += nthr) buf[i] = ofp_rect_db(buf[i], floor_db);
+        stream_trips(tid0, n4, nthr, [&](int64_t i) { return b4[i]; },
+                     [&](int64_t i, float4 v) { b4[i] = rect_db4(v, floor_db, tb); });
+        const int64_t i = (n4 << 2) + tid0;  // (at most three values are left, and nthr >= 256)
+        if (i < total) buf[i] = ofp_canon::rect_db(buf[i], floor_db, tb.r, tb.t);
         return;
     }
-    for (int64_t i = tid0; i < total; i += nthr) {
-        const int64_t chain = i / g.U, u = i - chain * g.U;
-        buf[i] = ofp_rect_db(xt[chain * g.Nv + u_src_planar(g, u)], floor_db);
-    }
+    stream_trips(tid0, total, nthr,
+                 [&](int64_t i) {
+                     const int64_t chain = i / g.U, u = i - chain * g.U;
+                     return xt[chain * g.Nv + u_src_planar(g, u)];
+                 },
+                 [&](int64_t i, float v) { buf[i] = ofp_canon::rect_db(v, floor_db, tb.r, tb.t); });
 }
 
 // k_rect_db and k_ar_sym_local in one pass over the filtered stream (symmetric slow follower, U and the follower
@@ -2099,11 +2142,15 @@ __global__ __launch_bounds__(256) void k_rect_db(Geom g, const float* __restrict
 // (k_ar_sym_combine) -- the dB stream is not read a second time for it.  The chunk is walked from its end, so
 // the weights only decrease (no overflow for any q in (0, 1)).  P is a guess generator: its summation order does
 // not matter, the chunk passes verify every state bit for bit.
-__global__ __launch_bounds__(64) void k_rect_db_sym(ArArgs a, float* __restrict__ buf, int64_t n_waves,
-                                                    double* __restrict__ P) {
-    const int64_t id = blockIdx.x;  // one wave per (chain, chunk)
+// Four such waves make a workgroup and share one copy of the log tables; a wave without a (chain, chunk) takes part in
+// the fill and its barrier and leaves after it.
+__global__ __launch_bounds__(256) void k_rect_db_sym(ArArgs a, float* __restrict__ buf, int64_t n_waves,
+                                                     double* __restrict__ P) {
+    __shared__ ofp_canon::LogTables tb;
+    ofp_canon::fill(tb);
+    const int64_t id = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // one wave per (chain, chunk)
     if (id >= n_waves) return;
-    const int lane = threadIdx.x;
+    const int lane = threadIdx.x & 63;
     const int64_t j = id % a.n_chunks;
     const int64_t chain = id / a.n_chunks;
     const int64_t base = j * a.L;
@@ -2120,26 +2167,25 @@ __global__ __launch_bounds__(64) void k_rect_db_sym(ArArgs a, float* __restrict_
     // Four groups per lane and trip, their loads issued together: one 16-byte load in flight per lane left the pass
     // latency-bound (a wave moved 1 KB per memory round trip + ~180 fp64 operations: 2.9 TB/s of traffic at full
     // occupancy on C3's 1.8 G samples, where a copy reaches 4.5+).
+    // The next trip's four loads are issued before this trip's arithmetic (stream_trips).
     auto one = [&](float4 v, int64_t g) {
-        v.x = ofp_rect_db(v.x, a.floor_db);
-        v.y = ofp_rect_db(v.y, a.floor_db);
-        v.z = ofp_rect_db(v.z, a.floor_db);
-        v.w = ofp_rect_db(v.w, a.floor_db);
+        v = rect_db4(v, a.floor_db, tb);
         xs[ng - 1 - g] = v;
         // t = 4 g + 0 for .w, + 1 for .z, + 2 for .y, + 3 for .x
         acc += w * ((double)v.w + q * ((double)v.z + q * ((double)v.y + q * (double)v.x)));
         w *= q256;
     };
-    int64_t g = lane;
-    for (; g + 192 < ng; g += 256) {
-        const float4 v0 = xs[ng - 1 - g], v1 = xs[ng - 1 - g - 64], v2 = xs[ng - 1 - g - 128], v3 = xs[ng - 1 - g - 192];
-        __builtin_amdgcn_sched_barrier(0);
-        one(v0, g);
-        one(v1, g + 64);
-        one(v2, g + 128);
-        one(v3, g + 192);
-    }
-    for (; g < ng; g += 64) one(xs[ng - 1 - g], g);
+    const int64_t n_full = ng - lane > 192 ? (ng - lane - 193) / 256 + 1 : 0;  // trips of four groups: g + 192 < ng
+    stream_trips(int64_t(lane), lane + 256 * n_full, int64_t(256),
+                 [&](int64_t g) { return Quad{xs[ng - 1 - g], xs[ng - 1 - g - 64], xs[ng - 1 - g - 128], xs[ng - 1 - g - 192]}; },
+                 [&](int64_t g, const Quad& v) {
+                     one(v.v0, g);
+                     one(v.v1, g + 64);
+                     one(v.v2, g + 128);
+                     one(v.v3, g + 192);
+                 });
+    stream_trips(lane + 256 * n_full, ng, int64_t(64), [&](int64_t g) { return xs[ng - 1 - g]; },
+                 [&](int64_t g, float4 v) { one(v, g); });
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if (lane == 0) P[id] = acc;
 }
@@ -2154,7 +2200,7 @@ __global__ __launch_bounds__(64) void k_rect_db_sym(ArArgs a, float* __restrict_
 __device__ __forceinline__ void rel_out_tile(const Geom& g, float* __restrict__ buf, float* __restrict__ rel_out,
                                              float floor_db, int TU, uint32_t* __restrict__ sum_max,
                                              uint32_t* __restrict__ sum_minv, int64_t nb, float* __restrict__ rel_warm,
-                                             int planar, int64_t tile_x, float* tile) {
+                                             int planar, int64_t tile_x, float* tile, const ofp_canon::ExpTable& tb) {
     // rel_warm: the rows of the warm-up part in the output's interleaved order ([clip][n_wb][C]), for the tracker's
     // *_il kernels; planar = 0: the planar series are not written back (nothing reads them then)
     // tile: [C][TU+4], then the tile's summaries [2][C][nbt]
@@ -2190,10 +2236,7 @@ __device__ __forceinline__ void rel_out_tile(const Geom& g, float* __restrict__ 
         };
         auto one = [&](int i, float4 v) {
             const int c = lq >= 0 ? i >> lq : i / q, t = (i - c * q) << 2;
-            v.x = ofp_rel_linear(v.x, floor_db);
-            v.y = ofp_rel_linear(v.y, floor_db);
-            v.z = ofp_rel_linear(v.z, floor_db);
-            v.w = ofp_rel_linear(v.w, floor_db);
+            v = rel_linear4(v, floor_db, tb);
             if (planar) *at(i) = v;
             *reinterpret_cast<float4*>(tile + c * S + t) = v;
             const int m = mbase + t;  // main row of the group's first value relative to block j0 (the four share a block)
@@ -2207,7 +2250,7 @@ __device__ __forceinline__ void rel_out_tile(const Geom& g, float* __restrict__ 
             }
         };
         // the loads of four groups per thread are issued together (see k_rect_db_sym: one in flight left the pass
-        // latency-bound)
+        // latency-bound; one register set, as in k_rel_out_il: a second one costs a wave of occupancy here too)
         int i = threadIdx.x;
         for (; i + 768 < q * C; i += 1024) {
             const float4 v0 = *at(i), v1 = *at(i + 256), v2 = *at(i + 512), v3 = *at(i + 768);
@@ -2217,15 +2260,19 @@ __device__ __forceinline__ void rel_out_tile(const Geom& g, float* __restrict__ 
             one(i + 512, v2);
             one(i + 768, v3);
         }
-        for (; i < q * C; i += 256) one(i, *at(i));
+        stream_trips(i, q * C, 256, [&](int i) { return *at(i); }, [&](int i, float4 v) { one(i, v); });
     } else {
-        for (int i = threadIdx.x; i < total; i += 256) {
+        auto at = [&](int i) -> float* {
             const int c = i / nt, t = i - c * nt;
-            float* p = buf + (clip * C + c) * g.U + u0 + t;
-            const float v = ofp_rel_linear(*p, floor_db);
-            if (planar) *p = v;
-            tile[c * S + t] = v;
-        }
+            return buf + (clip * C + c) * g.U + u0 + t;
+        };
+        stream_trips((int)threadIdx.x, total, 256, [&](int i) { return *at(i); },
+                     [&](int i, float x) {
+                         const int c = i / nt, t = i - c * nt;
+                         const float v = ofp_canon::rel_linear(x, floor_db, tb.t);
+                         if (planar) *at(i) = v;
+                         tile[c * S + t] = v;
+                     });
     }
     __syncthreads();
     if (sum) {
@@ -2275,15 +2322,18 @@ __global__ __launch_bounds__(256) void k_rel_out(Geom g, float* __restrict__ buf
                                                  uint32_t* __restrict__ sum_minv, int64_t nb, float* __restrict__ rel_warm,
                                                  int planar, int64_t n_tiles) {
     extern __shared__ float tile[];
+    __shared__ ofp_canon::ExpTable tb;
+    ofp_canon::fill(tb);
     for (int64_t tx = blockIdx.x; tx < n_tiles; tx += gridDim.x) {
-        rel_out_tile(g, buf, rel_out, floor_db, TU, sum_max, sum_minv, nb, rel_warm, planar, tx, tile);
+        rel_out_tile(g, buf, rel_out, floor_db, TU, sum_max, sum_minv, nb, rel_warm, planar, tx, tile, tb);
         __syncthreads();  // (the tile and its summaries are free again)
     }
 }
 
 // Back to linear where the followers have left their differences in the interleaved arrays themselves (Layout::ar_il:
 // walk_lines_to<CH> wrote rel [clip][Nm][CH] and rel_warm [clip][n_wb][CH]): nothing is left to transpose, so the pass is
-// a stream in place, shaped like k_rect_db_sym -- 16-byte accesses, four loads in flight per lane, no LDS, no barrier.
+// a stream in place, shaped like k_rect_db_sym -- 16-byte accesses, four loads in flight per lane, no LDS but the 256 bytes
+// of the canon's exp table, no barrier but the one after its fill.
 // One wave takes one block of B rows at a time (n_wb and Nm are whole blocks; per clip the n_wu blocks of the warm-up
 // rows, then the nb main ones), so no block is split between waves and its extremes (sum_max / sum_minv, encoding and
 // values as in rel_out_tile) leave as plain stores: no atomics here.  A 16-byte group holds four channels of one row and
@@ -2293,6 +2343,8 @@ template <int CH>
 __global__ __launch_bounds__(256) void k_rel_out_il(Geom g, float* __restrict__ rel, float* __restrict__ rel_warm, float floor_db,
                                                     uint32_t* __restrict__ sum_max, uint32_t* __restrict__ sum_minv,
                                                     int64_t nb, int64_t n_wu) {
+    __shared__ ofp_canon::ExpTable tb;
+    ofp_canon::fill(tb);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t clip = blockIdx.y;
@@ -2305,14 +2357,14 @@ __global__ __launch_bounds__(256) void k_rel_out_il(Geom g, float* __restrict__ 
         const float inf = __builtin_inff();
         float4 lo = make_float4(inf, inf, inf, inf);
         auto one = [&](int i, float4 v) {
-            v.x = ofp_rel_linear(v.x, floor_db);
-            v.y = ofp_rel_linear(v.y, floor_db);
-            v.z = ofp_rel_linear(v.z, floor_db);
-            v.w = ofp_rel_linear(v.w, floor_db);
+            v = rel_linear4(v, floor_db, tb);
             p[i] = v;
             hi.x = fmaxf(hi.x, v.x); hi.y = fmaxf(hi.y, v.y); hi.z = fmaxf(hi.z, v.z); hi.w = fmaxf(hi.w, v.w);
             lo.x = fminf(lo.x, v.x); lo.y = fminf(lo.y, v.y); lo.z = fminf(lo.z, v.z); lo.w = fminf(lo.w, v.w);
         };
+        // (one register set: a second one, for the next trip's loads, costs this kernel a wave of occupancy, and a block
+        //  of the common sizes is one or two trips.  A trip's waits are counted all the same: each leaves the trip's later
+        //  loads and its earlier stores in flight)
         int i = lane;
         for (; i + 192 < n4; i += 256) {
             const float4 v0 = p[i], v1 = p[i + 64], v2 = p[i + 128], v3 = p[i + 192];
@@ -2322,7 +2374,7 @@ __global__ __launch_bounds__(256) void k_rel_out_il(Geom g, float* __restrict__ 
             one(i + 128, v2);
             one(i + 192, v3);
         }
-        for (; i < n4; i += 64) one(i, p[i]);
+        stream_trips(i, n4, 64, [&](int i) { return p[i]; }, [&](int i, float4 v) { one(i, v); });
         if (sum_max == nullptr || !in_main) continue;
 #pragma unroll
         for (int o = 32; o >= CH / 4; o >>= 1) {  // lanes o apart hold the same channels
@@ -3821,7 +3873,7 @@ int decibels(Call& c) {
     const auto& p = c.d->p;
     const int64_t chains = c.chains();
     if (l.db_sym) {
-        hipLaunchKernelGGL(k_rect_db_sym, dim3((unsigned)(chains * l.ar_chunks)), dim3(64), 0, c.stream, ar_args(c), c.xdb,
+        hipLaunchKernelGGL(k_rect_db_sym, dim3((unsigned)cdiv(chains * l.ar_chunks, 4)), dim3(256), 0, c.stream, ar_args(c), c.xdb,
                            chains * l.ar_chunks, c.at<double>(l.o_ar_P));
         OFP_LAUNCH_CHECK("k_rect_db_sym");
     } else {

@@ -309,13 +309,19 @@ CANON_OPS = {"log10": 0, "exp10": 1, "rect_db": 2, "rel_linear": 3, "ar_step": 4
 def canon_eval(op, x, y=None, p0=0.0, p1=0.0, out=None):
     """The canon of include/ofp_math.h on the device, elementwise (ofp_canon_eval): x, y float32 CUDA tensors of one
     size (y for "ar_step", "min_step", "max_step" only); p0, p1 as the header lists them per op (floor; attack, release;
-    alpha, minmin; alpha).  Writes `out` (default: a new tensor like x) and returns it."""
+    alpha, minmin; alpha).  "rect_db_lds" and "rel_linear_lds" are "rect_db" and "rel_linear" with the canon's tables read
+    from LDS, as the detector's elementwise passes read them (ofp_canon_eval_lds; p0 = floor).  Writes `out` (default: a new
+    tensor like x) and returns it."""
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
     if y is not None:
         assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.numel() == x.numel()
     if out is None:
         out = torch.empty_like(x)
     assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.numel()
+    if op.endswith("_lds"):
+        check(_lib.lib().ofp_canon_eval_lds(CANON_OPS[op[:-4]], x.data_ptr(), x.numel(), p0, out.data_ptr(),
+                                            _stream_ptr(x.device)), "ofp_canon_eval_lds")
+        return out
     check(_lib.lib().ofp_canon_eval(CANON_OPS[op], x.data_ptr(), y.data_ptr() if y is not None else None, x.numel(),
                                     p0, p1, 0.0, out.data_ptr(), _stream_ptr(x.device)), "ofp_canon_eval")
     return out
