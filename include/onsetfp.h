@@ -984,6 +984,44 @@ int ofp_paired_solve(const double* d_sensors, int32_t S, const int32_t* d_lags, 
                      int32_t* d_ier, void* stream);
 int ofp_intensity_maps(const double* d_mics, int32_t r, double reflectivity, float* d_out, void* stream);
 
+/* ---- the voting locator of a stream ("The voting locator in the hop") -----------------------------
+ * MultilateratePaired.locate_cc as a stage of a stream: the grouping state machine and FIFO of the window regressor
+ * above (ofp_regress_state, with frame_length = left + right and pre_samples = left), and for the group that is due
+ * -- the first hop whose end is >= onset + right; the window is never clipped -- the first channel (the row's
+ * earliest, ties by channel) and its onset, ofp_find_lags' lags of the window x[onset - left : onset + right] against
+ * the two neighbours, and ofp_paired_vote's cell and coordinates.  A window that starts below sample 0 is reported
+ * with OFP_PAIRED_NEG_WINDOW (cell -1, lags INT32_MIN, NaN coordinates).  No vote grid is written.
+ * d_starts / d_sorted / d_vmin / n_buckets: the index ofp_vote_index built over the 2 S neighbour maps (map 2i + k is
+ * sensor i's neighbour k); they are read while a session or the replay runs and must outlive it.
+ * Envelope: S 2..OFP_REG_MAX_SIGNALS, left + right <= 1024, and 32 + 12 (left + right) + 4 ceil(side^2 / 32) bytes of
+ * LDS (partials, three rows, vote bitmap) at most 96 KiB; there is no global-memory fallback. */
+typedef struct ofp_hop_paired {
+    const int32_t* d_starts;
+    const int32_t* d_sorted;
+    const int32_t* d_vmin;
+    int32_t n_buckets, S, side;
+    double radius, tol;
+    int32_t left, right, max_distance, min_channels;
+} ofp_hop_paired;
+/* Replay, as ofp_regress_stream: d_audio [n_rows][S], the onset list in feed order, n_rows / block_size hops in ONE
+ * launch of one workgroup from an empty state.  Per hop h - 1: d_hit 1 when a group was evaluated, then d_status,
+ * d_onset_out, d_first, d_row [S], d_lags [2], d_cell, d_xy [2] and d_rphi [2] (untouched otherwise); d_pending the
+ * FIFO's length before the hop's evaluation; *d_flags the final OFP_REGF_*. */
+int ofp_locate_cc_stream(const ofp_hop_paired* p, const float* d_audio, int64_t n_rows, int32_t block_size,
+                         const int32_t* d_channel, const int64_t* d_onset, int64_t K, int32_t* d_hit, int32_t* d_status,
+                         int64_t* d_onset_out, int32_t* d_first, int64_t* d_row, int32_t* d_lags, int32_t* d_cell,
+                         double* d_xy, double* d_rphi, int32_t* d_pending, int32_t* d_flags, void* stream);
+/* The stage inside the hop graph of a session (before its first hop; the graph is captured again; on failure the
+ * session is the one it was).  It runs after the detector, in the detector's workgroup (one kernel form) or as one
+ * more node before the spectral node.  OFP_ERR_INVALID: S != the session's channels, a session that already has a
+ * locator or a regressor, a detector that backtracks, max_distance < block_size, and the queue and ring conditions of
+ * ofp_hop_set_regressor with frame_length = left + right, pre_samples = left.  ofp_hop_reset clears the state. */
+int ofp_hop_set_locator_paired(ofp_hop_session* s, const ofp_hop_paired* p);
+/* The block of the last collected hop: *hit 0 none / 1 evaluated, then *status, *onset, *first, h_row [S], h_lags [2],
+ * *cell, h_xy [2] and h_rphi [2]; *flags always. */
+int ofp_hop_collect_cc_hit(ofp_hop_session* s, int32_t* hit, int32_t* status, int64_t* onset, int32_t* first,
+                           int64_t* h_row, int32_t* h_lags, int32_t* cell, double* h_xy, double* h_rphi, int32_t* flags);
+
 /* ---- calibration: train_location_model, optimize_positions (calibration.py:563-754) ----------------------------
  * One workgroup runs one whole optimisation inside one launch (full-batch forward, mean loss, early stop, backward,
  * clip_grad_norm_ with max_norm 1, Adam with torch's defaults); the grid is the M independent problems.  fp32, no

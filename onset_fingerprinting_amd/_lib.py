@@ -162,6 +162,27 @@ class HopRegressor(ctypes.Structure):
     ]
 
 
+PAIR_MAX_WINDOW = 1024          # ofppair::MAX_WINDOW: left + right of the voting locator's stage
+PAIR_LDS_ENVELOPE = 96 * 1024   # ofpreg::LDS_SWITCH
+
+
+def paired_lds_bytes(window, side):
+    """ofppair::lds_bytes: the reductions' partials, three rows of the window and the vote bitmap."""
+    return 32 + 12 * window + 4 * ((side * side + 31) // 32)
+
+
+class HopPaired(ctypes.Structure):
+    _fields_ = [
+        ("d_starts", ctypes.c_void_p),
+        ("d_sorted", ctypes.c_void_p),
+        ("d_vmin", ctypes.c_void_p),
+        ("n_buckets", ctypes.c_int32), ("S", ctypes.c_int32), ("side", ctypes.c_int32),
+        ("radius", ctypes.c_double), ("tol", ctypes.c_double),
+        ("left", ctypes.c_int32), ("right", ctypes.c_int32), ("max_distance", ctypes.c_int32),
+        ("min_channels", ctypes.c_int32),
+    ]
+
+
 class CnnConfig(ctypes.Structure):
     _fields_ = [
         ("n_conv", ctypes.c_int32),
@@ -344,6 +365,12 @@ SIGNATURES = {
     "ofp_hop_set_regressor": (ctypes.c_int, [_vp, ctypes.POINTER(HopRegressor)]),
     "ofp_hop_collect_hit": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i64), _vp, _vp,
                                            ctypes.POINTER(_i32)]),
+    "ofp_locate_cc_stream": (ctypes.c_int, [ctypes.POINTER(HopPaired), _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofp_hop_set_locator_paired": (ctypes.c_int, [_vp, ctypes.POINTER(HopPaired)]),
+    "ofp_hop_collect_cc_hit": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i64),
+                                              ctypes.POINTER(_i32), _vp, _vp, ctypes.POINTER(_i32), _vp, _vp,
+                                              ctypes.POINTER(_i32)]),
     "ofp_find_lags": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp,
                                      _vp, _vp, _vp, _vp]),
     "ofp_vote_index": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

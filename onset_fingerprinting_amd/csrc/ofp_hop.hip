@@ -27,6 +27,10 @@
 // step (ofp_regress_dev.h): the hop's onsets go through the grouping state machine, and the group whose window the hop
 // completes goes through the model; a hop with nothing to feed, close or evaluate takes uniform branches only.
 //
+// With the voting locator attached (ofp_hop_set_locator_paired; a session's only stage) the workgroup / one node runs
+// MultilateratePaired.locate_cc's stage (ofp_paired_dev.h): the regressor's grouping state machine, then the lag search
+// and the vote on the window of the group that is due.
+//
 // A replay needs no argument update: the write cursor is a counter in device memory.  The frame the
 // spectral kernel computes for the hop that ends at sample e is bit-identical to frame (e - n_fft)/B
 // of the dense kernel (k_stft_power, hop = B) on the same stream: same tables, same FFT, same mel
@@ -42,6 +46,7 @@
 #include "ofp_fft.h"
 #include "ofp_locate_dev.h"
 #include "ofp_mlp.h"
+#include "ofp_paired_dev.h"
 #include "ofp_regress_dev.h"
 #include "ofp_stream_dev.h"
 
@@ -532,16 +537,18 @@ struct HopRegArgs {
     HopRegBlock* out;
 };
 
-// The window regressor's step for one hop, by one workgroup of 256 threads, after the detector and the locator stage:
-// the hop's n records in the locator stage's order (sorted by sample, ties in record order), rows by the same rule
-// (current hop from the hop buffer -- each needed sample is fetched once --, older rows from the ring, rows before
-// sample 0 zero).  h = hops pushed including this one; wake: the state's word of that name, loaded by the caller
-// before the detector ran, so that a hop with nothing to feed, close or evaluate leaves on one uniform comparison.
-__device__ __forceinline__ void hop_regress_stage(const HopArgs& a, const HopRegArgs& ra, int64_t h, int n, int64_t wake,
-                                                  const ofp_onset* recs, unsigned char* smem) {
+// How a grouping stage (the window regressor's, the voting locator's) takes one hop, by one workgroup of 256 threads
+// after the detector and the locator stage: the hop's n records in the locator stage's order (sorted by sample, ties
+// in record order), rows by the same rule (current hop from the hop buffer -- each needed sample is fetched once --,
+// older rows from the ring, rows before sample 0 zero).  h = hops pushed including this one; wake: the state's word of
+// that name, loaded by the caller before the detector ran, so that a hop with nothing to feed, close or evaluate
+// leaves on one uniform comparison.  g: the stage's configuration; run(n, rec, sample): its step.
+template <class G, class Run>
+__device__ __forceinline__ void hop_grouping_stage(const HopArgs& a, const G& g, int64_t h, int n, int64_t wake,
+                                                   const ofp_onset* recs, Run run) {
     const int C = a.C, B = a.B;
     n = n < C ? n : C;
-    if (ofpreg::idle(ra.g, h, n, wake)) return;
+    if (ofpreg::idle(g, h, n, wake)) return;
     __syncthreads();  // the detector and the locator stage are done with this LDS
     const int64_t first = (h - 1) * B;
     auto rec = [&](int i, int& ch, int64_t& s) {  // the i-th record of the stable argsort (n <= 8: by rank)
@@ -561,9 +568,52 @@ __device__ __forceinline__ void hop_regress_stage(const HopArgs& a, const HopReg
         if (t >= first) return a.hop[(t - first) * C + col];
         return a.ring[(t % a.R) * C + col];
     };
-    HopRegBlock* o = ra.out;
-    const int ev = ofpreg::step(ra.g, h, n, rec, sample, smem, &o->start, o->row, o->y, &o->flags);
-    if (ev && threadIdx.x == 0) o->hop = h;
+    run(n, rec, sample);
+}
+
+// The window regressor's step for one hop (ofp_regress_dev.h).
+__device__ __forceinline__ void hop_regress_stage(const HopArgs& a, const HopRegArgs& ra, int64_t h, int n, int64_t wake,
+                                                  const ofp_onset* recs, unsigned char* smem) {
+    hop_grouping_stage(a, ra.g, h, n, wake, recs, [&](int m, auto rec, auto sample) {
+        HopRegBlock* o = ra.out;
+        const int ev = ofpreg::step(ra.g, h, m, rec, sample, smem, &o->start, o->row, o->y, &o->flags);
+        if (ev && threadIdx.x == 0) o->hop = h;
+    });
+}
+
+// The block of the voting locator in the result block (ofp_hop_collect_cc_hit); `hop` as in HopRegBlock
+struct HopPairBlock {
+    int64_t hop;
+    int32_t flags, status;
+    int64_t onset;
+    int64_t row[OFP_REG_MAX_SIGNALS];
+    int32_t first, cell;
+    int32_t lags[2];
+    double xy[2], rphi[2];
+};
+
+struct HopPairArgs {
+    int enabled;
+    ofppair::Cfg g;
+    HopPairBlock* out;
+};
+
+// The voting locator's step for one hop (ofp_paired_dev.h), by one workgroup of 256 threads after the detector.
+__device__ __forceinline__ void hop_paired_stage(const HopArgs& a, const HopPairArgs& pa, int64_t h, int n, int64_t wake,
+                                                 const ofp_onset* recs, unsigned char* smem) {
+    hop_grouping_stage(a, pa.g, h, n, wake, recs, [&](int m, auto rec, auto sample) {
+        HopPairBlock* b = pa.out;
+        const ofppair::Out o{&b->onset, b->row, &b->first, &b->status, b->lags, &b->cell, b->xy, b->rphi, &b->flags};
+        const int ev = ofppair::step(pa.g, h, m, rec, sample, smem, o);
+        if (ev && threadIdx.x == 0) b->hop = h;
+    });
+}
+
+// Nodes form: the stage as a kernel of its own where the locate node is, before the spectral node.
+__global__ __launch_bounds__(256) void k_hop_paired(HopArgs a, HopPairArgs pa, const ofp_onset* recs) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t n = *a.count;
+    hop_paired_stage(a, pa, a.ctl[0], (int)(n < a.C ? n : a.C), pa.g.state->wake, recs, smem);
 }
 
 // Nodes form: the stage as a kernel of its own after the detector and the locate node.
@@ -587,21 +637,29 @@ struct FusedCfg {
 // arguments are the caller's (kernel arguments or a group's device arrays), never copies.
 // LOC: the instantiation of a session with a locator; without one the kernel is the one it always was.
 // REG: the instantiation of a session with a regressor (ra is read only then); the same holds.
-template <int F, bool LOC, bool REG>
+// PAIR: the instantiation of a session with the voting locator (pa is read only then; never with LOC or REG).
+template <int F, bool LOC, bool REG, bool PAIR = false>
 __device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream::StreamArgs& sa, const HopLocArgs& la,
-                                               const HopRegArgs* ra, unsigned char* smem) {
+                                               const HopRegArgs* ra, unsigned char* smem,
+                                               const HopPairArgs* pa = nullptr) {
+    static_assert(!PAIR || (!LOC && !REG), "the voting locator is a session's only stage");
     const int64_t done = a.ctl[0];  // hops completed before this one
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) *a.hop_index = done;
-        if constexpr (LOC || REG) {
+        if constexpr (LOC || REG || PAIR) {
             int64_t wake = 0;
             if constexpr (REG) wake = ra->g.state->wake;  // (in flight while the detector runs)
+            if constexpr (PAIR) wake = pa->g.state->wake;
             const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
             if constexpr (LOC)
                 if (n_on > 0) hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
             if constexpr (REG) {
                 static_assert(FusedCfg<F>::WGS == ofpnn::WG, "the per-item forward passes are written for 256 threads");
                 hop_regress_stage(a, *ra, done + 1, (int)(n_on < a.C ? n_on : a.C), wake, sa.mirror, smem);
+            }
+            if constexpr (PAIR) {
+                static_assert(FusedCfg<F>::WGS == ofppair::FT, "the lag search and the vote are written for 256 threads");
+                hop_paired_stage(a, *pa, done + 1, (int)(n_on < a.C ? n_on : a.C), wake, sa.mirror, smem);
             }
         } else {
             ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
@@ -642,6 +700,13 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_reg(HopArgs a, o
     hop_fused_body<F, LOC, true>(a, sa, la, &ra, smem);
 }
 
+// The fused hop of a session with the voting locator: again a kernel of its own.
+template <int F>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_pair(HopArgs a, ofpstream::StreamArgs sa, HopPairArgs pa) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    hop_fused_body<F, false, false, true>(a, sa, HopLocArgs{}, nullptr, smem, &pa);
+}
+
 // S sessions' hops in ONE launch: grid (C + 1 + strength, S), row blockIdx.y is member blockIdx.y of an
 // ofp_hop_group and runs hop_fused_body on that member's three argument structs in the group's device arrays
 // (uniform, read-only addresses: scalar loads, as for kernel arguments) -- the member's own ticket, counter and
@@ -667,6 +732,18 @@ __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group_reg(const 
     extern __shared__ __align__(16) unsigned char smem[];
     if (dry) return;
     hop_fused_body<F, LOC, true>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], rargs + blockIdx.y, smem);
+}
+
+// The group launch of members with a voting locator each (pargs: the members' stage arguments; locators, tol, left and
+// right may differ).
+template <int F>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group_pair(const HopArgs* __restrict__ args,
+                                                                           const ofpstream::StreamArgs* __restrict__ sargs,
+                                                                           const HopPairArgs* __restrict__ pargs, int dry) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (dry) return;
+    hop_fused_body<F, false, false, true>(args[blockIdx.y], sargs[blockIdx.y], HopLocArgs{}, nullptr, smem,
+                                          pargs + blockIdx.y);
 }
 
 }  // namespace
@@ -723,6 +800,11 @@ struct ofp_hop_session {
     float* d_reg_ws = nullptr;   // activations of a model too large for the LDS
     int64_t o_reg = 0;
     size_t lds_reg = 0;
+    // the voting locator (ofp_hop_set_locator_paired); its index tables are the caller's
+    HopPairArgs pargs;
+    ofp_regress_state* d_pair_state = nullptr;
+    int64_t o_pair = 0;
+    size_t lds_pair = 0;
     int device = 0;
     ofp_hop_group* owner = nullptr;  // the group whose launches carry this session's hops (ofp_hop_group_create)
 };
@@ -732,7 +814,7 @@ struct ofp_hop_session {
 struct ofp_hop_group {
     std::vector<ofp_hop_session*> members;
     int device = 0, n_fft = 0, grid_x = 0;
-    bool loc = false, reg = false;
+    bool loc = false, reg = false, pair = false;
     size_t lds = 0;
     hipStream_t stream = nullptr;
     hipGraph_t graph = nullptr;
@@ -741,6 +823,7 @@ struct ofp_hop_group {
     ofpstream::StreamArgs* d_sargs = nullptr;
     HopLocArgs* d_largs = nullptr;
     HopRegArgs* d_rargs = nullptr;
+    HopPairArgs* d_pargs = nullptr;
 };
 
 namespace {
@@ -794,11 +877,22 @@ int hop_fused_reg(ofp_hop_session* s) {
     return OFP_OK;
 }
 
+template <int F>
+int hop_fused_pair(ofp_hop_session* s) {
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_pair<F>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_pair<F>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
+                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->pargs);
+    OFP_LAUNCH_CHECK("k_hop_fused_pair");
+    return OFP_OK;
+}
+
 // the per-hop sequence, enqueued on the session's stream (captured once, then replayed)
 int enqueue_hop(ofp_hop_session* s) {
     if (s->fused)  // one kernel: no copy nodes, no begin kernel
         return with_n_fft(s->n_fft, [&](auto f) {
             constexpr int F = decltype(f)::value;
+            if (s->pargs.enabled) return hop_fused_pair<F>(s);
             if (s->rargs.enabled) return s->largs.enabled ? hop_fused_reg<F, true>(s) : hop_fused_reg<F, false>(s);
             return s->largs.enabled ? hop_fused<F, true>(s) : hop_fused<F, false>(s);
         });
@@ -817,6 +911,13 @@ int enqueue_hop(ofp_hop_session* s) {
                            reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
         OFP_LAUNCH_CHECK("k_hop_locate");
     }
+    if (s->pargs.enabled) {  // (where the locate node is: the ring holds the older hops only)
+        static ofp::LdsAttrCache attr;
+        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_paired), s->lds_pair, attr)) != OFP_OK) return rc;
+        hipLaunchKernelGGL(k_hop_paired, dim3(1), dim3(256), s->lds_pair, s->stream, s->args, s->pargs,
+                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
+        OFP_LAUNCH_CHECK("k_hop_paired");
+    }
     if (s->rargs.enabled) {  // (after the locate node, before the spectral node: the ring holds the older hops only)
         static ofp::LdsAttrCache attr;
         if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_regress), s->lds_reg, attr)) != OFP_OK) return rc;
@@ -831,9 +932,10 @@ int enqueue_hop(ofp_hop_session* s) {
     }
     rc = with_n_fft(s->n_fft, [&](auto f) { return hop_spectral<decltype(f)::value>(s); });
     if (rc != OFP_OK) return rc;
-    // (the hit block is the result block's tail: a session without a regressor copies the bytes it always copied)
-    OFP_HIP(hipMemcpyAsync(s->h_res, s->d_res, (size_t)(s->rargs.enabled ? s->res_bytes : s->o_reg), hipMemcpyDeviceToHost,
-                           s->stream));
+    // (the hit block and, after it, the voting locator's are the result block's tail: a session without them copies
+    //  the bytes it always copied)
+    const int64_t copied = s->pargs.enabled ? s->res_bytes : s->rargs.enabled ? s->o_pair : s->o_reg;
+    OFP_HIP(hipMemcpyAsync(s->h_res, s->d_res, (size_t)copied, hipMemcpyDeviceToHost, s->stream));
     return OFP_OK;
 }
 
@@ -845,6 +947,7 @@ int reset_state(ofp_hop_session* s) {
     OFP_HIP(hipMemsetAsync(s->d_res, 0, (size_t)s->res_bytes, s->stream));
     if (s->d_loc_state) OFP_HIP(hipMemsetAsync(s->d_loc_state, 0, sizeof(ofp_locate_state), s->stream));
     if (s->d_reg_state) OFP_HIP(hipMemsetAsync(s->d_reg_state, 0, sizeof(ofp_regress_state), s->stream));
+    if (s->d_pair_state) OFP_HIP(hipMemsetAsync(s->d_pair_state, 0, sizeof(ofp_regress_state), s->stream));
     if (s->d_sg) {
         OFP_HIP(hipMemsetAsync(s->d_sg, 0, s->sg_floats * 4, s->stream));
         OFP_HIP(hipMemcpyAsync(s->args.sg.st, s->sg_init, 16, hipMemcpyHostToDevice, s->stream));
@@ -950,6 +1053,16 @@ int hop_group_launch_reg(ofp_hop_group* g, int dry) {
     return OFP_OK;
 }
 
+template <int F>
+int hop_group_launch_pair(ofp_hop_group* g, int dry) {
+    static ofp::LdsAttrCache attr;
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group_pair<F>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_group_pair<F>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
+                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_pargs, dry);
+    OFP_LAUNCH_CHECK("k_hop_fused_group_pair");
+    return OFP_OK;
+}
+
 void group_free(ofp_hop_group* g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
@@ -958,6 +1071,7 @@ void group_free(ofp_hop_group* g) {
     if (g->d_sargs) (void)hipFree(g->d_sargs);
     if (g->d_largs) (void)hipFree(g->d_largs);
     if (g->d_rargs) (void)hipFree(g->d_rargs);
+    if (g->d_pargs) (void)hipFree(g->d_pargs);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -986,6 +1100,12 @@ int group_build(ofp_hop_group* g) {
         OFP_HIP(hipMalloc(&g->d_rargs, n * sizeof(HopRegArgs)));
         OFP_HIP(hipMemcpy(g->d_rargs, r.data(), n * sizeof(HopRegArgs), hipMemcpyHostToDevice));
     }
+    if (g->pair) {
+        std::vector<HopPairArgs> p(n);
+        for (size_t i = 0; i < n; ++i) p[i] = g->members[i]->pargs;
+        OFP_HIP(hipMalloc(&g->d_pargs, n * sizeof(HopPairArgs)));
+        OFP_HIP(hipMemcpy(g->d_pargs, p.data(), n * sizeof(HopPairArgs), hipMemcpyHostToDevice));
+    }
     // a member that joins mid-stream: its last stand-alone hop must have left its own stream
     for (ofp_hop_session* s : g->members)
         if (int rc = retire_last_hop(s)) return rc;
@@ -993,6 +1113,7 @@ int group_build(ofp_hop_group* g) {
     auto launch = [&](int dry) {
         return with_n_fft(g->n_fft, [&](auto f) {
             constexpr int F = decltype(f)::value;
+            if (g->pair) return hop_group_launch_pair<F>(g, dry);
             if (g->reg) return g->loc ? hop_group_launch_reg<F, true>(g, dry) : hop_group_launch_reg<F, false>(g, dry);
             return g->loc ? hop_group_launch<F, true>(g, dry) : hop_group_launch<F, false>(g, dry);
         });
@@ -1013,7 +1134,8 @@ int ofp_hop_destroy(ofp_hop_session* s) {
     if (s->exec) (void)hipGraphExecDestroy(s->exec);
     if (s->graph) (void)hipGraphDestroy(s->graph);
     void* dev[] = {s->d_state, s->d_hop, s->d_ring, s->d_ctl, s->d_twM, s->d_twF, s->d_win, s->d_wsym, s->d_tgw, s->d_sg, s->d_fb_i, s->d_fb_w,
-                   s->d_prm, s->d_res, s->d_loc_state, s->d_loc_prm, s->d_mirror, s->d_reg_state, s->d_reg_prm, s->d_reg_ws};
+                   s->d_prm, s->d_res, s->d_loc_state, s->d_loc_prm, s->d_mirror, s->d_reg_state, s->d_reg_prm, s->d_reg_ws,
+                   s->d_pair_state};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (s->h_hop) (void)hipHostFree(s->h_hop);
@@ -1082,7 +1204,8 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     s->o_sg = up8(s->o_rel + (s->want_rel ? (int64_t)B * C * 4 : 0));
     s->o_loc = up8(s->o_sg + 16 + (cfg->strength ? 4 * (int64_t)cfg->tg_win_length : 0));
     s->o_reg = up8(s->o_loc + (int64_t)sizeof(HopLocBlock));
-    s->res_bytes = up8(s->o_reg + (int64_t)sizeof(HopRegBlock));
+    s->o_pair = up8(s->o_reg + (int64_t)sizeof(HopRegBlock));
+    s->res_bytes = up8(s->o_pair + (int64_t)sizeof(HopPairBlock));
     const int M = s->n_fft / 2;
     s->lds = lds;
     s->lds_strength = lds_strength;
@@ -1130,6 +1253,7 @@ int ofp_hop_create(ofp_detector* det, const ofp_hop_config* cfg, ofp_hop_session
     std::memset(&a, 0, sizeof(a));
     std::memset(&s->largs, 0, sizeof(s->largs));
     std::memset(&s->rargs, 0, sizeof(s->rargs));
+    std::memset(&s->pargs, 0, sizeof(s->pargs));
     a.C = C;
     a.B = B;
     a.n_mels = s->n_mels;
@@ -1311,7 +1435,7 @@ int ofp_hop_ring_read(ofp_hop_session* s, int64_t n_rows, float* h_out) {
 // (T.planar: the kind; a planar locator reads no section, so no ring-length condition applies to it)
 static int hop_attach_locator(ofp_hop_session* s, const ofp_hop_locator* loc, ofp::LocTables T, const char* who) {
     OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
-    OFP_REQUIRE(!s->largs.enabled, "%s: the session already has a locator", who);
+    OFP_REQUIRE(!s->largs.enabled && !s->pargs.enabled, "%s: the session already has a locator", who);
     OFP_REQUIRE(!s->rargs.enabled, "%s: the session already has a regressor (attach the locator first)", who);
     OFP_REQUIRE(loc->S == s->C, "%s: %d sensors for %d channels", who, loc->S, s->C);
     OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
@@ -1414,6 +1538,7 @@ int ofp_hop_set_regressor(ofp_hop_session* s, const ofp_hop_regressor* r) {
     OFP_NOT_IN_GROUP(s, "ofp_hop_set_regressor");
     OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
     OFP_REQUIRE(!s->rargs.enabled, "%s: the session already has a regressor", who);
+    OFP_REQUIRE(!s->pargs.enabled, "%s: the session has a voting locator (the two grouping stages do not share a session)", who);
     ofpreg::Plan plan;
     if (int rc = ofp_regress_plan(r, who, &plan)) return rc;
     OFP_REQUIRE(r->channels == s->C, "%s: the model takes %d channels, the session has %d", who, r->channels, s->C);
@@ -1496,6 +1621,86 @@ int ofp_hop_collect_hit(ofp_hop_session* s, int32_t* status, int64_t* start, int
     return OFP_OK;
 }
 
+int ofp_hop_set_locator_paired(ofp_hop_session* s, const ofp_hop_paired* p) {
+    const char* who = "ofp_hop_set_locator_paired";
+    OFP_REQUIRE(s && p, "%s: NULL argument", who);
+    OFP_NOT_IN_GROUP(s, "ofp_hop_set_locator_paired");
+    OFP_REQUIRE(s->pushed == 0 && !s->in_flight, "%s: the session has already taken a hop", who);
+    OFP_REQUIRE(!s->pargs.enabled && !s->largs.enabled, "%s: the session already has a locator", who);
+    OFP_REQUIRE(!s->rargs.enabled, "%s: the session has a regressor (the two grouping stages do not share a session)", who);
+    ofppair::Cfg g;
+    if (int rc = ofp_paired_cfg(p, who, &g)) return rc;
+    OFP_REQUIRE(p->S == s->C, "%s: %d sensors for %d channels", who, p->S, s->C);
+    OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
+    OFP_REQUIRE(p->max_distance >= s->B, "%s: max_distance %d is shorter than one hop (%d): two groups could close in one hop",
+                who, p->max_distance, s->B);
+    // the bounds of ofp_hop_set_regressor with frame_length = left + right, pre_samples = left
+    const int64_t B = s->B, D = p->max_distance, span = D + (int64_t)p->right;
+    const int64_t K = std::max<int64_t>(0, (span + B - 1) / B - 1);
+    const int64_t pending = std::min<int64_t>(K + 1, (K * B + D - 1) / (D + 1) + 1);
+    OFP_REQUIRE(pending <= OFP_REG_QUEUE, "%s: up to %lld groups can be pending, the queue holds %d", who, (long long)pending,
+                OFP_REG_QUEUE);
+    const int64_t rows = D + p->left + (K + 1) * B;
+    OFP_REQUIRE(s->R >= rows, "%s: the ring (%lld rows) must hold the oldest row a pending window can need plus one hop (%lld)",
+                who, (long long)s->R, (long long)rows);
+    const size_t lds = ofppair::lds_bytes(g.F, g.side);
+    const size_t lds_fused = s->lds_fused;
+    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+        OFP_HIP(hipMalloc(&s->d_pair_state, sizeof(ofp_regress_state)));
+        OFP_HIP(hipMemset(s->d_pair_state, 0, sizeof(ofp_regress_state)));
+        g.B = s->B;
+        g.state = s->d_pair_state;
+        s->pargs.g = g;
+        s->pargs.out = reinterpret_cast<HopPairBlock*>(s->res_dev + s->o_pair);
+        s->lds_pair = lds;
+        if (s->fused) {
+            OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
+            OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
+            s->sargs.mirror = s->d_mirror;
+            s->lds_fused = std::max(s->lds_fused, lds);
+        }
+        s->pargs.enabled = 1;
+        return capture_hop(s);
+    };
+    const int rc = attach();
+    if (rc == OFP_OK) return OFP_OK;
+    // the session is again exactly the one it was, and a later call is accepted
+    const std::string why = ofp::err_buf();
+    void** dev[] = {(void**)&s->d_pair_state, (void**)&s->d_mirror};
+    for (void** q : dev) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    std::memset(&s->pargs, 0, sizeof(s->pargs));
+    s->sargs.mirror = nullptr;
+    s->lds_fused = lds_fused;
+    s->lds_pair = 0;
+    if (!s->exec) (void)capture_hop(s);  // (the failure came after the earlier graph had been given up)
+    return ofp::fail(rc, "%s", why.c_str());
+}
+
+int ofp_hop_collect_cc_hit(ofp_hop_session* s, int32_t* hit, int32_t* status, int64_t* onset, int32_t* first,
+                           int64_t* h_row, int32_t* h_lags, int32_t* cell, double* h_xy, double* h_rphi, int32_t* flags) {
+    OFP_REQUIRE(s, "ofp_hop_collect_cc_hit: NULL session");
+    OFP_REQUIRE(s->pargs.enabled, "ofp_hop_collect_cc_hit: the session has no voting locator");
+    OFP_REQUIRE(!s->in_flight && s->pushed > 0, "ofp_hop_collect_cc_hit: no collected hop");
+    HopPairBlock b;
+    std::memcpy(&b, s->h_res + s->o_pair, sizeof(b));
+    const bool got = b.hop == s->pushed;  // (a hop that evaluates nothing leaves the block of an earlier one)
+    if (hit) *hit = got ? 1 : 0;
+    if (flags) *flags = b.flags;
+    if (!got) return OFP_OK;
+    if (status) *status = b.status;
+    if (onset) *onset = b.onset;
+    if (first) *first = b.first;
+    if (h_row) std::memcpy(h_row, b.row, (size_t)s->C * sizeof(int64_t));
+    if (h_lags) std::memcpy(h_lags, b.lags, sizeof(b.lags));
+    if (cell) *cell = b.cell;
+    if (h_xy) std::memcpy(h_xy, b.xy, sizeof(b.xy));
+    if (h_rphi) std::memcpy(h_rphi, b.rphi, sizeof(b.rphi));
+    return OFP_OK;
+}
+
 int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group** out) {
     OFP_REQUIRE(sessions && out, "ofp_hop_group_create: NULL argument");
     OFP_REQUIRE(n >= 1 && n <= 1024, "ofp_hop_group_create: 1..1024 members (got %d)", n);
@@ -1521,6 +1726,8 @@ int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group*
                     i);
         OFP_REQUIRE(!s->rargs.enabled == !f->rargs.enabled, "ofp_hop_group_create: members 0 and %d differ in having a regressor",
                     i);
+        OFP_REQUIRE(!s->pargs.enabled == !f->pargs.enabled,
+                    "ofp_hop_group_create: members 0 and %d differ in having a voting locator (paired)", i);
         lds = std::max(lds, s->lds_fused);
     }
     ofp_hop_group* g = new (std::nothrow) ofp_hop_group();
@@ -1531,6 +1738,7 @@ int ofp_hop_group_create(ofp_hop_session* const* sessions, int n, ofp_hop_group*
     g->grid_x = f->C + 1 + (f->args.sg.enabled ? 1 : 0);
     g->loc = f->largs.enabled != 0;
     g->reg = f->rargs.enabled != 0;
+    g->pair = f->pargs.enabled != 0;
     g->lds = lds;
     int prev = 0;
     hipError_t e = hipGetDevice(&prev);

@@ -15,73 +15,32 @@
 // k_vote_grid:      the full vote grid (the reference's self.res) for a few hits.
 // k_paired_solve:   MultilateratePaired.locate per row, one lane each: the weighted guess, hybrj, polar.
 // k_intensity:      lag_intensity_map's two dB grids, one thread per cell and microphone.
+// k_locate_cc_stream: the replay of the voting locator's stream stage (ofp_paired_dev.h, which also holds the lag
+//                   search and the vote that k_find_lags and k_paired_vote run).
 #include <cmath>
 #include <climits>
+#include <cstring>
 
 #include "ofp_common.h"
 #include "ofp_hybrj.h"
+#include "ofp_paired_dev.h"
 #include "ofp_xcorr_canon.h"
 
 namespace {
 
 using ofp::cdiv;
+using ofppair::argmax_before;
+using ofppair::FT;  // threads per workgroup
+using ofppair::FW;  // wavefront
+using ofppair::polar;
+using ofppair::wg_argmax;
 
-constexpr int FT = 256;          // threads per workgroup
-constexpr int FW = 64;           // wavefront
 constexpr int F_MAXN = 4096;     // longest row
 constexpr int F_MAXTOP = 16;     // most peaks reported
 constexpr int64_t V_MAXCELLS = 1 << 20;  // largest grid the vote's LDS bitmap holds (128 KiB)
 constexpr int V_MAXBUCKETS = 32768;      // widest lag range of one map (LDS histogram of 128 KiB)
 
 ofp::LdsAttrCache g_find_lds, g_index_lds, g_vote_lds;
-
-// Is (ov, oi) before (v, i) in np.argmax order?  i < 0: empty slot; a NaN beats any number; ties by index.
-__device__ __forceinline__ bool argmax_before(float ov, int oi, float v, int i) {
-    if (oi < 0) return false;
-    if (i < 0) return true;
-    const bool on = isnan(ov), n = isnan(v);
-    if (on != n) return on;
-    if (n) return oi < i;
-    return ov > v || (ov == v && oi < i);
-}
-
-// Workgroup-wide argmax of one (value, index) per thread; s_v / s_i hold one slot per wave.  Every thread gets the
-// result.
-__device__ void wg_argmax(float& v, int& i, float* s_v, int* s_i) {
-    for (int o = FW / 2; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(i, o);
-        if (argmax_before(ov, oi, v, i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-    const int lane = threadIdx.x & (FW - 1), wave = threadIdx.x / FW;
-    __syncthreads();
-    if (lane == 0) {
-        s_v[wave] = v;
-        s_i[wave] = i;
-    }
-    __syncthreads();
-    v = s_v[0];
-    i = s_i[0];
-    for (int w = 1; w < FT / FW; ++w)
-        if (argmax_before(s_v[w], s_i[w], v, i)) {
-            v = s_v[w];
-            i = s_i[w];
-        }
-}
-
-__device__ int wg_min(int v, int* s_i) {
-    for (int o = FW / 2; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    const int lane = threadIdx.x & (FW - 1), wave = threadIdx.x / FW;
-    __syncthreads();
-    if (lane == 0) s_i[wave] = v;
-    __syncthreads();
-    v = s_i[0];
-    for (int w = 1; w < FT / FW; ++w) v = min(v, s_i[w]);
-    return v;
-}
 
 struct FindArgs {
     const float* a;
@@ -128,22 +87,14 @@ __global__ void __launch_bounds__(FT) k_find_lags(FindArgs A) {
     for (int t = threadIdx.x; t < lb; t += FT) sb[t] = gb[(int64_t)t * A.es];
     __syncthreads();
     const int n = la + lb - 1;
-    float bv = 0.f;
-    int bi = -1;
     bool bad = false;
-    for (int j = threadIdx.x; j < n; j += FT) {
-        const float v = (float)ofp::cc_dot(sa, la, sb, lb, j - (lb - 1));
+    const int bi = ofppair::lag_search(sa, la, sb, lb, s_v, s_i, [&](int j, float v) {
         if (A.top_n > 0) {
             cc[j] = v;
             flag[j] = 0;
         }
         bad |= !isfinite(v);
-        if (argmax_before(v, j, bv, bi)) {
-            bv = v;
-            bi = j;
-        }
-    }
-    wg_argmax(bv, bi, s_v, s_i);
+    });
     if (threadIdx.x == 0) {
         A.lag[row] = bi - (la - 1);
         if (A.top_n <= 0 && A.n_peaks) A.n_peaks[row] = 0;
@@ -344,20 +295,6 @@ __global__ void k_paired_windows(WinArgs A) {
     }
 }
 
-// numpy's cartesian_to_polar(x, y, radius): (sqrt(x^2 + y^2) / radius, degrees(arctan2(y, x) % 2 pi))
-__device__ __forceinline__ void polar(double x, double y, double radius, double* out) {
-    const double two_pi = 2.0 * M_PI;
-    double a = atan2(y, x);
-    double m = fmod(a, two_pi);  // npy_divmod: the remainder takes the divisor's sign
-    if (m != 0.0) {
-        if (m < 0.0) m += two_pi;
-    } else {
-        m = copysign(0.0, two_pi);
-    }
-    out[0] = sqrt(x * x + y * y) / radius;
-    out[1] = m * (180.0 / M_PI);
-}
-
 struct VoteArgs {
     const int32_t* starts;
     const int32_t* sorted;
@@ -373,26 +310,10 @@ struct VoteArgs {
     int32_t* status;
 };
 
-// The run of sorted cells of map m whose value v satisfies lag - tol < v < lag + tol.
-__device__ __forceinline__ void lag_run(const VoteArgs& A, int m, int lag, int64_t cells, int64_t* p0, int64_t* p1) {
-    const double lo = floor((double)lag - A.tol) + 1.0 - A.vmin[m];
-    const double hi = ceil((double)lag + A.tol) - 1.0 - A.vmin[m];
-    const int b0 = (int)fmin(fmax(lo, 0.0), (double)A.nb);  // clamped before the conversion
-    const int b1 = (int)fmax(fmin(hi, (double)(A.nb - 1)), -1.0);
-    const int32_t* st = A.starts + (int64_t)m * (A.nb + 1);
-    if (b0 > b1) {
-        *p0 = *p1 = 0;
-        return;
-    }
-    *p0 = (int64_t)m * cells + st[b0];
-    *p1 = (int64_t)m * cells + st[b1 + 1];
-}
-
 __global__ void __launch_bounds__(FT) k_paired_vote(VoteArgs A) {
     extern __shared__ unsigned int bits[];
     __shared__ int s_i[FT / FW];
     const int64_t h = blockIdx.x;
-    const int64_t cells = (int64_t)A.side * A.side;
     const int st = A.status_in[h];
     if (st != OFP_PAIRED_OK) {
         if (threadIdx.x == 0) {
@@ -405,37 +326,10 @@ __global__ void __launch_bounds__(FT) k_paired_vote(VoteArgs A) {
         }
         return;
     }
-    const int i = A.first[h];
-    int64_t a0, a1, b0 = 0, b1 = 0;
-    lag_run(A, 2 * i, A.lags[2 * h], cells, &a0, &a1);
-    if (A.S > 2) lag_run(A, 2 * i + 1, A.lags[2 * h + 1], cells, &b0, &b1);
-    int best = INT_MAX;
-    if (a0 < a1 && b0 < b1) {  // two votes possible: the smallest cell in both runs
-        const int words = (int)cdiv(cells, 32);
-        for (int w = threadIdx.x; w < words; w += FT) bits[w] = 0u;
-        __syncthreads();
-        for (int64_t p = b0 + threadIdx.x; p < b1; p += FT) {
-            const int c = A.sorted[p];
-            atomicOr(&bits[c >> 5], 1u << (c & 31));
-        }
-        __syncthreads();
-        int mine = INT_MAX;
-        for (int64_t p = a0 + threadIdx.x; p < a1; p += FT) {
-            const int c = A.sorted[p];
-            if (bits[c >> 5] & (1u << (c & 31))) mine = min(mine, c);
-        }
-        best = wg_min(mine, s_i);
-    }
-    if (best == INT_MAX) {  // at most one vote: the smallest cell of either run (cell 0 when both are empty)
-        int mine = INT_MAX;
-        for (int64_t p = a0 + threadIdx.x; p < a1; p += FT) mine = min(mine, A.sorted[p]);
-        for (int64_t p = b0 + threadIdx.x; p < b1; p += FT) mine = min(mine, A.sorted[p]);
-        best = wg_min(mine, s_i);
-        if (best == INT_MAX) best = 0;
-    }
+    const int best = ofppair::vote_cell(A, A.first[h], A.lags[2 * h], A.lags[2 * h + 1], bits, s_i);
     if (threadIdx.x == 0) {
-        const double half = (A.side - 1) / 2.0;
-        const double x = (double)(best % A.side) - half, y = half - (double)(best / A.side);
+        double x, y;
+        ofppair::cell_xy(best, A.side, &x, &y);
         A.status[h] = OFP_PAIRED_OK;
         A.cell[h] = best;
         A.xy[2 * h] = x;
@@ -514,9 +408,139 @@ __global__ void k_intensity(const double* __restrict__ mics, int r, double refl,
     out[m * cells + k] = (float)(10.0 * log10(a));
 }
 
+// The voting locator's stage (ofppair::step) over a resident recording and a given onset list: a loop over the hops,
+// by one workgroup, as k_regress_stream runs the window regressor's.
+struct CcReplayArgs {
+    ofppair::Cfg g;
+    const float* audio;
+    int64_t n_rows, K;
+    const int32_t* channel;
+    const int64_t* onset;
+    int32_t *hit, *status, *first, *lags, *cell, *pending, *flags;
+    int64_t *onset_out, *row;
+    double *xy, *rphi;
+};
+
+__global__ void __launch_bounds__(FT) k_locate_cc_stream(CcReplayArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int S = a.g.S, B = a.g.B;
+    const int64_t H = a.n_rows / B;
+    ofp_regress_state* st = a.g.state;
+    int64_t next = 0;  // first onset not yet fed (the same on every thread)
+    auto sample = [&](int64_t t, int col) -> float { return t < 0 ? 0.0f : a.audio[t * S + col]; };
+    for (int64_t h = 1; h <= H; ++h) {
+        const int64_t end = h * (int64_t)B;
+        int n = 0;
+        while (next + n < a.K && a.onset[next + n] < end) ++n;
+        const int64_t base = next;
+        auto rec = [&](int i, int& ch, int64_t& s) {
+            ch = a.channel[base + i];
+            s = a.onset[base + i];
+        };
+        int ev = 0;
+        const bool busy = !ofpreg::idle(a.g, h, n, st->wake);
+        __syncthreads();  // every thread has read `wake` before thread 0 of a busy hop stores the next one
+        if (busy) {
+            const int64_t k = h - 1;
+            const ofppair::Out o{a.onset_out + k, a.row + k * S, a.first + k, a.status + k, a.lags + 2 * k,
+                                 a.cell + k,      a.xy + 2 * k,  a.rphi + 2 * k, a.flags};
+            ev = ofppair::step(a.g, h, n, rec, sample, smem, o);
+        }
+        __syncthreads();  // the state thread 0 left, and the step's shared words, before the next hop reads them
+        if (threadIdx.x == 0) {
+            a.hit[h - 1] = ev;
+            a.pending[h - 1] = st->len + ev;  // (the FIFO is longest after the hop's closes, before its evaluation)
+        }
+        next += n;
+    }
+    if (threadIdx.x == 0) *a.flags = st->flags;
+}
+
 }  // namespace
 
+int ofp_paired_cfg(const ofp_hop_paired* p, const char* who, ofppair::Cfg* out) {
+    OFP_REQUIRE(p && out, "%s: NULL argument", who);
+    OFP_REQUIRE(p->d_starts && p->d_sorted && p->d_vmin, "%s: NULL index table", who);
+    OFP_REQUIRE(p->S >= 2 && p->S <= OFP_REG_MAX_SIGNALS, "%s: %d sensors (2..%d supported)", who, p->S, OFP_REG_MAX_SIGNALS);
+    OFP_REQUIRE(p->side >= 1 && (int64_t)p->side * p->side <= V_MAXCELLS, "%s: grid side %d (at most %lld cells)", who,
+                p->side, (long long)V_MAXCELLS);
+    OFP_REQUIRE(p->n_buckets >= 1 && p->n_buckets <= V_MAXBUCKETS, "%s: lag range of %d values", who, p->n_buckets);
+    OFP_REQUIRE(p->tol >= 0.0 && p->radius > 0.0, "%s: tol must be >= 0 and radius > 0", who);
+    OFP_REQUIRE(p->left >= 0 && p->right >= 1 && (int64_t)p->left + p->right <= ofppair::MAX_WINDOW,
+                "%s: left %d, right %d (left >= 0, right >= 1, a window of at most %d samples)", who, p->left, p->right,
+                ofppair::MAX_WINDOW);
+    OFP_REQUIRE(p->max_distance >= 0 && p->min_channels >= 1 && p->min_channels <= p->S,
+                "%s: need max_distance >= 0 and 1 <= min_channels <= %d", who, p->S);
+    const size_t lds = ofppair::lds_bytes(p->left + p->right, p->side);
+    OFP_REQUIRE(lds <= ofpreg::LDS_SWITCH, "%s: the stage needs %zu bytes of LDS (vote bitmap of a %d x %d grid and a %d-sample "
+                "window), %zu allowed", who, lds, p->side, p->side, p->left + p->right, ofpreg::LDS_SWITCH);
+    ofppair::Cfg g;
+    std::memset(&g, 0, sizeof(g));
+    g.starts = p->d_starts;
+    g.sorted = p->d_sorted;
+    g.vmin = p->d_vmin;
+    g.nb = p->n_buckets;
+    g.S = p->S;
+    g.side = p->side;
+    g.tol = p->tol;
+    g.radius = p->radius;
+    g.F = p->left + p->right;
+    g.pre = p->left;
+    g.D = p->max_distance;
+    g.min_channels = p->min_channels;
+    *out = g;
+    return OFP_OK;
+}
+
 extern "C" {
+
+int ofp_locate_cc_stream(const ofp_hop_paired* p, const float* d_audio, int64_t n_rows, int32_t block_size,
+                         const int32_t* d_channel, const int64_t* d_onset, int64_t K, int32_t* d_hit, int32_t* d_status,
+                         int64_t* d_onset_out, int32_t* d_first, int64_t* d_row, int32_t* d_lags, int32_t* d_cell,
+                         double* d_xy, double* d_rphi, int32_t* d_pending, int32_t* d_flags, void* stream) {
+    CcReplayArgs a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = ofp_paired_cfg(p, "ofp_locate_cc_stream", &a.g)) return rc;
+    OFP_REQUIRE(d_audio && d_hit && d_status && d_onset_out && d_first && d_row && d_lags && d_cell && d_xy && d_rphi &&
+                    d_pending && d_flags && (K == 0 || (d_channel && d_onset)),
+                "ofp_locate_cc_stream: NULL argument");
+    OFP_REQUIRE(block_size >= 1 && n_rows >= 0 && K >= 0, "ofp_locate_cc_stream: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    ofp_regress_state* d_state = nullptr;
+    OFP_HIP(hipMalloc(&d_state, sizeof(ofp_regress_state)));
+    auto run = [&]() -> int {
+        OFP_HIP(hipMemsetAsync(d_state, 0, sizeof(ofp_regress_state), st));
+        OFP_HIP(hipMemsetAsync(d_flags, 0, sizeof(int32_t), st));
+        a.g.B = block_size;
+        a.g.state = d_state;
+        a.audio = d_audio;
+        a.n_rows = n_rows;
+        a.K = K;
+        a.channel = d_channel;
+        a.onset = d_onset;
+        a.hit = d_hit;
+        a.status = d_status;
+        a.first = d_first;
+        a.lags = d_lags;
+        a.cell = d_cell;
+        a.pending = d_pending;
+        a.flags = d_flags;
+        a.onset_out = d_onset_out;
+        a.row = d_row;
+        a.xy = d_xy;
+        a.rphi = d_rphi;
+        const size_t lds = ofppair::lds_bytes(a.g.F, a.g.side);
+        static ofp::LdsAttrCache attr;
+        if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_locate_cc_stream), lds, attr)) return rc;
+        hipLaunchKernelGGL(k_locate_cc_stream, dim3(1), dim3(FT), lds, st, a);
+        OFP_LAUNCH_CHECK("k_locate_cc_stream");
+        OFP_HIP(hipStreamSynchronize(st));  // (the state is freed below)
+        return OFP_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_state);
+    return rc;
+}
 
 int ofp_find_lags(const float* d_a, const float* d_b, int64_t n_rows, int64_t a_stride, int64_t b_stride,
                   int32_t elem_stride, const int64_t* d_a_off, const int64_t* d_b_off, int32_t len_a, int32_t len_b,

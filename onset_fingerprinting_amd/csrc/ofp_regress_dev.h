@@ -95,9 +95,82 @@ __device__ __forceinline__ void evaluate(const Cfg& g, int64_t start, Sample sam
 
 // A hop with nothing to feed, close or evaluate: one comparison with the word the last busy hop left (`wake`: the
 // first hop end at which the open group times out or the FIFO's head is due).  The caller loads st->wake, as early
-// as it likes.
-__device__ __forceinline__ bool idle(const Cfg& g, int64_t h, int n, int64_t wake) {
+// as it likes.  G: a stage's configuration with B, F, pre, D, min_channels and state (this stage's Cfg, or the voting
+// locator's, ofp_paired_dev.h).
+template <class G>
+__device__ __forceinline__ bool idle(const G& g, int64_t h, int n, int64_t wake) {
     return n <= 0 && h * (int64_t)g.B < wake;
+}
+
+// The grouping state machine and the FIFO for one hop, by ONE thread: the hop's n onsets are fed, groups close, and
+// the head is taken off the FIFO if its window is complete.  Returns the head's slot (its q_start and q_row stay in
+// the state until a later group takes the slot), or -1 when nothing is due; then *o_start and o_row [C] are written.
+// *o_flags always.  h, n, rec as `step` takes them.
+template <class G, class Rec>
+__device__ __forceinline__ int queue_step(const G& g, int C, int64_t h, int n, Rec rec, int64_t* o_start, int64_t* o_row,
+                                          int32_t* o_flags) {
+    ofp_regress_state* st = g.state;
+    const int64_t end = h * (int64_t)g.B;
+    int open = st->open, head = st->head, len = st->len, flags = st->flags;
+    int64_t anchor = st->anchor;
+    auto close = [&] {
+        int present = 0;
+        int64_t first = -1;
+        for (int c = 0; c < C; ++c) {
+            const int64_t v = st->row[c];
+            if (v >= 0) {
+                ++present;
+                if (first < 0 || v < first) first = v;
+            }
+        }
+        if (present >= g.min_channels) {
+            if (len >= OFP_REG_QUEUE) {
+                flags |= OFP_REGF_QUEUE;
+            } else {
+                const int q = (head + len) % OFP_REG_QUEUE;
+                st->q_start[q] = first - g.pre;
+                for (int c = 0; c < C; ++c) st->q_row[q][c] = st->row[c];
+                ++len;
+            }
+        }
+        open = 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        int ch;
+        int64_t s;
+        rec(i, ch, s);
+        if (ch < 0 || ch >= C || s < 0) {
+            flags |= OFP_REGF_BAD_ONSET;
+            continue;
+        }
+        if (open && s - anchor > g.D) close();
+        if (!open) {
+            open = 1;
+            anchor = s;
+            for (int c = 0; c < C; ++c) st->row[c] = -1;
+        }
+        st->row[ch] = s;
+    }
+    if (open && end > anchor + g.D) close();
+    int slot = -1;
+    if (len > 0 && end >= st->q_start[head] + g.F) {
+        slot = head;
+        *o_start = st->q_start[head];
+        for (int c = 0; c < C; ++c) o_row[c] = st->q_row[head][c];
+        head = (head + 1) % OFP_REG_QUEUE;
+        --len;
+    }
+    int64_t wake = INT64_MAX;
+    if (open) wake = anchor + g.D + 1;
+    if (len > 0) wake = min(wake, (int64_t)(st->q_start[head] + g.F));
+    st->open = open;
+    st->anchor = anchor;
+    st->wake = wake;
+    st->head = head;
+    st->len = len;
+    st->flags = flags;
+    *o_flags = flags;
+    return slot;
 }
 
 // One hop of the stage that is not idle.  h: hops pushed including this one; rec(i) -> (channel, absolute sample) of
@@ -109,71 +182,10 @@ __device__ __forceinline__ int step(const Cfg& g, int64_t h, int n, Rec rec, Sam
                                     int64_t* o_start, int64_t* o_row, float* o_y, int32_t* o_flags) {
     __shared__ int s_eval;
     __shared__ int64_t s_start;
-    ofp_regress_state* st = g.state;
-    const int64_t end = h * (int64_t)g.B;
-    const int C = g.plan.C;
     if (threadIdx.x == 0) {
-        int open = st->open, head = st->head, len = st->len, flags = st->flags;
-        int64_t anchor = st->anchor;
-        auto close = [&] {
-            int present = 0;
-            int64_t first = -1;
-            for (int c = 0; c < C; ++c) {
-                const int64_t v = st->row[c];
-                if (v >= 0) {
-                    ++present;
-                    if (first < 0 || v < first) first = v;
-                }
-            }
-            if (present >= g.min_channels) {
-                if (len >= OFP_REG_QUEUE) {
-                    flags |= OFP_REGF_QUEUE;
-                } else {
-                    const int q = (head + len) % OFP_REG_QUEUE;
-                    st->q_start[q] = first - g.pre;
-                    for (int c = 0; c < C; ++c) st->q_row[q][c] = st->row[c];
-                    ++len;
-                }
-            }
-            open = 0;
-        };
-        for (int i = 0; i < n; ++i) {
-            int ch;
-            int64_t s;
-            rec(i, ch, s);
-            if (ch < 0 || ch >= C || s < 0) {
-                flags |= OFP_REGF_BAD_ONSET;
-                continue;
-            }
-            if (open && s - anchor > g.D) close();
-            if (!open) {
-                open = 1;
-                anchor = s;
-                for (int c = 0; c < C; ++c) st->row[c] = -1;
-            }
-            st->row[ch] = s;
-        }
-        if (open && end > anchor + g.D) close();
-        int eval = 0;
-        if (len > 0 && end >= st->q_start[head] + g.F) {
-            eval = 1;
-            s_start = st->q_start[head];
-            *o_start = s_start;
-            for (int c = 0; c < C; ++c) o_row[c] = st->q_row[head][c];
-            head = (head + 1) % OFP_REG_QUEUE;
-            --len;
-        }
-        int64_t wake = INT64_MAX;
-        if (open) wake = anchor + g.D + 1;
-        if (len > 0) wake = min(wake, (int64_t)(st->q_start[head] + g.F));
-        st->open = open;
-        st->anchor = anchor;
-        st->wake = wake;
-        st->head = head;
-        st->len = len;
-        st->flags = flags;
-        *o_flags = flags;
-        s_eval = eval;
+        const int slot = queue_step(g, g.plan.C, h, n, rec, o_start, o_row, o_flags);
+        s_eval = slot >= 0;
+        if (slot >= 0) s_start = g.state->q_start[slot];
     }
     __syncthreads();
     const int eval = s_eval;

@@ -934,6 +934,91 @@ class MultilateratePaired:
         return rphi, cell, status
 
 
+    def check_stage(self, what, n_signals, tol, left, right, max_distance, min_channels):
+        """The argument errors of the stream stage ("The voting locator in the hop") that need no GPU:
+        host attributes only."""
+        S = len(self.sensor_locs)
+        if S != n_signals:
+            raise ValueError(f"{what}: the locator has {S} sensors, the stream has {n_signals} signals")
+        if S > _lib.REG_MAX_SIGNALS:
+            raise ValueError(f"{what}: {S} sensors; the stage's grouping state holds {_lib.REG_MAX_SIGNALS}")
+        if float(tol) < 0:
+            raise ValueError(f"{what}: tol {tol} < 0")
+        if int(left) < 0:
+            raise ValueError(f"{what}: left {left} is negative")
+        if int(right) < 1:
+            raise ValueError(f"{what}: right {right} < 1")
+        if int(left) + int(right) > _lib.PAIR_MAX_WINDOW:
+            raise ValueError(f"{what}: a window of left + right = {int(left) + int(right)} samples; the stage's window "
+                             f"cap is {_lib.PAIR_MAX_WINDOW}")
+        lds = _lib.paired_lds_bytes(int(left) + int(right), self.side)
+        if lds > _lib.PAIR_LDS_ENVELOPE:
+            raise ValueError(f"{what}: the stage needs {lds} bytes of LDS (the vote bitmap of the {self.side} x {self.side} "
+                             f"grid and a {int(left) + int(right)}-sample window), outside its envelope of "
+                             f"{_lib.PAIR_LDS_ENVELOPE}; there is no global-memory fallback")
+        if max_distance < 0:
+            raise ValueError(f"{what}: max_distance {max_distance} is negative")
+        if not 1 <= min_channels <= n_signals:
+            raise ValueError(f"{what}: min_channels {min_channels} outside 1..{n_signals}")
+
+    def paired_struct(self, tol=2, left=0, right=256, max_distance=1000, min_channels=3):
+        """The ``ofp_hop_paired`` of this locator's index and the stage's parameters.  It points into this object's
+        device tables, which must outlive whatever runs with it (a session keeps a reference to the locator)."""
+        p = _lib.HopPaired()
+        p.d_starts, p.d_sorted, p.d_vmin = self.starts.data_ptr(), self.sorted_cells.data_ptr(), self.vmin.data_ptr()
+        p.n_buckets, p.S, p.side = self.n_buckets, len(self.sensor_locs), self.side
+        p.radius, p.tol = float(self.radius), float(tol)
+        p.left, p.right, p.max_distance, p.min_channels = int(left), int(right), int(max_distance), int(min_channels)
+        return p
+
+    def locate_cc_stream_device(self, audio, channels, onsets, block_size, tol=2, left=0, right=256, max_distance=1000,
+                                min_channels=3):
+        """What a ``HopSession(locator=self)`` would have answered on a finished recording, in ONE launch
+        (``ofp_locate_cc_stream``): the stage's grouping state machine, lag search and vote over ``audio`` [N, C]
+        float32 (numpy or a CUDA tensor, channel k is sensor k) and the onset list (``channels`` / ``onsets`` [K],
+        absolute samples; fed sorted by sample, stable), hop by hop (N // block_size hops).  Returns a dict of per-hop
+        arrays: ``hit`` bool [H], ``status`` int32 [H] (PAIRED_OK or PAIRED_NEG_WINDOW), ``onset`` int64 [H], ``first``
+        int32 [H], ``group`` int64 [H, C], ``lags`` int32 [H, 2], ``cell`` int32 [H], ``rphi`` float64 [H, 2] (NaN
+        where there is no hit or a status) and ``pending`` int32 [H], the FIFO's length before the hop's evaluation.
+        The ring and queue conditions of a session do not apply; a queue overflow or a refused onset raises
+        OnsetFPError."""
+        from . import realtime
+        what = "locate_cc_stream_device"
+        ad = audio if torch.is_tensor(audio) else torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+        if ad.dim() != 2:
+            raise ValueError(f"{what}: audio must be [N, C], got {tuple(ad.shape)}")
+        C = int(ad.shape[1])
+        self.check_stage(what, C, tol, left, right, max_distance, min_channels)
+        onsets = np.asarray(onsets, dtype=np.int64).reshape(-1)
+        channels = np.asarray(channels, dtype=np.int32).reshape(-1)
+        if len(onsets) != len(channels):
+            raise ValueError(f"{what}: {len(channels)} channels for {len(onsets)} onsets")
+        order = np.argsort(onsets, kind="stable")
+        onsets, channels = onsets[order], channels[order]
+        dev = self.device
+        ad = ad.to(dev, torch.float32).contiguous()
+        H = int(ad.shape[0]) // block_size
+        with torch.cuda.device(dev):
+            p = self.paired_struct(tol, left, right, max_distance, min_channels)
+            ch_d, on_d = torch.from_numpy(channels).to(dev), torch.from_numpy(onsets).to(dev)
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            hit, status, first, cell, pending = (z(H, torch.int32) for _ in range(5))
+            onset, rows, lags = z(H, torch.int64), z((H, C), torch.int64), z((H, 2), torch.int32)
+            xy = torch.full((H, 2), float("nan"), dtype=torch.float64, device=dev)
+            rphi = torch.full((H, 2), float("nan"), dtype=torch.float64, device=dev)
+            flags = z(1, torch.int32)
+            check(_lib.lib().ofp_locate_cc_stream(ctypes.byref(p), ad.data_ptr(), ad.shape[0], block_size,
+                                                  ch_d.data_ptr(), on_d.data_ptr(), len(onsets), hit.data_ptr(),
+                                                  status.data_ptr(), onset.data_ptr(), first.data_ptr(),
+                                                  rows.data_ptr(), lags.data_ptr(), cell.data_ptr(), xy.data_ptr(),
+                                                  rphi.data_ptr(), pending.data_ptr(), flags.data_ptr(), _stream(dev)),
+                  "ofp_locate_cc_stream")
+        realtime.check_regress_flags(int(flags.item()), what)
+        return dict(hit=hit.cpu().numpy().astype(bool), status=status.cpu().numpy(), onset=onset.cpu().numpy(),
+                    first=first.cpu().numpy(), group=rows.cpu().numpy(), lags=lags.cpu().numpy(),
+                    cell=cell.cpu().numpy(), rphi=rphi.cpu().numpy(), pending=pending.cpu().numpy())
+
+
 def _clips(x, what):
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (2, 3)):
         raise ValueError(f"{what}: x must be a float32 CUDA tensor [N, C] or [n_clips, N, C]")

@@ -174,6 +174,15 @@ class HopSession:
     no shift; at most one group per hop, after the locator stage).  The result dict gains ``hit``: None, or a dict
     with ``position`` float32 [n_out], ``group`` int64 [n_signals] (the group's row, -1 where a channel is missing)
     and ``start`` (the window's first sample).  INTEGRATION.md, "The window regressor in the hop", has the details.
+
+    ``locator`` may finally be a ``multilateration.MultilateratePaired`` (``ofp_hop_set_locator_paired``), with
+    ``tol``, ``left``, ``right`` (``locate_cc``'s) and ``max_distance``, ``min_channels`` (the grouping's): the hop's
+    graph then groups the stream's onsets as for a regressor and runs ``locate_cc`` on the group whose window
+    ``x[onset - left : onset + right]`` the hop completes.  The result dict gains ``location`` (None or the polar tuple
+    ``locate_cc`` returns) and ``cc_hit``: None, or a dict with ``status`` (PAIRED_OK, or PAIRED_NEG_WINDOW for a
+    window that starts below sample 0: no location), ``onset``, ``first``, ``group`` int64 [n_signals], ``lags`` int32
+    [2] and ``cell``.  The locator's ``res`` is not touched; a regressor cannot be attached beside it.  The session
+    keeps a reference to the locator, whose device tables it reads.  INTEGRATION.md, "The voting locator in the hop".
     """
 
     def __init__(self, n_signals, block_size=128, sr=96000, n_fft=2048, n_mels=40, classifier=None,
@@ -181,8 +190,34 @@ class HopSession:
                  fast_ar=(3.0, 383.0), slow_ar=(2205.0, 2205.0), on_threshold=0.5, off_threshold=0.1,
                  cooldown=1323, backtrack=False, backtrack_buffer_size=None, backtrack_smooth_size=5,
                  onset_strength=None, locator=None, locate_with_audio=True, regressor=None, frame_length=None,
-                 pre_samples=0, max_distance=1000, min_channels=3):
+                 pre_samples=0, max_distance=1000, min_channels=3, tol=2, left=0, right=256):
         ring_rows = max(int(round(ring_seconds * sr)), n_fft, block_size)  # realtime/config.py:45,59
+        self._paired = False
+        if locator is not None:
+            from . import multilateration as ml
+            self._paired = isinstance(locator, ml.MultilateratePaired)
+        if self._paired:  # argument errors before any GPU call, from the locator's host attributes
+            what = "HopSession"
+            if regressor is not None:
+                raise ValueError("HopSession: locator=MultilateratePaired and regressor= are both grouping stages; one "
+                                 "session runs one of them")
+            if backtrack:
+                raise ValueError("HopSession: a locator needs backtrack=False (a backtracked onset may lie behind the "
+                                 "current hop)")
+            locator.check_stage(what, n_signals, tol, left, right, max_distance, min_channels)
+            want = device.index or 0 if isinstance(device, torch.device) else int(device)
+            if (locator.device.index or 0) != want:
+                raise ValueError(f"HopSession: the locator lives on {locator.device}, the session on device {want}")
+            if max_distance < block_size:
+                raise ValueError(f"HopSession: max_distance {max_distance} is shorter than one hop ({block_size} "
+                                 "samples): two groups could close in one hop")
+            bounds = (block_size, int(left) + int(right), int(left), max_distance)  # the regress stage's, F and pre
+            if regress_pending_bound(*bounds) > _lib.REG_QUEUE:
+                raise ValueError(f"HopSession: up to {regress_pending_bound(*bounds)} groups can be pending with these "
+                                 f"parameters, the device queue holds {_lib.REG_QUEUE}")
+            if ring_rows < regress_ring_rows(*bounds):
+                raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the oldest row a pending "
+                                 f"window can still need plus one hop ({regress_ring_rows(*bounds)} rows)")
         if regressor is not None:  # argument errors before any GPU call
             what = "HopSession"
             if backtrack:
@@ -200,8 +235,7 @@ class HopSession:
             if ring_rows < regress_ring_rows(*bounds):
                 raise ValueError(f"HopSession: the ring of {ring_rows} rows is too short for the oldest row a pending "
                                  f"window can still need plus one hop ({regress_ring_rows(*bounds)} rows)")
-        if locator is not None:  # argument errors before any GPU call
-            from . import multilateration as ml
+        if locator is not None and not self._paired:  # argument errors before any GPU call
             if len(locator.sensor_locs) != n_signals:
                 raise ValueError(f"HopSession: the locator has {len(locator.sensor_locs)} sensors, the session "
                                  f"{n_signals} signals")
@@ -273,7 +307,23 @@ class HopSession:
         self.current_index = 0  # audio.py:120
         self._group = None  # the HopSessionGroup that carries this session's hops, if any
         self.locator = locator
-        if locator is not None:
+        if self._paired:
+            try:
+                p = locator.paired_struct(tol, left, right, max_distance, min_channels)  # (points into the locator's
+                with torch.cuda.device(self.device):                                     #  tables: self.locator)
+                    check(L.ofp_hop_set_locator_paired(self.handle, ctypes.byref(p)), "ofp_hop_set_locator_paired")
+            except Exception:
+                self.close()
+                raise
+            self.tol, self.left, self.right = tol, left, right
+            self.max_distance, self.min_channels = max_distance, min_channels
+            self._cc_i = [ctypes.c_int32() for _ in range(5)]  # hit, status, first, cell, flags
+            self._cc_onset = ctypes.c_int64()
+            self._cc_row = np.zeros(n_signals, dtype=np.int64)
+            self._cc_lags = np.zeros(2, dtype=np.int32)
+            self._cc_xy = np.zeros(2, dtype=np.float64)
+            self._cc_rphi = np.zeros(2, dtype=np.float64)
+        elif locator is not None:
             try:
                 if self._planar:
                     entry, loc = "ofp_hop_set_locator_2d", locator.locator_struct()
@@ -318,6 +368,22 @@ class HopSession:
                       if status.value == 1 else None)
         return out
 
+    def _cc_hit(self, out):
+        from . import multilateration as ml
+        hit, status, first, cell, flags = self._cc_i
+        check(self._L.ofp_hop_collect_cc_hit(self.handle, ctypes.byref(hit), ctypes.byref(status),
+                                             ctypes.byref(self._cc_onset), ctypes.byref(first), self._cc_row.ctypes.data,
+                                             self._cc_lags.ctypes.data, ctypes.byref(cell), self._cc_xy.ctypes.data,
+                                             self._cc_rphi.ctypes.data, ctypes.byref(flags)), "ofp_hop_collect_cc_hit")
+        check_regress_flags(flags.value, "HopSession")
+        out["location"] = out["cc_hit"] = None
+        if hit.value == 1:
+            out["cc_hit"] = dict(status=int(status.value), onset=int(self._cc_onset.value), first=int(first.value),
+                                 group=self._cc_row.copy(), lags=self._cc_lags.copy(), cell=int(cell.value))
+            if status.value == ml.PAIRED_OK:  # cartesian_to_polar of the cell, as locate_cc returns it
+                out["location"] = (np.float64(self._cc_rphi[0]), np.float64(self._cc_rphi[1]))
+        return out
+
     def _location(self, out):
         from . import multilateration as ml
         status, n, fed, dropped, flags = self._loc_i
@@ -339,6 +405,8 @@ class HopSession:
         from . import multilateration as ml
         if self.locator is None:
             raise ValueError("HopSession.ongoing: the session has no locator")
+        if self._paired:
+            raise ValueError("HopSession.ongoing: the voting locator keeps groups, not the trilaterating state")
         st = _lib.LocateState()
         check(self._L.ofp_hop_locator_state(self.handle, ctypes.byref(st)), "ofp_hop_locator_state")
         return ml.ongoing_list(st)
@@ -398,6 +466,8 @@ class HopSession:
             self._hit(out)
         if self.locator is None:
             return out
+        if self._paired:
+            return self._cc_hit(out)
         if k == 0:  # the stage did not run: nothing to read
             out.update(location=None, located_group=None, fed=0, dropped=0)
             return out
@@ -429,7 +499,8 @@ class HopSessionGroup:
     hops arrive on the same clock.
 
     ``sessions``: ``HopSession`` objects on one device with the same ``n_fft`` and channel count that agree on
-    having a locator, on having a regressor (its architecture may differ) and on having the onset strength; everything else (block size, ``sr``, detector arguments, ring
+    having a locator, on having a voting locator (``MultilateratePaired``; locators, ``tol``, ``left`` and ``right`` may
+    differ), on having a regressor (its architecture may differ) and on having the onset strength; everything else (block size, ``sr``, detector arguments, ring
     length, ``want_rel``, ``n_mels``, classifier, the locator's geometry and model) may differ.  They may be warmed
     up or mid-stream.  Each member keeps its own state and runs the device code it runs alone, so every output is
     bit for bit the stand-alone session's.  While grouped a member still takes ``reset()``,
@@ -450,6 +521,9 @@ class HopSessionGroup:
                 raise ValueError(f"HopSessionGroup: member {i} is listed twice")
             if s._group is not None:
                 raise ValueError(f"HopSessionGroup: member {i} already belongs to a group")
+            if s._paired != sessions[0]._paired:  # all or none: the group's one kernel runs one kind of stage
+                raise ValueError(f"HopSessionGroup: members 0 and {i} differ in having a voting locator "
+                                 "(MultilateratePaired)")
         self._L = _lib.lib()
         self.handle = None
         n = len(sessions)
