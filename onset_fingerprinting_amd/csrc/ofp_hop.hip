@@ -633,33 +633,42 @@ struct FusedCfg {
     static constexpr int WGS = HopCfg<F>::T <= 64 ? 256 : HopCfg<F>::T;
 };
 
+// Which hit stages the detector's workgroup runs after the detector: a compile-time kind.  Five are legal -- none, LOC,
+// REG, LOC | REG and PAIR (the voting locator is a session's only stage) -- and HitArgs<K> exists for those alone: the
+// stage argument structs that K names, and nothing else (a session without a stage passes no stage arguments).
+enum : int { HIT_NONE = 0, HIT_LOC = 1, HIT_REG = 2, HIT_PAIR = 4 };
+template <int K> struct HitArgs;
+template <> struct HitArgs<HIT_NONE> {};
+template <> struct HitArgs<HIT_LOC> { HopLocArgs la; };
+template <> struct HitArgs<HIT_REG> { HopRegArgs ra; };
+template <> struct HitArgs<HIT_LOC | HIT_REG> { HopLocArgs la; HopRegArgs ra; };
+template <> struct HitArgs<HIT_PAIR> { HopPairArgs pa; };
+
 // Everything a workgroup of the fused hop does, from the read of the hop counter to the completion word; the
-// arguments are the caller's (kernel arguments or a group's device arrays), never copies.
-// LOC: the instantiation of a session with a locator; without one the kernel is the one it always was.
-// REG: the instantiation of a session with a regressor (ra is read only then); the same holds.
-// PAIR: the instantiation of a session with the voting locator (pa is read only then; never with LOC or REG).
-template <int F, bool LOC, bool REG, bool PAIR = false>
-__device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream::StreamArgs& sa, const HopLocArgs& la,
-                                               const HopRegArgs* ra, unsigned char* smem,
-                                               const HopPairArgs* pa = nullptr) {
-    static_assert(!PAIR || (!LOC && !REG), "the voting locator is a session's only stage");
+// arguments are the caller's (kernel arguments or a group's device arrays), never copies.  K: the session's hit kind;
+// without a stage the detector's workgroup is the one it always was.
+template <int F, int K>
+__device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream::StreamArgs& sa, const HitArgs<K>& ha,
+                                               unsigned char* smem) {
+    static_assert(!(K & HIT_PAIR) || K == HIT_PAIR, "the voting locator is a session's only stage");
     const int64_t done = a.ctl[0];  // hops completed before this one
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) *a.hop_index = done;
-        if constexpr (LOC || REG || PAIR) {
+        if constexpr (K != HIT_NONE) {
             int64_t wake = 0;
-            if constexpr (REG) wake = ra->g.state->wake;  // (in flight while the detector runs)
-            if constexpr (PAIR) wake = pa->g.state->wake;
+            if constexpr (K & HIT_REG) wake = ha.ra.g.state->wake;  // (in flight while the detector runs)
+            if constexpr (K & HIT_PAIR) wake = ha.pa.g.state->wake;
             const long long n_on = ofpstream::stream_par_blocks<true>(sa, reinterpret_cast<float*>(smem));
-            if constexpr (LOC)
-                if (n_on > 0) hop_locate_stage(a, la, done + 1, (int)(n_on < a.C ? n_on : a.C), sa.mirror, smem);
-            if constexpr (REG) {
+            const int n = (int)(n_on < a.C ? n_on : a.C);
+            if constexpr (K & HIT_LOC)
+                if (n_on > 0) hop_locate_stage(a, ha.la, done + 1, n, sa.mirror, smem);
+            if constexpr (K & HIT_REG) {
                 static_assert(FusedCfg<F>::WGS == ofpnn::WG, "the per-item forward passes are written for 256 threads");
-                hop_regress_stage(a, *ra, done + 1, (int)(n_on < a.C ? n_on : a.C), wake, sa.mirror, smem);
+                hop_regress_stage(a, ha.ra, done + 1, n, wake, sa.mirror, smem);
             }
-            if constexpr (PAIR) {
+            if constexpr (K & HIT_PAIR) {
                 static_assert(FusedCfg<F>::WGS == ofppair::FT, "the lag search and the vote are written for 256 threads");
-                hop_paired_stage(a, *pa, done + 1, (int)(n_on < a.C ? n_on : a.C), wake, sa.mirror, smem);
+                hop_paired_stage(a, ha.pa, done + 1, n, wake, sa.mirror, smem);
             }
         } else {
             ofpstream::stream_par_blocks(sa, reinterpret_cast<float*>(smem));
@@ -686,64 +695,27 @@ __device__ __forceinline__ void hop_fused_body(const HopArgs& a, const ofpstream
     }
 }
 
-template <int F, bool LOC>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la) {
+template <int F, int K>
+__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused(HopArgs a, ofpstream::StreamArgs sa, HitArgs<K> ha) {
     extern __shared__ __align__(16) unsigned char smem[];
-    hop_fused_body<F, LOC, false>(a, sa, la, nullptr, smem);
-}
-
-// The fused hop of a session with a regressor: a kernel of its own, so that k_hop_fused keeps its arguments and code.
-template <int F, bool LOC>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_reg(HopArgs a, ofpstream::StreamArgs sa, HopLocArgs la,
-                                                                    HopRegArgs ra) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    hop_fused_body<F, LOC, true>(a, sa, la, &ra, smem);
-}
-
-// The fused hop of a session with the voting locator: again a kernel of its own.
-template <int F>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_pair(HopArgs a, ofpstream::StreamArgs sa, HopPairArgs pa) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    hop_fused_body<F, false, false, true>(a, sa, HopLocArgs{}, nullptr, smem, &pa);
+    hop_fused_body<F, K>(a, sa, ha, smem);
 }
 
 // S sessions' hops in ONE launch: grid (C + 1 + strength, S), row blockIdx.y is member blockIdx.y of an
 // ofp_hop_group and runs hop_fused_body on that member's three argument structs in the group's device arrays
 // (uniform, read-only addresses: scalar loads, as for kernel arguments) -- the member's own ticket, counter and
-// completion word.  Members share nothing and no workgroup waits for another, so a grid larger than the device simply
-// queues.  n_fft, the channel count, and whether a locator / the onset strength is on fix the instantiation and
-// gridDim.x: a group's members agree on these four.  dry != 0: every workgroup returns at once (the un-captured launch
-// at group creation that loads the code and sets the dynamic-LDS attribute must not touch a member's state).
-template <int F, bool LOC>
+// completion word; the stages' architectures, locators and windows may differ from member to member.  Members share
+// nothing and no workgroup waits for another, so a grid larger than the device simply queues.  n_fft, the channel
+// count, the hit kind and whether the onset strength is on fix the instantiation and gridDim.x: a group's members
+// agree on these four.  dry != 0: every workgroup returns at once (the un-captured launch at group creation that loads
+// the code and sets the dynamic-LDS attribute must not touch a member's state).
+template <int F, int K>
 __global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group(const HopArgs* __restrict__ args,
                                                                       const ofpstream::StreamArgs* __restrict__ sargs,
-                                                                      const HopLocArgs* __restrict__ largs, int dry) {
+                                                                      const HitArgs<K>* __restrict__ hargs, int dry) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (dry) return;
-    hop_fused_body<F, LOC, false>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], nullptr, smem);
-}
-
-// The group launch of members with a regressor each (rargs: the members' stage arguments, architectures may differ).
-template <int F, bool LOC>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group_reg(const HopArgs* __restrict__ args,
-                                                                          const ofpstream::StreamArgs* __restrict__ sargs,
-                                                                          const HopLocArgs* __restrict__ largs,
-                                                                          const HopRegArgs* __restrict__ rargs, int dry) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    if (dry) return;
-    hop_fused_body<F, LOC, true>(args[blockIdx.y], sargs[blockIdx.y], largs[blockIdx.y], rargs + blockIdx.y, smem);
-}
-
-// The group launch of members with a voting locator each (pargs: the members' stage arguments; locators, tol, left and
-// right may differ).
-template <int F>
-__global__ __launch_bounds__(FusedCfg<F>::WGS) void k_hop_fused_group_pair(const HopArgs* __restrict__ args,
-                                                                           const ofpstream::StreamArgs* __restrict__ sargs,
-                                                                           const HopPairArgs* __restrict__ pargs, int dry) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    if (dry) return;
-    hop_fused_body<F, false, false, true>(args[blockIdx.y], sargs[blockIdx.y], HopLocArgs{}, nullptr, smem,
-                                          pargs + blockIdx.y);
+    hop_fused_body<F, K>(args[blockIdx.y], sargs[blockIdx.y], hargs[blockIdx.y], smem);
 }
 
 }  // namespace
@@ -821,9 +793,7 @@ struct ofp_hop_group {
     hipGraphExec_t exec = nullptr;
     HopArgs* d_args = nullptr;
     ofpstream::StreamArgs* d_sargs = nullptr;
-    HopLocArgs* d_largs = nullptr;
-    HopRegArgs* d_rargs = nullptr;
-    HopPairArgs* d_pargs = nullptr;
+    void* d_hargs = nullptr;  // [members] HitArgs<K>, K the kind that loc, reg and pair name
 };
 
 namespace {
@@ -857,33 +827,47 @@ int hop_strength(ofp_hop_session* s) {
 
 constexpr size_t FUSED_LDS_THRESHOLD = 65536 - 20480;  // (the detector's static LDS comes on top)
 
-template <int F, bool LOC>
-int hop_fused(ofp_hop_session* s) {
+// The run-time flags of a session or a group as one of the five compile-time hit kinds: f(integral_constant<int, K>).
+template <class Fn>
+int with_hit_kind(bool loc, bool reg, bool pair, Fn f) {
+    switch ((loc ? HIT_LOC : 0) | (reg ? HIT_REG : 0) | (pair ? HIT_PAIR : 0)) {
+        case HIT_NONE: return f(std::integral_constant<int, HIT_NONE>());
+        case HIT_LOC: return f(std::integral_constant<int, HIT_LOC>());
+        case HIT_REG: return f(std::integral_constant<int, HIT_REG>());
+        case HIT_LOC | HIT_REG: return f(std::integral_constant<int, HIT_LOC | HIT_REG>());
+        case HIT_PAIR: return f(std::integral_constant<int, HIT_PAIR>());
+    }
+    return ofp::fail(OFP_ERR_INVALID, "the voting locator is a session's only stage");
+}
+
+// the stage arguments of a session of kind K, as the fused kernels take them
+template <int K>
+HitArgs<K> hit_args(const ofp_hop_session* s) {
+    HitArgs<K> ha{};
+    if constexpr (K & HIT_LOC) ha.la = s->largs;
+    if constexpr (K & HIT_REG) ha.ra = s->rargs;
+    if constexpr (K & HIT_PAIR) ha.pa = s->pargs;
+    return ha;
+}
+
+template <int F, int K>
+int hop_fused_launch(ofp_hop_session* s) {
     static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused<F, LOC>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused<F, LOC>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
-                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->largs);
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused<F, K>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused<F, K>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
+                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, hit_args<K>(s));
     OFP_LAUNCH_CHECK("k_hop_fused");
     return OFP_OK;
 }
 
-template <int F, bool LOC>
-int hop_fused_reg(ofp_hop_session* s) {
+// Nodes form: a hit stage as a node of its own, one workgroup of 256 threads on the records the detector node wrote.
+template <auto Kernel, class StageArgs>
+int hop_stage_node(ofp_hop_session* s, const StageArgs& stage, size_t lds, const char* name) {
     static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_reg<F, LOC>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused_reg<F, LOC>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
-                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->largs, s->rargs);
-    OFP_LAUNCH_CHECK("k_hop_fused_reg");
-    return OFP_OK;
-}
-
-template <int F>
-int hop_fused_pair(ofp_hop_session* s) {
-    static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_pair<F>, s->lds_fused, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused_pair<F>), dim3((unsigned)s->C + 1 + (s->args.sg.enabled ? 1 : 0)),
-                       dim3(FusedCfg<F>::WGS), s->lds_fused, s->stream, s->args, s->sargs, s->pargs);
-    OFP_LAUNCH_CHECK("k_hop_fused_pair");
+    if (int rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds, attr)) return rc;
+    hipLaunchKernelGGL(Kernel, dim3(1), dim3(256), lds, s->stream, s->args, stage,
+                       reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
+    OFP_LAUNCH_CHECK(name);
     return OFP_OK;
 }
 
@@ -891,10 +875,8 @@ int hop_fused_pair(ofp_hop_session* s) {
 int enqueue_hop(ofp_hop_session* s) {
     if (s->fused)  // one kernel: no copy nodes, no begin kernel
         return with_n_fft(s->n_fft, [&](auto f) {
-            constexpr int F = decltype(f)::value;
-            if (s->pargs.enabled) return hop_fused_pair<F>(s);
-            if (s->rargs.enabled) return s->largs.enabled ? hop_fused_reg<F, true>(s) : hop_fused_reg<F, false>(s);
-            return s->largs.enabled ? hop_fused<F, true>(s) : hop_fused<F, false>(s);
+            return with_hit_kind(s->largs.enabled, s->rargs.enabled, s->pargs.enabled,
+                                 [&](auto k) { return hop_fused_launch<decltype(f)::value, decltype(k)::value>(s); });
         });
     OFP_HIP(hipMemcpyAsync(s->d_hop, s->h_hop, (size_t)s->B * s->C * sizeof(float), hipMemcpyHostToDevice, s->stream));
     hipLaunchKernelGGL(k_hop_begin, dim3(1), dim3(64), 0, s->stream, s->args);
@@ -904,27 +886,12 @@ int enqueue_hop(ofp_hop_session* s) {
                                 reinterpret_cast<ofp_onset*>(s->d_res + s->o_rec), s->C,
                                 reinterpret_cast<int64_t*>(s->d_res + s->o_count), s->stream);
     if (rc != OFP_OK) return rc;
-    if (s->largs.enabled) {  // (before the spectral node: the ring holds the older hops only)
-        static ofp::LdsAttrCache attr;
-        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_locate), s->lds_loc, attr)) != OFP_OK) return rc;
-        hipLaunchKernelGGL(k_hop_locate, dim3(1), dim3(256), s->lds_loc, s->stream, s->args, s->largs,
-                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
-        OFP_LAUNCH_CHECK("k_hop_locate");
-    }
-    if (s->pargs.enabled) {  // (where the locate node is: the ring holds the older hops only)
-        static ofp::LdsAttrCache attr;
-        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_paired), s->lds_pair, attr)) != OFP_OK) return rc;
-        hipLaunchKernelGGL(k_hop_paired, dim3(1), dim3(256), s->lds_pair, s->stream, s->args, s->pargs,
-                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
-        OFP_LAUNCH_CHECK("k_hop_paired");
-    }
-    if (s->rargs.enabled) {  // (after the locate node, before the spectral node: the ring holds the older hops only)
-        static ofp::LdsAttrCache attr;
-        if ((rc = ofp::ensure_dynamic_lds(reinterpret_cast<const void*>(k_hop_regress), s->lds_reg, attr)) != OFP_OK) return rc;
-        hipLaunchKernelGGL(k_hop_regress, dim3(1), dim3(256), s->lds_reg, s->stream, s->args, s->rargs,
-                           reinterpret_cast<const ofp_onset*>(s->d_res + s->o_rec));
-        OFP_LAUNCH_CHECK("k_hop_regress");
-    }
+    if (s->largs.enabled)  // (before the spectral node: the ring holds the older hops only)
+        if ((rc = hop_stage_node<k_hop_locate>(s, s->largs, s->lds_loc, "k_hop_locate")) != OFP_OK) return rc;
+    if (s->pargs.enabled)  // (where the locate node is: the ring holds the older hops only)
+        if ((rc = hop_stage_node<k_hop_paired>(s, s->pargs, s->lds_pair, "k_hop_paired")) != OFP_OK) return rc;
+    if (s->rargs.enabled)  // (after the locate node, before the spectral node: the ring holds the older hops only)
+        if ((rc = hop_stage_node<k_hop_regress>(s, s->rargs, s->lds_reg, "k_hop_regress")) != OFP_OK) return rc;
     if (s->args.sg.enabled) {  // (before the spectral node: it reads ring rows the spectral node is about to overwrite
                                //  only for hops older than the ring, never the current one)
         rc = with_n_fft(s->n_fft, [&](auto f) { return hop_strength<decltype(f)::value>(s); });
@@ -1033,33 +1000,14 @@ int wait_done(const ofp_hop_session* s, hipStream_t stream, bool* synced = nullp
     OFP_REQUIRE(!(s)->owner, what ": the session is a member of an ofp_hop_group (its hops go through "            \
                                   "ofp_hop_group_submit; ofp_hop_group_destroy releases it)")
 
-template <int F, bool LOC>
+template <int F, int K>
 int hop_group_launch(ofp_hop_group* g, int dry) {
     static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group<F, LOC>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused_group<F, LOC>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
-                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_largs, dry);
+    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group<F, K>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
+    hipLaunchKernelGGL((k_hop_fused_group<F, K>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
+                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs,
+                       static_cast<const HitArgs<K>*>(g->d_hargs), dry);
     OFP_LAUNCH_CHECK("k_hop_fused_group");
-    return OFP_OK;
-}
-
-template <int F, bool LOC>
-int hop_group_launch_reg(ofp_hop_group* g, int dry) {
-    static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group_reg<F, LOC>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused_group_reg<F, LOC>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
-                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_largs, g->d_rargs, dry);
-    OFP_LAUNCH_CHECK("k_hop_fused_group_reg");
-    return OFP_OK;
-}
-
-template <int F>
-int hop_group_launch_pair(ofp_hop_group* g, int dry) {
-    static ofp::LdsAttrCache attr;
-    if (int rc = ofp::ensure_dynamic_lds((const void*)k_hop_fused_group_pair<F>, g->lds, attr, FUSED_LDS_THRESHOLD)) return rc;
-    hipLaunchKernelGGL((k_hop_fused_group_pair<F>), dim3((unsigned)g->grid_x, (unsigned)g->members.size()),
-                       dim3(FusedCfg<F>::WGS), g->lds, g->stream, g->d_args, g->d_sargs, g->d_pargs, dry);
-    OFP_LAUNCH_CHECK("k_hop_fused_group_pair");
     return OFP_OK;
 }
 
@@ -1069,58 +1017,106 @@ void group_free(ofp_hop_group* g) {
     if (g->graph) (void)hipGraphDestroy(g->graph);
     if (g->d_args) (void)hipFree(g->d_args);
     if (g->d_sargs) (void)hipFree(g->d_sargs);
-    if (g->d_largs) (void)hipFree(g->d_largs);
-    if (g->d_rargs) (void)hipFree(g->d_rargs);
-    if (g->d_pargs) (void)hipFree(g->d_pargs);
+    if (g->d_hargs) (void)hipFree(g->d_hargs);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
 
+// one argument struct per member, get(member), as a device array at *d
+template <class Get>
+int group_upload(const ofp_hop_group* g, void** d, Get get) {
+    std::vector<decltype(get(g->members[0]))> v;
+    for (const ofp_hop_session* s : g->members) v.push_back(get(s));
+    OFP_HIP(hipMalloc(d, v.size() * sizeof(v[0])));
+    OFP_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+    return OFP_OK;
+}
+
 // the group's resources on the members' device: the argument arrays, the dry launch, the captured graph
 int group_build(ofp_hop_group* g) {
-    const size_t n = g->members.size();
-    std::vector<HopArgs> a(n);
-    std::vector<ofpstream::StreamArgs> q(n);
-    std::vector<HopLocArgs> l(n);
-    std::vector<HopRegArgs> r(n);
-    for (size_t i = 0; i < n; ++i) {
-        a[i] = g->members[i]->args;
-        q[i] = g->members[i]->sargs;
-        l[i] = g->members[i]->largs;
-        r[i] = g->members[i]->rargs;
-    }
     OFP_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    OFP_HIP(hipMalloc(&g->d_args, n * sizeof(HopArgs)));
-    OFP_HIP(hipMalloc(&g->d_sargs, n * sizeof(ofpstream::StreamArgs)));
-    OFP_HIP(hipMalloc(&g->d_largs, n * sizeof(HopLocArgs)));
-    OFP_HIP(hipMemcpy(g->d_args, a.data(), n * sizeof(HopArgs), hipMemcpyHostToDevice));
-    OFP_HIP(hipMemcpy(g->d_sargs, q.data(), n * sizeof(ofpstream::StreamArgs), hipMemcpyHostToDevice));
-    OFP_HIP(hipMemcpy(g->d_largs, l.data(), n * sizeof(HopLocArgs), hipMemcpyHostToDevice));
-    if (g->reg) {
-        OFP_HIP(hipMalloc(&g->d_rargs, n * sizeof(HopRegArgs)));
-        OFP_HIP(hipMemcpy(g->d_rargs, r.data(), n * sizeof(HopRegArgs), hipMemcpyHostToDevice));
-    }
-    if (g->pair) {
-        std::vector<HopPairArgs> p(n);
-        for (size_t i = 0; i < n; ++i) p[i] = g->members[i]->pargs;
-        OFP_HIP(hipMalloc(&g->d_pargs, n * sizeof(HopPairArgs)));
-        OFP_HIP(hipMemcpy(g->d_pargs, p.data(), n * sizeof(HopPairArgs), hipMemcpyHostToDevice));
-    }
+    if (int rc = group_upload(g, (void**)&g->d_args, [](const ofp_hop_session* s) { return s->args; })) return rc;
+    if (int rc = group_upload(g, (void**)&g->d_sargs, [](const ofp_hop_session* s) { return s->sargs; })) return rc;
+    if (int rc = with_hit_kind(g->loc, g->reg, g->pair, [&](auto k) {
+            return group_upload(g, &g->d_hargs, [](const ofp_hop_session* s) { return hit_args<decltype(k)::value>(s); });
+        }))
+        return rc;
     // a member that joins mid-stream: its last stand-alone hop must have left its own stream
     for (ofp_hop_session* s : g->members)
         if (int rc = retire_last_hop(s)) return rc;
     // code loading and the kernel attribute may not happen during capture: one launch that touches nothing
     auto launch = [&](int dry) {
         return with_n_fft(g->n_fft, [&](auto f) {
-            constexpr int F = decltype(f)::value;
-            if (g->pair) return hop_group_launch_pair<F>(g, dry);
-            if (g->reg) return g->loc ? hop_group_launch_reg<F, true>(g, dry) : hop_group_launch_reg<F, false>(g, dry);
-            return g->loc ? hop_group_launch<F, true>(g, dry) : hop_group_launch<F, false>(g, dry);
+            return with_hit_kind(g->loc, g->reg, g->pair, [&](auto k) {
+                return hop_group_launch<decltype(f)::value, decltype(k)::value>(g, dry);
+            });
         });
     };
     if (int rc = launch(1)) return rc;
     OFP_HIP(hipStreamSynchronize(g->stream));
     return capture_graph(g->stream, [&] { return launch(0); }, &g->graph, &g->exec);
+}
+
+// What a hit stage owns of its session: its argument struct (largs / rargs / pargs), its LDS size (lds_loc / lds_reg /
+// lds_pair) and its device allocations.
+template <class StageArgs>
+struct StageOwned {
+    StageArgs& args;
+    size_t& lds;
+    void** dev[3];
+};
+
+// Attaches a hit stage that has passed its setter's checks: fill() makes the stage's allocations and fills its
+// arguments, the rest is the same for every stage.  The record mirror of the fused form belongs to the stage that finds
+// none (a regressor after a locator shares the locator's).  If anything from the first allocation on fails, the session
+// is again exactly the one it was and a later call is accepted.
+// (No stage is refused by the LDS bound that was accepted without it: ofp_paired_cfg allows the voting locator 96 KiB.)
+template <class StageArgs, class Fill>
+int attach_stage(ofp_hop_session* s, const char* who, size_t lds, Fill fill, StageOwned<StageArgs> own) {
+    OFP_REQUIRE(lds <= 128 * 1024, "%s: %zu bytes of LDS needed", who, lds);
+    const size_t lds_fused = s->lds_fused;
+    const bool own_mirror = s->fused && !s->d_mirror;
+    auto attach = [&]() -> int {
+        if (int rc = fill()) return rc;
+        own.lds = lds;
+        if (own_mirror) {
+            OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
+            OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
+            s->sargs.mirror = s->d_mirror;
+        }
+        if (s->fused) s->lds_fused = std::max(s->lds_fused, lds);
+        own.args.enabled = 1;
+        return capture_hop(s);
+    };
+    const int rc = attach();
+    if (rc == OFP_OK) return OFP_OK;
+    const std::string why = ofp::err_buf();
+    for (void** p : {own.dev[0], own.dev[1], own.dev[2], own_mirror ? (void**)&s->d_mirror : nullptr}) {
+        if (p && *p) (void)hipFree(*p);
+        if (p) *p = nullptr;
+    }
+    std::memset(&own.args, 0, sizeof(StageArgs));
+    if (own_mirror) s->sargs.mirror = nullptr;
+    s->lds_fused = lds_fused;
+    own.lds = 0;
+    if (!s->exec) (void)capture_hop(s);  // (the failure came after the earlier graph had been given up)
+    return ofp::fail(rc, "%s", why.c_str());
+}
+
+// The bounds of a grouping stage whose window reaches `before` samples before its anchor and `after` samples after it
+// (INTEGRATION.md): a group is evaluated at most K hops after the hop that closes it; that bounds the groups pending
+// at once and the oldest row a window still needs.  realtime.regress_hold_hops, regress_pending_bound and
+// regress_ring_rows state the same arithmetic.
+int grouping_bounds(const ofp_hop_session* s, const char* who, int64_t D, int64_t before, int64_t after) {
+    const int64_t B = s->B, span = D + after;
+    const int64_t K = std::max<int64_t>(0, (span + B - 1) / B - 1);
+    const int64_t pending = std::min<int64_t>(K + 1, (K * B + D - 1) / (D + 1) + 1);
+    OFP_REQUIRE(pending <= OFP_REG_QUEUE, "%s: up to %lld groups can be pending, the queue holds %d", who, (long long)pending,
+                OFP_REG_QUEUE);
+    const int64_t rows = D + before + (K + 1) * B;
+    OFP_REQUIRE(s->R >= rows, "%s: the ring (%lld rows) must hold the oldest row a pending window can need plus one hop (%lld)",
+                who, (long long)s->R, (long long)rows);
+    return OFP_OK;
 }
 
 }  // namespace
@@ -1443,9 +1439,7 @@ static int hop_attach_locator(ofp_hop_session* s, const ofp_hop_locator* loc, of
                 "%s: the ring (%lld rows) must hold the longest section (%d) and one hop (%d)", who, (long long)s->R,
                 loc->max_section, s->B);
     const size_t lds = ofp::loc_lds_bytes(s->threads, T.max_section, T.plan, (size_t)s->B * s->C * 4);  // (+ the hop rows)
-    OFP_REQUIRE(lds <= 128 * 1024, "%s: %zu bytes of LDS needed", who, lds);
-    const size_t lds_fused = s->lds_fused;
-    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+    auto fill = [&]() -> int {
         if (loc->mlp) {  // the session keeps its own copy: the handle may be destroyed afterwards
             OFP_HIP(hipMalloc(&s->d_loc_prm, (size_t)T.plan.n_params * 4));
             OFP_HIP(hipMemcpy(s->d_loc_prm, loc->mlp->d_params, (size_t)T.plan.n_params * 4, hipMemcpyDeviceToDevice));
@@ -1456,31 +1450,10 @@ static int hop_attach_locator(ofp_hop_session* s, const ofp_hop_locator* loc, of
         s->largs.T = T;
         s->largs.state = s->d_loc_state;
         s->largs.out = reinterpret_cast<HopLocBlock*>(s->res_dev + s->o_loc);
-        s->lds_loc = lds;
-        if (s->fused) {
-            OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
-            OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
-            s->sargs.mirror = s->d_mirror;
-            s->lds_fused = std::max(s->lds_fused, lds);
-        }
-        s->largs.enabled = 1;
-        return capture_hop(s);
+        return OFP_OK;
     };
-    const int rc = attach();
-    if (rc == OFP_OK) return OFP_OK;
-    // the session is again exactly the locator-less one it was, and a later call is accepted
-    const std::string why = ofp::err_buf();
-    void** dev[] = {(void**)&s->d_loc_prm, (void**)&s->d_loc_state, (void**)&s->d_mirror};
-    for (void** p : dev) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    std::memset(&s->largs, 0, sizeof(s->largs));
-    s->sargs.mirror = nullptr;
-    s->lds_fused = lds_fused;
-    s->lds_loc = 0;
-    if (!s->exec) (void)capture_hop(s);  // (the failure came after the locator-less graph had been given up)
-    return ofp::fail(rc, "%s", why.c_str());
+    return attach_stage(s, who, lds, fill,
+                        StageOwned<HopLocArgs>{s->largs, s->lds_loc, {(void**)&s->d_loc_prm, (void**)&s->d_loc_state}});
 }
 
 int ofp_hop_set_locator(ofp_hop_session* s, const ofp_hop_locator* loc) {
@@ -1545,21 +1518,8 @@ int ofp_hop_set_regressor(ofp_hop_session* s, const ofp_hop_regressor* r) {
     OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
     OFP_REQUIRE(r->max_distance >= s->B, "%s: max_distance %d is shorter than one hop (%d): two groups could close in one hop",
                 who, r->max_distance, s->B);
-    // a group is evaluated at most K hops after the hop that closes it; that bounds the groups
-    // pending at once and the oldest row a window still needs
-    const int64_t B = s->B, D = r->max_distance, span = D + (int64_t)r->frame_length - r->pre_samples;
-    const int64_t K = std::max<int64_t>(0, (span + B - 1) / B - 1);
-    const int64_t pending = std::min<int64_t>(K + 1, (K * B + D - 1) / (D + 1) + 1);
-    OFP_REQUIRE(pending <= OFP_REG_QUEUE, "%s: up to %lld groups can be pending, the queue holds %d", who, (long long)pending,
-                OFP_REG_QUEUE);
-    const int64_t rows = D + r->pre_samples + (K + 1) * B;
-    OFP_REQUIRE(s->R >= rows, "%s: the ring (%lld rows) must hold the oldest row a pending window can need plus one hop (%lld)",
-                who, (long long)s->R, (long long)rows);
-    const size_t lds = ofpreg::lds_bytes(plan);
-    OFP_REQUIRE(lds <= 128 * 1024, "%s: %zu bytes of LDS needed", who, lds);
-    const size_t lds_fused = s->lds_fused;
-    const bool own_mirror = s->fused && !s->d_mirror;
-    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+    if (int rc = grouping_bounds(s, who, r->max_distance, r->pre_samples, (int64_t)r->frame_length - r->pre_samples)) return rc;
+    auto fill = [&]() -> int {
         OFP_HIP(hipMalloc(&s->d_reg_prm, (size_t)plan.n_params * 4));
         OFP_HIP(hipMemcpy(s->d_reg_prm, r->d_params, (size_t)plan.n_params * 4, hipMemcpyDeviceToDevice));
         plan.params = s->d_reg_prm;
@@ -1576,33 +1536,11 @@ int ofp_hop_set_regressor(ofp_hop_session* s, const ofp_hop_regressor* r) {
         g.state = s->d_reg_state;
         g.ws = s->d_reg_ws;
         s->rargs.out = reinterpret_cast<HopRegBlock*>(s->res_dev + s->o_reg);
-        s->lds_reg = lds;
-        if (s->fused) {
-            if (own_mirror) {
-                OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
-                OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
-                s->sargs.mirror = s->d_mirror;
-            }
-            s->lds_fused = std::max(s->lds_fused, lds);
-        }
-        s->rargs.enabled = 1;
-        return capture_hop(s);
+        return OFP_OK;
     };
-    const int rc = attach();
-    if (rc == OFP_OK) return OFP_OK;
-    // the session is again exactly the one it was, and a later call is accepted
-    const std::string why = ofp::err_buf();
-    void** dev[] = {(void**)&s->d_reg_prm, (void**)&s->d_reg_state, (void**)&s->d_reg_ws, own_mirror ? (void**)&s->d_mirror : nullptr};
-    for (void** p : dev) {
-        if (p && *p) (void)hipFree(*p);
-        if (p) *p = nullptr;
-    }
-    std::memset(&s->rargs, 0, sizeof(s->rargs));
-    if (own_mirror) s->sargs.mirror = nullptr;
-    s->lds_fused = lds_fused;
-    s->lds_reg = 0;
-    if (!s->exec) (void)capture_hop(s);  // (the failure came after the earlier graph had been given up)
-    return ofp::fail(rc, "%s", why.c_str());
+    return attach_stage(s, who, ofpreg::lds_bytes(plan), fill,
+                        StageOwned<HopRegArgs>{s->rargs, s->lds_reg,
+                                               {(void**)&s->d_reg_prm, (void**)&s->d_reg_state, (void**)&s->d_reg_ws}});
 }
 
 int ofp_hop_collect_hit(ofp_hop_session* s, int32_t* status, int64_t* start, int64_t* h_row, float* h_y, int32_t* flags) {
@@ -1634,49 +1572,18 @@ int ofp_hop_set_locator_paired(ofp_hop_session* s, const ofp_hop_paired* p) {
     OFP_REQUIRE(!s->det->p.backtrack, "%s: a detector that backtracks moves onsets behind the hop", who);
     OFP_REQUIRE(p->max_distance >= s->B, "%s: max_distance %d is shorter than one hop (%d): two groups could close in one hop",
                 who, p->max_distance, s->B);
-    // the bounds of ofp_hop_set_regressor with frame_length = left + right, pre_samples = left
-    const int64_t B = s->B, D = p->max_distance, span = D + (int64_t)p->right;
-    const int64_t K = std::max<int64_t>(0, (span + B - 1) / B - 1);
-    const int64_t pending = std::min<int64_t>(K + 1, (K * B + D - 1) / (D + 1) + 1);
-    OFP_REQUIRE(pending <= OFP_REG_QUEUE, "%s: up to %lld groups can be pending, the queue holds %d", who, (long long)pending,
-                OFP_REG_QUEUE);
-    const int64_t rows = D + p->left + (K + 1) * B;
-    OFP_REQUIRE(s->R >= rows, "%s: the ring (%lld rows) must hold the oldest row a pending window can need plus one hop (%lld)",
-                who, (long long)s->R, (long long)rows);
-    const size_t lds = ofppair::lds_bytes(g.F, g.side);
-    const size_t lds_fused = s->lds_fused;
-    auto attach = [&]() -> int {  // everything from the first allocation on: undone below if any of it fails
+    if (int rc = grouping_bounds(s, who, p->max_distance, p->left, p->right)) return rc;
+    auto fill = [&]() -> int {
         OFP_HIP(hipMalloc(&s->d_pair_state, sizeof(ofp_regress_state)));
         OFP_HIP(hipMemset(s->d_pair_state, 0, sizeof(ofp_regress_state)));
         g.B = s->B;
         g.state = s->d_pair_state;
         s->pargs.g = g;
         s->pargs.out = reinterpret_cast<HopPairBlock*>(s->res_dev + s->o_pair);
-        s->lds_pair = lds;
-        if (s->fused) {
-            OFP_HIP(hipMalloc(&s->d_mirror, (size_t)s->C * sizeof(ofp_onset)));
-            OFP_HIP(hipMemset(s->d_mirror, 0, (size_t)s->C * sizeof(ofp_onset)));
-            s->sargs.mirror = s->d_mirror;
-            s->lds_fused = std::max(s->lds_fused, lds);
-        }
-        s->pargs.enabled = 1;
-        return capture_hop(s);
+        return OFP_OK;
     };
-    const int rc = attach();
-    if (rc == OFP_OK) return OFP_OK;
-    // the session is again exactly the one it was, and a later call is accepted
-    const std::string why = ofp::err_buf();
-    void** dev[] = {(void**)&s->d_pair_state, (void**)&s->d_mirror};
-    for (void** q : dev) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    std::memset(&s->pargs, 0, sizeof(s->pargs));
-    s->sargs.mirror = nullptr;
-    s->lds_fused = lds_fused;
-    s->lds_pair = 0;
-    if (!s->exec) (void)capture_hop(s);  // (the failure came after the earlier graph had been given up)
-    return ofp::fail(rc, "%s", why.c_str());
+    return attach_stage(s, who, ofppair::lds_bytes(g.F, g.side), fill,
+                        StageOwned<HopPairArgs>{s->pargs, s->lds_pair, {(void**)&s->d_pair_state}});
 }
 
 int ofp_hop_collect_cc_hit(ofp_hop_session* s, int32_t* hit, int32_t* status, int64_t* onset, int32_t* first,

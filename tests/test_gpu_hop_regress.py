@@ -431,6 +431,34 @@ def test_group_of_three_architectures_is_the_members_alone():
         s.close()
 
 
+@pytest.mark.gpu
+def test_group_with_locator_and_regressor_is_the_members_alone():
+    """The group launch of members that run both stages after the detector (models of different weights)."""
+    from onset_fingerprinting_amd import multilateration as ml
+    from onset_fingerprinting_amd import realtime
+    audio, det, args = stream()
+    models = [make("CNN", 256, 2, 3), make("CNN", 256, 2, 3, seed=4)]
+    both = lambda m_: session(det, 96000, locator=ml.Multilaterate3D(**args["layout"]), regressor=m_, **SESSION)
+    n = 450
+    alone = [play(both(m_), audio, n) for m_ in models]
+    members = [both(m_) for m_ in models]
+    group = realtime.HopSessionGroup(members)
+    hops = np.stack([audio] * 2)
+    for h in range(n):
+        out = group(np.ascontiguousarray(hops[:, h * 128:(h + 1) * 128]))
+        for i in range(2):
+            same_but(alone[i][h], out[i], ())
+            assert set(out[i]) == set(alone[i][h])
+    for i in range(2):
+        assert sum(r["hit"] is not None for r in alone[i]) >= 3
+        assert sum(r["location"] is not None for r in alone[i]) >= 3
+    first = [next(r["hit"]["position"] for r in a if r["hit"] is not None) for a in alone]
+    assert not np.array_equal(first[0], first[1])  # (each member's answers are its own model's)
+    group.close()
+    for s in members:
+        s.close()
+
+
 # ---- (d) a session without a regressor --------------------------------------------------------------------------
 
 @pytest.mark.gpu
