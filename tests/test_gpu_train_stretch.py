@@ -286,6 +286,16 @@ def refused(rc, what):
     assert last_error().strip(), (what, "no message")
 
 
+def cnnrnn_model():
+    from onset_fingerprinting_amd import model
+    return model.CNNRNN(W_, 2, channels=3, layer_sizes=[4, 6], n_hidden=8, dropout_rate=0.0)
+
+
+def rnn_model(**kw):
+    from onset_fingerprinting_amd import model
+    return model.RNN(W_, 2, channels=3, hidden_size=8, dropout_rate=0.0, **kw)
+
+
 def test_refusals():
     from onset_fingerprinting_amd import _lib, data, model
     L = lib()
@@ -314,23 +324,27 @@ def test_refusals():
     # the trainers' entries: nothing is touched before the options are checked, so the pointers can stay NULL
     cfg_cnn, _c, _b = model._cnn_arch(T.cnn_model(0.0), W_, None)
     cfg_cc, _c, _g = model._cccnn_arch(T.lcccnn_model(0.0), W_, None)
+    cfg_cr, _c, _b = model._cnnrnn_arch(cnnrnn_model(), W_, None)
+    cfg_rnn = model._rnn_arch(rnn_model())
+    cfg_rnn.width = W_
     src, _y = source()
     rnd, keep = model._train_random(0.0, 3, 0, src)
     none = _lib.TrainRandom()
     none.seed = 3
     epochs = ctypes.c_int32(0)
-    for name, cfg in (("cnn", cfg_cnn), ("cccnn", cfg_cc)):
+    for name, cfg, plain in (("cnn", cfg_cnn, "train_random"), ("cccnn", cfg_cc, "train_random"),
+                             ("cnnrnn", cfg_cr, "loss_grads_random"), ("rnn", cfg_rnn, "loss_grads_random")):
         ws_fn = getattr(L, f"ofp_{name}_train_stretch_workspace_bytes")
         assert ws_fn(ctypes.byref(cfg), src.n, 0, ctypes.byref(rnd), SPAN) > 0, last_error()
         assert ws_fn(ctypes.byref(cfg), src.n, 0, ctypes.byref(rnd), 0) == \
-            getattr(L, f"ofp_{name}_train_random_workspace_bytes")(ctypes.byref(cfg), src.n, 0, ctypes.byref(rnd))
+            getattr(L, f"ofp_{name}_{plain}_workspace_bytes")(ctypes.byref(cfg), src.n, 0, ctypes.byref(rnd))
         for what, (r, sp) in {"a span of 1": (ctypes.byref(rnd), 1), "a negative span": (ctypes.byref(rnd), -2),
                               "a span without options": (None, SPAN),
                               "a span without a window source": (ctypes.byref(none), SPAN),
                               "a span above the width": (ctypes.byref(rnd), W_ + 1)}.items():
             assert ws_fn(ctypes.byref(cfg), src.n, 0, r, sp) == -1, (name, what)
             assert last_error().strip(), (name, what)
-            extra = (None,) if name == "cnn" else ()  # d_stats
+            extra = (None,) if name in ("cnn", "cnnrnn") else ()  # d_stats
             rc = getattr(L, f"ofp_{name}_train_stretch")(ctypes.byref(cfg), src.n, None, None, 0, None, None, None, 5,
                                                         0, -1, None, *extra, None, None, ctypes.byref(epochs), None,
                                                         0, stream(), r, sp)
@@ -348,7 +362,10 @@ def test_refusals():
         too_long.windows(1, 0)
     still_right("width + span - 1 = 2049 through the class")
     xs, y = source()
-    for fit_fn, m_ in ((model.fit_cnn, T.cnn_model(0.0)), (model.fit_lcccnn, T.lcccnn_model(0.0))):
+    with pytest.raises(ValueError, match="permute_input=True"):
+        model.fit_rnn(rnn_model(permute_input=False).cuda(), xs, y.cuda(), max_epochs=2, seed=1)
+    for fit_fn, m_ in ((model.fit_cnn, T.cnn_model(0.0)), (model.fit_lcccnn, T.lcccnn_model(0.0)),
+                       (model.fit_cnnrnn, cnnrnn_model()), (model.fit_rnn, rnn_model())):
         with pytest.raises(ValueError, match="x_val"):
             fit_fn(m_.cuda(), xs, y.cuda(), x_val=xs, y_val=y.cuda(), max_epochs=2, seed=1)
         with pytest.raises(ValueError, match="needs seed="):
