@@ -19,6 +19,11 @@
 // p . dp) are one workgroup's fp64 sums in an order fixed by the thread index.  Sums over the batch (GroupNorm's
 // d gamma / d beta, the convolution's weight and bias gradients, the Linear head's) go through the partial-slab
 // reducer of ofp_train_chain.h.  Results are bitwise reproducible.
+//
+// Host side, by the contract of csrc/ofp_train_chain.h: this file's own Plan (GroupNorm and a strided stack: no part is
+// shared), enqueue_forward / _backward / _step / _reset for Run<Plan>, the traits Cccnn.  The ofp_cccnn_train* and
+// ofp_cccnn_loss_grads* entries forward into train_workspace_bytes / train_entry / loss_grads_entry<Cccnn>; the model
+// has no running statistics (ns = 0).
 #include "ofp_train_random.h"
 
 #include <algorithm>
@@ -330,20 +335,19 @@ int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int 
 }
 
 struct Plan : WsPlan {
-    int L, act, norm, pool, loss, O, C, K, V, F, np, group;
+    int L, act, norm, pool, loss, O, C, K, V, F, group;
     double eps;
     float mom, wd;
     Conv conv[kMaxConv];
     int wo[kMaxConv];
     int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], fcw_off, fcb_off;
     // work space, byte offsets
-    int64_t o_Z[kMaxConv], o_H[kMaxConv], o_stat[kMaxConv], o_P, o_out, o_dy, o_lpart, o_gh, o_gz, o_part, o_G, o_B,
-        o_ctl, o_HD, o_DP, o_X;  // o_HD: the dropped p, o_DP: its gradient; o_X: the epoch's shifted windows
+    int64_t o_Z[kMaxConv], o_H[kMaxConv], o_stat[kMaxConv], o_P, o_out, o_dy, o_lpart, o_gh, o_gz, o_part, o_B, o_HD,
+        o_DP;  // o_HD: the dropped p, o_DP: its gradient
     int64_t items(int64_t n) const { return group ? n : n * C; }
 };
 
-int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd = Random{}) {
-    const char* who = "cccnn training";
+int make_plan(const char* who, const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd) {
     OFP_REQUIRE(c != nullptr, "%s: config is NULL", who);
     OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "%s: %d conv layers (limit: 1..%d)", who, c->n_conv, kMaxConv);
     OFP_REQUIRE(c->sensors >= 1 && c->sensors <= kMaxCh, "%s: %d sensor channels (limit: 1..%d)", who, c->sensors,
@@ -428,16 +432,7 @@ int make_plan(const ofp_cccnn_config* c, int64_t n, int64_t n_val, Plan& p, cons
     return OFP_OK;
 }
 
-struct Run : WsRun {
-    const Plan* p;
-    float* P;   // packed parameters
-    float* G;   // packed gradients
-    Ctl* ctl;   // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
-    hipStream_t st;
-    Random rnd;  // dropout in front of the Linear head and the window source; both off by default
-};
-
-Norm norm_of(const Run& r, int l) {
+Norm norm_of(const Run<Plan>& r, int l) {
     const Plan& p = *r.p;
     Norm t{};
     t.C = p.conv[l].cout, t.wc = p.conv[l].wc, t.wo = p.wo[l], t.act = p.act, t.pool = p.pool, t.norm = p.norm;
@@ -504,14 +499,14 @@ int enqueue_head_bwd(const Ctl* ctl, const float* f, const float* prob, const fl
     return OFP_OK;
 }
 
-Fc fc_of(const Run& r, const float* h, int64_t n, const float* y) {
+Fc fc_of(const Run<Plan>& r, const float* h, int64_t n, const float* y) {
     const Plan& p = *r.p;
     return Fc{h, n, p.F, p.O, r.P + p.fcw_off, r.P + p.fcb_off, y};
 }
 
 // conv stack, correlation head and Linear of a batch, its mean loss into `curve`; train: model.loss, d loss / d out
 // kept and the Linear's bias gradient; else L1 and the early-stop rule
-int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
+int enqueue_forward(const Run<Plan>& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
     const Plan& p = *r.p;
     const int64_t items = p.items(n);
     const float* in = x;
@@ -536,7 +531,7 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
                               r.G + p.fcb_off, r.st);
 }
 
-int enqueue_backward(const Run& r, const float* x, int64_t n) {
+int enqueue_backward(const Run<Plan>& r, const float* x, int64_t n) {
     const Plan& p = *r.p;
     const int64_t items = p.items(n);
     float* GH = r.at<float>(p.o_gh);
@@ -567,13 +562,28 @@ int enqueue_backward(const Run& r, const float* x, int64_t n) {
     return OFP_OK;
 }
 
-int enqueue_step(const Run& r, const float* rates) {
+int enqueue_step(const Run<Plan>& r, const float* rates) {
     const Plan& p = *r.p;
     hipLaunchKernelGGL(k_sgd, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, rates, 0, p.mom, p.wd, r.P, r.G,
                        r.at<float>(p.o_B), (int64_t)p.np);
     OFP_LAUNCH_CHECK("k_sgd");
     return OFP_OK;
 }
+
+int enqueue_reset(const Run<Plan>& r) {
+    OFP_HIP(hipMemsetAsync(r.at<float>(r.p->o_B), 0, (size_t)r.p->np * 4, r.st));
+    return OFP_OK;
+}
+
+struct Cccnn {
+    using Config = ofp_cccnn_config;
+    using Plan = ::Plan;
+    static constexpr const char* train = "ofp_cccnn_train";
+    static constexpr const char* grads = "ofp_cccnn_loss_grads";
+    static constexpr const char* env = "OFP_CCCNN_GRAPH";
+    static Window window_of(const Config& c) { return Window{c.sensors, c.width}; }
+    static constexpr auto make_plan = ::make_plan;
+};
 
 }  // namespace
 
@@ -590,12 +600,7 @@ int64_t ofp_cccnn_train_random_workspace_bytes(const ofp_cccnn_config* cfg, int6
 
 int64_t ofp_cccnn_train_stretch_workspace_bytes(const ofp_cccnn_config* cfg, int64_t n, int64_t n_val,
                                                 const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    if (cfg == nullptr || make_random("cccnn training", random, stretch_span, n, cfg->sensors, cfg->width, true, rnd))
-        return -1;
-    if (make_plan(cfg, n, n_val, p, rnd)) return -1;
-    return p.bytes;
+    return train_workspace_bytes<Cccnn>(cfg, n, n_val, random, stretch_span);
 }
 
 int ofp_cccnn_train(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
@@ -622,27 +627,9 @@ int ofp_cccnn_train_stretch(const ofp_cccnn_config* cfg, int64_t n, const float*
                             int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
                             float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                             const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    OFP_REQUIRE(cfg != nullptr, "cccnn training: config is NULL");
-    if (int rc = make_random("ofp_cccnn_train", random, stretch_span, n, cfg->sensors, cfg->width, true, rnd))
-        return rc;
-    if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
-    if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
-    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
-    if (int rc = check_train("ofp_cccnn_train", a, num_epochs, d_params, h_epochs)) return rc;
-    if (int rc = check_ws("ofp_cccnn_train", d_ws, ws_bytes, p.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    Run r{{(char*)d_ws}, &p, d_params, nullptr, nullptr, st, rnd};
-    r.G = r.at<float>(p.o_G);
-    r.ctl = r.at<Ctl>(p.o_ctl);
-    return run_epochs(
-        "ofp_cccnn_train", "OFP_CCCNN_GRAPH", st, r.ctl, num_epochs, patience, h_epochs,
-        [&] {
-            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_B), 0, (size_t)p.np * 4, st));
-            return OFP_OK;
-        },
-        [&] { return enqueue_epoch(r, a); });
+    return train_entry<Cccnn>(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs, patience,
+                              d_params, nullptr, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream, random,
+                              stretch_span);
 }
 
 int ofp_cccnn_loss_grads(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
@@ -654,14 +641,7 @@ int ofp_cccnn_loss_grads(const ofp_cccnn_config* cfg, int64_t n, const float* d_
 int ofp_cccnn_loss_grads_random(const ofp_cccnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
                                 const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
                                 void* stream, const ofp_train_random* random) {
-    Plan p;
-    Random rnd;
-    if (int rc = make_random("ofp_cccnn_loss_grads", random, 0, n, 0, 0, false, rnd)) return rc;
-    if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
-    OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cccnn_loss_grads: NULL argument");
-    if (int rc = check_ws("ofp_cccnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
-    Run r{{(char*)d_ws}, &p, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream, rnd};
-    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
+    return loss_grads_entry<Cccnn>(cfg, n, d_x, d_y, d_params, d_loss, d_grads, d_ws, ws_bytes, stream, random);
 }
 
 int64_t ofp_conv1d_backward_strided_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,

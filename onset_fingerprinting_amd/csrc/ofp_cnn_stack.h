@@ -1,9 +1,13 @@
 // The conv stack of model.CNN as both of its trainers run it (csrc/ofp_cnn_train.hip, csrc/ofp_cnnrnn_train.hip): what
 // follows a convolution (activation, BatchNorm1d on batch or running statistics, MaxPool1d(2, 2)) forward and backward,
-// the NAdam step, the limits of the stack and the launch helpers of the BatchNorm reductions.  File-local like
-// ofp_train_chain.h and ofp_train_random.h, which it builds on: each trainer compiles its own copy.
+// the NAdam step, the limits of the stack and the launch helpers of the BatchNorm reductions; and the stack as a part of
+// a trainer's Plan (ofp_train_chain.h): ConvStack with plan_conv_stack, which makes the checks and takes the blocks,
+// post_of, enqueue_conv_stack_fwd and enqueue_conv_stack_bwd.  A trainer keeps what is behind the stack's features.
+// File-local like ofp_train_chain.h and ofp_train_random.h, which it builds on: each trainer compiles its own copy.
 #pragma once
 #include "ofp_train_random.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -212,6 +216,13 @@ __global__ __launch_bounds__(kT) void k_nadam(const Ctl* ctl, const float* __res
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
+// k_nadam's state: the zeroing of its two moments in front of the first epoch (every NAdam trainer's enqueue_reset)
+int zero_moments(float* m, float* v, int64_t np, hipStream_t st) {
+    OFP_HIP(hipMemsetAsync(m, 0, (size_t)np * 4, st));
+    OFP_HIP(hipMemsetAsync(v, 0, (size_t)np * 4, st));
+    return OFP_OK;
+}
+
 int check_conv(const char* who, int64_t n, int cin, int w, int cout, int k, int padding, int dilation, int groups) {
     OFP_REQUIRE(n >= 1 && n <= kMaxBatch, "%s: batch of %lld (limit: 1..%d)", who, (long long)n, kMaxBatch);
     OFP_REQUIRE(cin >= 1 && cin <= kMaxCh && cout >= 1 && cout <= kMaxCh, "%s: %d -> %d channels (limit: 1..%d)", who,
@@ -251,6 +262,138 @@ int enqueue_post_bwd(const Ctl* ctl, const Post& t, int64_t n, const float* z, c
     }
     hipLaunchKernelGGL(k_dz, dim3(grid_for(n * t.C * t.wc)), dim3(kT), 0, st, ctl, t, n, z, dh, s12, dz);
     OFP_LAUNCH_CHECK("k_dz");
+    return OFP_OK;
+}
+
+// ---- the stack as a part of a trainer's Plan -------------------------------------------------------------------------
+
+struct ConvStack {
+    int L, act, bn, pool;
+    double eps;
+    float mom;
+    Conv conv[kMaxConv];
+    int wo[kMaxConv];  // columns of a layer's output: conv[l].wc, halved by the pool
+    int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], rs_off[kMaxConv];
+    // work space, byte offsets: pre-activations and outputs per layer, the running gradient at an output and at a
+    // pre-activation, BatchNorm's saved statistics and its two backward sums
+    int64_t o_Z[kMaxConv], o_H[kMaxConv], o_gh, o_gz, o_save, o_s12;
+};
+
+// Checks the CNN part of a configuration for a training batch of n (the work space holds nmax = max(n, n_val) samples)
+// and plans the stack into `ws`: the layers' parameters go behind the caller's np, their running statistics behind ns,
+// max_part_bytes is raised to what the stack's partial sums need.  The last layer's channels and columns are
+// s.conv[s.L - 1].cout and s.wo[s.L - 1].
+int plan_conv_stack(const char* who, const ofp_cnn_config* c, int64_t n, int64_t nmax, WsPlan& ws, int& np, int& ns,
+                    int64_t& max_part_bytes, ConvStack& s) {
+    OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "%s: %d conv layers (limit: 1..%d)", who, c->n_conv, kMaxConv);
+    OFP_REQUIRE(c->act >= 0 && c->act <= OFP_ACT_TANH, "%s: unknown activation %d", who, c->act);
+    OFP_REQUIRE(c->loss == 0 || c->loss == 1, "%s: loss %d (0 = L1, 1 = MSE)", who, c->loss);
+    OFP_REQUIRE(c->n_out >= 1 && c->n_out <= kMaxOut, "%s: %d outputs (limit: 1..%d)", who, c->n_out, kMaxOut);
+    if (c->batch_norm)
+        OFP_REQUIRE(c->bn_momentum > 0.0f && c->bn_momentum <= 1.0f && c->bn_eps > 0.0,
+                    "%s: BatchNorm momentum %g, eps %g (a cumulative average, momentum=None, is not built)", who,
+                    (double)c->bn_momentum, c->bn_eps);
+    s = ConvStack{};
+    s.L = c->n_conv, s.act = c->act, s.bn = c->batch_norm ? 1 : 0, s.pool = c->pool ? 1 : 0;
+    s.eps = c->bn_eps, s.mom = c->bn_momentum;
+    int width = c->width;
+    int64_t max_h = 0, max_z = 0;
+    max_part_bytes = std::max<int64_t>(max_part_bytes, 2 * 8);
+    for (int l = 0; l < s.L; ++l) {
+        const int cin = c->channels[l], cout = c->channels[l + 1];
+        if (int rc = check_conv(who, n, cin, width, cout, c->kernel, c->padding, c->dilation, c->groups)) return rc;
+        Conv& v = s.conv[l];
+        v = Conv{cin, cout, width, width + 2 * c->padding - c->dilation * (c->kernel - 1), c->kernel, c->padding,
+                 c->dilation, c->groups, 1};
+        OFP_REQUIRE(v.wc <= 2 * kMaxWidth, "%s: layer %d is %d wide (limit: %d)", who, l + 1, v.wc, 2 * kMaxWidth);
+        s.wo[l] = s.pool ? v.wc / 2 : v.wc;
+        OFP_REQUIRE(s.wo[l] >= 1, "%s: the pool of layer %d leaves no output column", who, l + 1);
+        OFP_REQUIRE(!s.bn || n * v.wc >= 2, "%s: BatchNorm needs more than 1 value per channel", who);
+        const int T = cin / c->groups * c->kernel + 1;
+        s.w_off[l] = np, np += cout * (T - 1);
+        s.b_off[l] = np, np += cout;
+        if (s.bn) {
+            s.g_off[l] = np, np += cout;
+            s.be_off[l] = np, np += cout;
+            s.rs_off[l] = ns, ns += 2 * cout;
+        }
+        max_part_bytes = std::max<int64_t>(max_part_bytes, (int64_t)cout * T * slabs_of(n * v.wc) * 8);
+        max_h = std::max<int64_t>(max_h, nmax * cout * s.wo[l]);
+        max_z = std::max<int64_t>(max_z, nmax * cout * v.wc);
+        width = s.wo[l];
+    }
+    for (int l = 0; l < s.L; ++l) {
+        s.o_Z[l] = ws.take(nmax * s.conv[l].cout * s.conv[l].wc * 4);
+        s.o_H[l] = ws.take(nmax * s.conv[l].cout * s.wo[l] * 4);
+    }
+    s.o_gh = ws.take(max_h * 4);
+    s.o_gz = ws.take(max_z * 4);
+    s.o_save = ws.take((int64_t)ns * 4);
+    s.o_s12 = ws.take((int64_t)ns * 4);
+    return OFP_OK;
+}
+
+template <class Plan>
+Post post_of(const Run<Plan>& r, const ConvStack& s, int l, int mode) {
+    Post t{};
+    t.C = s.conv[l].cout, t.wc = s.conv[l].wc, t.wo = s.wo[l], t.act = s.act, t.pool = s.pool, t.mode = mode;
+    t.eps = s.eps;
+    if (mode) {
+        t.ga = r.P + s.g_off[l], t.be = r.P + s.be_off[l];
+        if (mode == 1) {
+            t.mean = r.template at<float>(s.o_save) + s.rs_off[l], t.rs = t.mean + t.C;
+        } else {
+            t.mean = r.RS + s.rs_off[l], t.rs = t.mean + t.C;
+        }
+    }
+    return t;
+}
+
+// the stack on a batch x [n][channels][width]; train: batch statistics (`part` takes the partial sums), else running
+// statistics.  *features is the last layer's output [n][channels][columns].
+template <class Plan>
+int enqueue_conv_stack_fwd(const Run<Plan>& r, const ConvStack& s, const float* x, int64_t n, bool train, double* part,
+                           const float** features) {
+    const float* in = x;
+    for (int l = 0; l < s.L; ++l) {
+        const Conv& c = s.conv[l];
+        float* Z = r.template at<float>(s.o_Z[l]);
+        float* H = r.template at<float>(s.o_H[l]);
+        hipLaunchKernelGGL(k_conv_fwd, dim3(grid_for(n * c.cout * c.wc)), dim3(kT), 0, r.st, r.ctl, c, n, in,
+                           r.P + s.w_off[l], r.P + s.b_off[l], Z);
+        OFP_LAUNCH_CHECK("k_conv_fwd");
+        const Post t = post_of(r, s, l, s.bn ? (train ? 1 : 2) : 0);
+        if (s.bn && train) {
+            float* save = r.template at<float>(s.o_save) + s.rs_off[l];
+            if (int rc = enqueue_bn_stats(r.ctl, Z, n, c.cout, c.wc, s.act, s.eps, s.mom, part, save, save + c.cout,
+                                          r.RS + s.rs_off[l], r.RS + s.rs_off[l] + c.cout, r.st))
+                return rc;
+        }
+        hipLaunchKernelGGL(k_post, dim3(grid_for(n * c.cout * s.wo[l])), dim3(kT), 0, r.st, r.ctl, t, n, Z, H);
+        OFP_LAUNCH_CHECK("k_post");
+        in = H;
+    }
+    *features = in;
+    return OFP_OK;
+}
+
+// backward of the stack from the gradient at its features, which the caller has put into o_gh (overwritten on the way
+// down); the parameters' gradients go to r.G
+template <class Plan>
+int enqueue_conv_stack_bwd(const Run<Plan>& r, const ConvStack& s, const float* x, int64_t n, double* part) {
+    float* GH = r.template at<float>(s.o_gh);
+    float* GZ = r.template at<float>(s.o_gz);
+    for (int l = s.L - 1; l >= 0; --l) {
+        const Post t = post_of(r, s, l, s.bn ? 1 : 0);
+        const float* Z = r.template at<float>(s.o_Z[l]);
+        if (int rc = enqueue_post_bwd(r.ctl, t, n, Z, GH, part, r.template at<float>(s.o_s12) + s.rs_off[l],
+                                      r.G + s.g_off[l], r.G + s.be_off[l], GZ, r.st))
+            return rc;
+        const float* in = l == 0 ? x : r.template at<float>(s.o_H[l - 1]);
+        if (int rc = enqueue_conv_bwd(r.ctl, s.conv[l], n, in, r.P + s.w_off[l], GZ, part, r.G + s.w_off[l],
+                                      r.G + s.b_off[l], l == 0 ? nullptr : GH, r.st))
+            return rc;
+    }
     return OFP_OK;
 }
 

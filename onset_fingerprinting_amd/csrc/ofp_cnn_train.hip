@@ -23,6 +23,11 @@
 // gradient are fp32 fmaf chains of at most cin/groups * k (cout/groups * k) terms, in k_conv1d's order.
 // What follows a convolution, the NAdam step and the stack's limits are in csrc/ofp_cnn_stack.h, shared with the CNNRNN
 // trainer (csrc/ofp_cnnrnn_train.hip).
+//
+// Host side, by the contract of csrc/ofp_train_chain.h: the Plan is the ConvStack part (its checks, offsets, blocks and
+// launch loops are in ofp_cnn_stack.h) and this file's own flat head with its dropout; enqueue_forward / _backward /
+// _step / _reset for Run<Plan>; the traits Cnn.  The ofp_cnn_train* and ofp_cnn_loss_grads* entries forward into
+// train_workspace_bytes / train_entry / loss_grads_entry<Cnn>.
 #include "ofp_cnn_stack.h"
 
 #include <algorithm>
@@ -43,142 +48,52 @@ __global__ __launch_bounds__(kT) void k_philox(const uint32_t* __restrict__ coun
 // ---- host side ------------------------------------------------------------------------------------------------------
 
 struct Plan : WsPlan {
-    int L, act, bn, pool, loss, O, F, np, ns;
-    double eps;
-    float mom;
-    Conv conv[kMaxConv];
-    int wo[kMaxConv];
-    int w_off[kMaxConv], b_off[kMaxConv], g_off[kMaxConv], be_off[kMaxConv], rs_off[kMaxConv], fcw_off, fcb_off;
+    ConvStack cs;
+    int loss, O, F;  // F: the features of the flat head, the last layer's channels x columns
+    int fcw_off, fcb_off;
     // work space, byte offsets
-    int64_t o_Z[kMaxConv], o_H[kMaxConv], o_out, o_dy, o_lpart, o_gh, o_gz, o_save, o_s12, o_part, o_G, o_M, o_V,
-        o_RS, o_ctl, o_HD, o_X;  // o_HD: the dropped features; o_X: the epoch's shifted windows
+    int64_t o_out, o_dy, o_lpart, o_part, o_M, o_V, o_HD;  // o_HD: the dropped features
 };
 
-int make_plan(const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd = Random{}) {
-    OFP_REQUIRE(c != nullptr, "cnn training: config is NULL");
-    OFP_REQUIRE(c->n_conv >= 1 && c->n_conv <= kMaxConv, "cnn training: %d conv layers (limit: 1..%d)", c->n_conv,
-                kMaxConv);
-    OFP_REQUIRE(n_val >= 0 && n_val <= kMaxBatch, "cnn training: validation batch of %lld (limit: 0..%d)",
-                (long long)n_val, kMaxBatch);
-    OFP_REQUIRE(c->act >= 0 && c->act <= OFP_ACT_TANH, "cnn training: unknown activation %d", c->act);
-    OFP_REQUIRE(c->loss == 0 || c->loss == 1, "cnn training: loss %d (0 = L1, 1 = MSE)", c->loss);
-    OFP_REQUIRE(c->n_out >= 1 && c->n_out <= kMaxOut, "cnn training: %d outputs (limit: 1..%d)", c->n_out, kMaxOut);
-    if (c->batch_norm)
-        OFP_REQUIRE(c->bn_momentum > 0.0f && c->bn_momentum <= 1.0f && c->bn_eps > 0.0,
-                    "cnn training: BatchNorm momentum %g, eps %g (a cumulative average, momentum=None, is not built)",
-                    (double)c->bn_momentum, c->bn_eps);
+int make_plan(const char* who, const ofp_cnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd) {
+    OFP_REQUIRE(c != nullptr, "%s: config is NULL", who);
+    OFP_REQUIRE(n_val >= 0 && n_val <= kMaxBatch, "%s: validation batch of %lld (limit: 0..%d)", who, (long long)n_val,
+                kMaxBatch);
     p = Plan{};
-    p.L = c->n_conv, p.act = c->act, p.bn = c->batch_norm ? 1 : 0, p.pool = c->pool ? 1 : 0, p.loss = c->loss;
-    p.O = c->n_out, p.eps = c->bn_eps, p.mom = c->bn_momentum;
     const int64_t nmax = n > n_val ? n : n_val;
-    int width = c->width, np = 0, ns = 0;
-    int64_t max_h = 0, max_z = 0, max_part = 2;
-    for (int l = 0; l < p.L; ++l) {
-        const int cin = c->channels[l], cout = c->channels[l + 1];
-        if (int rc = check_conv("cnn training", n, cin, width, cout, c->kernel, c->padding, c->dilation, c->groups))
-            return rc;
-        Conv& v = p.conv[l];
-        v = Conv{cin, cout, width, width + 2 * c->padding - c->dilation * (c->kernel - 1), c->kernel, c->padding,
-                 c->dilation, c->groups, 1};
-        OFP_REQUIRE(v.wc <= 2 * kMaxWidth, "cnn training: layer %d is %d wide (limit: %d)", l + 1, v.wc, 2 * kMaxWidth);
-        p.wo[l] = p.pool ? v.wc / 2 : v.wc;
-        OFP_REQUIRE(p.wo[l] >= 1, "cnn training: the pool of layer %d leaves no output column", l + 1);
-        OFP_REQUIRE(!p.bn || n * v.wc >= 2, "cnn training: BatchNorm needs more than 1 value per channel");
-        const int T = cin / c->groups * c->kernel + 1;
-        p.w_off[l] = np, np += cout * (T - 1);
-        p.b_off[l] = np, np += cout;
-        if (p.bn) {
-            p.g_off[l] = np, np += cout;
-            p.be_off[l] = np, np += cout;
-            p.rs_off[l] = ns, ns += 2 * cout;
-        }
-        const int64_t part = (int64_t)cout * T * slabs_of(n * v.wc);
-        max_part = part > max_part ? part : max_part;
-        max_h = std::max<int64_t>(max_h, nmax * cout * p.wo[l]);
-        max_z = std::max<int64_t>(max_z, nmax * cout * v.wc);
-        width = p.wo[l];
-    }
-    p.F = c->channels[p.L] * width;
-    max_part = std::max<int64_t>(max_part, (int64_t)fc_chunks(n) * p.O * p.F);
-    p.fcw_off = np, np += p.O * p.F;
-    p.fcb_off = np, np += p.O;
-    p.np = np, p.ns = ns;
-    for (int l = 0; l < p.L; ++l) {
-        p.o_Z[l] = p.take(nmax * p.conv[l].cout * p.conv[l].wc * 4);
-        p.o_H[l] = p.take(nmax * p.conv[l].cout * p.wo[l] * 4);
-    }
+    int64_t max_part = 0;  // bytes
+    if (int rc = plan_conv_stack(who, c, n, nmax, p, p.np, p.ns, max_part, p.cs)) return rc;
+    p.loss = c->loss, p.O = c->n_out;
+    p.F = p.cs.conv[p.cs.L - 1].cout * p.cs.wo[p.cs.L - 1];
+    max_part = std::max<int64_t>(max_part, (int64_t)fc_chunks(n) * p.O * p.F * 8);
+    p.fcw_off = p.np, p.np += p.O * p.F;
+    p.fcb_off = p.np, p.np += p.O;
     p.o_out = p.take(nmax * p.O * 4);
     p.o_dy = p.take(nmax * p.O * 4);
     p.o_lpart = p.take(nmax * 8);
-    p.o_gh = p.take(max_h * 4);
-    p.o_gz = p.take(max_z * 4);
-    p.o_save = p.take((int64_t)ns * 4);
-    p.o_s12 = p.take((int64_t)ns * 4);
-    p.o_part = p.take(max_part * 8);
-    p.o_G = p.take((int64_t)np * 4);
-    p.o_M = p.take((int64_t)np * 4);
-    p.o_V = p.take((int64_t)np * 4);
-    p.o_RS = p.take((int64_t)ns * 4);
+    p.o_part = p.take(max_part);
+    p.o_G = p.take((int64_t)p.np * 4);
+    p.o_M = p.take((int64_t)p.np * 4);
+    p.o_V = p.take((int64_t)p.np * 4);
+    p.o_RS = p.take((int64_t)p.ns * 4);
     p.o_ctl = p.take(sizeof(Ctl));
     if (rnd.drop) p.o_HD = p.take(n * p.F * 4);
     if (rnd.windows) p.o_X = p.take(n * c->channels[0] * c->width * 4);
     return OFP_OK;
 }
 
-struct Run : WsRun {
-    const Plan* p;
-    float* P;    // packed parameters
-    float* RS;   // packed running statistics
-    float* G;    // packed gradients
-    Ctl* ctl;    // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
-    hipStream_t st;
-    Random rnd;  // dropout in front of the Linear head and the window source; both off by default
-};
-
-Post post_of(const Run& r, int l, int mode) {
-    const Plan& p = *r.p;
-    Post t{};
-    t.C = p.conv[l].cout, t.wc = p.conv[l].wc, t.wo = p.wo[l], t.act = p.act, t.pool = p.pool, t.mode = mode;
-    t.eps = p.eps;
-    if (mode) {
-        t.ga = r.P + p.g_off[l], t.be = r.P + p.be_off[l];
-        if (mode == 1) {
-            t.mean = r.at<float>(p.o_save) + p.rs_off[l], t.rs = t.mean + t.C;
-        } else {
-            t.mean = r.RS + p.rs_off[l], t.rs = t.mean + t.C;
-        }
-    }
-    return t;
-}
-
-Fc fc_of(const Run& r, const float* h, int64_t n, const float* y) {
+Fc fc_of(const Run<Plan>& r, const float* h, int64_t n, const float* y) {
     const Plan& p = *r.p;
     return Fc{h, n, p.F, p.O, r.P + p.fcw_off, r.P + p.fcb_off, y};
 }
 
 // conv stack and head of a batch, its mean loss into `curve`; train: batch statistics, d loss / d out kept and the
 // head's bias gradient; else running statistics, L1 and the early-stop rule
-int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
+int enqueue_forward(const Run<Plan>& r, const float* x, const float* y, int64_t n, bool train, float* curve,
+                    int patience) {
     const Plan& p = *r.p;
-    const float* in = x;
-    for (int l = 0; l < p.L; ++l) {
-        const Conv& c = p.conv[l];
-        float* Z = r.at<float>(p.o_Z[l]);
-        float* H = r.at<float>(p.o_H[l]);
-        hipLaunchKernelGGL(k_conv_fwd, dim3(grid_for(n * c.cout * c.wc)), dim3(kT), 0, r.st, r.ctl, c, n, in,
-                           r.P + p.w_off[l], r.P + p.b_off[l], Z);
-        OFP_LAUNCH_CHECK("k_conv_fwd");
-        const Post t = post_of(r, l, p.bn ? (train ? 1 : 2) : 0);
-        if (p.bn && train) {
-            float* save = r.at<float>(p.o_save) + p.rs_off[l];
-            if (int rc = enqueue_bn_stats(r.ctl, Z, n, c.cout, c.wc, p.act, p.eps, p.mom, r.at<double>(p.o_part), save,
-                                          save + c.cout, r.RS + p.rs_off[l], r.RS + p.rs_off[l] + c.cout, r.st))
-                return rc;
-        }
-        hipLaunchKernelGGL(k_post, dim3(grid_for(n * c.cout * p.wo[l])), dim3(kT), 0, r.st, r.ctl, t, n, Z, H);
-        OFP_LAUNCH_CHECK("k_post");
-        in = H;
-    }
+    const float* in;
+    if (int rc = enqueue_conv_stack_fwd(r, p.cs, x, n, train, r.at<double>(p.o_part), &in)) return rc;
     if (train && r.rnd.drop) {
         float* HD = r.at<float>(p.o_HD);
         if (int rc = enqueue_dropout_fwd(r.ctl, r.rnd, in, HD, n * p.F, r.st)) return rc;
@@ -189,37 +104,40 @@ int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, boo
                               r.G + p.fcb_off, r.st);
 }
 
-int enqueue_backward(const Run& r, const float* x, int64_t n) {
+int enqueue_backward(const Run<Plan>& r, const float* x, int64_t n) {
     const Plan& p = *r.p;
-    float* GH = r.at<float>(p.o_gh);
-    float* GZ = r.at<float>(p.o_gz);
+    float* GH = r.at<float>(p.cs.o_gh);
     double* part = r.at<double>(p.o_part);
-    if (int rc = enqueue_fc_backward(r.ctl, fc_of(r, r.at<float>(r.rnd.drop ? p.o_HD : p.o_H[p.L - 1]), n, nullptr),
-                                     r.at<float>(p.o_dy), part, r.G + p.fcw_off, GH, r.st))
+    const float* feat = r.at<float>(r.rnd.drop ? p.o_HD : p.cs.o_H[p.cs.L - 1]);
+    if (int rc = enqueue_fc_backward(r.ctl, fc_of(r, feat, n, nullptr), r.at<float>(p.o_dy), part, r.G + p.fcw_off, GH,
+                                     r.st))
         return rc;
     if (r.rnd.drop)
         if (int rc = enqueue_dropout_bwd(r.ctl, r.rnd, GH, n * p.F, r.st)) return rc;
-    for (int l = p.L - 1; l >= 0; --l) {
-        const Post t = post_of(r, l, p.bn ? 1 : 0);
-        const float* Z = r.at<float>(p.o_Z[l]);
-        if (int rc = enqueue_post_bwd(r.ctl, t, n, Z, GH, part, r.at<float>(p.o_s12) + p.rs_off[l],
-                                      r.G + p.g_off[l], r.G + p.be_off[l], GZ, r.st))
-            return rc;
-        const float* in = l == 0 ? x : r.at<float>(p.o_H[l - 1]);
-        if (int rc = enqueue_conv_bwd(r.ctl, p.conv[l], n, in, r.P + p.w_off[l], GZ, part, r.G + p.w_off[l],
-                                      r.G + p.b_off[l], l == 0 ? nullptr : GH, r.st))
-            return rc;
-    }
-    return OFP_OK;
+    return enqueue_conv_stack_bwd(r, p.cs, x, n, part);
 }
 
-int enqueue_step(const Run& r, const float* rows) {
+int enqueue_step(const Run<Plan>& r, const float* rows) {
     const Plan& p = *r.p;
     hipLaunchKernelGGL(k_nadam, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, rows, r.P, r.G, r.at<float>(p.o_M),
                        r.at<float>(p.o_V), (int64_t)p.np);
     OFP_LAUNCH_CHECK("k_nadam");
     return OFP_OK;
 }
+
+int enqueue_reset(const Run<Plan>& r) {
+    return zero_moments(r.at<float>(r.p->o_M), r.at<float>(r.p->o_V), r.p->np, r.st);
+}
+
+struct Cnn {
+    using Config = ofp_cnn_config;
+    using Plan = ::Plan;
+    static constexpr const char* train = "ofp_cnn_train";
+    static constexpr const char* grads = "ofp_cnn_loss_grads";
+    static constexpr const char* env = "OFP_CNN_GRAPH";
+    static Window window_of(const Config& c) { return Window{c.channels[0], c.width}; }
+    static constexpr auto make_plan = ::make_plan;
+};
 
 }  // namespace
 
@@ -238,13 +156,7 @@ int64_t ofp_cnn_train_random_workspace_bytes(const ofp_cnn_config* cfg, int64_t 
 
 int64_t ofp_cnn_train_stretch_workspace_bytes(const ofp_cnn_config* cfg, int64_t n, int64_t n_val,
                                               const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    if (cfg == nullptr ||
-        make_random("cnn training", random, stretch_span, n, cfg->channels[0], cfg->width, true, rnd))
-        return -1;
-    if (make_plan(cfg, n, n_val, p, rnd)) return -1;
-    return p.bytes;
+    return train_workspace_bytes<Cnn>(cfg, n, n_val, random, stretch_span);
 }
 
 int ofp_cnn_train(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
@@ -271,29 +183,8 @@ int ofp_cnn_train_stretch(const ofp_cnn_config* cfg, int64_t n, const float* d_x
                           int32_t min_epochs, int32_t patience, float* d_params, float* d_stats, float* d_train_loss,
                           float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                           const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    OFP_REQUIRE(cfg != nullptr, "cnn training: config is NULL");
-    if (int rc = make_random("ofp_cnn_train", random, stretch_span, n, cfg->channels[0], cfg->width, true, rnd))
-        return rc;
-    if (int rc = make_plan(cfg, n, n_val, p, rnd)) return rc;
-    if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
-    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
-    if (int rc = check_train("ofp_cnn_train", a, num_epochs, d_params, h_epochs)) return rc;
-    OFP_REQUIRE(p.ns == 0 || d_stats, "ofp_cnn_train: BatchNorm statistics are NULL");
-    if (int rc = check_ws("ofp_cnn_train", d_ws, ws_bytes, p.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    Run r{{(char*)d_ws}, &p, d_params, d_stats, nullptr, nullptr, st, rnd};
-    r.G = r.at<float>(p.o_G);
-    r.ctl = r.at<Ctl>(p.o_ctl);
-    return run_epochs(
-        "ofp_cnn_train", "OFP_CNN_GRAPH", st, r.ctl, num_epochs, patience, h_epochs,
-        [&] {
-            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_M), 0, (size_t)p.np * 4, st));
-            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_V), 0, (size_t)p.np * 4, st));
-            return OFP_OK;
-        },
-        [&] { return enqueue_epoch(r, a); });
+    return train_entry<Cnn>(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs, patience, d_params,
+                            d_stats, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream, random, stretch_span);
 }
 
 int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
@@ -305,17 +196,7 @@ int ofp_cnn_loss_grads(const ofp_cnn_config* cfg, int64_t n, const float* d_x, c
 int ofp_cnn_loss_grads_random(const ofp_cnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
                               const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
                               void* stream, const ofp_train_random* random) {
-    Plan p;
-    Random rnd;
-    if (int rc = make_random("ofp_cnn_loss_grads", random, 0, n, 0, 0, false, rnd)) return rc;
-    if (int rc = make_plan(cfg, n, 0, p, rnd)) return rc;
-    OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_cnn_loss_grads: NULL argument");
-    if (int rc = check_ws("ofp_cnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
-    // the trainer's own forward and backward; the running statistics it would update are a scratch copy
-    Run r{{(char*)d_ws}, &p, const_cast<float*>(d_params), nullptr, d_grads, nullptr, (hipStream_t)stream, rnd};
-    r.RS = r.at<float>(p.o_RS);
-    OFP_HIP(hipMemsetAsync(r.RS, 0, (size_t)(p.ns > 0 ? p.ns : 1) * 4, r.st));
-    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
+    return loss_grads_entry<Cnn>(cfg, n, d_x, d_y, d_params, d_loss, d_grads, d_ws, ws_bytes, stream, random);
 }
 
 int64_t ofp_conv1d_backward_workspace_bytes(int64_t n, int32_t cin, int32_t w, int32_t cout, int32_t k,

@@ -20,6 +20,11 @@
 // ascending order and are added even + odd, then the slabs in slab order.  The input projection's weight gradient cuts
 // the n T rows into slabs of kInSlab; a workgroup takes (slab, 16 outputs), its 16 row lanes per output take rows sub,
 // sub + 16, ... in ascending order and are joined by an xor butterfly inside the wave and then in wave order.
+//
+// Host side, by the contract of csrc/ofp_train_chain.h: the Plan is this file's GRU stack and LayerNorm and the AttnHead
+// part (ofp_seq_train.h; it reads the LayerNorm output and hands dln back); enqueue_forward / _backward / _step / _reset
+// for Run<Plan>; the traits Rnn.  The ofp_rnn_train_stretch* and ofp_rnn_loss_grads_random entries forward into
+// train_workspace_bytes / train_entry / loss_grads_entry<Rnn>; the model has no running statistics (ns = 0).
 #include "ofp_seq_train.h"
 
 namespace {
@@ -382,17 +387,21 @@ int enqueue_stack_bwd(const Ctl* ctl, const Stack& s, const StackBufs& b, const 
     return OFP_OK;
 }
 
+// the strides of x [n][T][F] (permuted == 0) or [n][F][T] (the window as it is stored)
+InStrides strides_of(int T, int F, int permuted) {
+    return permuted ? InStrides{(int64_t)F * T, 1, T} : InStrides{(int64_t)T * F, F, 1};
+}
+
 // ---- the trainer -----------------------------------------------------------------------------------------------------
 
 struct Plan : WsPlan {
     Stack s;
-    int heads, O, loss, np;
+    AttnHead head;
     double eps;
     float wd;
-    int lnw_off, lnb_off, inw_off, inb_off, ow_off, ob_off, fcw_off, fcb_off;
-    int64_t o_wt, o_inwt, o_owt, o_gx, o_seqs, o_gates, o_drop, o_ln, o_mean, o_rstd, o_qkv, o_P, o_ctx, o_ao, o_out,
-        o_dy, o_lpart, o_dao, o_dctx, o_ds, o_dqkv, o_dln, o_dseq, o_dgx, o_dgh, o_hprev, o_part, o_G, o_M, o_V, o_ctl,
-        o_X;
+    int lnw_off, lnb_off;
+    int64_t o_wt, o_gx, o_seqs, o_gates, o_drop, o_ln, o_mean, o_rstd, o_dln, o_dseq, o_dgx, o_dgh, o_hprev, o_part, o_M,
+        o_V;
 };
 
 int make_plan(const char* who, const ofp_rnn_config* c, int64_t n, int64_t n_val, Plan& p, const Random& rnd) {
@@ -400,7 +409,6 @@ int make_plan(const char* who, const ofp_rnn_config* c, int64_t n, int64_t n_val
     OFP_REQUIRE(n_val >= 0 && n_val <= kMaxBatch, "%s: validation batch of %lld (limit: 0..%d)", who, (long long)n_val,
                 kMaxBatch);
     if (int rc = check_stack(who, n, c->width, c->channels, c->hidden, c->layers)) return rc;
-    if (int rc = check_attn(who, n, c->width, c->hidden, c->heads, kMaxSteps)) return rc;
     OFP_REQUIRE(n * c->heads * c->width * c->width < ((int64_t)1 << 32),
                 "%s: %lld x %d heads x %d^2 attention probabilities: the random stream indexes 2^32 elements", who,
                 (long long)n, c->heads, c->width);
@@ -411,76 +419,46 @@ int make_plan(const char* who, const ofp_rnn_config* c, int64_t n, int64_t n_val
     OFP_REQUIRE(!rnd.windows || c->permute_input, "%s: a window source gives [n][channels][width] (permute_input)", who);
     p = Plan{};
     const int T = c->width, F = c->channels, H = c->hidden, L = c->layers;
-    const InStrides sx = c->permute_input ? InStrides{(int64_t)F * T, 1, T} : InStrides{(int64_t)T * F, F, 1};
-    p.s = stack_of(n, T, F, H, L, sx);
-    p.heads = c->heads, p.O = c->n_out, p.loss = c->loss, p.eps = c->ln_eps, p.wd = c->weight_decay;
-    int np = p.s.np;
-    p.lnw_off = np, np += H;
-    p.lnb_off = np, np += H;
-    p.inw_off = np, np += 3 * H * H;
-    p.inb_off = np, np += 3 * H;
-    p.ow_off = np, np += H * H;
-    p.ob_off = np, np += H;
-    p.fcw_off = np, np += p.O * H;
-    p.fcb_off = np, np += p.O;
-    p.np = np;
-    const int64_t nmax = n > n_val ? n : n_val;
-    const int64_t rows = nmax * T, sq = nmax * p.heads * T * T;
-    int64_t max_part = std::max<int64_t>(stack_part_bytes(n, T, F, H), (int64_t)fc_chunks(n) * p.O * H * 8);
-    max_part = std::max(max_part, lin_part_bytes(n, H, H));
-    max_part = std::max(max_part, ln_part_bytes(n * T, H));
+    const int64_t nmax = n > n_val ? n : n_val, rows = nmax * T;
+    p.s = stack_of(n, T, F, H, L, strides_of(T, F, c->permute_input));
+    p.eps = c->ln_eps, p.wd = c->weight_decay;
+    p.np = p.s.np;
+    p.lnw_off = p.np, p.np += H;
+    p.lnb_off = p.np, p.np += H;
+    int64_t max_part = std::max(stack_part_bytes(n, T, F, H), ln_part_bytes(n * T, H));
     p.o_wt = p.take((int64_t)3 * H * H * 4);
-    p.o_inwt = p.take((int64_t)3 * H * H * 4);
-    p.o_owt = p.take((int64_t)H * H * 4);
+    if (int rc = plan_attn_head(who, n, T, H, c->heads, c->n_out, c->loss, kMaxSteps, p, p.np, max_part, p.head))
+        return rc;
     p.o_gx = p.take(rows * 3 * H * 4);
     p.o_seqs = p.take(L * rows * H * 4);
     p.o_gates = p.take(L * rows * 4 * H * 4);
     p.o_ln = p.take(rows * H * 4);
     p.o_mean = p.take(rows * 4);
     p.o_rstd = p.take(rows * 4);
-    p.o_qkv = p.take(rows * 3 * H * 4);
-    p.o_P = p.take(sq * 4);
-    p.o_ctx = p.take(nmax * H * 4);
-    p.o_ao = p.take(nmax * H * 4);
-    p.o_out = p.take(nmax * p.O * 4);
-    p.o_dy = p.take(nmax * p.O * 4);
-    p.o_lpart = p.take(nmax * 8);
-    p.o_dao = p.take(n * H * 4);
-    p.o_dctx = p.take(n * H * 4);
-    p.o_ds = p.take(n * p.heads * T * T * 4);
-    p.o_dqkv = p.take(n * T * 3 * H * 4);
+    take_attn_head_blocks(p, n, nmax, p.head);
     p.o_dln = p.take(n * T * H * 4);
     p.o_dseq = p.take(n * T * H * 4);
     p.o_dgx = p.take(n * T * 3 * H * 4);
     p.o_dgh = p.take(n * T * 3 * H * 4);
     p.o_hprev = p.take(n * T * H * 4);
     p.o_part = p.take(max_part);
-    p.o_G = p.take((int64_t)np * 4);
-    p.o_M = p.take((int64_t)np * 4);
-    p.o_V = p.take((int64_t)np * 4);
+    p.o_G = p.take((int64_t)p.np * 4);
+    p.o_M = p.take((int64_t)p.np * 4);
+    p.o_V = p.take((int64_t)p.np * 4);
     p.o_ctl = p.take(sizeof(Ctl));
     if (rnd.drop && L > 1) p.o_drop = p.take((int64_t)(L - 1) * n * T * H * 4);
     if (rnd.windows) p.o_X = p.take(n * F * T * 4);
     return OFP_OK;
 }
 
-struct Run : WsRun {
-    const Plan* p;
-    float* P;    // packed parameters
-    float* G;    // packed gradients
-    Ctl* ctl;    // NULL: a single pass, epoch rnd.st.epoch of the random stream
-    hipStream_t st;
-    Random rnd;  // dropout (between the layers, attention probabilities) and the window source; both off by default
-};
-
 // the stack's view of the work space for a batch of n sequences
-Stack stack_for(const Run& r, int64_t n) {
+Stack stack_for(const Run<Plan>& r, int64_t n) {
     Stack s = r.p->s;
     s.n = n;
     return s;
 }
 
-StackBufs bufs_of(const Run& r) {
+StackBufs bufs_of(const Run<Plan>& r) {
     const Plan& p = *r.p;
     return StackBufs{r.at<float>(p.o_wt),  r.at<float>(p.o_gx),    r.at<float>(p.o_seqs), r.at<float>(p.o_gates),
                      r.at<float>(p.o_drop), r.at<float>(p.o_dgx),  r.at<float>(p.o_dgh),  r.at<float>(p.o_hprev),
@@ -489,61 +467,35 @@ StackBufs bufs_of(const Run& r) {
 
 // the whole network on a batch, its mean loss into `curve`; train: both dropouts, d loss / d out kept and the head's
 // bias gradient; else no dropout, L1 and the early-stop rule
-int enqueue_forward(const Run& r, const float* x, const float* y, int64_t n, bool train, float* curve, int patience) {
+int enqueue_forward(const Run<Plan>& r, const float* x, const float* y, int64_t n, bool train, float* curve,
+                    int patience) {
     const Plan& p = *r.p;
     const Stack s = stack_for(r, n);
     const int T = s.T, H = s.H;
     if (int rc = enqueue_stack_fwd(r.ctl, s, bufs_of(r), r.rnd, train, x, r.P, r.st)) return rc;
     const float* top = r.at<float>(p.o_seqs) + (int64_t)(s.L - 1) * n * T * H;
     float* ln = r.at<float>(p.o_ln);
-    float* qkv = r.at<float>(p.o_qkv);
-    float* ctx = r.at<float>(p.o_ctx);
-    float* ao = r.at<float>(p.o_ao);
-    float* inwt = r.at<float>(p.o_inwt);
-    float* owt = r.at<float>(p.o_owt);
     if (int rc = enqueue_ln_fwd(r.ctl, top, n * T, H, r.P + p.lnw_off, r.P + p.lnb_off, p.eps, ln,
                                 r.at<float>(p.o_mean), r.at<float>(p.o_rstd), r.st))
         return rc;
-    if (int rc = enqueue_transpose(r.ctl, r.P + p.inw_off, 3 * H, H, inwt, r.st)) return rc;
-    if (int rc = enqueue_transpose(r.ctl, r.P + p.ow_off, H, H, owt, r.st)) return rc;
-    if (int rc = enqueue_lin_fwd(r.ctl, ln, n * T, H, 3 * H, inwt, r.P + p.inb_off, qkv, r.st)) return rc;
-    if (int rc = enqueue_attn_fwd(r.ctl, attn_of(n, T, H, p.heads, r.rnd, train), kMaxSteps, qkv, r.at<float>(p.o_P),
-                                  ctx, r.st))
-        return rc;
-    if (int rc = enqueue_lin_fwd(r.ctl, ctx, n, H, H, owt, r.P + p.ob_off, ao, r.st)) return rc;
-    const Fc f{ao, n, H, p.O, r.P + p.fcw_off, r.P + p.fcb_off, y};
-    return enqueue_fc_forward(r.ctl, f, p.loss, r.at<float>(p.o_out), train ? r.at<float>(p.o_dy) : nullptr,
-                              r.at<double>(p.o_lpart), curve, patience, r.G + p.fcb_off, r.st);
+    return enqueue_attn_head_fwd(r, p.head, kMaxSteps, ln, n, y, train, curve, patience);
 }
 
-int enqueue_backward(const Run& r, const float* x, int64_t n) {
+int enqueue_backward(const Run<Plan>& r, const float* x, int64_t n) {
     const Plan& p = *r.p;
     const Stack s = stack_for(r, n);
     const int T = s.T, H = s.H;
     double* part = r.at<double>(p.o_part);
-    float* dao = r.at<float>(p.o_dao);
-    float* dctx = r.at<float>(p.o_dctx);
-    float* dqkv = r.at<float>(p.o_dqkv);
     float* dln = r.at<float>(p.o_dln);
     const float* top = r.at<float>(p.o_seqs) + (int64_t)(s.L - 1) * n * T * H;
-    const Fc f{r.at<float>(p.o_ao), n, H, p.O, r.P + p.fcw_off, r.P + p.fcb_off, nullptr};
-    if (int rc = enqueue_fc_backward(r.ctl, f, r.at<float>(p.o_dy), part, r.G + p.fcw_off, dao, r.st)) return rc;
-    if (int rc = enqueue_lin_bwd(r.ctl, r.at<float>(p.o_ctx), n, H, H, r.P + p.ow_off, dao, part, dctx,
-                                 r.G + p.ow_off, r.G + p.ob_off, r.st))
-        return rc;
-    if (int rc = enqueue_attn_bwd(r.ctl, attn_of(n, T, H, p.heads, r.rnd, true), kMaxSteps, r.at<float>(p.o_qkv),
-                                  r.at<float>(p.o_P), dctx, r.at<float>(p.o_ds), dqkv, r.st))
-        return rc;
-    if (int rc = enqueue_lin_bwd(r.ctl, r.at<float>(p.o_ln), n * T, H, 3 * H, r.P + p.inw_off, dqkv, part, dln,
-                                 r.G + p.inw_off, r.G + p.inb_off, r.st))
-        return rc;
+    if (int rc = enqueue_attn_head_bwd(r, p.head, kMaxSteps, r.at<float>(p.o_ln), n, part, dln)) return rc;
     if (int rc = enqueue_ln_bwd(r.ctl, top, n * T, H, r.P + p.lnw_off, r.at<float>(p.o_mean), r.at<float>(p.o_rstd),
                                 dln, part, r.at<float>(p.o_dseq), r.G + p.lnw_off, r.G + p.lnb_off, r.st))
         return rc;
     return enqueue_stack_bwd(r.ctl, s, bufs_of(r), r.rnd, x, r.P, r.G, r.st);
 }
 
-int enqueue_step(const Run& r, const float* rows) {
+int enqueue_step(const Run<Plan>& r, const float* rows) {
     const Plan& p = *r.p;
     hipLaunchKernelGGL(k_nadam_decay, dim3(grid_for(p.np)), dim3(kT), 0, r.st, r.ctl, rows, r.P, r.G,
                        r.at<float>(p.o_M), r.at<float>(p.o_V), (int64_t)p.np, p.wd);
@@ -551,10 +503,19 @@ int enqueue_step(const Run& r, const float* rows) {
     return OFP_OK;
 }
 
-// the strides of a stand-alone stack call's x [n][T][F] (permuted == 0) or [n][F][T] (the window as it is stored)
-InStrides strides_of(int T, int F, int permuted) {
-    return permuted ? InStrides{(int64_t)F * T, 1, T} : InStrides{(int64_t)T * F, F, 1};
+int enqueue_reset(const Run<Plan>& r) {
+    return zero_moments(r.at<float>(r.p->o_M), r.at<float>(r.p->o_V), r.p->np, r.st);
 }
+
+struct Rnn {
+    using Config = ofp_rnn_config;
+    using Plan = ::Plan;
+    static constexpr const char* train = "ofp_rnn_train";
+    static constexpr const char* grads = "ofp_rnn_loss_grads";
+    static constexpr const char* env = "OFP_RNN_GRAPH";
+    static Window window_of(const Config& c) { return Window{c.channels, c.width}; }
+    static constexpr auto make_plan = ::make_plan;
+};
 
 }  // namespace
 
@@ -562,12 +523,7 @@ extern "C" {
 
 int64_t ofp_rnn_train_stretch_workspace_bytes(const ofp_rnn_config* cfg, int64_t n, int64_t n_val,
                                               const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    if (cfg == nullptr || make_random("rnn training", random, stretch_span, n, cfg->channels, cfg->width, true, rnd))
-        return -1;
-    if (make_plan("rnn training", cfg, n, n_val, p, rnd)) return -1;
-    return p.bytes;
+    return train_workspace_bytes<Rnn>(cfg, n, n_val, random, stretch_span);
 }
 
 int ofp_rnn_train_stretch(const ofp_rnn_config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
@@ -575,27 +531,8 @@ int ofp_rnn_train_stretch(const ofp_rnn_config* cfg, int64_t n, const float* d_x
                           int32_t min_epochs, int32_t patience, float* d_params, float* d_train_loss,
                           float* d_val_loss, int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream,
                           const ofp_train_random* random, int32_t stretch_span) {
-    Plan p;
-    Random rnd;
-    OFP_REQUIRE(cfg != nullptr, "rnn training: config is NULL");
-    if (int rc = make_random("ofp_rnn_train", random, stretch_span, n, cfg->channels, cfg->width, true, rnd)) return rc;
-    if (int rc = make_plan("ofp_rnn_train", cfg, n, n_val, p, rnd)) return rc;
-    if (rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
-    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
-    if (int rc = check_train("ofp_rnn_train", a, num_epochs, d_params, h_epochs)) return rc;
-    if (int rc = check_ws("ofp_rnn_train", d_ws, ws_bytes, p.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    Run r{{(char*)d_ws}, &p, d_params, nullptr, nullptr, st, rnd};
-    r.G = r.at<float>(p.o_G);
-    r.ctl = r.at<Ctl>(p.o_ctl);
-    return run_epochs(
-        "ofp_rnn_train", "OFP_RNN_GRAPH", st, r.ctl, num_epochs, patience, h_epochs,
-        [&] {
-            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_M), 0, (size_t)p.np * 4, st));
-            OFP_HIP(hipMemsetAsync(r.at<float>(p.o_V), 0, (size_t)p.np * 4, st));
-            return OFP_OK;
-        },
-        [&] { return enqueue_epoch(r, a); });
+    return train_entry<Rnn>(cfg, n, d_x, d_y, n_val, d_x_val, d_y_val, d_rates, num_epochs, min_epochs, patience, d_params,
+                            nullptr, d_train_loss, d_val_loss, h_epochs, d_ws, ws_bytes, stream, random, stretch_span);
 }
 
 int64_t ofp_rnn_loss_grads_random_workspace_bytes(const ofp_rnn_config* cfg, int64_t n, int64_t n_val,
@@ -606,14 +543,7 @@ int64_t ofp_rnn_loss_grads_random_workspace_bytes(const ofp_rnn_config* cfg, int
 int ofp_rnn_loss_grads_random(const ofp_rnn_config* cfg, int64_t n, const float* d_x, const float* d_y,
                               const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes,
                               void* stream, const ofp_train_random* random) {
-    Plan p;
-    Random rnd;
-    if (int rc = make_random("ofp_rnn_loss_grads", random, 0, n, 0, 0, false, rnd)) return rc;
-    if (int rc = make_plan("ofp_rnn_loss_grads", cfg, n, 0, p, rnd)) return rc;
-    OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "ofp_rnn_loss_grads: NULL argument");
-    if (int rc = check_ws("ofp_rnn_loss_grads", d_ws, ws_bytes, p.bytes)) return rc;
-    const Run r{{(char*)d_ws}, &p, const_cast<float*>(d_params), d_grads, nullptr, (hipStream_t)stream, rnd};
-    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
+    return loss_grads_entry<Rnn>(cfg, n, d_x, d_y, d_params, d_loss, d_grads, d_ws, ws_bytes, stream, random);
 }
 
 int ofp_layernorm_train_forward(const float* d_x, int64_t rows, int32_t E, const float* d_gamma, const float* d_beta,

@@ -2,8 +2,9 @@
 // csrc/ofp_rnn_train.hip): the dense layer forward and its three gradients, the GRU recurrence that keeps its gates and
 // back-propagation through time, self-attention with the mean over time forward and backward (LDS capacity as a
 // template parameter: 128 steps for the CNNRNN, 512 for the RNN), the mask of one site of the random stream, and their
-// launch helpers and limit checks.  File-local like ofp_cnn_stack.h, which it builds on: each trainer compiles its own
-// copy.
+// launch helpers and limit checks; and the attention head as a part of a trainer's Plan (ofp_train_chain.h): AttnHead
+// with plan_attn_head, take_attn_head_blocks, enqueue_attn_head_fwd and enqueue_attn_head_bwd, the capacity an argument.  File-local like
+// ofp_cnn_stack.h, which it builds on: each trainer compiles its own copy.
 //
 // Every dense layer (GRU input projection, in_proj, out_proj) runs k_lin_fwd on a transposed copy of its weight
 // (k_transpose, once per forward); its backward is k_lin_fwd again for dx = dy W (W as stored is the transposed operand)
@@ -492,6 +493,102 @@ int check_attn(const char* who, int64_t n, int T, int E, int heads, int max_step
                 "%s: width %d with %d heads (limits: width 1..%d, heads 1..%d dividing the width)", who, E, heads,
                 kMaxHidden, kMaxHeads);
     return OFP_OK;
+}
+
+// ---- the attention head as a part of a trainer's Plan ----------------------------------------------------------------
+// in_proj -> self-attention with the mean over time -> out_proj -> Linear with the loss, on sequences [n][T][H]
+
+struct AttnHead {
+    int T, H, heads, O, loss;
+    int inw_off, inb_off, ow_off, ob_off, fcw_off, fcb_off;
+    // work space, byte offsets: both transposed weights, what the forward keeps, the gradients on the way back
+    int64_t o_inwt, o_owt, o_qkv, o_P, o_ctx, o_ao, o_out, o_dy, o_lpart, o_dao, o_dctx, o_ds, o_dqkv;
+};
+
+// Checks the head's dimensions against `cap` and plans it for a training batch of n: its parameters go behind the
+// caller's np, max_part_bytes is raised to what its partial sums need, and the two transposed weights take their blocks
+// from `ws`.  The other eleven blocks are taken by take_attn_head_blocks, which the trainer calls after the blocks of what
+// feeds the head, so that the large buffers keep the order they had when each trainer planned them itself
+// (profiles/README.md, r10, has the timings behind this).
+int plan_attn_head(const char* who, int64_t n, int T, int H, int heads, int O, int loss, int cap,
+                   WsPlan& ws, int& np, int64_t& max_part_bytes, AttnHead& a) {
+    if (int rc = check_attn(who, n, T, H, heads, cap)) return rc;
+    a = AttnHead{};
+    a.T = T, a.H = H, a.heads = heads, a.O = O, a.loss = loss;
+    a.inw_off = np, np += 3 * H * H;
+    a.inb_off = np, np += 3 * H;
+    a.ow_off = np, np += H * H;
+    a.ob_off = np, np += H;
+    a.fcw_off = np, np += O * H;
+    a.fcb_off = np, np += O;
+    max_part_bytes = std::max<int64_t>(max_part_bytes, (int64_t)fc_chunks(n) * O * H * 8);
+    max_part_bytes = std::max<int64_t>(max_part_bytes, lin_part_bytes(n * T, H, 3 * H));
+    max_part_bytes = std::max<int64_t>(max_part_bytes, lin_part_bytes(n, H, H));
+    a.o_inwt = ws.take((int64_t)3 * H * H * 4);
+    a.o_owt = ws.take((int64_t)H * H * 4);
+    return OFP_OK;
+}
+
+// what the head's forward keeps and its backward writes, for nmax = max(n, n_val) and n samples
+void take_attn_head_blocks(WsPlan& ws, int64_t n, int64_t nmax, AttnHead& a) {
+    const int T = a.T, H = a.H, heads = a.heads, O = a.O;
+    a.o_qkv = ws.take(nmax * T * 3 * H * 4);
+    a.o_P = ws.take(nmax * heads * T * T * 4);
+    a.o_ctx = ws.take(nmax * H * 4);
+    a.o_ao = ws.take(nmax * H * 4);
+    a.o_out = ws.take(nmax * O * 4);
+    a.o_dy = ws.take(nmax * O * 4);
+    a.o_lpart = ws.take(nmax * 8);
+    a.o_dao = ws.take(n * H * 4);
+    a.o_dctx = ws.take(n * H * 4);
+    a.o_ds = ws.take(n * heads * T * T * 4);
+    a.o_dqkv = ws.take(n * T * 3 * H * 4);
+}
+
+// the head on `in` [n T][H] with targets y, the batch's mean loss into `curve` (enqueue_fc_forward); train: dropout on
+// the probabilities, d loss / d out kept and the Linear's bias gradient
+template <class Plan>
+int enqueue_attn_head_fwd(const Run<Plan>& r, const AttnHead& a, int cap, const float* in, int64_t n, const float* y,
+                          bool train, float* curve, int patience) {
+    const int T = a.T, H = a.H;
+    float* inwt = r.template at<float>(a.o_inwt);
+    float* owt = r.template at<float>(a.o_owt);
+    float* qkv = r.template at<float>(a.o_qkv);
+    float* ctx = r.template at<float>(a.o_ctx);
+    float* ao = r.template at<float>(a.o_ao);
+    if (int rc = enqueue_transpose(r.ctl, r.P + a.inw_off, 3 * H, H, inwt, r.st)) return rc;
+    if (int rc = enqueue_transpose(r.ctl, r.P + a.ow_off, H, H, owt, r.st)) return rc;
+    if (int rc = enqueue_lin_fwd(r.ctl, in, n * T, H, 3 * H, inwt, r.P + a.inb_off, qkv, r.st)) return rc;
+    if (int rc = enqueue_attn_fwd(r.ctl, attn_of(n, T, H, a.heads, r.rnd, train), cap, qkv,
+                                  r.template at<float>(a.o_P), ctx, r.st))
+        return rc;
+    if (int rc = enqueue_lin_fwd(r.ctl, ctx, n, H, H, owt, r.P + a.ob_off, ao, r.st)) return rc;
+    const Fc f{ao, n, H, a.O, r.P + a.fcw_off, r.P + a.fcb_off, y};
+    return enqueue_fc_forward(r.ctl, f, a.loss, r.template at<float>(a.o_out),
+                              train ? r.template at<float>(a.o_dy) : nullptr, r.template at<double>(a.o_lpart), curve,
+                              patience, r.G + a.fcb_off, r.st);
+}
+
+// backward of the head from the d loss / d out its forward kept: the head's gradients go to r.G, the gradient at `in`
+// to d_in [n T][H]; `part` takes the partial sums
+template <class Plan>
+int enqueue_attn_head_bwd(const Run<Plan>& r, const AttnHead& a, int cap, const float* in, int64_t n, double* part,
+                          float* d_in) {
+    const int T = a.T, H = a.H;
+    float* dao = r.template at<float>(a.o_dao);
+    float* dctx = r.template at<float>(a.o_dctx);
+    float* dqkv = r.template at<float>(a.o_dqkv);
+    const Fc f{r.template at<float>(a.o_ao), n, H, a.O, r.P + a.fcw_off, r.P + a.fcb_off, nullptr};
+    if (int rc = enqueue_fc_backward(r.ctl, f, r.template at<float>(a.o_dy), part, r.G + a.fcw_off, dao, r.st))
+        return rc;
+    if (int rc = enqueue_lin_bwd(r.ctl, r.template at<float>(a.o_ctx), n, H, H, r.P + a.ow_off, dao, part, dctx,
+                                 r.G + a.ow_off, r.G + a.ob_off, r.st))
+        return rc;
+    if (int rc = enqueue_attn_bwd(r.ctl, attn_of(n, T, H, a.heads, r.rnd, true), cap, r.template at<float>(a.o_qkv),
+                                  r.template at<float>(a.o_P), dctx, r.template at<float>(a.o_ds), dqkv, r.st))
+        return rc;
+    return enqueue_lin_bwd(r.ctl, in, n * T, H, 3 * H, r.P + a.inw_off, dqkv, part, d_in, r.G + a.inw_off,
+                           r.G + a.inb_off, r.st);
 }
 
 // the random options of a stand-alone attention call: dropout alone, no window source

@@ -1,8 +1,10 @@
-// Device code and launch helpers shared by the two epoch-graph trainers (csrc/ofp_cnn_train.hip, csrc/ofp_cccnn_train.hip):
-// the control block of a run, the partial-slab reducer's shape, the convolution's forward and three gradients (any
-// stride), the Linear head with its loss, and the chain's first and last kernels; on the host the work space's base,
-// the checks both trainers make, one epoch, and the driver that captures it as a graph and replays it.  Everything here
-// is file-local (anonymous namespace): each trainer compiles its own copy.
+// Device code and launch helpers shared by the four epoch-graph trainers (csrc/ofp_cnn_train.hip, ofp_cccnn_train.hip,
+// ofp_cnnrnn_train.hip, ofp_rnn_train.hip): the control block of a run, the partial-slab reducer's shape, the convolution's
+// forward and three gradients (any stride), the Linear head with its loss, and the chain's first and last kernels; on the
+// host the work space's base, the checks every trainer makes, one epoch, the driver that captures it as a graph and
+// replays it, and the bodies of the public entries (train_workspace_bytes, train_entry, loss_grads_entry), which a trainer
+// instantiates with its traits -- the contract is spelt out in front of them.  Everything here is file-local (anonymous
+// namespace): each trainer compiles its own copy.
 #pragma once
 #include "ofp_common.h"
 #include "ofp_mlp.h"
@@ -401,15 +403,26 @@ int conv_bwd_alone(const char* who, int64_t need, const float* d_x, int64_t n, i
     return enqueue_conv_bwd(nullptr, c, n, d_x, d_w, d_dz, (double*)d_ws, d_dw, d_db, d_dx, (hipStream_t)stream);
 }
 
-// ---- one epoch and its driver ---------------------------------------------------------------------------------------
-// A trainer derives its Plan from WsPlan and its Run from WsRun and defines enqueue_forward(r, x, y, n, train, curve,
-// patience), which ends in enqueue_fc_forward, enqueue_backward(r, x, n) and enqueue_step(r, rates), its optimiser, for
-// its own Run; the templates below find them by the Run they are called with.  Of the Run they read p, ctl, st and rnd
-// (csrc/ofp_train_random.h), of the Plan o_X.
+// ---- one epoch, its driver and the entries ---------------------------------------------------------------------------
+// What a trainer supplies.
+//   * Its Plan, derived from WsPlan: the dimensions, the parameter offsets and the byte offsets of its work-space blocks.
+//     Parts that more than one trainer has plan themselves into it: ConvStack (csrc/ofp_cnn_stack.h) and AttnHead
+//     (csrc/ofp_seq_train.h) take their blocks from the Plan's bump allocator, advance its parameter and statistics
+//     counters and raise its partial-sum size.
+//   * For Run<Plan>, found by overload: enqueue_forward(r, x, y, n, train, curve, patience), which ends in
+//     enqueue_fc_forward; enqueue_backward(r, x, n); enqueue_step(r, rates), its optimiser; enqueue_reset(r), which zeroes
+//     the optimiser's state in front of the first epoch.
+//   * A traits struct T for the entry templates at the end of this file: Config and Plan (types), train and grads (the
+//     names of the public training and loss-and-gradients entries, as messages give them), env (the variable that turns
+//     graph capture off), window_of(cfg) -> Window, and make_plan(who, cfg, n, n_val, plan, rnd).
+// The extern "C" functions of a trainer are one-line forwards into the entry templates.
 
-// base of a Plan: the byte offsets of the work space's blocks come from a bump allocator
+// base of a Plan: the byte offsets of the work space's blocks come from a bump allocator.  Every block is rounded up on
+// its own, so the size does not depend on the order in which the parts take theirs.
 struct WsPlan {
     int64_t bytes;  // taken so far; in the end the work space's size
+    int np, ns;     // packed parameters; packed running statistics (0: the model has none)
+    int64_t o_G, o_RS, o_ctl, o_X;  // gradients, scratch running statistics (ns > 0), Ctl, the epoch's windows (a source)
     int64_t take(int64_t n) {
         const int64_t at = bytes;
         bytes += ofp::align_up(n > 0 ? n : 1, 256);
@@ -424,6 +437,28 @@ struct WsRun {
     T* at(int64_t off) const {
         return reinterpret_cast<T*>(ws + off);
     }
+};
+
+// The random options of a run are csrc/ofp_train_random.h's Random.  That header builds on this one (its kernels take
+// Ctl and kT), so the type is only declared here and enters Run as a defaulted template parameter: it is complete where
+// a trainer instantiates Run and the templates below, and make_random / enqueue_windows are found there by their
+// Random argument.
+struct Random;
+
+template <class Plan, class Rnd = Random>
+struct Run : WsRun {
+    const Plan* p;
+    float* P;    // packed parameters
+    float* RS;   // packed running statistics; NULL where the model has none
+    float* G;    // packed gradients
+    Ctl* ctl;    // NULL: a single pass, epoch 0 (rnd.st.epoch for the random stream)
+    hipStream_t st;
+    Rnd rnd;     // the model's dropouts and the window source; all off by default
+};
+
+// what a configuration's windows look like to the window source
+struct Window {
+    int channels, width;
 };
 
 struct TrainArgs {
@@ -532,6 +567,69 @@ int run_epochs(const char* who, const char* env, hipStream_t st, Ctl* ctl, int n
     if (he != hipSuccess) return ofp::fail(OFP_ERR_HIP, "%s: %s", who, hipGetErrorString(he));
     *h_epochs = seen.epoch;
     return OFP_OK;
+}
+
+// ---- the public entries ------------------------------------------------------------------------------------------------
+// Refusals come in this order: config, random options, plan, arguments, statistics, work space.
+
+// a training call's random options into r.rnd, then its plan
+template <class T>
+int plan_train(const typename T::Config* cfg, int64_t n, int64_t n_val, const ofp_train_random* random, int span,
+               typename T::Plan& p, Run<typename T::Plan>& r) {
+    OFP_REQUIRE(cfg != nullptr, "%s: config is NULL", T::train);
+    const Window w = T::window_of(*cfg);
+    if (int rc = make_random(T::train, random, span, n, w.channels, w.width, true, r.rnd)) return rc;
+    return T::make_plan(T::train, cfg, n, n_val, p, r.rnd);
+}
+
+template <class T>
+int64_t train_workspace_bytes(const typename T::Config* cfg, int64_t n, int64_t n_val, const ofp_train_random* random,
+                              int span) {
+    typename T::Plan p;
+    Run<typename T::Plan> r{};
+    return plan_train<T>(cfg, n, n_val, random, span, p, r) ? -1 : p.bytes;
+}
+
+// d_stats is NULL for a model without running statistics
+template <class T>
+int train_entry(const typename T::Config* cfg, int64_t n, const float* d_x, const float* d_y, int64_t n_val,
+                const float* d_x_val, const float* d_y_val, const float* d_rates, int num_epochs, int min_epochs,
+                int patience, float* d_params, float* d_stats, float* d_train_loss, float* d_val_loss,
+                int32_t* h_epochs, void* d_ws, int64_t ws_bytes, void* stream, const ofp_train_random* random,
+                int span) {
+    typename T::Plan p;
+    Run<typename T::Plan> r{};
+    if (int rc = plan_train<T>(cfg, n, n_val, random, span, p, r)) return rc;
+    if (r.rnd.windows && d_ws) d_x = reinterpret_cast<const float*>((const char*)d_ws + p.o_X);
+    const TrainArgs a{d_x, d_y, n, d_x_val, d_y_val, n_val, d_rates, min_epochs, patience, d_train_loss, d_val_loss};
+    if (int rc = check_train(T::train, a, num_epochs, d_params, h_epochs)) return rc;
+    OFP_REQUIRE(p.ns == 0 || d_stats, "%s: BatchNorm statistics are NULL", T::train);
+    if (int rc = check_ws(T::train, d_ws, ws_bytes, p.bytes)) return rc;
+    r.ws = (char*)d_ws, r.p = &p, r.P = d_params, r.RS = d_stats, r.st = (hipStream_t)stream;
+    r.G = r.template at<float>(p.o_G);
+    r.ctl = r.template at<Ctl>(p.o_ctl);
+    return run_epochs(
+        T::train, T::env, r.st, r.ctl, num_epochs, patience, h_epochs, [&] { return enqueue_reset(r); },
+        [&] { return enqueue_epoch(r, a); });
+}
+
+// the trainer's own forward and backward on the caller's batch; the running statistics it would update are a scratch copy
+template <class T>
+int loss_grads_entry(const typename T::Config* cfg, int64_t n, const float* d_x, const float* d_y,
+                     const float* d_params, float* d_loss, float* d_grads, void* d_ws, int64_t ws_bytes, void* stream,
+                     const ofp_train_random* random) {
+    typename T::Plan p;
+    Run<typename T::Plan> r{};
+    if (int rc = make_random(T::grads, random, 0, n, 0, 0, false, r.rnd)) return rc;
+    if (int rc = T::make_plan(T::grads, cfg, n, 0, p, r.rnd)) return rc;
+    OFP_REQUIRE(d_x && d_y && d_params && d_loss && d_grads, "%s: NULL argument", T::grads);
+    if (int rc = check_ws(T::grads, d_ws, ws_bytes, p.bytes)) return rc;
+    r.ws = (char*)d_ws, r.p = &p, r.P = const_cast<float*>(d_params), r.G = d_grads, r.st = (hipStream_t)stream;
+    if (p.ns > 0) {
+        r.RS = r.template at<float>(p.o_RS);
+        OFP_HIP(hipMemsetAsync(r.RS, 0, (size_t)p.ns * 4, r.st));
+    }
+    return enqueue_loss_grads(r, d_x, d_y, n, d_loss);
 }
 
 }  // namespace
